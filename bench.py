@@ -12,10 +12,14 @@ of the joints when N > 1).  Weak scaling: every rank runs --batch frames (BASELI
 Nothing is recorded inside the timed region; per-launch and per-stage durations come from a SEPARATE short pass with HIP
 events on the launch stream (SURVEY.md §8d "Timing").
 Consecutive steps are issued round-robin on `--streams` HIP streams (default 3, sceneego_amd/pipeline.py): each step is still one
-complete forward of --batch frames, the K steps are all inside the timed bracket, and `extra.single_stream` reports the same K
-steps issued on one stream beside the headline; `config.streams` says which form `value` is.
+complete forward of --batch frames, the K steps are all inside the timed bracket, and (with --full) `extra.single_stream` reports
+the same K steps issued on one stream beside the headline; `config.streams` says which form `value` is.
 
-Extra objects on the line:
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, --dump-outputs if given, the line.
+`--dump-outputs DIR` writes what the timed path handed back in its LAST timed step as float32 .npy files (dump_outputs below).
+Everything else moves behind `--full` (off by default); the --no-* switches, --profile-steps, --dump-kernel-events and
+--dump-launch-order refine a --full run.  With --full the line also carries step_ms, repeat_values, latency_ms, single_stream_value,
+shard_check / allgather_us (N > 1) and the objects below:
   roofline     — dominant V2V kernel (3x3x3 conv 32->32 at 64^3, 9 launches/step), bound "mfma":
                  achieved = EXECUTED matrix-core FLOP per launch / mean launch duration, frac = achieved / 157.3 TFLOP/s
                  (<= 1); the Winograd saving over the direct convolution is reported separately as algorithmic_speedup.
@@ -83,7 +87,16 @@ def parse():
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-started launcher (0: torchrun --standalone binds a free one itself)")
     ap.add_argument("--no-repeats", action="store_true", help="skip the two repeat brackets that show the spread of the headline")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison of the timed output (profiling runs)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: repeat brackets, the single-stream run, per-step device times, the per-launch "
+                         "timing pass and roofline, the oracle parity gate, the CPU baseline, the cross-rank shard check and the side "
+                         "configurations (the --no-* switches above trim a --full run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32; outputs above DUMP_SAMPLE elements as a fixed sample)")
+    args = ap.parse_args()
+    if not args.full and (args.dump_kernel_events or args.dump_launch_order):
+        ap.error("--dump-kernel-events and --dump-launch-order come from the per-launch timing pass: add --full")
+    return args
 
 
 def self_launch(args):
@@ -262,6 +275,50 @@ def timing_pass(step, steps):
     return _lib.stop_profile()
 
 
+def headline_line(args, world, G, bf16, n_streams, dt, rank_ms, world_backend):
+    """The fields of the result line that a plain run prints: the headline bracket (K steps in dt seconds, max over ranks)."""
+    frames = args.batch * world * args.steps
+    line = {
+        "metric": "frames/sec VoxelNetDepth forward (256x256 img+depth, 64^3 grid)" if G == 64 else
+                  f"frames/sec VoxelNetDepth forward (256x256 img+depth, {G}^3 grid)",
+        "value": round(frames / dt, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": ("bf16 storage + f32 accumulate (V2V), " + args.backbone_dtype + " backbone") if bf16 else
+                 ("f32" if args.backbone_dtype == "fp32" else "f32 V2V, bf16 backbone"), "data": "synthetic",
+        "config": {"workload": f"batch={args.batch}/GPU synthetic 256x256 image N(0,1) + {args.depth_kind} depth 1024x1280, "
+                               f"{G}^3 grid, 15 joints, " + ("bf16 V2V (BASELINE configs[2])" if bf16 else "fp32 (BASELINE configs[1])"),
+                   "batch_per_gpu": args.batch, "global_batch": args.batch * world, "volume_size": G,
+                   "parallelism": f"dp{world}" + (" + RCCL all_gather of [B,15,3] joints" if world > 1 else ""),
+                   "hipgraph": bool(args.graphs), "streams": n_streams},
+    }
+    if world > 1:
+        line["rccl_ranks"] = world_backend
+        line["rank_ms_per_step"] = [round(v, 4) for v in rank_ms]
+    return line
+
+
+DUMP_SAMPLE = 1 << 22      # elements written of a larger output: 16 MB of float32 per array, 48 MB for the three at most
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 .npy files under ``path``:
+    joints.npy [B*N,15,3] (all ranks' frames, gathered), features.npy [B,32,64,64] and volumes.npy (this rank's frames; the forward's
+    second and third return values).  An output of more than DUMP_SAMPLE elements is written as a fixed sample, flattened: its flat
+    range is cut into DUMP_SAMPLE equal strata and one element is taken from each at an offset drawn by numpy's default_rng(0), so
+    the same arguments give the same positions in every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(("joints", "features", "volumes"), outputs):
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            stride = n // DUMP_SAMPLE
+            idx = np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + np.random.default_rng(0).integers(0, stride, DUMP_SAMPLE)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -299,9 +356,10 @@ def main():
             print(f"bench.py: pipelined mode unavailable ({type(e).__name__}: {e}); running --streams 1", file=sys.stderr)
             pipe, n_streams = None, 1
 
+    # a step returns (joints of every rank, this rank's features, this rank's volumes): what its caller receives (--dump-outputs)
     def step_single():
-        kp = net(img, net.grid_coord_proj_batch, net.coord_volumes, depth_map_batch=depth)[0]
-        return sdist.all_gather_joints(kp)
+        out = net(img, net.grid_coord_proj_batch, net.coord_volumes, depth_map_batch=depth)
+        return sdist.all_gather_joints(out[0]), out[1], out[2]
 
     def step():
         if pipe is None:
@@ -312,9 +370,9 @@ def main():
         # behind step i's all-gather, i.e. behind step i
         out, done = pipe(img, net.grid_coord_proj_batch, net.coord_volumes, depth_map_batch=depth, inputs_ready=False)
         if world == 1:
-            return out[0]                    # nothing to gather; the caller synchronises the device before reading it
+            return out[0], out[1], out[2]    # nothing to gather; the caller synchronises the device before reading them
         PipelinedForward.hand_over(out[0], done)     # main stream waits for the forward; joints recorded on it for the collective
-        return sdist.all_gather_joints(out[0])
+        return sdist.all_gather_joints(out[0]), out[1], out[2]
 
     with torch.no_grad():
         if pipe is not None:
@@ -340,10 +398,19 @@ def main():
             mine = time.perf_counter() - t0
             return o, sdist.max_over_ranks(mine, device), mine
 
-        out, dt, dt_mine = timed(step)                  # <- the headline
+        last, dt, dt_mine = timed(step)                 # <- the headline
+    out = last[0]
     rank_ms = sdist.gather_values(dt_mine / args.steps * 1e3, device)
     assert tuple(out.shape) == (args.batch * world, 15, 3) and bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)           # before any later forward (a replayed graph's outputs are static) overwrites them
+    del last
     timed_joints = out[rank * args.batch:(rank + 1) * args.batch].detach().cpu()     # this rank's frames of the LAST timed step
+    if not args.full:
+        sdist.barrier()
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, G, bf16, n_streams, dt, rank_ms, sdist.describe() if world > 1 else None)))
+        return
     # spread: the same timed bracket twice more (reported beside the headline, never instead of it)
     repeats = []
     with torch.no_grad():
@@ -395,29 +462,14 @@ def main():
     if rank != 0:
         return
     psteps = args.profile_steps
-    ms_per_step = dt / args.steps * 1e3
     frames = args.batch * world * args.steps
-    line = {
-        "metric": "frames/sec VoxelNetDepth forward (256x256 img+depth, 64^3 grid)" if G == 64 else
-                  f"frames/sec VoxelNetDepth forward (256x256 img+depth, {G}^3 grid)",
-        "value": round(frames / dt, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": ("bf16 storage + f32 accumulate (V2V), " + args.backbone_dtype + " backbone") if bf16 else
-                 ("f32" if args.backbone_dtype == "fp32" else "f32 V2V, bf16 backbone"), "data": "synthetic",
-        "config": {"workload": f"batch={args.batch}/GPU synthetic 256x256 image N(0,1) + {args.depth_kind} depth 1024x1280, "
-                               f"{G}^3 grid, 15 joints, " + ("bf16 V2V (BASELINE configs[2])" if bf16 else "fp32 (BASELINE configs[1])"),
-                   "batch_per_gpu": args.batch, "global_batch": args.batch * world, "volume_size": G,
-                   "parallelism": f"dp{world}" + (" + RCCL all_gather of [B,15,3] joints" if world > 1 else ""),
-                   "hipgraph": bool(args.graphs), "streams": n_streams},
-    }
+    line = headline_line(args, world, G, bf16, n_streams, dt, rank_ms, world_backend)
     line["step_ms"] = step_ms
     if repeats:
         vals = [line["value"]] + [round(frames / r, 3) for r in repeats]
         line["repeat_values"] = {"values": vals, "min": min(vals), "max": max(vals),
                                  "what": "the headline bracket (first entry = `value`) and two more identical K-step brackets in the same process"}
     if world > 1:
-        line["rccl_ranks"] = world_backend
-        line["rank_ms_per_step"] = [round(v, 4) for v in rank_ms]
         ag = [v for k, v in prof.items() if k[0] == "allgather"]
         if ag:
             line["allgather_us"] = {"median": round(statistics.median(ag[0]) * 1e3, 1), "max": round(max(ag[0]) * 1e3, 1), "n": len(ag[0]),

@@ -221,7 +221,7 @@ def test_two_ranks_launch_sharding_and_all_gather():
     if not two:
         env.update(SCENEEGO_SHARE_GPU="1", SCENEEGO_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "2",
-                        "--no-cpu-baseline", "--no-extras", "--profile-steps", "2"], capture_output=True, text=True, env=env, timeout=1200)
+                        "--full", "--no-cpu-baseline", "--no-extras", "--profile-steps", "2"], capture_output=True, text=True, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 4 and line["config"]["streams"] == 3
@@ -248,7 +248,7 @@ def test_eight_ranks_launch_on_whatever_gpus_there_are(batch, steps, streams):
     if not full:
         env.update(SCENEEGO_SHARE_GPU="1", SCENEEGO_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", str(steps), "--warmup", "1", "--batch", str(batch),
-                        "--streams", str(streams), "--no-cpu-baseline", "--no-extras", "--no-kernel-events", "--no-repeats"],
+                        "--streams", str(streams), "--full", "--no-cpu-baseline", "--no-extras", "--no-kernel-events", "--no-repeats"],
                        capture_output=True, text=True, env=env, timeout=2400)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -2,7 +2,7 @@
 # batch-1 A/B of the fused 1x1 convolutions' routing rule: one stream, eager and as a captured graph
 export TMPDIR=/tmp
 run() {
-  python bench.py --batch 1 --streams 1 $2 --no-extras --no-cpu-baseline --no-repeats --no-kernel-events --steps 200 --warmup 20 2>/dev/null | python -c "
+  python bench.py --full --batch 1 --streams 1 $2 --no-extras --no-cpu-baseline --no-repeats --no-kernel-events --steps 200 --warmup 20 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1 $2', d['value'], 'ms', d['ms_per_step'], 'parity', d['parity']['max_joint_err_m'])"

@@ -1,7 +1,7 @@
 #!/bin/bash
 export TMPDIR=/tmp
 run() {
-  python bench.py --batch ${B:-1} --streams 1 --graphs --no-extras --no-cpu-baseline --no-repeats --no-kernel-events --steps 200 --warmup 20 2>/dev/null | python -c "
+  python bench.py --full --batch ${B:-1} --streams 1 --graphs --no-extras --no-cpu-baseline --no-repeats --no-kernel-events --steps 200 --warmup 20 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('B=${B:-1} graph $1', d['value'], 'ms', d['ms_per_step'])"

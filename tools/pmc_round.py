@@ -7,8 +7,8 @@ pass (separate runs, --kernel-trace only: MI355X_MICROARCH.md "HBM" / "rocprofv3
 cuts the dispatch stream into steps at the gather / voxelise launch that opens a forward, labels every dispatch position of the
 last step with the launch key bench.py's own profiling pass recorded (--dump-launch-order) and writes
 
-    gpurun_out/<TAG>_pmc.json        - what bench.py prints as roofline.traffic / roofline.hbm (copy to profiles/<TAG>_pmc.json)
-    gpurun_out/<TAG>_pmc_table.txt   - every library dispatch of one step with all counters (copy to profiles/)
+    $OUT_DIR/<TAG>_pmc.json          - what bench.py prints as roofline.traffic / roofline.hbm (copy to profiles/<TAG>_pmc.json)
+    $OUT_DIR/<TAG>_pmc_table.txt     - every library dispatch of one step with all counters (copy to profiles/)
 
 Both carry the ABI version and the hash of sceneego_amd/csrc they were taken on (sceneego_amd/_lib.py: source_fingerprint);
 bench.py refuses a record whose fingerprint differs from the checkout it runs in.
@@ -26,7 +26,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.path.join(ROOT, os.environ.get("OUT_DIR", "prof_out"))
 TAG = "r06"
 PASSES = [
     ["FETCH_SIZE"],
@@ -37,7 +37,7 @@ PASSES = [
     ["SQ_ACTIVE_INST_VALU", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_ACTIVE_INST_LDS"],      # round 4: how busy the vector ALUs are beside the MFMAs
     ["SQ_INSTS_VALU_MFMA_MOPS_F32", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR", "SQ_ACTIVE_INST_VMEM", "SQ_INST_CYCLES_SALU"],
 ]
-BENCH = ["python3", "bench.py", "--steps", "2", "--warmup", "1", "--streams", "1", "--no-cpu-baseline", "--no-parity",
+BENCH = ["python3", "bench.py", "--full", "--steps", "2", "--warmup", "1", "--streams", "1", "--no-cpu-baseline", "--no-parity",
          "--no-kernel-events", "--no-extras"]
 OURS = ("conv3d_", "deconv3d_", "maxpool2", "pointwise_chain3", "softargmax_", "::gather_", "voxelize_", "splitk_reduce", "fft7_")
 FRONT = ("conv3d_k7", "fft7_fwd")       # the 7^3 front layer: Winograd kernel, or pass 1 of the frequency-domain form
@@ -143,7 +143,7 @@ def main():
 
     # launch keys in issue order, from bench.py's own HIP-event pass (no profiler attached)
     order_file = os.path.join(OUT, TAG + "_launch_order.json")
-    rc = subprocess.run(["python3", "bench.py", "--steps", "3", "--warmup", "2", "--streams", "1", "--no-cpu-baseline", "--no-parity",
+    rc = subprocess.run(["python3", "bench.py", "--full", "--steps", "3", "--warmup", "2", "--streams", "1", "--no-cpu-baseline", "--no-parity",
                          "--no-extras", "--batch", str(batch), "--volume-size", str(G), "--dump-launch-order", order_file],
                         cwd=ROOT, stdout=open(os.path.join(OUT, TAG + "_order_bench.log"), "w"), stderr=subprocess.STDOUT).returncode
     order = json.load(open(order_file)) if rc == 0 and os.path.isfile(order_file) else []
