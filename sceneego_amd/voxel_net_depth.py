@@ -240,9 +240,18 @@ class VoxelNetwork_depth(nn.Module):
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             out = self._forward_impl(s_img, grid_coord_proj_batch, coord_volumes, None, s_depth)
-        ent = (graph, s_img, s_depth, out)
+        ent = (graph, s_img, s_depth, out, self._captured_buffers())
         self._graphs[key] = ent
         return ent
+
+    def _captured_buffers(self):
+        """Every persistent buffer a captured forward addresses but does not own: the V2V input buffer(s), the program (packed weights,
+        split-K workspaces) with its FFT workspace, the folded backbone and the device tables.  A graph entry holds them, so a later
+        forward of another shape that replaces one of them (``_xbuf.clear()``, a larger ``_fft_ws``, rebuilt tables) cannot free
+        memory a held graph still writes or reads."""
+        prog = self.volume_net._program
+        return (tuple(self._xbuf.values()), prog, getattr(prog, "_fft_ws", None), getattr(prog, "workspace_side", None), self._folded,
+                self._gather_idx, self._gather_w, self._ray_tab, self._coord_flat)
 
     @torch.no_grad()
     def forward(self, images, grid_coord_proj_batch, coord_volumes, scene_volumes=None, depth_map_batch=None):
@@ -253,7 +262,7 @@ class VoxelNetwork_depth(nn.Module):
             return None
         if getattr(self, "use_graphs", False) and depth_map_batch is not None and scene_volumes is None \
                 and _lib._prof is None and images.dtype == torch.float32 and depth_map_batch.dtype == torch.float32:
-            graph, s_img, s_depth, out = self._graph_for(images.contiguous(), depth_map_batch.contiguous(),
+            graph, s_img, s_depth, out, _ = self._graph_for(images.contiguous(), depth_map_batch.contiguous(),
                                                          grid_coord_proj_batch, coord_volumes)
             s_img.copy_(images)
             s_depth.copy_(depth_map_batch)

@@ -38,17 +38,75 @@ def _forward(net, img, depth):
     return out
 
 
+def _forward_capture(net, img, depth):
+    """_forward, also returning the V2V input buffer and the (unscaled) logits of the call, captured at V2VProgram.run."""
+    from sceneego_amd.v2v import V2VProgram
+    cap = {}
+    orig = V2VProgram.run
+
+    def run(prog, x, B, G, *a, **k):
+        out = orig(prog, x, B, G, *a, **k)
+        cap["x"] = x.clone()
+        cap["logits"] = out.clone() / (prog.output_scale if k.get("scaled") else 1.0)
+        return out
+    V2VProgram.run = run
+    try:
+        out = _forward(net, img, depth)
+    finally:
+        V2VProgram.run = orig
+    return out, cap["x"], cap["logits"]
+
+
+def _input_channels(x, B, N, lo, hi):
+    """Channels [lo, hi) of the V2V input buffer as [B, hi - lo, N]: planar [B,C,G,G,G] or channels-last [B,G,G,G,C]."""
+    if x.dim() == 5 and x.shape[-1] == x.shape[-2] == x.shape[-3] and x.shape[1] != x.shape[2]:
+        return x.reshape(B, x.shape[1], N)[:, lo:hi]
+    return x.reshape(B, N, x.shape[-1])[:, :, lo:hi].transpose(1, 2)
+
+
+# Regression gates beside the north-star bars: 5x the value measured on MI355X, rounded up to one significant digit, never above the
+# bar they sit beside.  Measured per golden case (b1_floor / b2_uniform / b1_intersection / b1_g128_floor):
+JOINT_GATE = {"b1_g128_floor": JOINT_TOL}      # joints: 3.0e-5 / 3.7e-5 / 2.4e-5 m -> 2e-4 m; at 128^3 2.8e-4 m (the reference's float32
+JOINT_GATE_DEFAULT = 2e-4                      # einsum over 2 M voxels, host-dependent) -> 5x is above 1e-3: the north-star bar stays
+FEATURE_GATE = 4e-5        # features64_sub, max|d|: 6.7e-6 / 7.6e-6 / 5.7e-6 / 7.6e-6 (the bar: rtol = atol = 2e-3)
+VOLUME_GATE = 6e-6         # volumes_samples, max|d| / volumes_max: 2.6e-7 / 2.9e-7 / 1.1e-6 / 3.8e-7 (the bar: 2e-3)
+LOGIT_GATE = 1e-4          # logits at sample_pos vs logits_samples, of max|logits_samples| (the oracle's bar): 5.6e-6 .. 1.0e-5 measured
+FEATVOL_GATE = 2e-3        # feature volume (and intersection channels) at sample_pos, max|d|: 1.9e-4 / 1.7e-4 / 1.7e-4 / 2.9e-4 (the
+                           # backbone's MIOpen-vs-oneDNN difference through the gather; 5x rounds up to the features' own bar)
+
+
 def _check_against_golden(net, g, m):
     img, depth = synth.make_inputs(m["input_seed"], m["batch"], m["depth_kind"])
-    kp, feats, vols, cv = _forward(net, img, depth)
+    (kp, feats, vols, cv), x, logits = _forward_capture(net, img, depth)
     B, N = m["batch"], m["volume_size"] ** 3
     assert tuple(kp.shape) == (B, 15, 3) and tuple(vols.shape) == (B, 15) + (m["volume_size"],) * 3
     err = float(np.abs(kp.cpu().numpy() - g["joints"]).max())
     assert err <= JOINT_TOL, f"joints differ from the reference golden by {err}"
     pos = torch.from_numpy(g["sample_pos"]).to(DEV)
     vs = vols.reshape(B, 15, N)[:, :, pos].cpu().numpy()
-    assert np.abs(vs - g["volumes_samples"]).max() <= 2e-3 * g["volumes_max"].max() + 1e-7
+    v_err = float(np.abs(vs - g["volumes_samples"]).max())
+    assert v_err <= 2e-3 * g["volumes_max"].max() + 1e-7
     np.testing.assert_allclose(feats[:, :, ::8, ::8].float().cpu().numpy(), g["features64_sub"], rtol=2e-3, atol=2e-3)
+    f_err = float(np.abs(feats[:, :, ::8, ::8].float().cpu().numpy() - g["features64_sub"]).max())
+    # what the goldens hold beyond joints / volumes: the logits and the V2V input at the sample positions
+    l_err = float(np.abs(logits.reshape(B, 15, N)[:, :, pos].cpu().numpy() - g["logits_samples"]).max())
+    l_max = float(np.abs(g["logits_samples"]).max())
+    fv = _input_channels(x, B, N, 0, 32)[:, :, pos].cpu().numpy()
+    fv_err = float(np.abs(fv - g["feature_volume_samples"]).max())
+    msg = (f"{m['name']}: joints {err:.2e} m, volumes {v_err:.2e} (x {float(g['volumes_max'].max()):.2e}), features {f_err:.2e}, "
+           f"logits {l_err:.2e} of {l_max:.2e}, feature volume {fv_err:.2e}")
+    if "intersection_samples" in g:
+        inter = _input_channels(x, B, N, 32, 64)
+        occ = _input_channels(x, B, N, 64, 65)
+        assert torch.equal(inter, _input_channels(x, B, N, 0, 32) * occ), "intersection channels != feature x occupancy"
+        i_err = float(np.abs(inter[:, :, pos].cpu().numpy() - g["intersection_samples"]).max())
+        msg += f", intersection {i_err:.2e}"
+        assert i_err <= FEATVOL_GATE, msg
+    print(msg)
+    assert l_err <= LOGIT_GATE * l_max, msg
+    assert fv_err <= FEATVOL_GATE, msg
+    assert err <= JOINT_GATE.get(m["name"], JOINT_GATE_DEFAULT), msg
+    assert f_err <= FEATURE_GATE and v_err <= VOLUME_GATE * float(g["volumes_max"].max()), msg
     return err
 
 
@@ -207,6 +265,45 @@ def test_v2v_stagewise_vs_oracle(net64, oracle_constants):
     assert float((vols.cpu() - ovols).abs().max()) <= 2e-3 * float(ovols.max())
 
 
+@pytest.mark.parametrize("G", [32, 96])
+def test_forward_other_grids_vs_oracle(G, oracle_constants):
+    """Grid sizes the reference accepts (EncoderDecorder takes any 32k): G=32 puts the middle block at 1^3, G=96 runs the levels
+    48 / 24 / 12 / 6 / 3 (24^3 on the 1-D F(4,3) kernel; 3^3 odd for convolution, deconvolution and pool).  Whole forward, B=1,
+    against the oracle (float64 soft-argmax): joints at the north-star bar, logits at 1e-4 of their maximum."""
+    net = _build(volume_size=G)
+    sd = synthetic_state_dict(False)
+    img, depth = synth.make_inputs(3200 + G, 1, "floor")
+    taps = {}
+    oj, _, _ = O.forward(sd, oracle_constants(G), img, depth, taps=taps, accumulate64=True)
+    (kp, _, vols, _), _, logits = _forward_capture(net, img, depth)
+    assert tuple(vols.shape) == (1, 15, G, G, G)
+    scale = float(taps["logits"].abs().max())
+    l_err = float((logits.cpu().reshape(taps["logits"].shape) - taps["logits"]).abs().max())
+    j_err = float((kp.cpu() - oj).abs().max())
+    print(f"G={G}: logits {l_err:.2e} of max {scale:.2f}, joints {j_err:.2e} m")
+    assert l_err <= 1e-4 * scale, (l_err, scale)
+    assert j_err <= JOINT_TOL, j_err
+
+
+def test_forward_intersection_b8_vs_oracle(oracle_constants):
+    """with_intersection (65 input channels, channels-last V2V input, se_intersection_f32) at the headline batch 8: the last frame's
+    logits and joints against the oracle on that frame, and its intersection channels equal feature x occupancy exactly."""
+    net = _build(with_intersection=True)
+    sd = synthetic_state_dict(True)
+    img, depth = synth.make_inputs(808, 8, "floor")
+    taps = {}
+    oj, _, _ = O.forward(sd, oracle_constants(64), img[7:8], depth[7:8], with_intersection=True, taps=taps, accumulate64=True)
+    (kp, _, _, _), x, logits = _forward_capture(net, img, depth)
+    N = 64 ** 3
+    assert torch.equal(_input_channels(x, 8, N, 32, 64), _input_channels(x, 8, N, 0, 32) * _input_channels(x, 8, N, 64, 65))
+    scale = float(taps["logits"].abs().max())
+    l_err = float((logits[7:8].cpu().reshape(taps["logits"].shape) - taps["logits"]).abs().max())
+    j_err = float((kp[7:8].cpu() - oj).abs().max())
+    print(f"with_intersection B=8, frame 7: logits {l_err:.2e} of max {scale:.2f}, joints {j_err:.2e} m")
+    assert l_err <= 1e-4 * scale, (l_err, scale)
+    assert j_err <= JOINT_TOL, j_err
+
+
 def test_forward_17_joints_unfused_tail_vs_oracle(oracle_constants):
     """`num_joints` > 16 leaves the fused tail (one MFMA column block holds 16 output channels) and runs
     back_layers.1 / .2 / output_layer as three launches with the planar store of the direct kernel (sceneego_amd/v2v.py, the branch
@@ -310,6 +407,64 @@ def test_hipgraph_replay_matches_eager(net64):
     assert float((kp_g1 - kp_eager).abs().max()) < 5e-5
     assert float((kp_g2 - kp_g1).abs().max()) < 5e-5
     assert float((kp_other - kp_g1).abs().max()) > 1e-3     # the replay really consumed the new inputs
+
+
+def _held_tensors(obj, seen=None):
+    """data_ptr of every tensor reachable from a graph entry (tuples, lists, dicts and plain objects such as the V2V program)."""
+    seen = set() if seen is None else seen
+    if id(obj) in seen:
+        return set()
+    seen.add(id(obj))
+    if isinstance(obj, torch.Tensor):
+        return {obj.data_ptr()}
+    out = set()
+    items = obj.values() if isinstance(obj, dict) else obj if isinstance(obj, (tuple, list)) else ()
+    if hasattr(obj, "__dict__") and not isinstance(obj, (torch.nn.Module, torch.cuda.CUDAGraph)):
+        items = list(vars(obj).values())
+    elif hasattr(obj, "__slots__") and not isinstance(obj, torch.Tensor):
+        items = [getattr(obj, s, None) for s in obj.__slots__]
+    for o in items:
+        out |= _held_tensors(o, seen)
+    return out
+
+
+def test_hipgraph_replay_two_batch_sizes():
+    """A graph captured at B=1 stays valid after a capture at B=2: that second capture re-creates the V2V input buffer
+    (``_xbuf.clear()``) and grows the FFT workspace (``V2VProgram._front0_fft``), so the B=1 entry must keep the buffers its
+    launches address.  Checked before any replay (a replay into freed memory is what the check exists to prevent), then
+    B=1, B=2, B=1 replays against the eager joints."""
+    net = _build()
+    img1, depth1 = synth.make_inputs(93, 1, "floor")
+    img2, depth2 = synth.make_inputs(94, 2, "uniform")
+    eager1 = _forward(net, img1, depth1)[0].clone()
+    eager2 = _forward(net, img2, depth2)[0].clone()
+    net._invalidate()
+    d1, d2 = img1.to(DEV).contiguous(), depth1.to(DEV).contiguous()
+    net._graph_for(d1, d2, net.grid_coord_proj_batch, net.coord_volumes)
+    prog = net.volume_net.program
+    used1 = {t.data_ptr() for t in net._xbuf.values()} | {prog._fft_ws.data_ptr(), prog.workspace.data_ptr(),
+                                                          net._gather_idx.data_ptr(), net._gather_w.data_ptr(),
+                                                          net._ray_tab.data_ptr(), net._coord_flat.data_ptr()}
+    fft1 = prog._fft_ws.numel()
+    net._graph_for(img2.to(DEV).contiguous(), depth2.to(DEV).contiguous(), net.grid_coord_proj_batch, net.coord_volumes)
+    torch.cuda.synchronize()
+    assert prog._fft_ws.numel() > fft1 and not (used1 & {t.data_ptr() for t in net._xbuf.values()}), \
+        "the B=2 capture did not replace the B=1 buffers: the test no longer covers the case it was written for"
+    ent1 = [e for k, e in net._graphs.items() if k[0][0] == 1]
+    assert len(ent1) <= 1
+    if ent1:
+        missing = used1 - _held_tensors(ent1[0])
+        assert not missing, f"{len(missing)} buffer(s) of the B=1 capture are no longer held by its graph entry"
+    net.enable_graphs(True)
+    try:
+        g1 = _forward(net, img1, depth1)[0].clone()
+        g2 = _forward(net, img2, depth2)[0].clone()
+        g1b = _forward(net, img1, depth1)[0].clone()
+    finally:
+        net.enable_graphs(False)
+    errs = [float((g1 - eager1).abs().max()), float((g2 - eager2).abs().max()), float((g1b - eager1).abs().max())]
+    print(f"graph replay B=1, B=2, B=1 vs eager: {errs}")
+    assert max(errs) < 5e-5, errs
 
 
 def test_demo_cli_single_frame(tmp_path, golden, golden_meta):

@@ -1491,3 +1491,112 @@ def test_integration_md_bottleneck_stub_runs_as_written():
         want = blk(x)
         got = ns["bottleneck_forward"](blk, x)
     assert float((got - want).abs().max()) < 2e-5 * float(want.abs().max())
+
+
+# ------------------------------------------------------------------------------------------------
+# level sizes the pyramid reaches at G = 32 (..., 2, 1) and G = 96 (48, 24, 12, 6, 3), against float64 references on the CPU
+# ------------------------------------------------------------------------------------------------
+def _conv_bn64(conv, bn, x, res=None, relu=True):
+    import copy
+    c, b = copy.deepcopy(conv).double(), copy.deepcopy(bn).double()
+    with torch.no_grad():
+        y = b(c(x.double()))
+        if res is not None:
+            y = y + res.double()
+        return F.relu(y) if relu else y
+
+
+EDGE_CONV_CASES = [
+    # (B, dim, cin, cout, residual)
+    (2, 1, 128, 128, True),     # G=32 mid_res at 1^3: every tap but the centre reads padding (direct / grid split-K)
+    (5, 1, 128, 128, False),    # ... an odd batch of single voxels
+    (2, 3, 128, 128, True),     # G=96 mid_res at 3^3: odd, ragged level
+    (3, 6, 128, 128, True),     # G=96 5th level (enc4 / skip5 / dec5): 648 voxels, in-workgroup split-K kernel
+    (2, 12, 128, 128, True),    # G=96 4th level: 3456 voxels, in-workgroup split-K without the halo tiles (dim not 8 / 16)
+    (1, 12, 64, 128, False),    # ... the encoder block's first convolution shape at a 12^3 level
+    (2, 24, 64, 128, False),    # G=96 24^3 level (enc2 conv1): the only production route onto the 1-D F(4,3) kernel (algo 1)
+    (1, 24, 128, 128, True),    # ... enc2 conv2 / skip3 / decoder_res3 at 24^3
+    (2, 48, 32, 64, False),     # G=96 48^3 level (enc1 conv1): 2-D Winograd kernel at a level that is not a power of two
+    (1, 48, 64, 64, True),      # ... skip2 / enc1 conv2 / decoder_res2 at 48^3
+    (3, 48, 16, 32, True),      # ... 16-channel input at 48^3 (front_layers.1 conv1 shape at G=48 levels)
+]
+
+
+@pytest.mark.parametrize("B,dim,cin,cout,residual", EDGE_CONV_CASES)
+def test_conv3d_pyramid_edge_dims_vs_float64(B, dim, cin, cout, residual):
+    seed = 4000 + dim * 7 + cin + cout + B
+    conv, bn = _conv_bn(cin, cout, 3, seed)
+    x = torch.from_numpy(synth.normal(seed, "x", (B, cin, dim, dim, dim)))
+    res = torch.from_numpy(synth.normal(seed, "r", (B, cout, dim, dim, dim))) if residual else None
+    want64 = _conv_bn64(conv, bn, x, res)
+    tol = 2e-5 * max(1.0, float(want64.abs().max()))
+    pc = _PackedConv(conv.to(DEV), bn.to(DEV))
+    flags = _lib.EPI_RELU | (_lib.EPI_RES_PRE_RELU if residual else 0)
+    out = torch.empty((B, dim, dim, dim, cout), device=DEV)
+    xd, rd = _ndhwc(x).to(DEV), (_ndhwc(res).to(DEV) if residual else None)
+    ws = torch.empty(32 << 20, device=DEV)
+    errs = []
+    for workspace in (None, ws):      # without / with the split-K workspace (V2VProgram passes one; the small levels use it)
+        out.fill_(float("nan"))
+        _lib.conv3d(xd, pc.w, pc.b, rd, out, B, dim, cin, cin, cout, 3, flags, workspace)
+        err = float((_ncdhw(out.cpu()).double() - want64).abs().max())
+        errs.append(err)
+        assert err <= tol, (err, tol, workspace is not None, _lib.conv3d_variant(B, dim, cin, cout, 3, 0))
+    if dim == 48:
+        # the forms V2VProgram._planar picks at 48^3 (octet-planar at these unit counts) and the pooled epilogue of an encoder input
+        kind = "quad" if _lib.conv3d_variant(B, dim, cin, cout, 3, _lib.IN_QUAD) == 3 else "oct"
+        assert _lib.conv3d_variant(B, dim, cin, cout, 3, _lib.IN_OCTET | _lib.OUT_OCTET) == 2
+        to_pl, from_pl, _, IN, OUT, RES = _lay(kind)
+        fl = _lib.EPI_RELU | IN | OUT | ((_lib.EPI_RES_PRE_RELU | RES) if residual else 0)
+        out_pl = to_pl(torch.full((B, dim, dim, dim, cout), float("nan"), device=DEV))
+        pooled = torch.full((B, dim // 2, dim // 2, dim // 2, cout), float("nan"), device=DEV)
+        _lib.conv3d(to_pl(xd), pc.w, pc.b, to_pl(rd) if residual else None, out_pl, B, dim, cin, cin, cout, 3, fl, ws,
+                    pool_out=pooled)
+        full = _ncdhw(from_pl(out_pl).cpu())
+        e_pl = float((full.double() - want64).abs().max())
+        assert e_pl <= tol, (kind, e_pl, tol)
+        assert torch.equal(_ncdhw(pooled.cpu()), F.max_pool3d(full, 2, 2)), "pooled epilogue differs from max_pool3d of the output"
+        errs.append(e_pl)
+    print(f"conv3d {cin}->{cout} @{dim}^3 B={B} variant {_lib.conv3d_variant(B, dim, cin, cout, 3, 0)}: {errs} (tol {tol:.1e})")
+
+
+@pytest.mark.parametrize("B,dim,cin,cout", [
+    (2, 1, 128, 128),     # G=32 decoder_upsample5: 1^3 -> 2^3
+    (1, 3, 128, 128),     # G=96 decoder_upsample5: 3^3 -> 6^3, odd input
+    (3, 6, 128, 128),     # G=96 decoder_upsample4
+    (2, 12, 128, 128),    # G=96 decoder_upsample3
+    (1, 24, 128, 64),     # G=96 decoder_upsample2: 24^3 -> 48^3 (24 % 16 != 0: no quad-planar output form, _up_quad_ok)
+    (2, 24, 128, 64),
+])
+def test_deconv_pyramid_edge_dims_vs_float64(B, dim, cin, cout):
+    seed = 5000 + dim + cin + cout + B
+    up = nn.ConvTranspose3d(cin, cout, 2, stride=2)
+    with torch.no_grad():
+        up.weight.copy_(torch.from_numpy(synth.normal(seed, "w", tuple(up.weight.shape), (2.0 / cin) ** 0.5)))
+        up.bias.copy_(torch.from_numpy(synth.uniform(seed, "cb", (cout,), -0.2, 0.2)))
+    bn = _rand_bn(cout, seed)
+    x = torch.from_numpy(synth.normal(seed, "x", (B, cin, dim, dim, dim)))
+    sk = torch.from_numpy(synth.normal(seed, "s", (B, cout, 2 * dim, 2 * dim, 2 * dim)))
+    want64 = _conv_bn64(up, bn, x) + sk.double()         # relu(bn(convT(x))) + skip: the decoder's add (reference v2v.py:124-137)
+    pc = _PackedConv(up.to(DEV), bn.to(DEV))
+    out = torch.full((B, 2 * dim, 2 * dim, 2 * dim, cout), float("nan"), device=DEV)
+    _lib.deconv3d_k2s2(_ndhwc(x).to(DEV), pc.w, pc.b, _ndhwc(sk).to(DEV), out, B, dim, cin, cout,
+                       _lib.EPI_RELU | _lib.EPI_RES_POST_RELU)
+    err = float((_ncdhw(out.cpu()).double() - want64).abs().max())
+    assert err <= 2e-5 * max(1.0, float(want64.abs().max())), err
+    assert not (dim % 16 == 0 and (cin, cout) in ((64, 32), (128, 64)))      # (the quad-planar form is covered by test_deconv_vs_torch)
+
+
+@pytest.mark.parametrize("B,dim,c,octet", [
+    (3, 2, 128, False),    # G=32: enc5's pool 2^3 -> 1^3
+    (2, 6, 128, False),    # G=96: 6^3 -> 3^3, an odd output
+    (2, 48, 64, False),    # G=96: 48^3 -> 24^3 (enc2's input)
+    (1, 48, 32, True),     # ... from an octet-planar block output (maxpool3d_2 with in_octet)
+])
+def test_maxpool_pyramid_edge_dims_exact(B, dim, c, octet):
+    x = torch.from_numpy(synth.normal(6000 + dim, "x", (B, c, dim, dim, dim)))
+    want = F.max_pool3d(x, 2, 2)
+    xd = _ndhwc(x).to(DEV)
+    out = torch.full((B, dim // 2, dim // 2, dim // 2, c), float("nan"), device=DEV)
+    _lib.maxpool3d_2(_oct(xd) if octet else xd, out, B, dim, c, in_octet=octet)
+    assert torch.equal(_ncdhw(out.cpu()), want)
