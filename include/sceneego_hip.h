@@ -399,6 +399,30 @@ int se_conv3d_f32_algo(int dim, int cin, int cout, int ksize);
  * with the quad bits first: 3 = use them; otherwise the octet bits (2 = use those).  bench.py prices every launch with it. */
 int se_conv3d_f32_variant(int batch, int dim, int cin, int cout, int ksize, int flags);
 
+/* PIZ-compressed scanline OpenEXR chunks -> float32 on the device (stands in for cv2.imread of the depth maps,
+ * dataset/test_dataset.py:173-178, and for sceneego_amd/exr.py read_depth_exr; bit-identical to the latter).
+ *   chunk_desc  int64 [n_chunks][16], one row per chunk: 0 byte offset of the chunk's block (after y and size) in `payload`,
+ *               1 block bytes, 2 file index (row of channel_desc, sample of out), 3 first row (y - ymin), 4 rows, 5 stored
+ *               uncompressed (size == expected bytes), 6 minNonZero, 7 maxNonZero, 8 offset of the Huffman data in the block,
+ *               9 its bytes, 10 im, 11 iM, 12 nBits, 13 scratch offset and 14 record capacity (both written by
+ *               se_exr_piz_scratch_bytes), 15 unused
+ *   channel_desc int32 [n_files][8]: 0 width, 1 height, 2 pixel type of the selected channel (0 UINT, 1 HALF, 2 FLOAT), 3 16-bit
+ *               words per pixel of the channels stored before it, 4 its words per pixel (1 or 2), 5 words per pixel of all
+ *               channels, 6-7 unused
+ * se_exr_piz_scratch_bytes: HOST pointers; lays out the per-chunk scratch slices (fills columns 13, 14 of chunk_desc) and returns
+ *   the scratch bytes se_exr_piz_decode_f32 needs, or SE_ERR_BAD_ARG.
+ * se_exr_piz_decode_f32: device pointers; out float32 [n_files][out_h][out_w] gets, for every chunk, the output rows whose nearest
+ *   source row (min(floor(y * (height / out_h)), height - 1), same for columns) lies in the chunk; values above `clamp` are set to
+ *   it when clamp > 0 (NaN kept).  status int32 [n_chunks][2]: {code, words decoded}; code 0 ok, 1 descriptor out of range,
+ *   2 code-length table past the Huffman bytes, 3 table larger than its scratch, 4 nBits past the bytes, 5 no code matches,
+ *   6 stream ended after `words decoded` symbols, 7 run past the end of the output.  A chunk with a non-zero code writes nothing
+ *   to `out`.  Kernels se_exr_piz_huffman_kernel, se_exr_piz_wavelet_kernel; every read stays inside payload_bytes / the chunk's
+ *   block, every write inside its scratch slice and its rows of `out`. */
+long long se_exr_piz_scratch_bytes(long long* chunk_desc, int n_chunks, const int* channel_desc, int n_files);
+int se_exr_piz_decode_f32(const void* payload, long long payload_bytes, const long long* chunk_desc, int n_chunks,
+                          const int* channel_desc, int n_files, float* out, int out_h, int out_w, float clamp,
+                          void* scratch, long long scratch_bytes, int* status, void* stream);
+
 #ifdef SE_DEVTOOLS
 /* Development builds only (csrc/build.sh --devtools; absent from the production library): A/B kernel selection for
  * tools/bench_conv.py and the cycle-stamp diagnostics.  The selector is thread-local. */

@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""Sequence evaluation of the reference (``test.py`` + ``dataset/test_dataset.py``) on this project's forward: one recorded sequence
+-> predicted joints of every frame, MPJPE / PA-MPJPE against its ground truth, frames/s of the whole run.
+
+    python run_sequence.py --root_dir data --seq_name new_diogo1 --estimated_depth_name matterport_green \\
+                           --output out/no_body_diogo1.pkl [--weights synthetic] [--depth_decode device|host] [--streams 2]
+
+Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
+with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
+map is ``<seq>/<estimated_depth_name>/img_%06d.jpg.exr`` or ``<seq>/rendered/depths/img_%06d/Image0001.exr``.  Frames run in
+batches of ``config.test.batch_size`` (a partial last batch included).  JPEGs are decoded by a small host thread pool one batch
+ahead; the image path is demo.py's (``se_preprocess_image_u8`` for 1280x1024 frames); depth maps go through
+``exr_device.decode_depth_exr_batch(..., out_hw=(1024, 1280))`` (PIZ decoded on the device) or, with ``--depth_decode host``,
+through ``exr.py`` + ``prepare_depth`` - the same values either way (``TestDataset.__getitem__``: nearest resize to 1280x1024, clamp
+to 10 m).  The pickle holds the list of float32 [15, 3] predictions, as ``test.py`` writes it.
+"""
+import argparse
+import json
+import os
+import pickle
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+MAX_WORKERS = 16
+
+
+def frame_list(root_dir, seq_name, estimated_depth_name=None):
+    """(image paths, ground-truth poses, depth paths) of a sequence, in the order and with the skips of ``TestDataset.get_gt_data``."""
+    base = os.path.join(root_dir, seq_name)
+    img_dir = os.path.join(base, "imgs")
+    depth_dir = os.path.join(base, estimated_depth_name) if estimated_depth_name is not None else os.path.join(base, "rendered", "depths")
+    with open(os.path.join(base, "syn.json")) as f:
+        syn = json.load(f)
+    with open(os.path.join(base, "local_pose_gt.pkl"), "rb") as f:
+        pose_gt = pickle.load(f)
+    images, poses, depths = [], [], []
+    for item in pose_gt:
+        pose = item["ego_pose_gt"]
+        if pose is None:
+            continue
+        ego_id = item["ext_id"] - syn["ext"] + syn["ego"]
+        img = os.path.join(img_dir, "img_%06d.jpg" % ego_id)
+        if not os.path.exists(img):
+            continue
+        images.append(img)
+        if estimated_depth_name is not None:
+            depths.append(os.path.join(depth_dir, "img_%06d.jpg.exr" % ego_id))
+        else:
+            depths.append(os.path.join(depth_dir, "img_%06d" % ego_id, "Image0001.exr"))
+        poses.append(pose)
+    return images, poses, depths
+
+
+class SequenceRunner:
+    def __init__(self, config, weights=None, streams=1, depth_decode="device", workers=8):
+        from sceneego_amd import synth
+        from sceneego_amd.pipeline import PipelinedForward
+        from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
+        if not torch.cuda.is_available():
+            raise RuntimeError("run_sequence.py needs an MI355X (HIP device); the hot path has no CPU fallback")
+        if depth_decode not in ("device", "host"):
+            raise ValueError(f"--depth_decode must be device or host, got {depth_decode}")
+        self.device = torch.device("cuda")
+        self.config = config
+        self.depth_decode = depth_decode
+        self.workers = max(1, min(int(workers), MAX_WORKERS))
+        net = VoxelNetwork_depth(config, device="cpu", verbose=False)
+        if weights == "synthetic":
+            net.load_state_dict(synth.make_state_dict(net.state_dict(), seed=0), strict=True)
+        else:
+            loads = torch.load(weights or config.test.model_path, map_location="cpu")
+            net.load_state_dict(loads["state_dict"])
+        self.net = net.to(self.device).eval()
+        self.pipe = PipelinedForward(self.net, n_streams=streams) if streams > 1 else None
+
+    def _images(self, frames):
+        from sceneego_amd.preprocess import preprocess_image, preprocess_image_device
+        shape = self.config.image_shape
+        full = (4 * shape[0], 4 * shape[1] + 256)
+        if all(f.shape[:2] == full for f in frames):
+            u8 = torch.from_numpy(np.stack(frames)).to(self.device)
+            return preprocess_image_device(u8, shape)
+        return torch.stack([preprocess_image(f, shape) for f in frames]).to(self.device)
+
+    def _depths(self, paths):
+        from sceneego_amd.exr_device import decode_depth_exr_batch
+        from sceneego_amd.preprocess import DEPTH_CLAMP, load_depth, prepare_depth
+        W, H = self.config.dataset.image_width, self.config.dataset.image_height
+        if self.depth_decode == "device":
+            return decode_depth_exr_batch(paths, self.device, out_hw=(H, W), clamp=DEPTH_CLAMP)
+        return torch.stack([prepare_depth(load_depth(p), W, H) for p in paths]).to(self.device)
+
+    @torch.no_grad()
+    def run(self, images, depths, batch_size):
+        from sceneego_amd.preprocess import load_image_bgr
+        batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
+        preds, pending = [], []
+
+        def drain(keep):
+            while len(pending) > keep:
+                kp, done = pending.pop(0)
+                if done is not None:
+                    done.synchronize()
+                preds.extend(np.asarray(k, dtype=np.float32) for k in kp.cpu().numpy())
+
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            ahead = [pool.submit(load_image_bgr, p) for p in batches[0][0]] if batches else []
+            for i, (imgs, deps) in enumerate(batches):
+                frames = [f.result() for f in ahead]
+                if i + 1 < len(batches):
+                    ahead = [pool.submit(load_image_bgr, p) for p in batches[i + 1][0]]
+                img = self._images(frames)
+                depth = self._depths(deps)
+                if self.pipe is None:
+                    kp, _, _, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
+                    pending.append((kp, None))
+                else:
+                    (kp, _, _, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
+                    pending.append((kp, done))
+                drain(len(self.pipe) - 1 if self.pipe is not None else 0)
+            drain(0)
+        return preds
+
+
+def main(argv=None):
+    from sceneego_amd import load_config
+    from sceneego_amd import metrics as M
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--config", default=os.path.join(ROOT, "experiments", "sceneego", "test", "sceneego.yaml"))
+    ap.add_argument("--root_dir", required=True, help="directory holding the sequence directories")
+    ap.add_argument("--seq_name", required=True)
+    ap.add_argument("--estimated_depth_name", default=None, help="<seq>/<name>/img_%%06d.jpg.exr (default: rendered/depths)")
+    ap.add_argument("--weights", default=None, help="checkpoint path, or 'synthetic' (default: config.test.model_path)")
+    ap.add_argument("--depth_decode", default="device", choices=("device", "host"))
+    ap.add_argument("--streams", type=int, default=1, help="forwards in flight (PipelinedForward when > 1)")
+    ap.add_argument("--workers", type=int, default=8, help=f"JPEG decode threads (at most {MAX_WORKERS})")
+    ap.add_argument("--output", default=None, help="pickle of the predicted [15,3] joints of every frame")
+    args = ap.parse_args(argv)
+    config = load_config(args.config)
+    images, poses, depths = frame_list(args.root_dir, args.seq_name, args.estimated_depth_name)
+    if not images:
+        raise SystemExit("no frames: every pose is None or every image is missing")
+    print(f"dataset length: {len(images)}")
+    runner = SequenceRunner(config, weights=args.weights, streams=args.streams, depth_decode=args.depth_decode,
+                            workers=args.workers)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    preds = runner.run(images, depths, config.test.batch_size)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    pred = np.stack(preds).astype(np.float64)
+    gt = np.stack([np.asarray(p, dtype=np.float64) for p in poses])
+    mpjpe, pampjpe = M.mpjpe(pred, gt), M.pa_mpjpe(pred, gt)
+    print("mpjpe: {}".format(mpjpe))
+    print("pa mpjpe: {}".format(pampjpe))
+    print(f"frames/s: {len(preds) / dt:.2f} ({len(preds)} frames in {dt:.3f} s, depth decode on the {args.depth_decode})")
+    if args.output:
+        os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
+        with open(args.output, "wb") as f:
+            pickle.dump(preds, f)
+    return {"frames": len(preds), "mpjpe": mpjpe, "pa_mpjpe": pampjpe, "fps": len(preds) / dt, "predictions": preds}
+
+
+if __name__ == "__main__":
+    main()

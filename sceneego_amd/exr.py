@@ -294,6 +294,11 @@ def read_exr(path: str) -> dict:
     """Returns {channel name: float32 [H, W]} (UINT channels as float32 too)."""
     with open(path, "rb") as f:
         buf = f.read()
+    return read_exr_buffer(buf)
+
+
+def read_exr_buffer(buf: bytes) -> dict:
+    """:func:`read_exr` of a file's bytes."""
     hdr = _parse_header(buf)
     xmin, ymin, xmax, ymax = hdr["window"]
     W, H = xmax - xmin + 1, ymax - ymin + 1
@@ -332,7 +337,11 @@ def read_exr(path: str) -> dict:
 
 def read_depth_exr(path: str) -> np.ndarray:
     """First channel (alphabetical: 'Y' for the demo files; 'B' for BGR files, matching cv2's ``[:, :, 0]``)."""
-    planes = read_exr(path)
+    return depth_channel(read_exr(path))
+
+
+def depth_channel(planes: dict) -> np.ndarray:
+    """The plane :func:`read_depth_exr` returns out of :func:`read_exr`'s dict."""
     for pref in ("Y", "B", "Z", "R"):
         if pref in planes:
             return planes[pref]

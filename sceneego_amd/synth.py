@@ -147,3 +147,42 @@ def make_inputs(seed: int, batch: int, depth_kind: str = "uniform", image_hw=(25
     else:
         raise ValueError(depth_kind)
     return torch.from_numpy(imgs), torch.from_numpy(depth)
+
+
+def make_sequence(root_dir: str, seq_name: str, n_frames: int, depth_sources, estimated_depth_name: str = "est_depth",
+                  seed: int = 0, ego_start: int = 1000, ext_start: int = 10):
+    """A recorded sequence in the reference's test layout (``dataset/test_dataset.py``) under ``root_dir/seq_name``: ``syn.json``,
+    ``local_pose_gt.pkl`` (with one pose-less item and one item whose image is missing, both skipped by the frame list),
+    ``n_frames`` 1280x1024 JPEGs ``imgs/img_%06d.jpg`` and depth maps ``<estimated_depth_name>/img_%06d.jpg.exr``, copied
+    round-robin from ``depth_sources`` (EXR files).  Returns the number of frames the frame list keeps (``n_frames``)."""
+    import pickle
+    import shutil
+
+    from PIL import Image
+    base = os.path.join(root_dir, seq_name)
+    os.makedirs(os.path.join(base, "imgs"), exist_ok=True)
+    os.makedirs(os.path.join(base, estimated_depth_name), exist_ok=True)
+    with open(os.path.join(base, "syn.json"), "w") as f:
+        json.dump({"ego": ego_start, "ext": ext_start}, f)
+    ys, xs = np.meshgrid(np.arange(1024, dtype=np.float64), np.arange(1280, dtype=np.float64), indexing="ij")
+    items = []
+    ext_id = ext_start
+    for i in range(n_frames + 2):
+        ego_id = ext_id - ext_start + ego_start
+        pose = uniform(seed + i, "sequence/pose", (15, 3), -0.8, 0.8) + np.array([0, 0, 1.0], dtype=np.float32)
+        if i == 1:
+            items.append({"ext_id": ext_id, "ego_pose_gt": None})          # skipped: no pose
+        elif i == 3:
+            items.append({"ext_id": ext_id, "ego_pose_gt": pose})          # skipped: image missing
+        else:
+            items.append({"ext_id": ext_id, "ego_pose_gt": pose})
+            ph = uniform(seed + i, "sequence/phase", (3,), 0.0, 6.283)
+            rgb = np.stack([127 + 100 * np.sin(xs / (37 + 9 * c) + ys / (53 - 7 * c) + ph[c]) for c in range(3)], axis=-1)
+            Image.fromarray(np.clip(rgb, 0, 255).astype(np.uint8)).save(os.path.join(base, "imgs", "img_%06d.jpg" % ego_id),
+                                                                       quality=90)
+            src = depth_sources[i % len(depth_sources)]
+            shutil.copyfile(src, os.path.join(base, estimated_depth_name, "img_%06d.jpg.exr" % ego_id))
+        ext_id += 1
+    with open(os.path.join(base, "local_pose_gt.pkl"), "wb") as f:
+        pickle.dump(items, f)
+    return n_frames
