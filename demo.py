@@ -16,6 +16,7 @@ import pickle
 import torch
 
 from sceneego_amd import load_config, synth
+from sceneego_amd.jpeg_device import JpegFile, decode_jpeg_batch
 from sceneego_amd.preprocess import (DEPTH_CLAMP, load_depth, load_image_bgr, prepare_depth, preprocess_image,
                                      preprocess_image_device)
 from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
@@ -26,11 +27,12 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 
 class Demo:
-    def __init__(self, config, img_dir, depth_dir, weights=None):
+    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device"):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
         self.config = config
+        self.image_decode = image_decode
         self.items = []
         for img_name in sorted(os.listdir(img_dir)):
             img_path = os.path.join(img_dir, img_name)
@@ -52,9 +54,13 @@ class Demo:
         results = []
         with torch.no_grad():
             for img_path, depth_path in self.items:
-                frame = load_image_bgr(img_path)
                 W, H = self.config.dataset.image_width, self.config.dataset.image_height
-                if frame.shape[:2] == (4 * self.config.image_shape[0], 4 * self.config.image_shape[1] + 256):
+                full = (4 * self.config.image_shape[0], 4 * self.config.image_shape[1] + 256)
+                jpeg = JpegFile(img_path) if self.image_decode == "device" else None
+                if jpeg is not None and jpeg.device and (jpeg.H, jpeg.W) == full:
+                    # JPEG decoded on the device (bit-identical to load_image_bgr), then se_preprocess_image_u8
+                    img = preprocess_image_device(decode_jpeg_batch([jpeg], self.device), self.config.image_shape)
+                elif (frame := load_image_bgr(img_path)).shape[:2] == full:
                     # raw uint8 frame to the device; crop / quarter-resize / normalise there (se_preprocess_image_u8)
                     img = preprocess_image_device(torch.from_numpy(frame).to(self.device), self.config.image_shape)
                 else:

@@ -423,6 +423,36 @@ int se_exr_piz_decode_f32(const void* payload, long long payload_bytes, const lo
                           const int* channel_desc, int n_files, float* out, int out_h, int out_w, float clamp,
                           void* scratch, long long scratch_bytes, int* status, void* stream);
 
+/* Baseline JPEG frames -> uint8 B, G, R on the device (stands in for sceneego_amd/preprocess.py load_image_bgr, PIL on libjpeg-turbo;
+ * bit-identical to it).  sceneego_amd/jpeg_device.py parses, validates and unstuffs on the host.
+ *   img_desc  int32 [n_images][64]: 0 width, 1 height, 2 components (1 or 3), 3 MCUs per row, 4 MCU rows, 5 blocks per MCU (<= 10),
+ *             6 first segment, 7 segments, 8 output slot (sample of out), 9 hmax, 10 vmax, 12-14 h per component (frame order),
+ *             15-17 v, 18-20 quantisation slot (== component), 21-23 DC table slot (0-3), 24-26 AC table slot (4-7), 27-29 plane
+ *             width (8 * h * MCUs per row), 30-32 plane height (8 * v * MCU rows), 33-35 first block of the component in the MCU,
+ *             36 first global block and 37-39 plane byte offsets (both written by se_jpeg_scratch_bytes), 40-49 component of every
+ *             block of the MCU, 50 restart interval (informational); gray images use one block per MCU of 8x8 pixels.
+ *   seg_desc  int64 [n_segs][8], one row per restart segment, ordered by image then segment: 0 byte offset of its unstuffed
+ *             entropy-coded data in `payload` (4-byte aligned; the slot holds ((len + 3) & ~3) + 8 bytes, zero after len),
+ *             1 len, 2 image (row of img_desc), 3 first MCU, 4 MCUs, 5 first lane, 6 lanes, 7 first global block (5-7 written by
+ *             se_jpeg_scratch_bytes).
+ *   tables    [n_images][8] records of 1536 bytes (slots 0-3 DC, 4-7 AC): uint16 lookahead[512] (9 bits; length << 8 | symbol, 0
+ *             for a longer code), int32 maxcode[18] (-1 for none), int32 valoffset[18] at byte 1096, uint8 values[256] at byte 1168.
+ *   quant     int32 [n_images][4][64], natural order, each value already cast to int16 as libjpeg's ISLOW_MULT_TYPE.
+ * se_jpeg_scratch_bytes: HOST pointers; fills the derived columns and layout int64[4] = {blocks, lanes, plane bytes, longest
+ *   per-(segment, component) block run}, returns the scratch bytes se_jpeg_decode_bgr_u8 needs, or SE_ERR_BAD_ARG.
+ * se_jpeg_decode_bgr_u8: device pointers except `layout` (host, from se_jpeg_scratch_bytes); out uint8 [n_out][out_h][out_w][3]
+ *   (B, G, R) gets every image at its output slot.  `rounds`: inter-workgroup synchronisation launches (< 0: the default, 3); 0
+ *   leaves every unsynchronised workgroup to the sequential repair kernel, with the same result.  status int32 [n_segs][2]:
+ *   {code, value}; 0 ok, 1 descriptor out of range, 2 no code matches (value: bit offset in the segment), 3 stream ended (value:
+ *   blocks completed of mcus * blocks per MCU).  Kernels se_jpeg_sync_intra_kernel, se_jpeg_sync_inter_kernel,
+ *   se_jpeg_sync_repair_kernel, se_jpeg_scan_kernel, se_jpeg_scan_top_kernel, se_jpeg_write_kernel, se_jpeg_dc_kernel,
+ *   se_jpeg_idct_kernel, se_jpeg_color_kernel; every read stays inside payload_bytes and the segment's slot, every write inside
+ *   the scratch layout and out. */
+long long se_jpeg_scratch_bytes(int* img_desc, int n_images, long long* seg_desc, int n_segs, long long* layout);
+int se_jpeg_decode_bgr_u8(const void* payload, long long payload_bytes, const int* img_desc, int n_images, const long long* seg_desc,
+                          int n_segs, const void* tables, const int* quant, const long long* layout, unsigned char* out, int n_out,
+                          int out_h, int out_w, void* scratch, long long scratch_bytes, int* status, int rounds, void* stream);
+
 #ifdef SE_DEVTOOLS
 /* Development builds only (csrc/build.sh --devtools; absent from the production library): A/B kernel selection for
  * tools/bench_conv.py and the cycle-stamp diagnostics.  The selector is thread-local. */

@@ -3,13 +3,15 @@
 -> predicted joints of every frame, MPJPE / PA-MPJPE against its ground truth, frames/s of the whole run.
 
     python run_sequence.py --root_dir data --seq_name new_diogo1 --estimated_depth_name matterport_green \\
-                           --output out/no_body_diogo1.pkl [--weights synthetic] [--depth_decode device|host] [--streams 2]
+                           --output out/no_body_diogo1.pkl [--weights synthetic] [--depth_decode device|host]
+                           [--image_decode device|host] [--streams 2]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
 map is ``<seq>/<estimated_depth_name>/img_%06d.jpg.exr`` or ``<seq>/rendered/depths/img_%06d/Image0001.exr``.  Frames run in
-batches of ``config.test.batch_size`` (a partial last batch included).  JPEGs are decoded by a small host thread pool one batch
-ahead; the image path is demo.py's (``se_preprocess_image_u8`` for 1280x1024 frames); depth maps go through
+batches of ``config.test.batch_size`` (a partial last batch included).  A small host thread pool reads and parses the JPEGs one batch
+ahead; they are decoded on the device (``jpeg_device.decode_jpeg_batch``, bit-identical to PIL) or, with ``--image_decode host``, by
+PIL in that pool; the image path is then demo.py's (``se_preprocess_image_u8`` for 1280x1024 frames); depth maps go through
 ``exr_device.decode_depth_exr_batch(..., out_hw=(1024, 1280))`` (PIZ decoded on the device) or, with ``--depth_decode host``,
 through ``exr.py`` + ``prepare_depth`` - the same values either way (``TestDataset.__getitem__``: nearest resize to 1280x1024, clamp
 to 10 m).  The pickle holds the list of float32 [15, 3] predictions, as ``test.py`` writes it.
@@ -60,7 +62,7 @@ def frame_list(root_dir, seq_name, estimated_depth_name=None):
 
 
 class SequenceRunner:
-    def __init__(self, config, weights=None, streams=1, depth_decode="device", workers=8):
+    def __init__(self, config, weights=None, streams=1, depth_decode="device", workers=8, image_decode="device"):
         from sceneego_amd import synth
         from sceneego_amd.pipeline import PipelinedForward
         from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
@@ -68,6 +70,9 @@ class SequenceRunner:
             raise RuntimeError("run_sequence.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         if depth_decode not in ("device", "host"):
             raise ValueError(f"--depth_decode must be device or host, got {depth_decode}")
+        if image_decode not in ("device", "host"):
+            raise ValueError(f"--image_decode must be device or host, got {image_decode}")
+        self.image_decode = image_decode
         self.device = torch.device("cuda")
         self.config = config
         self.depth_decode = depth_decode
@@ -82,8 +87,10 @@ class SequenceRunner:
         self.pipe = PipelinedForward(self.net, n_streams=streams) if streams > 1 else None
 
     def _images(self, frames):
-        from sceneego_amd.preprocess import preprocess_image, preprocess_image_device
+        from sceneego_amd.preprocess import preprocess_image, preprocess_image_device, preprocess_jpeg_batch
         shape = self.config.image_shape
+        if self.image_decode == "device":             # parsed JpegFile objects
+            return preprocess_jpeg_batch(frames, self.device, shape)
         full = (4 * shape[0], 4 * shape[1] + 256)
         if all(f.shape[:2] == full for f in frames):
             u8 = torch.from_numpy(np.stack(frames)).to(self.device)
@@ -100,7 +107,9 @@ class SequenceRunner:
 
     @torch.no_grad()
     def run(self, images, depths, batch_size):
+        from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.preprocess import load_image_bgr
+        load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
         preds, pending = [], []
 
@@ -112,11 +121,11 @@ class SequenceRunner:
                 preds.extend(np.asarray(k, dtype=np.float32) for k in kp.cpu().numpy())
 
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
-            ahead = [pool.submit(load_image_bgr, p) for p in batches[0][0]] if batches else []
+            ahead = [pool.submit(load, p) for p in batches[0][0]] if batches else []
             for i, (imgs, deps) in enumerate(batches):
                 frames = [f.result() for f in ahead]
                 if i + 1 < len(batches):
-                    ahead = [pool.submit(load_image_bgr, p) for p in batches[i + 1][0]]
+                    ahead = [pool.submit(load, p) for p in batches[i + 1][0]]
                 img = self._images(frames)
                 depth = self._depths(deps)
                 if self.pipe is None:
@@ -140,8 +149,9 @@ def main(argv=None):
     ap.add_argument("--estimated_depth_name", default=None, help="<seq>/<name>/img_%%06d.jpg.exr (default: rendered/depths)")
     ap.add_argument("--weights", default=None, help="checkpoint path, or 'synthetic' (default: config.test.model_path)")
     ap.add_argument("--depth_decode", default="device", choices=("device", "host"))
+    ap.add_argument("--image_decode", default="device", choices=("device", "host"))
     ap.add_argument("--streams", type=int, default=1, help="forwards in flight (PipelinedForward when > 1)")
-    ap.add_argument("--workers", type=int, default=8, help=f"JPEG decode threads (at most {MAX_WORKERS})")
+    ap.add_argument("--workers", type=int, default=8, help=f"JPEG read / parse (host decode: decode) threads (at most {MAX_WORKERS})")
     ap.add_argument("--output", default=None, help="pickle of the predicted [15,3] joints of every frame")
     args = ap.parse_args(argv)
     config = load_config(args.config)
@@ -150,7 +160,7 @@ def main(argv=None):
         raise SystemExit("no frames: every pose is None or every image is missing")
     print(f"dataset length: {len(images)}")
     runner = SequenceRunner(config, weights=args.weights, streams=args.streams, depth_decode=args.depth_decode,
-                            workers=args.workers)
+                            workers=args.workers, image_decode=args.image_decode)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     preds = runner.run(images, depths, config.test.batch_size)
@@ -161,7 +171,7 @@ def main(argv=None):
     mpjpe, pampjpe = M.mpjpe(pred, gt), M.pa_mpjpe(pred, gt)
     print("mpjpe: {}".format(mpjpe))
     print("pa mpjpe: {}".format(pampjpe))
-    print(f"frames/s: {len(preds) / dt:.2f} ({len(preds)} frames in {dt:.3f} s, depth decode on the {args.depth_decode})")
+    print(f"frames/s: {len(preds) / dt:.2f} ({len(preds)} frames in {dt:.3f} s, depth decode on the {args.depth_decode}, image decode on the {args.image_decode})")
     if args.output:
         os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
         with open(args.output, "wb") as f:

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -88,6 +88,8 @@ SIGNATURES = {
     "se_conv3d_k3_split3_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "se_exr_piz_scratch_bytes": (_ll, [_vp, _i, _vp, _i]),
     "se_exr_piz_decode_f32": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _ll, _vp, _vp]),
+    "se_jpeg_scratch_bytes": (_ll, [_vp, _i, _vp, _i, _vp]),
+    "se_jpeg_decode_bgr_u8": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _i, _vp]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -269,6 +271,34 @@ def exr_piz_decode(payload_ptr, payload_bytes, desc_ptr, n_chunks, chan_ptr, n_f
     _check(load().se_exr_piz_decode_f32(_vp(payload_ptr), int(payload_bytes), _vp(desc_ptr), n_chunks, _vp(chan_ptr), n_files,
                                         _ptr(out), out.shape[1], out.shape[2], float(clamp), _ptr(scratch), scratch.numel(),
                                         _ptr(status), _stream()), "se_exr_piz_decode_f32")
+
+
+def jpeg_scratch_bytes(img_desc, seg_desc, layout) -> int:
+    """img_desc int32 [n, 64], seg_desc int64 [m, 8] and layout int64 [>= 4] (HOST numpy arrays, include/sceneego_hip.h): fills the
+    derived columns and the layout in place and returns the scratch bytes of se_jpeg_decode_bgr_u8."""
+    import numpy as np
+    assert img_desc.dtype == np.int32 and img_desc.flags.c_contiguous and img_desc.shape[1:] == (64,)
+    assert seg_desc.dtype == np.int64 and seg_desc.flags.c_contiguous and seg_desc.shape[1:] == (8,)
+    assert layout.dtype == np.int64 and layout.flags.c_contiguous and layout.size >= 4
+    n = load().se_jpeg_scratch_bytes(img_desc.ctypes.data_as(_vp), img_desc.shape[0], seg_desc.ctypes.data_as(_vp),
+                                     seg_desc.shape[0], layout.ctypes.data_as(_vp))
+    if n < 0:
+        raise HipExtensionError(f"se_jpeg_scratch_bytes failed with code {n} (bad argument)")
+    return int(n)
+
+
+def jpeg_decode(payload_ptr, payload_bytes, img_ptr, n_images, seg_ptr, n_segs, tables_ptr, quant_ptr, layout, out, scratch, status,
+                rounds=-1):
+    """JPEG segments -> out uint8 [B, H, W, 3] (B, G, R) on the current stream.  *_ptr: device addresses (ints) inside a buffer the
+    caller keeps alive; layout: the host int64 array se_jpeg_scratch_bytes filled; status int32 [n_segs, 2]."""
+    require_hip(out, scratch, status)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 4 and out.shape[3] == 3
+    assert scratch.dtype == torch.uint8 and status.dtype == torch.int32 and status.shape == (n_segs, 2) and status.is_contiguous()
+    _check(load().se_jpeg_decode_bgr_u8(_vp(payload_ptr), int(payload_bytes), _vp(img_ptr), n_images, _vp(seg_ptr), n_segs,
+                                        _vp(tables_ptr), _vp(quant_ptr), layout.ctypes.data_as(_vp), _ptr(out), out.shape[0],
+                                        out.shape[1], out.shape[2], _ptr(scratch), scratch.numel(), _ptr(status), int(rounds),
+                                        _stream()), "se_jpeg_decode_bgr_u8")
+
 
 def unproject_gather(feat, idx, w, out, batch, texels, channels, voxels, out_stride_c, out_c_offset):
     require_hip(feat, idx, w, out)

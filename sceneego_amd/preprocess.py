@@ -66,6 +66,22 @@ def preprocess_image_device(img_bgr_u8: torch.Tensor, image_shape=(256, 256)) ->
     return _lib.preprocess_image_u8(x.contiguous(), out, 128, IMG_MEAN, IMG_STD)
 
 
+def preprocess_jpeg_batch(sources, device, image_shape=(256, 256)) -> torch.Tensor:
+    """JPEG frames (paths, bytes or parsed ``jpeg_device.JpegFile``) -> normalised [B,3,256,256] float32 on ``device``.  When every
+    frame is a full frame the device path takes (``jpeg_device``), they are decoded there (``decode_jpeg_batch``, bit-identical to
+    :func:`load_image_bgr`) and pre-processed by :func:`preprocess_image_device`; otherwise every frame takes the host path:
+    :func:`load_image_bgr`'s decode, then :func:`preprocess_image_device` for full frames or :func:`preprocess_image`."""
+    from .jpeg_device import JpegFile, decode_jpeg_batch
+    files = [s if isinstance(s, JpegFile) else JpegFile(s, i) for i, s in enumerate(sources)]
+    full = (4 * image_shape[0], 4 * image_shape[1] + 256)
+    if files and all(f.device and (f.H, f.W) == full for f in files):
+        return preprocess_image_device(decode_jpeg_batch(files, device), image_shape)
+    frames = [f.host_decode() for f in files]
+    if frames and all(f.shape[:2] == full for f in frames):
+        return preprocess_image_device(torch.from_numpy(np.stack(frames)).to(device), image_shape)
+    return torch.stack([preprocess_image(f, image_shape) for f in frames]).to(device)
+
+
 def normalize_u8(small_bgr_u8: np.ndarray) -> torch.Tensor:
     """[256,256,3] uint8 (BGR) -> normalised CHW float32 (reference ``demo_dataset.py:76-82``: /255, -mean, /std, ToTensor)."""
     img = small_bgr_u8.astype(np.float64) / 255.0
