@@ -423,6 +423,32 @@ int se_exr_piz_decode_f32(const void* payload, long long payload_bytes, const lo
                           const int* channel_desc, int n_files, float* out, int out_h, int out_w, float clamp,
                           void* scratch, long long scratch_bytes, int* status, void* stream);
 
+/* ZIP (16 lines per chunk), ZIPS (1 line) and uncompressed (NONE) scanline OpenEXR chunks -> float32 on the device (the same call
+ * sites; bit-identical to sceneego_amd/exr.py read_depth_exr).
+ *   chunk_desc  int64 [n_chunks][16], one row per chunk: 0 byte offset of the chunk's block (after y and size) in `payload`,
+ *               1 block bytes, 2 file index (row of channel_desc, sample of out), 3 first row (y - ymin), 4 rows, 5 stored
+ *               uncompressed (block bytes == bytes_per_line * rows, and every NONE chunk; only its first bytes_per_line * rows
+ *               bytes are read), 6-12 unused, 13 scratch offset and 14 scratch bytes (both written by se_exr_zip_scratch_bytes),
+ *               15 unused.  A chunk that is not stored holds one zlib stream (RFC 1950 / 1951).
+ *   channel_desc int32 [n_files][8]: as for se_exr_piz_decode_f32 (bytes_per_line = 2 * column 5 * width).
+ * se_exr_zip_scratch_bytes: HOST pointers; lays out the per-chunk scratch slices (fills columns 13, 14 of chunk_desc: each slice
+ *   16-byte aligned, bytes_per_line * rows bytes for a compressed chunk, none for a stored one) and returns the scratch bytes
+ *   se_exr_zip_decode_f32 needs, or SE_ERR_BAD_ARG.
+ * se_exr_zip_decode_f32: device pointers; `out` as for se_exr_piz_decode_f32 (nearest resize, clamp).  A stream is accepted exactly
+ *   when zlib.decompress accepts it and it inflates to bytes_per_line * rows bytes (exr.py would read a longer or shorter stream;
+ *   here it is a bad stream).  status int32 [n_chunks][2]: {code, bytes inflated when the decode stopped}; codes distinct from the
+ *   PIZ ones so that one status vector covers a mixed batch: 0 ok, 1 descriptor out of range, 8 bad zlib header (CM, CINFO,
+ *   FCHECK, FDICT), 9 block type 3, 10 stored block LEN != ~NLEN, 11 bad code-length set (over-subscribed, incomplete, no
+ *   end-of-block, HLIT > 286 or HDIST > 30), 12 invalid symbol or code-length repeat, 13 distance too far back, 14 stream ended
+ *   before the final block and its Adler-32, 15 decompressed size != bytes_per_line * rows, 16 Adler-32 mismatch.  A chunk with a
+ *   non-zero code writes nothing to `out`.  Kernels se_exr_zip_inflate_kernel (one wavefront per chunk), se_exr_zip_recon_kernel
+ *   (predictor, de-interleave, conversion, resize); every read stays inside payload_bytes / the chunk's block, every write inside
+ *   its scratch slice and its rows of `out`. */
+long long se_exr_zip_scratch_bytes(long long* chunk_desc, int n_chunks, const int* channel_desc, int n_files);
+int se_exr_zip_decode_f32(const void* payload, long long payload_bytes, const long long* chunk_desc, int n_chunks,
+                          const int* channel_desc, int n_files, float* out, int out_h, int out_w, float clamp,
+                          void* scratch, long long scratch_bytes, int* status, void* stream);
+
 /* Baseline JPEG frames -> uint8 B, G, R on the device (stands in for sceneego_amd/preprocess.py load_image_bgr, PIL on libjpeg-turbo;
  * bit-identical to it).  sceneego_amd/jpeg_device.py parses, validates and unstuffs on the host.
  *   img_desc  int32 [n_images][64]: 0 width, 1 height, 2 components (1 or 3), 3 MCUs per row, 4 MCU rows, 5 blocks per MCU (<= 10),

@@ -12,7 +12,8 @@ map is ``<seq>/<estimated_depth_name>/img_%06d.jpg.exr`` or ``<seq>/rendered/dep
 batches of ``config.test.batch_size`` (a partial last batch included).  A small host thread pool reads and parses the JPEGs one batch
 ahead; they are decoded on the device (``jpeg_device.decode_jpeg_batch``, bit-identical to PIL) or, with ``--image_decode host``, by
 PIL in that pool; the image path is then demo.py's (``se_preprocess_image_u8`` for 1280x1024 frames); depth maps go through
-``exr_device.decode_depth_exr_batch(..., out_hw=(1024, 1280))`` (PIZ decoded on the device) or, with ``--depth_decode host``,
+``exr_device.decode_depth_exr_batch(..., out_hw=(1024, 1280))`` (PIZ, ZIP, ZIPS and NONE decoded on the device) or, with
+``--depth_decode host``,
 through ``exr.py`` + ``prepare_depth`` - the same values either way (``TestDataset.__getitem__``: nearest resize to 1280x1024, clamp
 to 10 m).  The pickle holds the list of float32 [15, 3] predictions, as ``test.py`` writes it.
 """

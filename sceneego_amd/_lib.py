@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -88,6 +88,8 @@ SIGNATURES = {
     "se_conv3d_k3_split3_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "se_exr_piz_scratch_bytes": (_ll, [_vp, _i, _vp, _i]),
     "se_exr_piz_decode_f32": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _ll, _vp, _vp]),
+    "se_exr_zip_scratch_bytes": (_ll, [_vp, _i, _vp, _i]),
+    "se_exr_zip_decode_f32": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _ll, _vp, _vp]),
     "se_jpeg_scratch_bytes": (_ll, [_vp, _i, _vp, _i, _vp]),
     "se_jpeg_decode_bgr_u8": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _i, _vp]),
 }
@@ -271,6 +273,31 @@ def exr_piz_decode(payload_ptr, payload_bytes, desc_ptr, n_chunks, chan_ptr, n_f
     _check(load().se_exr_piz_decode_f32(_vp(payload_ptr), int(payload_bytes), _vp(desc_ptr), n_chunks, _vp(chan_ptr), n_files,
                                         _ptr(out), out.shape[1], out.shape[2], float(clamp), _ptr(scratch), scratch.numel(),
                                         _ptr(status), _stream()), "se_exr_piz_decode_f32")
+
+
+def exr_zip_scratch_bytes(chunk_desc, channel_desc) -> int:
+    """chunk_desc int64 [n, 16] and channel_desc int32 [files, 8] (HOST numpy arrays, include/sceneego_hip.h): fills the scratch
+    offset / bytes columns of chunk_desc in place and returns the scratch bytes of se_exr_zip_decode_f32."""
+    import numpy as np
+    assert chunk_desc.dtype == np.int64 and chunk_desc.flags.c_contiguous and chunk_desc.shape[1:] == (16,)
+    assert channel_desc.dtype == np.int32 and channel_desc.flags.c_contiguous and channel_desc.shape[1:] == (8,)
+    n = load().se_exr_zip_scratch_bytes(chunk_desc.ctypes.data_as(_vp), chunk_desc.shape[0], channel_desc.ctypes.data_as(_vp),
+                                        channel_desc.shape[0])
+    if n < 0:
+        raise HipExtensionError(f"se_exr_zip_scratch_bytes failed with code {n} (bad argument)")
+    return int(n)
+
+
+def exr_zip_decode(payload_ptr, payload_bytes, desc_ptr, n_chunks, chan_ptr, n_files, out, clamp, scratch, status):
+    """ZIP / ZIPS / NONE chunks -> out float32 [n_files, H_out, W_out] on the current stream.  payload_ptr / desc_ptr / chan_ptr:
+    device addresses (ints) inside a buffer the caller keeps alive; status int32 [n_chunks, 2]."""
+    require_hip(out, scratch, status)
+    _chk_f32(out)
+    assert out.dim() == 3 and out.shape[0] == n_files and status.dtype == torch.int32 and status.shape == (n_chunks, 2)
+    assert scratch.dtype == torch.uint8 and status.is_contiguous()
+    _check(load().se_exr_zip_decode_f32(_vp(payload_ptr), int(payload_bytes), _vp(desc_ptr), n_chunks, _vp(chan_ptr), n_files,
+                                        _ptr(out), out.shape[1], out.shape[2], float(clamp), _ptr(scratch), scratch.numel(),
+                                        _ptr(status), _stream()), "se_exr_zip_decode_f32")
 
 
 def jpeg_scratch_bytes(img_desc, seg_desc, layout) -> int:
