@@ -19,7 +19,7 @@
 // The LDS-tiled kernels for the 64^3/32^3 levels live in conv3d_tiled.hip.
 #include "common.h"
 
-#include "conv_common.h"
+#include "conv3d_plan.h"
 #include "wino47_matrices.h"
 #include "wino67_matrices.h"
 
@@ -1081,53 +1081,39 @@ int launch_direct(const ConvArgs& a, hipStream_t s) {
 
 extern "C" int se_abi_version(void) { return 25; }
 
-// Mirrors the dispatch of se_conv3d_f32 -> se_conv3d_tiled_try -> se_conv3d_wino_try / se_conv3d_k7_wino_try for the
-// default channels-last call (no SE_EPI_OUT_PLANAR / SE_EPI_RES_POST_RELU flags).
+// Which family of kernels a default channels-last call (no SE_EPI_OUT_PLANAR / SE_EPI_RES_POST_RELU, cin_pad == cin) of this shape
+// belongs to: 2 = 2-D Winograd, 1 = 1-D Winograd F(4,3), 7 = Winograd 7^3, 0 = none of them.  The shape predicates are the plan's.
 extern "C" int se_conv3d_f32_algo(int dim, int cin, int cout, int ksize) {
     if (ksize == 3 && se_wino2d_shape_ok(dim, cin, cout)) return 2;
-    if (ksize == 3 && dim >= 16 && (dim & 7) == 0 && (cout & 31) == 0 && (cin & 15) == 0) return 1;
-    if (ksize == 7 && dim >= 16 && (dim & 7) == 0 && cout == 16) return 7;
+    if (ksize == 3 && se_wino1d_shape_ok(dim, cin, cout)) return 1;
+    if (ksize == 7 && se_k7_wino_shape_ok(dim, cout)) return 7;
     return 0;
 }
 
+// flags that ask for one of the forms only the 2-D Winograd kernels have: octet- / quad-planar tensors, the fused skip convolution
+constexpr int SE_FORM_FLAGS = SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS | SE_EPI_SKIPCONV16;
+// a 2-D Winograd shape that is left to the in-workgroup split-K kernel of the small levels (conv_common.h: se_conv3d_small_volume)
+static bool small_plain_call(int batch, int dim, int flags) { return !(flags & SE_FORM_FLAGS) && se_conv3d_small_volume(batch, dim); }
+
 // Which kernel a launch of `batch` samples with these layout flags (SE_IN_OCTET ...) runs on: se_conv3d_f32_algo's value, except
 //   3 = the F(4,3) x F(4,3) ping-pong kernel (conv3d_wino44pp.hip; a member of the 2-D Winograd family: same layouts, flags and fused
-//       forms as algo 2) - it declines a channels-last input with >= 32 channels, which stays on algo 2 (se_conv3d_wino44pp_takes);
+//       forms as algo 2) - it declines a channels-last input with >= 32 channels, which stays on algo 2 (se_conv3d_wino44pp_layout_ok);
 //   0 for a 2-D Winograd shape with <= 4096 voxels in the batch when the call asks for no octet-planar / pooled / fused form.
-// Mirrors se_conv3d_tiled_try / se_conv3d_wino2d_try for the WHOLE batch (a batch above 32 is cut into slices that keep this decision).
-bool se_conv3d_wino44pp_shape(int batch, int dim, int cout);      // conv3d_wino44pp.hip
-bool se_conv3d_wino44pp_layout_ok(int cin, int flags);
+// Computed from the predicates of se_conv3d_plan, for the call this signature can describe: cin_pad == cin, no second output, and
+// of the flags only the SE_FORM_FLAGS are looked at.  The plan sees more, and where it does this answer is the LESS strict one: with
+// cin_pad != cin, SE_EPI_RES_POST_RELU or SE_EPI_OUT_PLANAR no 2-D Winograd kernel runs (the call goes to the 1-D / tiled / direct
+// kernels, or is SE_ERR_BAD_ARG if it asks for a planar form), yet 2 or 3 is returned here; and a pooled output keeps a small volume
+// on the 2-D kernel where 0 is returned here.  V2VProgram asks with cin_pad == cin and none of those flags, where both agree.
 extern "C" int se_conv3d_f32_variant(int batch, int dim, int cin, int cout, int ksize, int flags) {
     const int algo = se_conv3d_f32_algo(dim, cin, cout, ksize);
-    const bool forms = flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS | SE_EPI_SKIPCONV16);
-    if (algo == 2 && !forms && se_conv3d_small_volume(batch, dim)) return 0;       // a plain channels-last call runs the in-workgroup split-K form
+    if (algo == 2 && small_plain_call(batch, dim, flags)) return 0;
     if (algo == 2 && g_variant != 64 && se_conv3d_wino44pp_shape(batch, dim, cout) && se_conv3d_wino44pp_layout_ok(cin, flags)) return 3;
     return algo;
 }
 
-static long long packed_elems_a(int cout, int cin_pad, int ksize, int transposed) {
-    const long long taps = transposed ? 8 : (long long)ksize * ksize * ksize;
-    return taps * (cin_pad / 16) * (round_up16(cout) / 16) * 256;
-}
-
 extern "C" long long se_conv3d_packed_elems(int cout, int cin_pad, int ksize, int transposed) {
-    long long n = packed_elems_a(cout, cin_pad, ksize, transposed);
-    if (!transposed && ksize == 7) n += (long long)(cin_pad / 4) * SE_K7_GROUPS * (round_up16(cout) / 16) * 256;
-    if (!transposed && ksize == 7 && cout <= 16) n += (long long)(cin_pad / 4) * SE_K7W_CHUNK_FLOATS;
-    if (!transposed && ksize == 7 && cout <= 16) n += (long long)((cin_pad + 2) / 3) * (SE_K7F_CHUNK_FLOATS + SE_K7H_CHUNK_FLOATS);     // sections F, H (last)
-    if (!transposed && ksize == 3 && cout % 32 == 0)
-        n += (long long)(cin_pad / 16) * (cout / 32) * (SE_WINO_CHUNK_FLOATS + SE_WINO43_CHUNK_FLOATS);
-    if (!transposed && ksize == 3 && cout % 32 == 0) n += (long long)(cin_pad / 8) * (cout / 32) * SE_WINO2D_CHUNK_FLOATS;   // section G
-    if (!transposed && ksize == 3 && cout % 32 == 0) n += (long long)(cin_pad / 4) * (cout / 32) * SE_WINO44_CHUNK_FLOATS;   // section I (last)
-    return n;
+    return se_conv3d_pack_layout(cout, cin_pad, ksize, transposed).total;
 }
-
-// conv3d_wino2d.hip
-int se_conv3d_pack_wino2d(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin,
-                          int cin_pad, hipStream_t s);
-// conv3d_wino44.hip
-int se_conv3d_pack_wino44(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin,
-                          int cin_pad, hipStream_t s);
 
 extern "C" int se_conv3d_pack_f32(const float* w, const float* b, const float* gamma, const float* beta,
                                   const float* mean, const float* var, float eps, float* wpack, float* bpack,
@@ -1138,38 +1124,206 @@ extern "C" int se_conv3d_pack_f32(const float* w, const float* b, const float* g
         (gamma != nullptr) != (var != nullptr))
         return SE_ERR_BAD_ARG;
     const int taps = ksize * ksize * ksize;
-    const long long total = se_conv3d_packed_elems(cout, cin_pad, ksize, transposed);
-    const long long total_a = packed_elems_a(cout, cin_pad, ksize, transposed);
-    const long long threads = total > round_up16(cout) ? total : round_up16(cout);
-    long long total_main = total;
-    if (!transposed && ksize == 7 && cout <= 16) total_main -= (long long)((cin_pad + 2) / 3) * (SE_K7F_CHUNK_FLOATS + SE_K7H_CHUNK_FLOATS);
-    const long long n_g = (!transposed && ksize == 3 && cout % 32 == 0) ? (long long)(cin_pad / 8) * (cout / 32) * SE_WINO2D_CHUNK_FLOATS : 0;
-    const long long n_i = n_g ? (long long)(cin_pad / 4) * (cout / 32) * SE_WINO44_CHUNK_FLOATS : 0;
-    total_main -= n_g + n_i;
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, se_stream(stream), w, b,
-                       gamma, beta, mean, var, eps, wpack, bpack, cout, cin, cin_pad, taps, transposed, total_a, total_main);
+    const SePackLayout l = se_conv3d_pack_layout(cout, cin_pad, ksize, transposed);
+    hipStream_t s = se_stream(stream);
+    // pack_kernel: bpack and the sections in front of the first one that has a packer of its own - A, then B D (k = 7) or C E (k = 3)
+    const long long n_main = l.f >= 0 ? l.f : l.g >= 0 ? l.g : l.total;
+    const long long threads = l.total > round_up16(cout) ? l.total : round_up16(cout);
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, w, b, gamma, beta, mean, var, eps, wpack,
+                       bpack, cout, cin, cin_pad, taps, transposed, l.b >= 0 ? l.b : l.c >= 0 ? l.c : l.total, n_main);
     SE_CHECK_LAUNCH();
-    if (n_g) {
-        const int rc = se_conv3d_pack_wino2d(w, gamma, var, eps, wpack + total_main, cout, cin, cin_pad, se_stream(stream));
+    if (l.g >= 0) {
+        const int rc = se_conv3d_pack_wino2d(w, gamma, var, eps, wpack + l.g, cout, cin, cin_pad, l.i - l.g, s);
         if (rc) return rc;
-        return se_conv3d_pack_wino44(w, gamma, var, eps, wpack + total_main + n_g, cout, cin, cin_pad, se_stream(stream));
+        return se_conv3d_pack_wino44(w, gamma, var, eps, wpack + l.i, cout, cin, cin_pad, l.total - l.i, s);
     }
-    if (total_main != total) {
-        const long long nf = (long long)((cin_pad + 2) / 3) * SE_K7F_CHUNK_FLOATS, nh = total - total_main - nf;
-        hipLaunchKernelGGL(pack_k7f_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, se_stream(stream), w, gamma, var, eps,
-                           wpack + total_main, cout, cin, nf);
+    if (l.f >= 0) {
+        const long long nf = l.h - l.f, nh = l.total - l.h;
+        hipLaunchKernelGGL(pack_k7f_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, w, gamma, var, eps, wpack + l.f, cout, cin, nf);
         SE_CHECK_LAUNCH();
-        hipLaunchKernelGGL(pack_k7h_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, se_stream(stream), w, gamma, var, eps,
-                           wpack + total_main + nf, cout, cin, nh);
+        hipLaunchKernelGGL(pack_k7h_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, w, gamma, var, eps, wpack + l.h, cout, cin, nh);
         SE_CHECK_LAUNCH();
     }
     return 0;
 }
 
-// implemented in conv3d_tiled.hip; returns 1 if it took the launch, 0 if the shape is not covered, <0 / hipError on failure
-int se_conv3d_tiled_try(const ConvArgs& a, int batch, int ksize, hipStream_t s);
+#ifndef SE_HALO64
+#define SE_HALO64 1
+#endif
 
-#define g_variant_direct (g_variant == 18 ? 1 : g_variant == 19 ? 2 : 0)   // se_debug_set_variant(18): A/B, grid-level split-K for every small level; (19): in-workgroup split-K for every small level
+// The plan of one call.  Order of preference: the 2-D Winograd kernels, the 1-D Winograd kernel, the LDS-tiled direct kernels (these
+// run in slices of the batch), then the kernels of the small levels and the direct kernel (whole batch).  A call that asks for a
+// tensor layout or fused output which the kernel its shape and flags lead to does not have is an error: no other kernel would read
+// or write those tensors the way the caller laid them out.
+SeConvPlan se_conv3d_plan(const ConvArgs& a, int batch, int ksize) {
+    const int dim = a.dim, flags = a.flags, cus = se_num_cus();
+    SeConvPlan p = {SE_CONV_DIRECT, ksize, batch, 1, 0, 0};
+    // samples per launch of the sliced kernels.  Unit-table budget: the smallest table among the persistent kernels holds ~430 entries
+    // per workgroup; at most 32 samples (weak-scaling config 4 runs 32 samples per GPU, i.e. exactly one slice)
+    const long long t8 = dim / 8;
+    const long long units_per_sample = ksize == 7 ? t8 * t8 * t8 : (long long)(a.cout >= 32 ? a.cout / 32 : 1) * (dim / 4) * t8 * t8;
+    const long long budget = units_per_sample > 0 ? 400LL * cus / units_per_sample : 32;
+    const int slice = (int)(budget < 1 ? 1 : budget > 32 ? 32 : budget);
+    const int n = batch < slice ? batch : slice, tail = batch % n;   // every launch has n samples, the last one `tail` if that is not 0
+    const auto sliced = [&p, n](int kernel, int form) {
+        p.kernel = kernel, p.form = form, p.slice = n;
+        if (form < 0) p.error = SE_ERR_BAD_ARG;
+        return p;
+    };
+    const auto bad_arg = [&p] { p.error = SE_ERR_BAD_ARG; return p; };
+    const auto fits = [n, tail](auto&& pred) { return pred(n) && (!tail || pred(tail)); };
+
+    const bool forms = (flags & SE_FORM_FLAGS) || a.pool_out || a.skip_w;
+    const bool plain_epilogue = !(flags & (SE_EPI_RES_POST_RELU | SE_EPI_OUT_PLANAR));
+    const bool in_2d = ksize == 3 && a.wpack_g && a.cin_pad == a.cin && se_wino2d_shape_ok(dim, a.cin, a.cout) && plain_epilogue;
+    const bool in_1d = ksize == 3 && a.wpack_b && a.wpack_e && a.cin_pad == a.cin && se_wino1d_shape_ok(dim, a.cin, a.cout) && plain_epilogue &&
+                       !(flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS));
+    const bool in_tiled = dim >= 16 && (dim & 7) == 0 && (a.cout & 15) == 0 && (ksize == 3 || (ksize == 7 && a.nts == 1));
+    const bool in_k7w = ksize == 7 && a.wpack_d && a.wpack_f && se_k7_wino_shape_ok(dim, a.cout) && !a.res && !(flags & SE_EPI_OUT_PLANAR);
+    const bool fits_2d = fits([&](int nb) { return se_conv3d_wino2d_fits(nb, dim, a.cout); });
+    const bool fits_1d = in_1d && fits([&](int nb) { return se_conv3d_wino1d_fits(SE_CONV_WINO43PP_1D, nb, dim, a.cout, cus); });
+
+    // what is tried at all: everything, unless a development build's A/B selection says otherwise
+    bool small_to_splitk = true, try_2d = true, try_44pp = true, try_1d = true, try_k7w = true, try_67 = true, try_wavesplit = true;
+    long long wavesplit_min_vox = 2048;
+#ifdef SE_DEVTOOLS
+    // se_debug_set_variant(g): which families g switches off, and the retired kernels and experiments it names (each where the
+    // production order would reach it).  The only place of the plan that knows about variants; g = 0 is the production plan.
+    if (const int g = g_variant) {
+        small_to_splitk = false;
+        try_2d = g >= 40 && g < 70, try_44pp = g == 40;                         // 64: the 2-D family stays on F(4,3) x F(2,3)
+        try_1d = g == 4 || g == 30 || (g >= 10 && g < 20);                      // 30: 1-D instead of 2-D
+        try_k7w = g >= 10, try_67 = g != 47;                                    // 47: F(4,7) instead of F(6,7)
+        try_wavesplit = g != 18, wavesplit_min_vox = g == 19 ? 0 : 2048;        // 18 / 19: grid / in-workgroup split-K for every small level
+        const bool past_2d = !(try_2d && in_2d && fits_2d) && !forms, past_1d = past_2d && !(try_1d && fits_1d);
+        if (try_2d && in_2d && g == 63 && se_conv3d_wino44_takes(a))
+            return sliced(SE_CONV_DEV_WINO44, 0);
+        if (try_2d && in_2d && fits_2d && g >= 41) {                            // 41 - 61: experiments of the F(4,3) x F(2,3) kernel, which exist
+            const int octets = ((flags & SE_IN_OCTET) ? 1 : 0) | ((flags & SE_OUT_OCTET) ? 2 : 0) | ((flags & SE_RES_OCTET) && a.res ? 4 : 0);
+            const bool quad_ok = !(flags & SE_LAYOUT_QUAD_BITS) || se_conv3d_wino2d_form(a) >= 0;   // for forms 0 and 3 (and run AS those)
+            if (quad_ok && (octets == 0 || octets == 3)) {
+                p.exp = g;
+                return sliced(SE_CONV_WINO2D, octets);
+            }
+        }
+        if (past_2d && in_1d && g == 4 && fits([&](int nb) { return se_conv3d_wino1d_fits(SE_CONV_DEV_WINO23_1D, nb, dim, a.cout, cus); }))
+            return sliced(SE_CONV_DEV_WINO23_1D, 0);
+        if (past_2d && in_1d && g == 19 && fits([&](int nb) { return se_conv3d_wino1d_fits(SE_CONV_DEV_WINO43_1D, nb, dim, a.cout, cus); }))
+            return sliced(SE_CONV_DEV_WINO43_1D, 0);
+        if (past_1d && in_tiled && ksize == 3 && g >= 21 && g <= 23 && a.nts % 2 == 0 && dim % 16 == 0)
+            return sliced(SE_CONV_DEV_TILED_K3_TZ, 4 << (g - 21));
+        if (past_1d && in_tiled && ksize == 3 && (g == 2 || g == 3) && a.cout == 32 && dim >= 32 && (a.cin == 16 || a.cin == 32) && a.cin_pad == a.cin && plain_epilogue)
+            return sliced(SE_CONV_DEV_K3_C32_PERSISTENT, a.cin / 16 | (g == 3 ? 4 : 0));
+        if (!forms && in_tiled && try_k7w && in_k7w && (g == 17 || g == 19)) {
+            if (flags & SE_IN_PLANAR3) return bad_arg();                        // only the F(4,7) / F(6,7) kernels read the triplet-planar layout
+            const int k = g == 17 ? SE_CONV_DEV_K7_WINO27 : SE_CONV_DEV_K7_WINO27PP;
+            if (fits([&](int nb) { return se_conv3d_wino1d_fits(k, nb, dim, a.cout, cus); })) return sliced(k, 0);
+            try_k7w = false;
+        }
+        if (!forms && in_tiled && ksize == 7 && g == 2 && !(flags & SE_IN_PLANAR3) && dim >= 32 && a.cout == 16 && !a.res && !(flags & SE_EPI_OUT_PLANAR))
+            return sliced(SE_CONV_DEV_K7_PERSISTENT, 0);
+    }
+#endif
+
+    // tiny volumes of 2-D Winograd shapes (16^3 at batch 1: 32 work units for 256 CUs): a plain channels-last call is left to the
+    // in-workgroup split-K kernel of the 8^3 level (47 against 92 us per 128 -> 128 launch); a caller that asks for an octet-planar /
+    // pooled / fused-skip form gets the 2-D kernel
+    const bool to_small_levels = small_to_splitk && in_2d && !forms && small_plain_call(batch, dim, flags);
+    if (!to_small_levels) {
+        if (try_2d && in_2d) {
+            // the 64^3 / 32^3 levels run on the F(4,3) x F(4,3) ping-pong kernel (1/4 of the direct MFMAs; the F(4,3) x F(2,3) kernel: 1/3)
+            if (try_44pp && a.wpack_i && se_conv3d_wino44pp_layout_ok(a.cin, flags) && se_conv3d_wino44pp_shape(batch, dim, a.cout) &&
+                fits([&](int nb) { return se_conv3d_wino44pp_fits(nb, dim, a.cout); }))
+                return sliced(SE_CONV_WINO44PP, se_conv3d_wino44pp_form(a));
+            if (fits_2d) return sliced(SE_CONV_WINO2D, se_conv3d_wino2d_form(a));
+        }
+        if (forms) return bad_arg();
+        if (try_1d && fits_1d) return sliced(SE_CONV_WINO43PP_1D, 0);
+        if (in_tiled && ksize == 3) return sliced(SE_CONV_TILED_K3, a.nts % 4 == 0 ? 4 : a.nts % 2 == 0 ? 2 : 1);
+        if (in_tiled) {   // 7^3 with 16 output channels
+            const bool p3 = flags & SE_IN_PLANAR3;
+            if (try_k7w && in_k7w) {
+                if (try_67 && a.wpack_h && (dim & 15) == 0 && fits([&](int nb) { return se_conv3d_k7_wino67_fits(a, nb, cus); }))
+                    return sliced(SE_CONV_K7_WINO67, 0);
+                if (fits([&](int nb) { return se_conv3d_k7_wino47_fits(nb, dim, cus); }))
+                    return sliced(p3 ? SE_CONV_K7_WINO47_P3 : SE_CONV_K7_WINO47_CL, 0);
+            }
+            if (p3) return bad_arg();
+            return sliced(SE_CONV_TILED_K7, 0);
+        }
+    }
+
+    // the small levels, odd volumes and the planar 15-channel output layer: channels-last input, whole batch in one launch
+    if (flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS | SE_IN_PLANAR3)) return bad_arg();
+    const bool cout_pairs = ksize == 3 && !(flags & SE_EPI_OUT_PLANAR) && a.nts % 2 == 0;   // these kernels own two cout tiles per workgroup
+    if (cout_pairs && try_wavesplit && a.total_vox <= 8192 && a.total_vox * a.cin_pad * 4LL < (1LL << 31) && a.total_vox >= wavesplit_min_vox) {
+        // 8^3-sized levels: in-workgroup split-K, single launch (0.063 vs 0.077 ms for grid split-K + reduce at B = 8)
+        if (SE_HALO64 && a.total_vox >= 2048 && (dim == 8 || dim == 16) && (a.cin & 31) == 0) p.kernel = SE_CONV_HALO64, p.form = dim;
+        else p.kernel = SE_CONV_WAVESPLIT, p.form = a.total_vox >= 2048 ? 4 : a.total_vox >= 256 ? 8 : 16;
+        return p;
+    }
+    if (cout_pairs && a.ws) {
+        // small volumes with wide channels: split the taps over grid.z when the plain launch would not fill the chip
+        const long long wgs = (a.total_vox + 63) / 64 * (a.nts / 2);
+        int splits = 27;                                  // taps per split: 1, 3, 9 (or no split)
+        while (splits > 1 && (wgs * (splits / 3) >= 2048 || (long long)splits * a.total_vox * a.cout > a.ws_elems)) splits /= 3;
+        if (wgs < 1024 && splits > 1) p.kernel = SE_CONV_SPLITK_GRID, p.splits = splits;
+    }
+    return p;
+}
+
+// One launch of the planned kernel on `batch` samples (a slice of the call, or all of it).
+static int launch_planned(const SeConvPlan& p, const ConvArgs& a, int batch, hipStream_t s) {
+    const long long tiles = (a.total_vox + 15) / 16;
+    switch (p.kernel) {
+        case SE_CONV_WINO44PP: return se_conv3d_wino44pp_launch(a, batch, p.form, s);
+        case SE_CONV_WINO2D: return se_conv3d_wino2d_launch(a, batch, p.form, p.exp, s);
+        case SE_CONV_K7_WINO67:
+        case SE_CONV_K7_WINO47_P3:
+        case SE_CONV_K7_WINO47_CL: return se_conv3d_k7_wino_launch(a, batch, p.kernel, s);
+        case SE_CONV_WINO43PP_1D: return se_conv3d_wino1d_launch(a, batch, p.kernel, s);
+        case SE_CONV_TILED_K3:
+        case SE_CONV_TILED_K7: return se_conv3d_tiled_launch(a, batch, p.kernel, p.form, s);
+        case SE_CONV_HALO64: {   // 64-voxel tiles, activations through LDS
+            const dim3 grid((unsigned)(a.total_vox / 64), a.nts / 2);
+            if (p.form == 8) {
+                SE_ENSURE_LDS(conv3d_k3_halo64_kernel<8>, Halo64<8>::LDS_BYTES);
+                hipLaunchKernelGGL((conv3d_k3_halo64_kernel<8>), grid, dim3(512), Halo64<8>::LDS_BYTES, s, a);
+            } else {
+                SE_ENSURE_LDS(conv3d_k3_halo64_kernel<16>, Halo64<16>::LDS_BYTES);
+                hipLaunchKernelGGL((conv3d_k3_halo64_kernel<16>), grid, dim3(512), Halo64<16>::LDS_BYTES, s, a);
+            }
+            break;
+        }
+        case SE_CONV_WAVESPLIT:
+            if (p.form == 4) hipLaunchKernelGGL((conv3d_k3_wavesplit_kernel<2, 4>), dim3((unsigned)((tiles + 1) / 2), a.nts / 2), dim3(256), 0, s, a);
+            else if (p.form == 8) hipLaunchKernelGGL((conv3d_k3_wavesplit_kernel<1, 8>), dim3((unsigned)tiles, a.nts / 2), dim3(512), 0, s, a);
+            else hipLaunchKernelGGL((conv3d_k3_wavesplit_kernel<1, 16>), dim3((unsigned)tiles, a.nts / 2), dim3(1024), 0, s, a);
+            break;
+        case SE_CONV_SPLITK_GRID: {
+            hipLaunchKernelGGL((conv3d_k3_splitk_kernel<2>), dim3((unsigned)((a.total_vox + 63) / 64), a.nts / 2, p.splits), dim3(256), 0, s, a, a.ws,
+                               27 / p.splits);
+            SE_CHECK_LAUNCH();
+            const long long threads = a.total_vox * (a.cout / 4);
+            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a, a.ws, p.splits);
+            break;
+        }
+        case SE_CONV_DIRECT: return p.form == 1 ? launch_direct<1>(a, s) : p.form == 3 ? launch_direct<3>(a, s) : launch_direct<7>(a, s);
+#ifdef SE_DEVTOOLS
+        case SE_CONV_DEV_WINO44: return se_conv3d_wino44_launch(a, batch, s);
+        case SE_CONV_DEV_WINO23_1D:
+        case SE_CONV_DEV_WINO43_1D: return se_conv3d_wino1d_launch(a, batch, p.kernel, s);
+        case SE_CONV_DEV_K7_WINO27:
+        case SE_CONV_DEV_K7_WINO27PP: return se_conv3d_k7_wino_launch(a, batch, p.kernel, s);
+        case SE_CONV_DEV_TILED_K3_TZ:
+        case SE_CONV_DEV_K3_C32_PERSISTENT:
+        case SE_CONV_DEV_K7_PERSISTENT: return se_conv3d_tiled_launch(a, batch, p.kernel, p.form, s);
+#endif
+        default: return SE_ERR_BAD_ARG;
+    }
+    SE_CHECK_LAUNCH();
+    return 0;
+}
 
 static int conv3d_f32_impl(const float* in, const float* wpack, const float* bpack, const float* residual, float* out,
                            float* pool_out, const float* skip_w, int batch, int dim, int cin, int cin_pad, int cout, int ksize, int flags,
@@ -1180,95 +1334,47 @@ static int conv3d_f32_impl(const float* in, const float* wpack, const float* bpa
     if (!planar && (cout & 15)) return SE_ERR_BAD_ARG;
     if (planar && (flags & (SE_EPI_RES_PRE_RELU | SE_EPI_RES_POST_RELU))) return SE_ERR_BAD_ARG;
     if ((flags & SE_EPI_RES_PRE_RELU) && (flags & SE_EPI_RES_POST_RELU)) return SE_ERR_BAD_ARG;
-    hipStream_t s = se_stream(stream);
-    ConvArgs a;
-    a.in = in; a.wpack = wpack; a.bpack = bpack; a.res = residual; a.out = out;
-    a.total_vox = (long long)batch * dim * dim * dim;
-    a.dim = dim; a.cin = cin; a.cin_pad = cin_pad; a.cout = cout; a.nts = round_up16(cout) / 16; a.flags = flags;
-    a.wpack_b = wpack + packed_elems_a(cout, cin_pad, ksize, 0);
-    a.wpack_d = nullptr;
-    if (ksize == 7 && cout <= 16)
-        a.wpack_d = a.wpack_b + (long long)(cin_pad / 4) * SE_K7_GROUPS * (round_up16(cout) / 16) * 256;
-    a.wpack_f = nullptr;
-    if (ksize == 7 && cout <= 16) a.wpack_f = a.wpack_d + (long long)(cin_pad / 4) * SE_K7W_CHUNK_FLOATS;
-    a.wpack_h = nullptr;
-    if (ksize == 7 && cout <= 16) a.wpack_h = a.wpack_f + (long long)((cin_pad + 2) / 3) * SE_K7F_CHUNK_FLOATS;
-    a.wpack_e = nullptr;
-    if (ksize == 3 && cout % 32 == 0) a.wpack_e = a.wpack_b + (long long)(cin_pad / 16) * (cout / 32) * SE_WINO_CHUNK_FLOATS;
-    a.wpack_g = nullptr;
-    if (ksize == 3 && cout % 32 == 0) a.wpack_g = a.wpack_e + (long long)(cin_pad / 16) * (cout / 32) * SE_WINO43_CHUNK_FLOATS;
-    a.wpack_i = nullptr;
-    if (ksize == 3 && cout % 32 == 0) a.wpack_i = a.wpack_g + (long long)(cin_pad / 8) * (cout / 32) * SE_WINO2D_CHUNK_FLOATS;
-    a.pool_out = pool_out;
-    a.skip_w = skip_w;
-    a.ws = workspace;
-    a.ws_elems = workspace ? workspace_elems : 0;
+    const int algo = se_conv3d_f32_algo(dim, cin, cout, ksize);
     if (!skip_w && (flags & SE_EPI_SKIPCONV16)) return SE_ERR_BAD_ARG;
-    if (skip_w && (!residual || se_conv3d_f32_algo(dim, cin, cout, ksize) != 2 || cin_pad != cin)) return SE_ERR_BAD_ARG;
-    if (pool_out && ((dim & 1) || se_conv3d_f32_algo(dim, cin, cout, ksize) != 2 || cin_pad != cin)) return SE_ERR_BAD_ARG;   // only the 2-D Winograd kernel pools
-    if (ksize == 3 && (cout % 32)) a.wpack_b = nullptr;
-    if (ksize == 1) a.wpack_b = nullptr;
+    if (skip_w && (!residual || algo != 2 || cin_pad != cin)) return SE_ERR_BAD_ARG;
+    if (pool_out && ((dim & 1) || algo != 2 || cin_pad != cin)) return SE_ERR_BAD_ARG;   // only the 2-D Winograd kernels pool
     if ((flags & SE_IN_PLANAR3) && ksize != 7) return SE_ERR_BAD_ARG;
-    if ((flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS)) && se_conv3d_f32_algo(dim, cin, cout, ksize) != 2) return SE_ERR_BAD_ARG;
+    if ((flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS)) && algo != 2) return SE_ERR_BAD_ARG;
     if ((flags & SE_LAYOUT_OCTET_BITS) && (flags & SE_LAYOUT_QUAD_BITS)) return SE_ERR_BAD_ARG;
     // quad-planar tensors exist in the F(4,3) x F(4,3) kernel only - and as the OUTPUT of a channels-last launch of the F(4,3) x F(2,3) one
     if ((flags & SE_LAYOUT_QUAD_BITS) && se_conv3d_f32_variant(batch, dim, cin, cout, ksize, flags) != 3 &&
         (flags & SE_LAYOUT_QUAD_BITS) != SE_OUT_QUAD)
         return SE_ERR_BAD_ARG;
-    const int took = se_conv3d_tiled_try(a, batch, ksize, s);
-    if (took != SE_TILED_NOT_TAKEN) return took;
-    if (flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS)) return SE_ERR_BAD_ARG;   // only the 2-D Winograd kernels know the planar forms
-    if (flags & SE_IN_PLANAR3) return SE_ERR_BAD_ARG;
-    // small volumes with wide channels: split the taps over grid.z when the plain launch would not fill the chip
-    if (ksize == 3 && !planar && a.nts % 2 == 0 && a.total_vox <= 8192 && (a.total_vox * cin_pad * 4LL) < (1LL << 31) && g_variant_direct != 1 &&
-        (a.total_vox >= 2048 || g_variant_direct == 2)) {
-        // 8^3-sized levels: in-workgroup split-K, single launch (round 2: 0.063 vs 0.077 ms for grid split-K + reduce at B = 8)
-        const long long tiles = (a.total_vox + 15) / 16;
-#ifndef SE_HALO64
-#define SE_HALO64 1
-#endif
-        if (SE_HALO64 && a.total_vox >= 2048 && (dim == 8 || dim == 16) && (a.cin & 31) == 0 && !(flags & SE_EPI_OUT_PLANAR)) {   // 64-voxel tiles, activations through LDS
-            const dim3 grid((unsigned)(a.total_vox / 64), a.nts / 2);
-            if (dim == 8) {
-                SE_ENSURE_LDS(conv3d_k3_halo64_kernel<8>, Halo64<8>::LDS_BYTES);
-                hipLaunchKernelGGL((conv3d_k3_halo64_kernel<8>), grid, dim3(512), Halo64<8>::LDS_BYTES, s, a);
-            } else {
-                SE_ENSURE_LDS(conv3d_k3_halo64_kernel<16>, Halo64<16>::LDS_BYTES);
-                hipLaunchKernelGGL((conv3d_k3_halo64_kernel<16>), grid, dim3(512), Halo64<16>::LDS_BYTES, s, a);
-            }
-        } else if (a.total_vox >= 2048)
-            hipLaunchKernelGGL((conv3d_k3_wavesplit_kernel<2, 4>), dim3((unsigned)((tiles + 1) / 2), a.nts / 2), dim3(256), 0, s, a);
-        else if (a.total_vox >= 256)
-            hipLaunchKernelGGL((conv3d_k3_wavesplit_kernel<1, 8>), dim3((unsigned)tiles, a.nts / 2), dim3(512), 0, s, a);
-        else
-            hipLaunchKernelGGL((conv3d_k3_wavesplit_kernel<1, 16>), dim3((unsigned)tiles, a.nts / 2), dim3(1024), 0, s, a);
-        SE_CHECK_LAUNCH();
-        return 0;
+    const long long vox = (long long)dim * dim * dim;
+    const SePackLayout l = se_conv3d_pack_layout(cout, cin_pad, ksize, 0);
+    const auto section = [wpack](long long at) { return at >= 0 ? wpack + at : nullptr; };
+    ConvArgs a;
+    a.in = in; a.wpack = wpack; a.bpack = bpack; a.res = residual; a.out = out;
+    a.wpack_b = section(ksize == 7 ? l.b : l.c);
+    a.wpack_d = section(l.d); a.wpack_e = section(l.e); a.wpack_f = section(l.f);
+    a.wpack_g = section(l.g); a.wpack_h = section(l.h); a.wpack_i = section(l.i);
+    a.total_vox = batch * vox;
+    a.dim = dim; a.cin = cin; a.cin_pad = cin_pad; a.cout = cout; a.nts = round_up16(cout) / 16; a.flags = flags;
+    a.pool_out = pool_out;
+    a.skip_w = skip_w;
+    a.ws = workspace;
+    a.ws_elems = workspace ? workspace_elems : 0;
+    const SeConvPlan p = se_conv3d_plan(a, batch, ksize);
+    if (p.error) return p.error;
+    hipStream_t s = se_stream(stream);
+    for (int b0 = 0; b0 < batch; b0 += p.slice) {
+        const int nb = batch - b0 < p.slice ? batch - b0 : p.slice;
+        ConvArgs sl = a;
+        // floats per voxel of the input: channels-last record, or 3 x ceil(cin/3) planes for the triplet-planar 7^3 input
+        sl.in = a.in + b0 * vox * ((flags & SE_IN_PLANAR3) ? (cin + 2) / 3 * 3 : cin_pad);
+        sl.out = a.out + b0 * vox * cout;
+        if (a.res) sl.res = a.res + b0 * vox * ((flags & SE_EPI_SKIPCONV16) ? 16 : cout);
+        if (a.pool_out) sl.pool_out = a.pool_out + b0 * (vox / 8) * cout;
+        sl.total_vox = nb * vox;
+        const int rc = launch_planned(p, sl, nb, s);
+        if (rc) return rc;
     }
-    if (ksize == 3 && !planar && workspace && a.nts % 2 == 0) {
-        const long long m_blocks = (a.total_vox + 63) / 64;
-        const long long wgs = m_blocks * (a.nts / 2);
-        if (wgs < 1024) {
-            int splits = 27;                                  // taps per split: 1, 3, 9 (or no split)
-            while (splits > 1 && (wgs * (splits / 3) >= 2048 || (long long)splits * a.total_vox * cout > workspace_elems))
-                splits /= 3;
-            if (splits > 1) {
-                hipLaunchKernelGGL((conv3d_k3_splitk_kernel<2>), dim3((unsigned)m_blocks, a.nts / 2, splits), dim3(256), 0, s,
-                                   a, workspace, 27 / splits);
-                SE_CHECK_LAUNCH();
-                const long long threads = a.total_vox * (cout / 4);
-                hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a,
-                                   workspace, splits);
-                SE_CHECK_LAUNCH();
-                return 0;
-            }
-        }
-    }
-    switch (ksize) {
-        case 1: return launch_direct<1>(a, s);
-        case 3: return launch_direct<3>(a, s);
-        default: return launch_direct<7>(a, s);
-    }
+    return 0;
 }
 
 extern "C" int se_conv3d_f32(const float* in, const float* wpack, const float* bpack, const float* residual,

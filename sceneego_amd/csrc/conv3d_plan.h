@@ -1,0 +1,77 @@
+// Which kernel a float32 3D convolution call (se_conv3d_f32 / _pool_f32 / _skip16_f32) runs on: decided ONCE per call, on the whole
+// batch, before anything is launched (se_conv3d_plan, conv3d.hip).  Every kernel file exports what the plan needs to know about its
+// kernel - a `_fits` predicate next to the constants that bound its unit table, a `_form` function next to the list of template
+// instances - and a `_launch` function whose preconditions the plan has checked.
+#pragma once
+#include "conv_common.h"
+
+enum SeConvKernel {
+    SE_CONV_WINO44PP,        // 2-D Winograd F(4,3) x F(4,3), ping-pong (conv3d_wino44pp.hip); form: L of conv3d_k3_wino44pp_kernel<L>
+    SE_CONV_WINO2D,          // 2-D Winograd F(4,3) x F(2,3) (conv3d_wino2d.hip); form: L of conv3d_k3_wino2d_kernel<E, L>
+    SE_CONV_WINO43PP_1D,     // 1-D Winograd F(4,3), ping-pong (conv3d_wino.hip)
+    SE_CONV_K7_WINO67,       // 7^3: 1-D Winograd F(6,7) (conv3d_wino67.hip), either input layout
+    SE_CONV_K7_WINO47_P3,    // 7^3: 1-D Winograd F(4,7), triplet-planar input (conv3d_wino47.hip)
+    SE_CONV_K7_WINO47_CL,    // 7^3: 1-D Winograd F(4,7), channels-last input
+    SE_CONV_TILED_K3,        // LDS-tiled direct 3^3 (conv3d_tiled.hip); form: cout tiles per workgroup (4, 2, 1)
+    SE_CONV_TILED_K7,        // LDS-tiled direct 7^3
+    SE_CONV_HALO64,          // small levels (conv3d.hip): 64-voxel tiles through LDS; form: dim (8, 16)
+    SE_CONV_WAVESPLIT,       // small levels: in-workgroup split-K; form: waves per workgroup (4: two cout tile pairs of 2 x 4 waves, 8, 16)
+    SE_CONV_SPLITK_GRID,     // small levels: taps split over grid.z into the caller's workspace + reduce; `splits`
+    SE_CONV_DIRECT,          // any shape: activations straight from global memory; form: ksize
+#ifdef SE_DEVTOOLS           // retired kernels, reachable only through se_debug_set_variant (devtools/*.inc, conv3d_wino44.hip)
+    SE_CONV_DEV_WINO44,            // (63) F(4,3) x F(4,3), lockstep form; form: octet layout bits
+    SE_CONV_DEV_WINO23_1D,         // (4) 1-D Winograd F(2,3)
+    SE_CONV_DEV_WINO43_1D,         // (19) 1-D Winograd F(4,3), single-phase form
+    SE_CONV_DEV_TILED_K3_TZ,       // (21-23) LDS-tiled direct 3^3 with 8 x 8 x form output tiles (4, 8, 16), 2 cout tiles
+    SE_CONV_DEV_K3_C32_PERSISTENT, // (2, 3) persistent direct 3^3, 32 output channels; form: cin / 16 | (variant 3 ? 4 : 0)
+    SE_CONV_DEV_K7_WINO27,         // (17) 7^3: 1-D Winograd F(2,7), single-phase form
+    SE_CONV_DEV_K7_WINO27PP,       // (19) 7^3: 1-D Winograd F(2,7), ping-pong form
+    SE_CONV_DEV_K7_PERSISTENT,     // (2) persistent direct 7^3
+#endif
+};
+
+struct SeConvPlan {
+    int kernel;   // SeConvKernel
+    int form;     // the template / layout selector of that kernel's launcher (see SeConvKernel)
+    int slice;    // samples per launch: the persistent kernels keep a table of their work units in LDS, a larger batch is cut up
+    int splits;   // SE_CONV_SPLITK_GRID: parts the 27 taps are split into
+    int exp;      // development builds: the se_debug_set_variant experiment of conv3d_k3_wino2d_kernel<E, L> (0: none)
+    int error;    // SE_ERR_BAD_ARG: no kernel serves the call as its tensors are laid out; else 0
+};
+
+// Pure: launches nothing, allocates nothing, reads a (wpack_* say which weight sections exist) and se_num_cus().
+SeConvPlan se_conv3d_plan(const ConvArgs& a, int batch, int ksize);
+
+// ---- what the kernel files export; `batch` is the number of samples of ONE launch, preconditions are the plan's to check ----
+// conv3d_wino44pp.hip.  _shape: on the batch of the whole call; _form: L, or -1 for a combination that is not instantiated
+bool se_conv3d_wino44pp_shape(int batch, int dim, int cout);
+bool se_conv3d_wino44pp_layout_ok(int cin, int flags);
+bool se_conv3d_wino44pp_fits(int batch, int dim, int cout);
+int se_conv3d_wino44pp_form(const ConvArgs& a);
+int se_conv3d_wino44pp_launch(const ConvArgs& a, int batch, int form, hipStream_t s);
+int se_conv3d_pack_wino44(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin, int cin_pad,
+                          long long elems, hipStream_t s);   // section I
+// conv3d_wino2d.hip
+bool se_conv3d_wino2d_fits(int batch, int dim, int cout);
+int se_conv3d_wino2d_form(const ConvArgs& a);
+int se_conv3d_wino2d_launch(const ConvArgs& a, int batch, int form, int exp, hipStream_t s);
+int se_conv3d_pack_wino2d(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin, int cin_pad,
+                          long long elems, hipStream_t s);   // section G
+// conv3d_wino.hip: the 1-D Winograd kernels; `kernel` is the plan's (SE_CONV_WINO43PP_1D, SE_CONV_K7_*, in development builds their
+// retired forms).  _fits: the unit table of `kernel` holds a launch of `batch` samples
+bool se_conv3d_wino1d_fits(int kernel, int batch, int dim, int cout, int num_cus);
+int se_conv3d_wino1d_launch(const ConvArgs& a, int batch, int kernel, hipStream_t s);
+int se_conv3d_k7_wino_launch(const ConvArgs& a, int batch, int kernel, hipStream_t s);
+// conv3d_wino67.hip, conv3d_wino47.hip (one translation unit per input layout, the same unit table)
+bool se_conv3d_k7_wino67_fits(const ConvArgs& a, int batch, int num_cus);
+int se_conv3d_k7_wino67_launch(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
+bool se_conv3d_k7_wino47_fits(int batch, int dim, int num_cus);
+int se_conv3d_k7_wino47_launch_cl(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
+int se_conv3d_k7_wino47_launch_p3(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
+// conv3d_tiled.hip: SE_CONV_TILED_K3 / _K7 (development builds: the retired persistent direct kernels too)
+int se_conv3d_tiled_launch(const ConvArgs& a, int batch, int kernel, int form, hipStream_t s);
+#ifdef SE_DEVTOOLS
+// conv3d_wino44.hip
+bool se_conv3d_wino44_takes(const ConvArgs& a);
+int se_conv3d_wino44_launch(const ConvArgs& a, int batch, hipStream_t s);
+#endif

@@ -17,7 +17,7 @@
 //
 // Why this is MFMA-bound, not LDS/HBM-bound: per step a wave issues M_T ds_read_b128 + N_T global 16-B loads for
 // 4*M_T*N_T MFMAs of 32 cycles each (k3 32->32: 6 loads for 32 MFMAs = 1024 SIMD cycles).
-#include "conv_common.h"
+#include "conv3d_plan.h"
 
 #include <type_traits>
 
@@ -184,100 +184,24 @@ int launch_tiled(const ConvArgs& a, int batch, hipStream_t s) {
 
 }  // namespace
 
-// Returns 0 if a tiled kernel took the launch, SE_TILED_NOT_TAKEN if the shape is left to the direct kernel,
-// otherwise the hipError_t of the failed launch.
-int se_conv3d_wino_try(const ConvArgs& a, int batch, hipStream_t s);   // conv3d_wino.hip
-int se_conv3d_wino2d_try(const ConvArgs& a, int batch, int launch_batch, hipStream_t s); // conv3d_wino2d.hip
-int se_conv3d_k7_wino_try(const ConvArgs& a, int batch, hipStream_t s);
-
-static int tiled_try_one(const ConvArgs& a, int batch, int launch_batch, int ksize, hipStream_t s);
-
-// The persistent kernels keep a per-workgroup table of their work units in the LDS left over beside weights and tiles
-// (a few hundred entries): large batches are cut into slices of 32 samples, one launch each (weak-scaling config 4 runs
-// 32 samples per GPU, i.e. exactly one slice).
-int se_conv3d_tiled_try(const ConvArgs& a, int batch, int ksize, hipStream_t s) {
-    // unit-table budget: the smallest table among the persistent kernels holds ~430 entries per workgroup
-    const long long t8 = a.dim / 8;
-    const long long units_per_sample = ksize == 7 ? t8 * t8 * t8 : (long long)(a.cout >= 32 ? a.cout / 32 : 1) * (a.dim / 4) * t8 * t8;
-    long long budget = units_per_sample > 0 ? 400LL * se_num_cus() / units_per_sample : 32;
-    const int SLICE = (int)(budget < 1 ? 1 : budget > 32 ? 32 : budget);
-    if (batch <= SLICE) return tiled_try_one(a, batch, batch, ksize, s);
-    const long long vox = (long long)a.dim * a.dim * a.dim;
-    for (int b0 = 0; b0 < batch; b0 += SLICE) {
-        const int nb = batch - b0 < SLICE ? batch - b0 : SLICE;
-        ConvArgs sl = a;
-        // floats per voxel of the input: channels-last record, or 3 x ceil(cin/3) planes for the triplet-planar 7^3 input
-        sl.in = a.in + (long long)b0 * vox * ((a.flags & SE_IN_PLANAR3) ? (a.cin + 2) / 3 * 3 : a.cin_pad);
-        sl.out = a.out + (long long)b0 * vox * a.cout;
-        if (a.res) sl.res = a.res + (long long)b0 * vox * ((a.flags & SE_EPI_SKIPCONV16) ? 16 : a.cout);
-        if (a.pool_out) sl.pool_out = a.pool_out + (long long)b0 * (vox / 8) * a.cout;
-        sl.total_vox = (long long)nb * vox;
-        // batch-dependent decisions (small-volume early-out, which 2-D Winograd kernel) are taken on the WHOLE batch, so every slice
-        // decides alike (a one-sample tail slice used to say "not taken" after the first slices had been launched)
-        const int rc = tiled_try_one(sl, nb, batch, ksize, s);
-        if (rc != 0) return rc;   // not taken (same decision for every slice: nothing launched yet) or an error
-    }
-    return 0;
-}
-
-// `batch` samples are launched; `launch_batch` = samples of the whole call this slice belongs to (what batch-dependent choices look at)
-static int tiled_try_one(const ConvArgs& a, int batch, int launch_batch, int ksize, hipStream_t s) {
-    const int dim = a.dim;
-    // tiny volumes of 2-D Winograd shapes (16^3 at batch 1: 32 work units for 256 CUs): a plain channels-last call is left to the
-    // in-workgroup split-K kernel of the 8^3 level (conv_common.h: se_conv3d_small_volume; 47 against 92 us per 128 -> 128 launch);
-    // a caller that asks for an octet-planar / pooled / fused-skip form gets the 2-D kernel as before
-    if (ksize == 3 && g_variant == 0 && se_conv3d_small_volume(launch_batch, dim) && a.cin_pad == a.cin && se_wino2d_shape_ok(dim, a.cin, a.cout) &&
-        !(a.flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS | SE_EPI_SKIPCONV16 | SE_EPI_RES_POST_RELU | SE_EPI_OUT_PLANAR)) && !a.pool_out &&
-        !a.skip_w && (a.nts % 2) == 0)
-        return SE_TILED_NOT_TAKEN;
-    if (ksize == 3 && (g_variant == 0 || (g_variant >= 40 && g_variant < 70))) {   // production: 2-D Winograd F(4,3) x F(2,3), register accumulators
-        const int rc = se_conv3d_wino2d_try(a, batch, launch_batch, s);
-        if (rc != SE_TILED_NOT_TAKEN) return rc;
-    }
-    // octet-planar tensors, the pooled second output and the fused 16-channel skip convolution exist in the 2-D Winograd kernel only:
-    // a launch that asks for one of them and was declined (cin_pad != cin, SE_EPI_RES_POST_RELU / SE_EPI_OUT_PLANAR, ...) is an error -
-    // none of the kernels below would read or write those tensors the way the caller laid them out
-    if ((a.flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS | SE_EPI_SKIPCONV16)) || a.pool_out || a.skip_w) return SE_ERR_BAD_ARG;
-    if (ksize == 3 && (g_variant == 0 || g_variant == 4 || g_variant == 30 || (g_variant >= 10 && g_variant < 20))) {   // 1-D Winograd F(4,3) (se_debug_set_variant(30): instead of the 2-D kernel)
-        const int rc = se_conv3d_wino_try(a, batch, s);
-        if (rc != SE_TILED_NOT_TAKEN) return rc;
-    }
-    if (dim < 16 || (dim & 7)) return SE_TILED_NOT_TAKEN;   // small / odd volumes: direct kernel
-    if (a.cout & 15) return SE_TILED_NOT_TAKEN;               // planar 15-channel output layer: direct kernel
-    const int nts = a.nts;
-    if (ksize == 3) {
+// The LDS-tiled direct kernels: shapes no Winograd kernel covers (3^3 with cout % 32 != 0 or cin % 16 != 0; 7^3 with a residual or
+// planar output).  Preconditions (se_conv3d_plan): channels-last tensors, dim >= 16, dim % 8 == 0, cout % 16 == 0; 7^3: cout == 16.
+// `form`: cout tiles per workgroup of SE_CONV_TILED_K3 (divides a.nts).  Development builds: the retired persistent direct kernels.
+int se_conv3d_tiled_launch(const ConvArgs& a, int batch, int kernel, int form, hipStream_t s) {
+    switch (kernel) {
+        case SE_CONV_TILED_K3: return form == 4 ? launch_tiled<3, 16, 4, 4>(a, batch, s) : form == 2 ? launch_tiled<3, 16, 4, 2>(a, batch, s) : launch_tiled<3, 16, 4, 1>(a, batch, s);
+        case SE_CONV_TILED_K7: return launch_tiled<7, 4, 4, 1>(a, batch, s);
 #ifdef SE_DEVTOOLS
-        // BASELINE config 5 (LDS tile-size sweep, tools/bench_conv.py --variants 21,22,23): non-persistent LDS-tiled direct
-        // kernel with 8x8x{4,8,16} output tiles = 38 / 64 / 115 KB of halo per 16-channel chunk
-        if (g_variant >= 21 && g_variant <= 23 && nts % 2 == 0 && dim % 16 == 0) {
-            if (g_variant == 21) return launch_tiled<3, 16, 4, 2>(a, batch, s);
-            if (g_variant == 22) return launch_tiled<3, 16, 8, 2>(a, batch, s);
-            return launch_tiled<3, 16, 16, 2>(a, batch, s);
-        }
-        if ((g_variant == 2 || g_variant == 3) && a.cout == 32 && dim >= 32 && (a.cin == 16 || a.cin == 32) && a.cin_pad == a.cin &&
-            !(a.flags & (SE_EPI_RES_POST_RELU | SE_EPI_OUT_PLANAR))) {
-            if (g_variant == 2)
-                return a.cin == 32 ? launch_k3_c32_persistent<2, false>(a, batch, s) : launch_k3_c32_persistent<1, false>(a, batch, s);
-            return a.cin == 32 ? launch_k3_c32_persistent<2, true>(a, batch, s) : launch_k3_c32_persistent<1, true>(a, batch, s);
-        }
+        // BASELINE config 5 (LDS tile-size sweep, tools/bench_conv.py --variants 21,22,23): 8x8x{4,8,16} output tiles = 38 / 64 / 115 KB
+        // of halo per 16-channel chunk (needs nts % 2 == 0, dim % 16 == 0)
+        case SE_CONV_DEV_TILED_K3_TZ: return form == 4 ? launch_tiled<3, 16, 4, 2>(a, batch, s) : form == 8 ? launch_tiled<3, 16, 8, 2>(a, batch, s) : launch_tiled<3, 16, 16, 2>(a, batch, s);
+        case SE_CONV_DEV_K3_C32_PERSISTENT:   // cout 32, cin 16 / 32 = cin_pad, dim >= 32, no SE_EPI_RES_POST_RELU / SE_EPI_OUT_PLANAR
+            if (form & 4) return (form & 3) == 2 ? launch_k3_c32_persistent<2, true>(a, batch, s) : launch_k3_c32_persistent<1, true>(a, batch, s);
+            return (form & 3) == 2 ? launch_k3_c32_persistent<2, false>(a, batch, s) : launch_k3_c32_persistent<1, false>(a, batch, s);
+        case SE_CONV_DEV_K7_PERSISTENT: return launch_k7_persistent(a, batch, s);   // dim >= 32, cout 16, no residual, channels-last output
 #endif
-        // shapes no Winograd kernel covers (cout % 32 != 0, cin % 16 != 0): LDS-tiled direct kernel
-        if (nts % 4 == 0) return launch_tiled<3, 16, 4, 4>(a, batch, s);
-        if (nts % 2 == 0) return launch_tiled<3, 16, 4, 2>(a, batch, s);
-        return launch_tiled<3, 16, 4, 1>(a, batch, s);
+        default: return SE_ERR_BAD_ARG;
     }
-    if (ksize == 7 && nts == 1) {
-        if (g_variant == 0 || g_variant >= 10) {   // production: F(4,7) Winograd persistent kernel
-            const int rc = se_conv3d_k7_wino_try(a, batch, s);
-            if (rc != SE_TILED_NOT_TAKEN) return rc;
-        }
-        if (a.flags & SE_IN_PLANAR3) return SE_ERR_BAD_ARG;
-#ifdef SE_DEVTOOLS
-        if (g_variant == 2 && dim >= 32 && a.cout == 16 && !a.res && !(a.flags & SE_EPI_OUT_PLANAR)) return launch_k7_persistent(a, batch, s);
-#endif
-        return launch_tiled<7, 4, 4, 1>(a, batch, s);
-    }
-    return SE_TILED_NOT_TAKEN;
 }
 
 #ifdef SE_DEVTOOLS

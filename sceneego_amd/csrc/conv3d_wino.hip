@@ -17,15 +17,10 @@
 // prefetched one item ahead; residual add + ReLU happen on the last chunk.
 // Wave w of 8: z pair w>>2 (outputs z = 2*zp, 2*zp+1 of the tile), rows 2*(w&3), 2*(w&3)+1 -> one 16-position tile,
 // 4 xi x 2 cout tiles = 8 accumulators.
-#include "conv_common.h"
+#include "conv3d_plan.h"
 
 #include <type_traits>
 #include <utility>
-
-// F(4,7) 7^3 kernel, one translation unit per input layout (conv3d_wino47.hip compiled with -DSE_K7F_PLANAR=0 / 1)
-int se_conv3d_k7_wino47_launch_cl(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
-int se_conv3d_k7_wino47_launch_p3(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
-int se_conv3d_k7_wino67_launch(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);   // conv3d_wino67.hip
 
 namespace {
 
@@ -368,54 +363,65 @@ __global__ __launch_bounds__(512) void conv3d_k3_wino43pp_kernel(ConvArgs a, int
 [[maybe_unused]] unsigned long long* g_wino_dbg = nullptr;
 unsigned long long* g_wino_dbg43 = nullptr;
 
+constexpr int LDS43 = 160 * 1024;
+
+// work units of one launch per persistent workgroup (min(units, CUs) workgroups)
+int per_wg(int n_units, int num_cus) {
+    const int grid = n_units < num_cus ? n_units : num_cus;
+    return (n_units + grid - 1) / grid;
+}
+
 }  // namespace
 
-// Returns 0 on launch, SE_TILED_NOT_TAKEN if the shape/flags are not covered, else a hipError_t.
-// Production: the ping-pong F(4,3) kernel (shapes the 2-D kernel of conv3d_wino2d.hip does not take, e.g. dim % 16 != 0).
-// Development builds add the retired forms: se_debug_set_variant(4) F(2,3), (19) single-phase F(4,3), stamp builds.
-int se_conv3d_wino_try(const ConvArgs& a, int batch, hipStream_t s) {
-    const int dim = a.dim;
-    if (!a.wpack_b || !a.wpack_e || dim < 16 || (dim & 7) || (a.cout & 31) || (a.cin & 15) || a.cin_pad != a.cin) return SE_TILED_NOT_TAKEN;
-    if (a.flags & (SE_EPI_RES_POST_RELU | SE_EPI_OUT_PLANAR | SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS)) return SE_TILED_NOT_TAKEN;
-    constexpr int LDS43 = 160 * 1024;
-    constexpr int MAXPP = (LDS43 - (W43_FLOATS + 2 * PP_VH_FLOATS) * 4) / 16;
-    const int num_cus = se_num_cus();
-    const int tiles = dim / 8, ztiles = dim / 4;
+// The unit table (16 B per unit in the LDS left beside weights and tiles) of `kernel` holds a launch of `batch` samples.
+bool se_conv3d_wino1d_fits(int kernel, int batch, int dim, int cout, int num_cus) {
+    const int total_tiles = batch * (dim / 4) * (dim / 8) * (dim / 8);   // 4 x 8 x 8 output tiles
+    int n_units = (cout / 32) * total_tiles, fixed_floats;              // 3^3: a unit is (tile, 32-cout block);  LDS floats beside the table
+    switch (kernel) {
+        case SE_CONV_WINO43PP_1D: fixed_floats = W43_FLOATS + 2 * PP_VH_FLOATS; break;
+#ifdef SE_DEVTOOLS
+        case SE_CONV_DEV_WINO23_1D: fixed_floats = SE_WINO_CHUNK_FLOATS + 2 * TILE_FLOATS; break;
+        case SE_CONV_DEV_WINO43_1D: fixed_floats = W43_FLOATS + V43_FLOATS; break;
+        case SE_CONV_DEV_K7_WINO27:
+        case SE_CONV_DEV_K7_WINO27PP: n_units = total_tiles; fixed_floats = K7_W_FLOATS + K7_VT_FLOATS; break;
+#endif
+        default: return false;
+    }
+    return n_units > 0 && per_wg(n_units, num_cus) <= (LDS43 - fixed_floats * 4) / 16;
+}
+
+// The 1-D Winograd 3^3 kernels: the ping-pong F(4,3) kernel (shapes the 2-D kernels do not take, e.g. dim % 16 != 0); development
+// builds add the retired forms (F(2,3): its stamp build if se_debug_set_stamp_buffer gave a buffer; single-phase F(4,3)).
+// Preconditions (se_conv3d_plan): se_wino1d_shape_ok, cin_pad == cin, channels-last tensors, no SE_EPI_RES_POST_RELU /
+// SE_EPI_OUT_PLANAR, sections C and E present, se_conv3d_wino1d_fits.
+int se_conv3d_wino1d_launch(const ConvArgs& a, int batch, int kernel, hipStream_t s) {
+    const int tiles = a.dim / 8, ztiles = a.dim / 4;
     const int total_tiles = batch * ztiles * tiles * tiles;
     const int n_cb = a.cout / 32;
     const int n_units = n_cb * total_tiles;
-    const int grid = n_units < num_cus ? n_units : num_cus;
-    const int per = (n_units + grid - 1) / grid;
+    const int per = per_wg(n_units, se_num_cus());
+    const dim3 grid((n_units + per - 1) / per);
 #ifdef SE_DEVTOOLS
-    {
-        constexpr int LDS_FIXED = (SE_WINO_CHUNK_FLOATS + 2 * TILE_FLOATS) * 4;
-        constexpr int MAX_UNITS_PER_WG = (LDS43 - LDS_FIXED) / 16;
-        constexpr int MAX43 = (LDS43 - (W43_FLOATS + V43_FLOATS) * 4) / 16;
-        if ((g_variant == 4 || g_wino_dbg) && per <= MAX_UNITS_PER_WG) {
-            SE_ENSURE_LDS(conv3d_k3_wino_kernel<false>, LDS43);
-            SE_ENSURE_LDS(conv3d_k3_wino_kernel<true>, LDS43);
-            if (g_wino_dbg)
-                hipLaunchKernelGGL(conv3d_k3_wino_kernel<true>, dim3((n_units + per - 1) / per), dim3(512), LDS43, s, a, tiles, ztiles,
-                                   total_tiles, n_cb, per, 0, g_wino_dbg);
-            else
-                hipLaunchKernelGGL(conv3d_k3_wino_kernel<false>, dim3((n_units + per - 1) / per), dim3(512), LDS43, s, a, tiles, ztiles,
-                                   total_tiles, n_cb, per, 0, nullptr);
-            SE_CHECK_LAUNCH();
-            return 0;
-        }
-        if (g_variant == 19 && per <= MAX43) {
-            SE_ENSURE_LDS(conv3d_k3_wino43_kernel, LDS43);
-            hipLaunchKernelGGL(conv3d_k3_wino43_kernel, dim3((n_units + per - 1) / per), dim3(512), LDS43, s, a, tiles, ztiles,
-                               total_tiles, n_cb, per, 0, g_wino_dbg43);
-            SE_CHECK_LAUNCH();
-            return 0;
-        }
+    if (kernel == SE_CONV_DEV_WINO23_1D) {
+        SE_ENSURE_LDS(conv3d_k3_wino_kernel<false>, LDS43);
+        SE_ENSURE_LDS(conv3d_k3_wino_kernel<true>, LDS43);
+        if (g_wino_dbg)
+            hipLaunchKernelGGL(conv3d_k3_wino_kernel<true>, grid, dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, n_cb, per, 0, g_wino_dbg);
+        else
+            hipLaunchKernelGGL(conv3d_k3_wino_kernel<false>, grid, dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, n_cb, per, 0, nullptr);
+        SE_CHECK_LAUNCH();
+        return 0;
+    }
+    if (kernel == SE_CONV_DEV_WINO43_1D) {
+        SE_ENSURE_LDS(conv3d_k3_wino43_kernel, LDS43);
+        hipLaunchKernelGGL(conv3d_k3_wino43_kernel, grid, dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, n_cb, per, 0, g_wino_dbg43);
+        SE_CHECK_LAUNCH();
+        return 0;
     }
 #endif
-    if (per > MAXPP) return SE_TILED_NOT_TAKEN;      // cannot happen behind se_conv3d_tiled_try's unit-budget batch slices
+    if (kernel != SE_CONV_WINO43PP_1D) return SE_ERR_BAD_ARG;
     SE_ENSURE_LDS(conv3d_k3_wino43pp_kernel, LDS43);
-    hipLaunchKernelGGL(conv3d_k3_wino43pp_kernel, dim3((n_units + per - 1) / per), dim3(512), LDS43, s, a, tiles, ztiles, total_tiles,
-                       n_cb, per, 0, g_wino_dbg43);
+    hipLaunchKernelGGL(conv3d_k3_wino43pp_kernel, grid, dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, n_cb, per, 0, g_wino_dbg43);
     SE_CHECK_LAUNCH();
     return 0;
 }
@@ -431,46 +437,31 @@ extern "C" void se_debug_set_stamp_buffer(void* p) {
 }
 #endif
 
-// Returns 0 on launch, SE_TILED_NOT_TAKEN if not covered, else a hipError_t.
-// Production: the F(4,7) kernel of conv3d_wino47.hip.  Development builds add the retired F(2,7) kernels
-// (se_debug_set_variant(17) single-phase, (19) ping-pong).
-int se_conv3d_k7_wino_try(const ConvArgs& a, int batch, hipStream_t s) {
-    const int dim = a.dim;
-    if (!a.wpack_d || !a.wpack_f || dim < 16 || (dim & 7) || a.cout != 16 || a.res || (a.flags & (SE_EPI_OUT_PLANAR))) return SE_TILED_NOT_TAKEN;
+// The Winograd 7^3 kernels: F(6,7) (conv3d_wino67.hip), F(4,7) per input layout (conv3d_wino47.hip); development builds add the
+// retired F(2,7) kernels.  Preconditions (se_conv3d_plan): se_k7_wino_shape_ok, no residual, channels-last output, sections D and F
+// (F(6,7): H) present, the kernel's _fits; only F(6,7) and F(4,7) read the triplet-planar input.
+int se_conv3d_k7_wino_launch(const ConvArgs& a, int batch, int kernel, hipStream_t s) {
     const int num_cus = se_num_cus();
+    switch (kernel) {
+        case SE_CONV_K7_WINO67: return se_conv3d_k7_wino67_launch(a, batch, num_cus, s, g_wino_dbg43);
+        case SE_CONV_K7_WINO47_P3: return se_conv3d_k7_wino47_launch_p3(a, batch, num_cus, s, g_wino_dbg43);
+        case SE_CONV_K7_WINO47_CL: return se_conv3d_k7_wino47_launch_cl(a, batch, num_cus, s, g_wino_dbg43);
 #ifdef SE_DEVTOOLS
-    if (g_variant == 17 || g_variant == 19) {
-        if (a.flags & SE_IN_PLANAR3) return SE_ERR_BAD_ARG;   // only the F(4,7) kernel reads the triplet-planar layout
-        constexpr int LDS_BYTES = 160 * 1024;
-        constexpr int MAX_UNITS = (LDS_BYTES - (K7_W_FLOATS + K7_VT_FLOATS) * 4) / 16;
-        const int tiles = dim / 8, ztiles = dim / 4;
-        const int total_tiles = batch * ztiles * tiles * tiles;
-        const int grid = total_tiles < num_cus ? total_tiles : num_cus;
-        const int per = (total_tiles + grid - 1) / grid;
-        if (per > MAX_UNITS) return SE_TILED_NOT_TAKEN;
-        SE_ENSURE_LDS(conv3d_k7_wino_kernel, LDS_BYTES);
-        SE_ENSURE_LDS(conv3d_k7_winopp_kernel, LDS_BYTES);
-        if (g_variant == 17)
-            hipLaunchKernelGGL(conv3d_k7_wino_kernel, dim3((total_tiles + per - 1) / per), dim3(512), LDS_BYTES, s, a, tiles, ztiles,
-                               total_tiles, per);
-        else
-            hipLaunchKernelGGL(conv3d_k7_winopp_kernel, dim3((total_tiles + per - 1) / per), dim3(512), LDS_BYTES, s, a, tiles, ztiles,
-                               total_tiles, per);
-        SE_CHECK_LAUNCH();
-        return 0;
-    }
+        case SE_CONV_DEV_K7_WINO27:
+        case SE_CONV_DEV_K7_WINO27PP: {
+            const int tiles = a.dim / 8, ztiles = a.dim / 4;
+            const int total_tiles = batch * ztiles * tiles * tiles;
+            const int per = per_wg(total_tiles, num_cus);
+            SE_ENSURE_LDS(conv3d_k7_wino_kernel, LDS43);
+            SE_ENSURE_LDS(conv3d_k7_winopp_kernel, LDS43);
+            if (kernel == SE_CONV_DEV_K7_WINO27)
+                hipLaunchKernelGGL(conv3d_k7_wino_kernel, dim3((total_tiles + per - 1) / per), dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, per);
+            else
+                hipLaunchKernelGGL(conv3d_k7_winopp_kernel, dim3((total_tiles + per - 1) / per), dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, per);
+            SE_CHECK_LAUNCH();
+            return 0;
+        }
 #endif
-    // dim % 16 == 0: the tile-outer F(6,7) kernel (conv3d_wino67.hip); development builds keep the F(4,7) kernel selectable (variant 47)
-    if (a.wpack_h && (dim & 15) == 0
-#ifdef SE_DEVTOOLS
-        && g_variant != 47
-#endif
-    ) {
-        const int rc67 = se_conv3d_k7_wino67_launch(a, batch, num_cus, s, g_wino_dbg43);
-        if (rc67 != SE_TILED_NOT_TAKEN) return rc67;
+        default: return SE_ERR_BAD_ARG;
     }
-    const int rc = (a.flags & SE_IN_PLANAR3) ? se_conv3d_k7_wino47_launch_p3(a, batch, num_cus, s, g_wino_dbg43)
-                                             : se_conv3d_k7_wino47_launch_cl(a, batch, num_cus, s, g_wino_dbg43);
-    if (rc == SE_TILED_NOT_TAKEN && (a.flags & SE_IN_PLANAR3)) return SE_ERR_BAD_ARG;   // cannot happen behind the unit-budget batch slices
-    return rc;
 }

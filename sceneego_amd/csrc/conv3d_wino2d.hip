@@ -25,7 +25,7 @@
 // LDS operand reads are conflict-free: W is lane-linear; V records are 216 floats apart (see v_rec_offset).
 #include "common.h"
 
-#include "conv_common.h"
+#include "conv3d_plan.h"
 
 #include <type_traits>
 #include <utility>
@@ -742,41 +742,37 @@ __global__ void pack_k3_wino2d_kernel(const float* __restrict__ w, const float* 
 }
 
 int se_conv3d_pack_wino2d(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin,
-                          int cin_pad, hipStream_t s) {
-    const long long total = (long long)(cout / 32) * (cin_pad / 8) * SE_WINO2D_CHUNK_FLOATS;
-    hipLaunchKernelGGL(pack_k3_wino2d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, gamma, var, eps, out, cout,
-                       cin, cin_pad, total);
+                          int cin_pad, long long elems, hipStream_t s) {
+    hipLaunchKernelGGL(pack_k3_wino2d_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, w, gamma, var, eps, out, cout,
+                       cin, cin_pad, elems);
     SE_CHECK_LAUNCH();
     return 0;
 }
 
-bool se_conv3d_wino44pp_takes(const ConvArgs& a, int batch);                  // conv3d_wino44pp.hip: F(4,3) x F(4,3), ping-pong form
-int se_conv3d_wino44pp_launch(const ConvArgs& a, int batch, hipStream_t s);
-#ifdef SE_DEVTOOLS
-bool se_conv3d_wino44_takes(const ConvArgs& a);                               // conv3d_wino44.hip (development builds)
-int se_conv3d_wino44_launch(const ConvArgs& a, int batch, hipStream_t s);
-#endif
+// work units (4 x 8 x 16 tile, 32-cout block) of one launch: the kernel packs a unit index into 30 bits
+static long long wino2d_units(int batch, int dim, int cout) { return (long long)batch * (dim / 16) * (dim / 8) * (dim / 4) * (cout / 32); }
+bool se_conv3d_wino2d_fits(int batch, int dim, int cout) { return wino2d_units(batch, dim, cout) < (1LL << 30); }
 
-// Returns 0 on launch, SE_TILED_NOT_TAKEN if the shape/flags are not covered, else a hipError_t.
-int se_conv3d_wino2d_try(const ConvArgs& a, int batch, int launch_batch, hipStream_t s) {
+// The instance conv3d_k3_wino2d_kernel<0, L> of a call: bits 1 / 2 / 4 = octet-planar input / output / skip tensor, + 8 pooled
+// second output, + 16 fused 16-channel skip convolution, 32 = channels-last in, quad-planar out; -1 for a combination that is not
+// instantiated.  This kernel's planar layout is octet-planar; the one quad-planar form it has is 32 (no skip tensor).
+int se_conv3d_wino2d_form(const ConvArgs& a) {
+    const int layout = ((a.flags & SE_IN_OCTET) ? 1 : 0) | ((a.flags & SE_OUT_OCTET) ? 2 : 0) | ((a.flags & SE_RES_OCTET) && a.res ? 4 : 0);
+    if (a.flags & SE_LAYOUT_QUAD_BITS)
+        return ((a.flags & SE_LAYOUT_QUAD_BITS) == SE_OUT_QUAD && !(a.flags & SE_LAYOUT_OCTET_BITS) && !a.res && !a.pool_out &&
+                !(a.flags & SE_EPI_SKIPCONV16)) ? 32 : -1;
+    if (a.flags & SE_EPI_SKIPCONV16) return (layout == 3 && !a.pool_out && a.skip_w && a.res) ? 19 : -1;
+    if (a.pool_out) return (layout == 3 || layout == 7) ? 8 + layout : -1;   // pooled output: octet-planar in / out only (what the V2V program uses)
+    return layout;
+}
+
+// Preconditions (se_conv3d_plan): se_wino2d_shape_ok, cin_pad == cin, no SE_EPI_RES_POST_RELU / SE_EPI_OUT_PLANAR, _fits, section G
+// present, form from _form.  Development builds: exp != 0 (a se_debug_set_variant number) runs experiment E of it, forms 0 and 3 only.
+int se_conv3d_wino2d_launch(const ConvArgs& a, int batch, int form, int exp, hipStream_t s) {
     const int dim = a.dim;
-    if (!a.wpack_g || a.cin_pad != a.cin || !se_wino2d_shape_ok(dim, a.cin, a.cout)) return SE_TILED_NOT_TAKEN;
-    if (a.flags & (SE_EPI_RES_POST_RELU | SE_EPI_OUT_PLANAR)) return SE_TILED_NOT_TAKEN;
-#ifdef SE_DEVTOOLS
-    // experiment (round 3, se_debug_set_variant(63)): F(4,3) x F(4,3), lockstep form with an LDS-DMA weight stream (conv3d_wino44.hip)
-    if (g_variant == 63 && se_conv3d_wino44_takes(a)) return se_conv3d_wino44_launch(a, batch, s);
-#endif
-    // round 4: the 64^3 / 32^3 levels run on the F(4,3) x F(4,3) ping-pong kernel (1/4 of the direct MFMAs; this kernel: 1/3);
-    // development builds: se_debug_set_variant(64) keeps them here (A/B)
-    if (g_variant != 64 && g_variant < 41 && se_conv3d_wino44pp_takes(a, launch_batch)) return se_conv3d_wino44pp_launch(a, batch, s);
-    // this kernel's planar layout is octet-planar; the one quad-planar form it has: channels-last in, quad-planar out, no skip tensor
-    const bool quad_out_only = (a.flags & SE_LAYOUT_QUAD_BITS) == SE_OUT_QUAD && !(a.flags & SE_LAYOUT_OCTET_BITS) && !a.res && !a.pool_out &&
-                               !(a.flags & SE_EPI_SKIPCONV16);
-    if ((a.flags & SE_LAYOUT_QUAD_BITS) && !quad_out_only) return SE_ERR_BAD_ARG;
     const int tx = dim / 16, ty = dim / 8, tz = dim / 4;
     const long long total_tiles = (long long)batch * tx * ty * tz;
-    const long long n_units = total_tiles * (a.cout / 32);
-    if (n_units >= (1LL << 30)) return SE_TILED_NOT_TAKEN;
+    const long long n_units = wino2d_units(batch, dim, a.cout);
     const int cus = se_num_cus();
     const int grid = (int)(n_units < cus ? n_units : cus);
     const int per = (int)((n_units + grid - 1) / grid);
@@ -791,11 +787,10 @@ int se_conv3d_wino2d_try(const ConvArgs& a, int batch, int launch_batch, hipStre
         hipLaunchKernelGGL(kern, dim3((unsigned)((n_units + per - 1) / per)), dim3(512), W2_LDS_BYTES, s, a, a.wpack_g, tx, ty, \
                            tz, (int)total_tiles, (int)n_units, per, dbg);                                                       \
     } while (0)
-    const int layout = ((a.flags & SE_IN_OCTET) ? 1 : 0) | ((a.flags & SE_OUT_OCTET) ? 2 : 0) | ((a.flags & SE_RES_OCTET) && a.res ? 4 : 0);
 #ifdef SE_DEVTOOLS
-    if ((layout == 0 || layout == 3) && g_variant >= 41) {
-#define W2_VAR(E) do { if (layout == 3) W2_LAUNCH(E, 3); else W2_LAUNCH(E, 0); } while (0)
-        switch (g_variant) {
+    if (exp) {
+#define W2_VAR(E) do { if (form == 3) W2_LAUNCH(E, 3); else W2_LAUNCH(E, 0); } while (0)
+        switch (exp) {
             case 41: W2_VAR(0x2000); break;   // packed epilogue arithmetic
             case 42: W2_VAR(0x1000); break;   // input loads in the staging phase
             case 43: W2_VAR(0x1800); break;   // both
@@ -821,25 +816,8 @@ int se_conv3d_wino2d_try(const ConvArgs& a, int batch, int launch_batch, hipStre
         return 0;
     }
 #endif
-    if (a.flags & SE_EPI_SKIPCONV16) {
-        if (layout != 3 || a.pool_out || !a.skip_w || !a.res) return SE_ERR_BAD_ARG;
-        W2_LAUNCH(0, 19);
-        SE_CHECK_LAUNCH();
-        return 0;
-    }
-    if (a.pool_out) {
-        if (layout == 3) W2_LAUNCH(0, 11);
-        else if (layout == 7) W2_LAUNCH(0, 15);
-        else return SE_ERR_BAD_ARG;       // pooled output: octet-planar in / out only (what the V2V program uses)
-        SE_CHECK_LAUNCH();
-        return 0;
-    }
-    if (quad_out_only) {
-        W2_LAUNCH(0, 32);
-        SE_CHECK_LAUNCH();
-        return 0;
-    }
-    switch (layout) {
+    switch (form) {
+        case 0: W2_LAUNCH(0, 0); break;
         case 1: W2_LAUNCH(0, 1); break;
         case 2: W2_LAUNCH(0, 2); break;
         case 3: W2_LAUNCH(0, 3); break;
@@ -847,7 +825,11 @@ int se_conv3d_wino2d_try(const ConvArgs& a, int batch, int launch_batch, hipStre
         case 5: W2_LAUNCH(0, 5); break;
         case 6: W2_LAUNCH(0, 6); break;
         case 7: W2_LAUNCH(0, 7); break;
-        default: W2_LAUNCH(0, 0); break;
+        case 11: W2_LAUNCH(0, 11); break;
+        case 15: W2_LAUNCH(0, 15); break;
+        case 19: W2_LAUNCH(0, 19); break;
+        case 32: W2_LAUNCH(0, 32); break;
+        default: return SE_ERR_BAD_ARG;
     }
 #undef W2_LAUNCH
     SE_CHECK_LAUNCH();

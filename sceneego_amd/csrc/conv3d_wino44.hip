@@ -20,7 +20,7 @@
 //                  tile T, barrier, pass 2: B^T along z from T into V; after the last chunk the output transform + epilogue.
 // Weight stream: ONE chunk buffer, refilled by global_load_lds_dwordx4 in two regions while the other one is read (quads 5..8 of
 // the current chunk during quads 0..4, quads 0..4 of the next chunk during quads 5..8), a barrier between the halves.
-#include "conv_common.h"
+#include "conv3d_plan.h"
 
 #include <type_traits>
 #include <utility>
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(512) void conv3d_k3_wino44_kernel(ConvArgs a, const
 
 // (section I of the packed weights is written by conv3d_wino44pp.hip, the production form of this experiment)
 
-// Shapes / flag sets this kernel takes (the caller, se_conv3d_wino2d_try, has checked se_wino2d_shape_ok and cin_pad == cin):
+// Shapes / flag sets this kernel takes (se_conv3d_plan has checked se_wino2d_shape_ok, cin_pad == cin and the epilogue flags):
 // no pooled output, no fused skip convolution, dim >= 32 (at 16^3 a batch of 8 has only 128 tiles of 8 x 8 x 16).
 bool se_conv3d_wino44_takes(const ConvArgs& a) {
     return a.wpack_i && a.dim >= 32 && !a.pool_out && !a.skip_w && !(a.flags & SE_EPI_SKIPCONV16);

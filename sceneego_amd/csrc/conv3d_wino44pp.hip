@@ -32,7 +32,7 @@
 //                       of step i: group 1 has just finished with it), waited in front of their staging phase's mid barrier, which
 //                       is the barrier in front of group 0's first read of it.
 // LDS: 3 x 30,720 (slots) + 42,624 (V) + 17,280 (T) = 152,064 B.
-#include "conv_common.h"
+#include "conv3d_plan.h"
 
 #include <type_traits>
 #include <utility>
@@ -770,16 +770,15 @@ __global__ void pack_k3_wino44_kernel(const float* __restrict__ w, const float* 
 }
 
 int se_conv3d_pack_wino44(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin,
-                          int cin_pad, hipStream_t s) {
-    const long long total = (long long)(cout / 32) * (cin_pad / 4) * SE_WINO44_CHUNK_FLOATS;
-    hipLaunchKernelGGL(pack_k3_wino44_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, gamma, var, eps, out, cout,
-                       cin, cin_pad, total);
+                          int cin_pad, long long elems, hipStream_t s) {
+    hipLaunchKernelGGL(pack_k3_wino44_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, w, gamma, var, eps, out, cout,
+                       cin, cin_pad, elems);
     SE_CHECK_LAUNCH();
     return 0;
 }
 
-// Shapes this kernel takes (the caller, se_conv3d_wino2d_try, has checked se_wino2d_shape_ok and cin_pad == cin): dim >= 32 - at 16^3
-// a batch of 8 has only 128 tiles of 8 x 8 x 16 per cout block - and enough units to give every CU one.
+// Shapes this kernel takes among those of se_wino2d_shape_ok: dim >= 32 - at 16^3 a batch of 8 has only 128 tiles of 8 x 8 x 16 per
+// cout block - and enough units to give every CU one.
 bool se_conv3d_wino44pp_shape(int batch, int dim, int cout) {
     if (dim < 32) return false;
     const long long units = (long long)batch * (dim / 16) * (dim / 8) * (dim / 8) * (cout / 32);
@@ -793,22 +792,30 @@ bool se_conv3d_wino44pp_layout_ok(int cin, int flags) {
     if (flags & (SE_IN_OCTET | SE_OUT_OCTET | SE_RES_OCTET)) return false;
     return (flags & SE_IN_QUAD) || cin < 32;
 }
-bool se_conv3d_wino44pp_takes(const ConvArgs& a, int batch) {
-    if (!se_conv3d_wino44pp_layout_ok(a.cin, a.flags)) return false;
-    return a.wpack_i && se_conv3d_wino44pp_shape(batch, a.dim, a.cout);
-}
+// work units (8 x 8 x 16 tile, 32-cout block) of one launch: the kernel packs a unit index into 30 bits
+static long long wino44pp_units(int batch, int dim, int cout) { return (long long)batch * (dim / 16) * (dim / 8) * (dim / 8) * (cout / 32); }
+bool se_conv3d_wino44pp_fits(int batch, int dim, int cout) { return wino44pp_units(batch, dim, cout) < (1LL << 30); }
 
 #if defined(SE_STAMP44P)
 extern "C" void se_debug_set_stamp_buffer_44p(void* p) { g_w44p_dbg = reinterpret_cast<unsigned long long*>(p); }
 #endif
 
-// Returns 0 on launch, SE_ERR_BAD_ARG for a flag combination that is not instantiated, else a hipError_t.
-int se_conv3d_wino44pp_launch(const ConvArgs& a, int batch, hipStream_t s) {
+// The instance conv3d_k3_wino44pp_kernel<L> of a call: bits 1 / 2 / 4 = quad-planar input / output / skip tensor, + 8 pooled second
+// output, + 16 fused 16-channel skip convolution; -1 for a combination that is not instantiated.
+int se_conv3d_wino44pp_form(const ConvArgs& a) {
+    const int layout = ((a.flags & SE_IN_QUAD) ? 1 : 0) | ((a.flags & SE_OUT_QUAD) ? 2 : 0) | ((a.flags & SE_RES_QUAD) && a.res ? 4 : 0);
+    if (a.flags & SE_EPI_SKIPCONV16)      // 23: the 16-channel skip input is quad-planar too
+        return ((layout == 3 || layout == 7) && !a.pool_out && a.skip_w && a.res) ? 16 + layout : -1;
+    if (a.pool_out) return (layout == 3 || layout == 7) ? 8 + layout : -1;   // pooled output: quad-planar in / out only (what the V2V program uses)
+    return layout;
+}
+
+// Preconditions (se_conv3d_plan): se_wino2d_shape_ok, cin_pad == cin, _shape, _layout_ok, _fits, section I present, form from _form.
+int se_conv3d_wino44pp_launch(const ConvArgs& a, int batch, int form, hipStream_t s) {
     const int dim = a.dim;
     const int tx = dim / 16, ty = dim / 8, tz = dim / 8;
     const long long total_tiles = (long long)batch * tx * ty * tz;
-    const long long n_units = total_tiles * (a.cout / 32);
-    if (n_units >= (1LL << 30)) return SE_TILED_NOT_TAKEN;
+    const long long n_units = wino44pp_units(batch, dim, a.cout);
     const int cus = se_num_cus();
     const int grid = (int)(n_units < cus ? n_units : cus);
     const int per = (int)((n_units + grid - 1) / grid);
@@ -817,36 +824,16 @@ int se_conv3d_wino44pp_launch(const ConvArgs& a, int batch, hipStream_t s) {
     dbg = g_w44p_dbg;
 #endif
 #define P_LAUNCH(L)                                                                                                             \
-    do {                                                                                                                        \
+    case L: {                                                                                                                   \
         auto kern = conv3d_k3_wino44pp_kernel<L>;                                                                               \
         SE_ENSURE_LDS(kern, P_LDS_BYTES);                                                                                       \
         hipLaunchKernelGGL(kern, dim3((unsigned)((n_units + per - 1) / per)), dim3(512), P_LDS_BYTES, s, a, a.wpack_i, tx, ty,  \
                            tz, (int)total_tiles, (int)n_units, per, dbg);                                                       \
-    } while (0)
-    const int layout = ((a.flags & SE_IN_QUAD) ? 1 : 0) | ((a.flags & SE_OUT_QUAD) ? 2 : 0) | ((a.flags & SE_RES_QUAD) && a.res ? 4 : 0);
-    if (a.flags & SE_EPI_SKIPCONV16) {
-        if ((layout != 3 && layout != 7) || a.pool_out || !a.skip_w || !a.res) return SE_ERR_BAD_ARG;
-        if (layout == 7) P_LAUNCH(23);      // the 16-channel skip input is quad-planar
-        else P_LAUNCH(19);
-        SE_CHECK_LAUNCH();
-        return 0;
-    }
-    if (a.pool_out) {
-        if (layout == 3) P_LAUNCH(11);
-        else if (layout == 7) P_LAUNCH(15);
-        else return SE_ERR_BAD_ARG;       // pooled output: quad-planar in / out only (what the V2V program uses)
-        SE_CHECK_LAUNCH();
-        return 0;
-    }
-    switch (layout) {
-        case 1: P_LAUNCH(1); break;
-        case 2: P_LAUNCH(2); break;
-        case 3: P_LAUNCH(3); break;
-        case 4: P_LAUNCH(4); break;
-        case 5: P_LAUNCH(5); break;
-        case 6: P_LAUNCH(6); break;
-        case 7: P_LAUNCH(7); break;
-        default: P_LAUNCH(0); break;
+    } break
+    switch (form) {
+        P_LAUNCH(0); P_LAUNCH(1); P_LAUNCH(2); P_LAUNCH(3); P_LAUNCH(4); P_LAUNCH(5); P_LAUNCH(6); P_LAUNCH(7);
+        P_LAUNCH(11); P_LAUNCH(15); P_LAUNCH(19); P_LAUNCH(23);
+        default: return SE_ERR_BAD_ARG;
     }
 #undef P_LAUNCH
     SE_CHECK_LAUNCH();

@@ -21,7 +21,7 @@
 //      issue of the 10 loads per thread costs the MFMA waves ~7k of ~33k cycles per item (measured by removing the fetch);
 //   1  triplet-planar [B][chunks][D][D][D][3] (SE_IN_PLANAR3, written by se_unproject_gather_planar3_f32 / se_voxelize_planar3_f64):
 //      14 consecutive columns of a halo row are 168 contiguous bytes, ~12 lines per instruction.
-#include "conv_common.h"
+#include "conv3d_plan.h"
 #include "wino47_matrices.h"
 
 #include <type_traits>
@@ -352,22 +352,31 @@ __global__ __launch_bounds__(512) void conv3d_k7_wino47_kernel(ConvArgs a, int t
 
 }  // namespace
 
-// Returns 0 on launch, SE_TILED_NOT_TAKEN if the unit table does not fit, else a hipError_t.  Preconditions (checked by the caller,
-// se_conv3d_k7_wino_try): ksize 7, cout 16, dim % 8 == 0, dim >= 16, no residual, channels-last output, a.wpack_f set.
+namespace {
+constexpr int LDS_BYTES = 160 * 1024;
+[[maybe_unused]] constexpr int MAX_UNITS = (LDS_BYTES - (K7F_W_FLOATS + K7F_VT_FLOATS) * 4) / 16;
+// 8^3 tiles of one launch per workgroup
+int k47_per(int batch, int dim, int num_cus) {
+    const int tl = dim / 8, total = batch * tl * tl * tl;
+    const int grid = total < num_cus ? total : num_cus;
+    return (total + grid - 1) / grid;
+}
+}  // namespace
+
+#if !SE_K7F_PLANAR   // the unit table is the same for both input layouts
+bool se_conv3d_k7_wino47_fits(int batch, int dim, int num_cus) { return k47_per(batch, dim, num_cus) <= MAX_UNITS; }
+#endif
+
+// Preconditions (se_conv3d_plan): ksize 7, cout 16, dim % 8 == 0, dim >= 16, no residual, channels-last output, section F present, _fits.
 #if SE_K7F_PLANAR
 int se_conv3d_k7_wino47_launch_p3(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg) {
 #else
 int se_conv3d_k7_wino47_launch_cl(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg) {
 #endif
-    constexpr int LDS_BYTES = 160 * 1024;
-    constexpr int LDS_FIXED = (K7F_W_FLOATS + K7F_VT_FLOATS) * 4;
-    constexpr int MAX_UNITS = (LDS_BYTES - LDS_FIXED) / 16;
     SE_ENSURE_LDS(conv3d_k7_wino47_kernel, LDS_BYTES);
     const int tl = a.dim / 8;
     const int total = batch * tl * tl * tl;
-    const int grid = total < num_cus ? total : num_cus;
-    const int per = (total + grid - 1) / grid;
-    if (per > MAX_UNITS) return SE_TILED_NOT_TAKEN;
+    const int per = k47_per(batch, a.dim, num_cus);
     hipLaunchKernelGGL(conv3d_k7_wino47_kernel, dim3((total + per - 1) / per), dim3(512), LDS_BYTES, s, a, tl, tl, total, per, dbg);
     SE_CHECK_LAUNCH();
     return 0;

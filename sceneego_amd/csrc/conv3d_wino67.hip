@@ -21,7 +21,7 @@
 // inside the MFMA stream; L2 serves the 113 KB per item.  Measured steps (33->16 @64^3, B = 8; F(4,7) kernel 2.34 ms): first form
 // with register-staged refill and global loads 1.97, + A^T per item 2.06 (accuracy), operand reads 3 + 3 ahead of 10 MFMAs 2.02,
 // buffer loads 1.92, LDS-DMA 1.80 ms; without any rider 1.63 ms = the MFMA issue time (profiles/r03_k67_*).
-#include "conv_common.h"
+#include "conv3d_plan.h"
 #include "wino67_matrices.h"
 
 #include <type_traits>
@@ -390,30 +390,45 @@ __global__ __launch_bounds__(256) void k7_combine_kernel(float* __restrict__ out
 
 }  // namespace
 
-// Returns 0 on launch, SE_TILED_NOT_TAKEN if the shape / unit table is not covered, else a hipError_t.  Preconditions (checked by the
-// caller, se_conv3d_k7_wino_try): ksize 7, cout 16, no residual, channels-last output, a.wpack_h set.
-int se_conv3d_k7_wino67_launch(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg) {
-    constexpr int LDS_BYTES = 160 * 1024;
-    constexpr int MAX_UNITS = (LDS_BYTES - S_LDS_FIXED) / 16;
-    const int dim = a.dim;
-    if (dim < 16 || (dim & 15)) return SE_TILED_NOT_TAKEN;
-    // 32-bit buffer offsets inside one sample (channels-last) / one chunk volume (triplet-planar); bit 31 marks out-of-volume lanes
-    if ((long long)dim * dim * dim * ((a.flags & SE_IN_PLANAR3) ? 12 : a.cin_pad * 4) >= (1LL << 31)) return SE_TILED_NOT_TAKEN;
-    const int tx = dim / S_TX, ty = dim / S_TY, tz = (dim + S_TZ - 1) / S_TZ;
-    const long long total_ll = (long long)batch * tx * ty * tz;
-    if (total_ll > (1 << 30)) return SE_TILED_NOT_TAKEN;
 #ifndef SE_K67_SPLIT
 #define SE_K67_SPLIT 1
 #endif
+namespace {
+constexpr int LDS_BYTES = 160 * 1024;
+constexpr int MAX_UNITS = (LDS_BYTES - S_LDS_FIXED) / 16;
+struct K67Geom {
+    int tx, ty, tz, halves, total, per;
+};
+// Launch geometry of `batch` samples; false if the kernel cannot run them: dim % 16, 32-bit buffer offsets inside one sample
+// (channels-last) / one chunk volume (triplet-planar; bit 31 marks out-of-volume lanes), 30-bit unit indices, the unit table.
+bool k67_geom(const ConvArgs& a, int batch, int num_cus, K67Geom* g) {
+    const int dim = a.dim;
+    if (dim < 16 || (dim & 15)) return false;
+    if ((long long)dim * dim * dim * ((a.flags & SE_IN_PLANAR3) ? 12 : a.cin_pad * 4) >= (1LL << 31)) return false;
+    g->tx = dim / S_TX, g->ty = dim / S_TY, g->tz = (dim + S_TZ - 1) / S_TZ;
+    const long long total_ll = (long long)batch * g->tx * g->ty * g->tz;
+    if (total_ll > (1 << 30)) return false;
     // fewer than two tiles per CU (batch 1 at 64^3: 352 tiles = two rounds for 1.4 tiles' worth of work): units of half a tile's chunks
     // (704 units, at most 17 instead of 22 items per workgroup); needs the caller's workspace for the second halves' sums
-    const long long out_elems = a.total_vox * 16;
-    const bool split = SE_K67_SPLIT && total_ll < 2LL * num_cus && (a.cin + 2) / 3 >= 2 && a.ws && a.ws_elems >= out_elems;
-    const int halves = split ? 2 : 1;
-    const int total = (int)total_ll * halves;
-    const int grid = total < num_cus ? total : num_cus;
-    const int per = (total + grid - 1) / grid;
-    if (per > MAX_UNITS) return SE_TILED_NOT_TAKEN;
+    const bool split = SE_K67_SPLIT && total_ll < 2LL * num_cus && (a.cin + 2) / 3 >= 2 && a.ws && a.ws_elems >= (long long)batch * dim * dim * dim * 16;
+    g->halves = split ? 2 : 1;
+    g->total = (int)total_ll * g->halves;
+    const int grid = g->total < num_cus ? g->total : num_cus;
+    g->per = (g->total + grid - 1) / grid;
+    return g->per <= MAX_UNITS;
+}
+}  // namespace
+
+bool se_conv3d_k7_wino67_fits(const ConvArgs& a, int batch, int num_cus) {
+    K67Geom g;
+    return k67_geom(a, batch, num_cus, &g);
+}
+
+// Preconditions (se_conv3d_plan): ksize 7, cout 16, no residual, channels-last output, section H present, _fits.
+int se_conv3d_k7_wino67_launch(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg) {
+    K67Geom g;
+    if (!k67_geom(a, batch, num_cus, &g)) return SE_ERR_BAD_ARG;
+    const int tx = g.tx, ty = g.ty, tz = g.tz, total = g.total, per = g.per, halves = g.halves;
     if (a.flags & SE_IN_PLANAR3) {
         SE_ENSURE_LDS(conv3d_k7_wino67_kernel<true>, LDS_BYTES);
         hipLaunchKernelGGL(conv3d_k7_wino67_kernel<true>, dim3((total + per - 1) / per), dim3(512), LDS_BYTES, s, a, tx, ty, tz, total, per, halves, a.ws, dbg);
@@ -422,8 +437,8 @@ int se_conv3d_k7_wino67_launch(const ConvArgs& a, int batch, int num_cus, hipStr
         hipLaunchKernelGGL(conv3d_k7_wino67_kernel<false>, dim3((total + per - 1) / per), dim3(512), LDS_BYTES, s, a, tx, ty, tz, total, per, halves, a.ws, dbg);
     }
     SE_CHECK_LAUNCH();
-    if (split) {
-        const long long n4 = out_elems / 4;
+    if (halves == 2) {
+        const long long n4 = a.total_vox * 16 / 4;
         hipLaunchKernelGGL(k7_combine_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.out, a.ws, n4, (a.flags & SE_EPI_RELU) ? 1 : 0);
         SE_CHECK_LAUNCH();
     }

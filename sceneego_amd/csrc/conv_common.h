@@ -5,7 +5,6 @@
 // 7x7x7 tiled kernel: the 343 taps are taken 4 at a time on the MFMA k lanes -> 86 groups (last one has 1 pad tap)
 #define SE_K7_TAPS 343
 #define SE_K7_GROUPS 86
-#define SE_TILED_NOT_TAKEN (-1000)
 // 1-D Winograd section of the packed 3x3x3 weights: per (16-cin group, 32-cout block): 9 (dy,dx) x 4 xi x 2 cout tiles x 1 KiB
 #define SE_WINO_CHUNK_FLOATS (9 * 4 * 2 * 256)
 // F(4,3) variant (section E): 9 (dy,dx) x 6 xi x 2 cout tiles x 1 KiB = 108 KB per (16-cin group, 32-cout block)
@@ -71,17 +70,56 @@ inline bool se_wino2d_shape_ok(int dim, int cin, int cout) {
 // in-workgroup split-K kernel of the 8^3 level (32-voxel tiles, 512 workgroups, 47 us).  se_conv3d_f32_variant() reports it, the
 // V2V program asks per (batch, level).
 inline bool se_conv3d_small_volume(int batch, int dim) { return (long long)batch * dim * dim * dim <= 4096; }
+// Shapes of the 1-D Winograd F(4,3) 3^3 kernel (conv3d_wino.hip; 4 x 8 x 8 tiles, 16-channel chunks, 32-cout blocks) and of the
+// Winograd 7^3 kernels (conv3d_wino67.hip, conv3d_wino47.hip; 16 output channels) - as se_wino2d_shape_ok, for the plan and the queries.
+inline bool se_wino1d_shape_ok(int dim, int cin, int cout) { return dim >= 16 && (dim & 7) == 0 && (cout & 31) == 0 && (cin & 15) == 0; }
+inline bool se_k7_wino_shape_ok(int dim, int cout) { return dim >= 16 && (dim & 7) == 0 && cout == 16; }
+
+// The packed-weight buffer of one layer (se_conv3d_pack_f32): which sections it has, where each starts (in floats; -1: absent) and
+// its total size.  The ONE place that states a section's size and the condition under which it exists: se_conv3d_packed_elems
+// returns `total`, the packer writes every section at these offsets, the launcher points ConvArgs::wpack_* at them.
+//   A  every layer:        direct form                      [cg][tap][nt][lane][4]
+//   B  k = 7:              tap-lane form of the tiled kernel [chunk4][group 86][nt][lane][4]
+//   C  k = 3, cout % 32 == 0: 1-D Winograd F(2,3)            (development builds read it)
+//   D  k = 7, cout <= 16:  1-D Winograd F(2,7)               [chunk4][g13][xi8][lane][4] (development builds read it)
+//   E  k = 3, cout % 32 == 0: 1-D Winograd F(4,3)
+//   F  k = 7, cout <= 16:  1-D Winograd F(4,7)               [chunk3][g13][xi10][lane][3]
+//   G  k = 3, cout % 32 == 0: 2-D Winograd F(4,3) x F(2,3)
+//   H  k = 7, cout <= 16:  1-D Winograd F(6,7)               [chunk3][g37][lane][xi12]
+//   I  k = 3, cout % 32 == 0: 2-D Winograd F(4,3) x F(4,3)
+// Buffer order: A B D F H (k = 7), A C E G I (k = 3), A alone (k = 1, transposed k = 2).
+struct SePackLayout {
+    long long a, b, c, d, e, f, g, h, i, total;
+};
+inline SePackLayout se_conv3d_pack_layout(int cout, int cin_pad, int ksize, int transposed) {
+    const long long nts = round_up16(cout) / 16, cb = cout / 32, taps = transposed ? 8 : (long long)ksize * ksize * ksize;
+    const bool k7 = !transposed && ksize == 7, k7w = k7 && cout <= 16, k3w = !transposed && ksize == 3 && cout % 32 == 0;
+    long long n = 0;
+    auto section = [&n](bool present, long long elems) { const long long at = n; if (present) n += elems; return present ? at : -1LL; };
+    SePackLayout l;
+    l.a = section(true, taps * (cin_pad / 16) * nts * 256);
+    l.b = section(k7, (long long)(cin_pad / 4) * SE_K7_GROUPS * nts * 256);
+    l.c = section(k3w, (cin_pad / 16) * cb * SE_WINO_CHUNK_FLOATS);
+    l.d = section(k7w, (long long)(cin_pad / 4) * SE_K7W_CHUNK_FLOATS);
+    l.e = section(k3w, (cin_pad / 16) * cb * SE_WINO43_CHUNK_FLOATS);
+    l.f = section(k7w, (long long)((cin_pad + 2) / 3) * SE_K7F_CHUNK_FLOATS);
+    l.g = section(k3w, (cin_pad / 8) * cb * SE_WINO2D_CHUNK_FLOATS);
+    l.h = section(k7w, (long long)((cin_pad + 2) / 3) * SE_K7H_CHUNK_FLOATS);
+    l.i = section(k3w, (cin_pad / 4) * cb * SE_WINO44_CHUNK_FLOATS);
+    l.total = n;
+    return l;
+}
 
 struct ConvArgs {
     const float* in;
-    const float* wpack;    // section A: [cg][tap][nt][lane][4]
-    const float* wpack_b;  // k = 7: section B [chunk4][group][nt][lane][4];  k = 3: Winograd section C (NULL if cout % 32)
-    const float* wpack_e;  // k = 3, cout % 32 == 0: Winograd F(4,3) section E (else NULL)
-    const float* wpack_d;  // k = 7, cout <= 16: Winograd F(2,7) section D [chunk4][g13][xi8][lane][4] (else NULL)
-    const float* wpack_f;  // k = 7, cout <= 16: Winograd F(4,7) section F [chunk3][g13][xi10][lane][3] (else NULL)
-    const float* wpack_h;  // k = 7, cout <= 16: Winograd F(6,7) section H [chunk3][g37][lane][xi12] (else NULL)
-    const float* wpack_i;  // k = 3, cout % 32 == 0: 2-D Winograd F(4,3) x F(4,3) section I (else NULL)
-    const float* wpack_g;  // k = 3, cout % 32 == 0: 2-D Winograd F(4,3) x F(2,3) section G (else NULL)
+    const float* wpack;    // section A
+    const float* wpack_b;  // k = 7: section B;  k = 3: section C (NULL when absent, as every section pointer below)
+    const float* wpack_e;  // section E
+    const float* wpack_d;  // section D
+    const float* wpack_f;  // section F
+    const float* wpack_h;  // section H
+    const float* wpack_i;  // section I
+    const float* wpack_g;  // section G
     const float* skip_w;   // SE_EPI_SKIPCONV16: folded 1x1x1 skip weights [cout][16]; `res` then is the skip convolution's 16-channel input
     float* pool_out;       // 2-D Winograd kernel only: also write max_pool3d(out, 2, 2), channels-last [B][D/2][D/2][D/2][cout] (else NULL)
     const float* bpack;

@@ -13,10 +13,12 @@ NP = int(os.environ.get("SE_STAMP_PHASES", "4"))
 dbg = torch.zeros(256 * 8 * NP, dtype=torch.int64, device=dev)
 for _ in range(3):
     _lib.conv3d(x, pc.w, pc.b, res, out, B, dim, cin, cin, cout, 3, 3, None)
+lib.se_debug_set_variant(4)        # the retired 1-D F(2,3) kernel: the one that has this stamp build
 lib.se_debug_set_stamp_buffer(ctypes.c_void_p(dbg.data_ptr()))
 _lib.conv3d(x, pc.w, pc.b, res, out, B, dim, cin, cin, cout, 3, 3, None)
 torch.cuda.synchronize()
 lib.se_debug_set_stamp_buffer(None)
+lib.se_debug_set_variant(0)
 d = dbg.view(256, 8, NP).double()
 tot = d.sum(dim=2)
 print("per-wave total cycles: mean %.0f min %.0f max %.0f" % (tot.mean(), tot.min(), tot.max()))
