@@ -3,11 +3,12 @@
 15x3 joints per image.
 
     python demo.py --config experiments/sceneego/test/sceneego.yaml --img_dir data/demo/imgs \\
-                   --depth_dir data/demo/depths --output_dir data/demo/out [--weights synthetic]
+                   --depth_dir data/demo/depths --output_dir data/demo/out [--weights synthetic] [--stats true]
 
 Differences: ``--vis`` (open3d GUI) is out of scope; depth maps are read from ``<img_name>.exr`` (the reference's format:
 scanline OpenEXR, NONE/ZIP/PIZ, decoded by ``sceneego_amd/exr.py``) or ``.npy`` / ``.npz``; ``--weights synthetic`` uses the portable seeded weights when no checkpoint exists
-(``config.test.model_path`` is loaded strictly otherwise, exactly like ``demo.py:29-31``).
+(``config.test.model_path`` is loaded strictly otherwise, exactly like ``demo.py:29-31``); ``--stats true`` writes
+``<img_name>.stats.pkl`` beside each ``<img_name>.pkl``: the per-joint statistics of ``VoxelNetwork_depth.joint_statistics``.
 """
 import argparse
 import os
@@ -17,6 +18,7 @@ import torch
 
 from sceneego_amd import load_config, synth
 from sceneego_amd.jpeg_device import JpegFile, decode_jpeg_batch
+from sceneego_amd.op import joint_statistics_to_numpy
 from sceneego_amd.preprocess import (DEPTH_CLAMP, load_depth, load_image_bgr, prepare_depth, preprocess_image,
                                      preprocess_image_device)
 from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
@@ -27,12 +29,13 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 
 class Demo:
-    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device"):
+    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
         self.config = config
         self.image_decode = image_decode
+        self.stats = stats
         self.items = []
         for img_name in sorted(os.listdir(img_dir)):
             img_path = os.path.join(img_dir, img_name)
@@ -72,14 +75,17 @@ class Demo:
                     depth = torch.from_numpy(d).to(self.device).clamp_(max=DEPTH_CLAMP)[None]
                 else:
                     depth = prepare_depth(d, W, H)[None].to(self.device)
-                kp, _, _, _ = self.network(img, self.network.grid_coord_proj_batch, self.network.coord_volumes,
-                                           depth_map_batch=depth)
+                kp, _, volumes, _ = self.network(img, self.network.grid_coord_proj_batch, self.network.coord_volumes,
+                                                 depth_map_batch=depth)
                 assert len(kp) == 1
                 results.append({"img_path": img_path, "predicted_keypoints": kp.cpu().numpy()[0]})
+                if self.stats:
+                    # the volumes are the replayed graph's static buffers: reduced here, before the next frame overwrites them
+                    results[-1]["stats"] = joint_statistics_to_numpy(self.network.joint_statistics(volumes, kp))[0]
         return results
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="experiments/sceneego/test/sceneego.yaml")
     ap.add_argument("--img_dir", type=str, default="data/demo/imgs")
@@ -87,17 +93,30 @@ def main():
     ap.add_argument("--output_dir", type=str, default="data/demo/out")
     ap.add_argument("--vis", type=str, default="false")
     ap.add_argument("--weights", type=str, default=None, help="checkpoint path, or 'synthetic'")
-    args = ap.parse_args()
+    ap.add_argument("--stats", type=str, default="false",
+                    help="true: also write <img_name>.stats.pkl (per-joint cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
+    args = ap.parse_args(argv)
     if args.vis.lower() == "true":
         raise SystemExit("--vis true (open3d visualisation) is out of scope of this build")
+    if args.stats.lower() not in ("true", "false"):
+        raise SystemExit("--stats must be true or false")
+    args.stats = args.stats.lower() == "true"
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     config = load_config(args.config)
-    demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights)
+    demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats)
     os.makedirs(args.output_dir, exist_ok=True)
     for r in demo.run():
         out_path = os.path.join(args.output_dir, os.path.split(r["img_path"])[1] + ".pkl")
         with open(out_path, "wb") as f:
             pickle.dump(r["predicted_keypoints"], f)      # np.float32 [15,3], reference demo.py:88-97
         print(out_path, r["predicted_keypoints"][0])
+        if args.stats:
+            with open(out_path[:-4] + ".stats.pkl", "wb") as f:
+                pickle.dump(r["stats"], f)                # dict of numpy arrays, the keys of op.joint_statistics
 
 
 if __name__ == "__main__":

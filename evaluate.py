@@ -21,7 +21,7 @@ if ROOT not in sys.path:
 
 
 def load_predictions(pred_dir):
-    names = sorted(n for n in os.listdir(pred_dir) if n.endswith(".pkl"))
+    names = sorted(n for n in os.listdir(pred_dir) if n.endswith(".pkl") and not n.endswith(".stats.pkl"))
     if not names:
         raise SystemExit(f"no .pkl predictions in {pred_dir}")
     poses = []
@@ -32,6 +32,25 @@ def load_predictions(pred_dir):
             raise SystemExit(f"{n}: expected a [15,3] pose, got {p.shape}")
         poses.append(p)
     return names, np.stack(poses)
+
+
+def load_sigma(path, names):
+    """[T,15] sigma of the frames behind the prediction files ``names``: from a directory of ``<image name>.stats.pkl`` files or from
+    one pickle holding the list of per-frame dicts in the same (sorted file) order."""
+    if os.path.isdir(path):
+        frames = []
+        for n in names:
+            with open(os.path.join(path, n[:-4] + ".stats.pkl"), "rb") as f:
+                frames.append(pickle.load(f))
+    else:
+        with open(path, "rb") as f:
+            frames = pickle.load(f)
+    if len(frames) != len(names):
+        raise SystemExit(f"{path}: statistics of {len(frames)} frames for {len(names)} predictions")
+    sigma = np.stack([np.asarray(fr["sigma"], dtype=np.float64) for fr in frames])
+    if sigma.shape != (len(names), 15):
+        raise SystemExit(f"{path}: expected sigma of shape ({len(names)}, 15), got {sigma.shape}")
+    return sigma
 
 
 def match_ground_truth(gt, names):
@@ -61,6 +80,9 @@ def main(argv=None):
     ap.add_argument("--gt", required=True, help="pickle: dict name -> [15,3], or [T,15,3] in sorted file order")
     ap.add_argument("--no-scale", action="store_true", help="rigid instead of similarity alignment (align_skeleton(scale=False))")
     ap.add_argument("--unit", default="m", help="label only; the numbers are in the unit of the inputs")
+    ap.add_argument("--stats", default=None, help="joint statistics of the same frames: a directory of <image name>.stats.pkl files "
+                    "(demo.py --stats true) or the one pickle of run_sequence.py --stats_output; adds the error per sigma quantile")
+    ap.add_argument("--stats_bins", type=int, default=4, help="number of sigma quantile bins of --stats")
     args = ap.parse_args(argv)
     names, pred = load_predictions(args.pred_dir)
     with open(args.gt, "rb") as f:
@@ -69,6 +91,12 @@ def main(argv=None):
     print(f"{r['frames']} frames  MPJPE {r['mpjpe']:.6f} {args.unit}  PA-MPJPE {r['pa_mpjpe']:.6f} {args.unit}  "
           f"root trajectory {r['root_trajectory']:.6f} {args.unit}")
     print("per joint: " + " ".join(f"{v:.4f}" for v in r["per_joint"]))
+    if args.stats is not None:
+        from sceneego_amd import metrics as M
+        c = M.error_by_confidence(pred, gt, load_sigma(args.stats, names), bins=args.stats_bins)
+        r["by_confidence"] = c
+        print("error by sigma quantile (low to high): " + " ".join(f"{v:.4f}" for v in c["bin_mean_error"]) + f" {args.unit}")
+        print(f"spearman(error, sigma): {c['spearman']:.4f} over {c['pairs']} joints")
     return r
 
 

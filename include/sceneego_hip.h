@@ -255,6 +255,26 @@ int se_softargmax3d_finish_f32(const float* vol, const float* scratch, float* ou
                                int mode, void* stream);
 long long se_softargmax3d_scratch_elems(int rows);
 
+/* Per-joint statistics of the softmaxed volumes (no counterpart in the reference, which returns the volumes and leaves it at that).
+ *   prob   [rows][voxels] float32 probabilities, as se_softargmax3d_f32 / se_softargmax3d_finish_f32 write them in mode 1
+ *   coord  [voxels][3] float32 voxel-centre coordinates
+ *   joints [rows][3] the soft-argmax joints
+ *   stats  [rows][12]: 0..5  cxx cyy czz cxy cxz cyz, c_ab = sum_n p_n (c_na - j_a)(c_nb - j_b): the second central moment ABOUT
+ *                            `joints` (m^2)
+ *                      6     entropy -sum_n p_n ln p_n (nats; p_n == 0 contributes 0)
+ *                      7     peak_p = max_n p_n
+ *                      8..10 coord[peak_index]
+ *                      11    sigma = sqrtf((cxx + cyy) + czz) (m)
+ *   peak_index [rows] int32: the LOWEST flat index with p_n == peak_p
+ *   scratch: se_joint_stats_scratch_elems(rows) floats of workspace.
+ * A row that holds a NaN probability gets 12 NaNs and peak_index -1; other rows are unaffected.  Two launches on `stream`
+ * (se_sa_splits(rows) chunks per row as the soft-argmax, then one wave per row), no atomics: bitwise identical from run to run.
+ * Allocates nothing (legal inside hipGraph capture).  rows <= 0, rows > 65535, voxels <= 0, voxels & 3, a null pointer or a
+ * prob / coord that is not 16-byte aligned -> SE_ERR_BAD_ARG.                                                                 */
+int se_joint_stats_f32(const float* prob, const float* coord, const float* joints, float* stats, int* peak_index,
+                       float* scratch, int rows, int voxels, void* stream);
+long long se_joint_stats_scratch_elems(int rows);
+
 /* Producers of the triplet-planar float32 V2V input [B][triplets_total][voxels][3] (SE_IN_PLANAR3; the 7^3 front layer
  * fetches its halo columns from ~5x fewer cache lines than from the channels-last record).  Same arithmetic, bit for bit, as
  * se_unproject_gather_f32 / se_voxelize_strided_f64.  The gather writes channels [0, channels) (channels = 16, 32 or 64) and

@@ -4,7 +4,7 @@
 
     python run_sequence.py --root_dir data --seq_name new_diogo1 --estimated_depth_name matterport_green \\
                            --output out/no_body_diogo1.pkl [--weights synthetic] [--depth_decode device|host]
-                           [--image_decode device|host] [--streams 2]
+                           [--image_decode device|host] [--streams 2] [--stats_output out/no_body_diogo1.stats.pkl]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -15,7 +15,8 @@ PIL in that pool; the image path is then demo.py's (``se_preprocess_image_u8`` f
 ``exr_device.decode_depth_exr_batch(..., out_hw=(1024, 1280))`` (PIZ, ZIP, ZIPS and NONE decoded on the device) or, with
 ``--depth_decode host``,
 through ``exr.py`` + ``prepare_depth`` - the same values either way (``TestDataset.__getitem__``: nearest resize to 1280x1024, clamp
-to 10 m).  The pickle holds the list of float32 [15, 3] predictions, as ``test.py`` writes it.
+to 10 m).  The pickle holds the list of float32 [15, 3] predictions, as ``test.py`` writes it.  ``--stats_output`` adds a second
+pickle: the per-joint statistics of every frame (``VoxelNetwork_depth.joint_statistics``), taken per batch on the stream it ran on.
 """
 import argparse
 import json
@@ -107,19 +108,23 @@ class SequenceRunner:
         return torch.stack([prepare_depth(load_depth(p), W, H) for p in paths]).to(self.device)
 
     @torch.no_grad()
-    def run(self, images, depths, batch_size):
+    def run(self, images, depths, batch_size, stats=False):
+        """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts)."""
         from sceneego_amd.jpeg_device import JpegFile
+        from sceneego_amd.op import joint_statistics_to_numpy
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
-        preds, pending = [], []
+        preds, frame_stats, pending = [], [], []
 
         def drain(keep):
             while len(pending) > keep:
-                kp, done = pending.pop(0)
+                kp, st, done = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 preds.extend(np.asarray(k, dtype=np.float32) for k in kp.cpu().numpy())
+                if st is not None:
+                    frame_stats.extend(joint_statistics_to_numpy(st))
 
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             ahead = [pool.submit(load, p) for p in batches[0][0]] if batches else []
@@ -130,14 +135,23 @@ class SequenceRunner:
                 img = self._images(frames)
                 depth = self._depths(deps)
                 if self.pipe is None:
-                    kp, _, _, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
-                    pending.append((kp, None))
+                    kp, _, vol, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
+                    pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None))
                 else:
-                    (kp, _, _, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
-                    pending.append((kp, done))
+                    net, stream = self.pipe.next_slot()
+                    (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
+                    st = None
+                    if stats:
+                        # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
+                        # buffers back only after the statistics are complete
+                        with torch.cuda.stream(stream):
+                            st = net.joint_statistics(vol, kp)
+                            done = torch.cuda.Event()
+                            done.record(stream)
+                    pending.append((kp, st, done))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             drain(0)
-        return preds
+        return (preds, frame_stats) if stats else preds
 
 
 def main(argv=None):
@@ -154,6 +168,8 @@ def main(argv=None):
     ap.add_argument("--streams", type=int, default=1, help="forwards in flight (PipelinedForward when > 1)")
     ap.add_argument("--workers", type=int, default=8, help=f"JPEG read / parse (host decode: decode) threads (at most {MAX_WORKERS})")
     ap.add_argument("--output", default=None, help="pickle of the predicted [15,3] joints of every frame")
+    ap.add_argument("--stats_output", default=None, help="pickle of the per-frame joint statistics (list of dicts of numpy arrays: "
+                    "cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
     args = ap.parse_args(argv)
     config = load_config(args.config)
     images, poses, depths = frame_list(args.root_dir, args.seq_name, args.estimated_depth_name)
@@ -164,7 +180,10 @@ def main(argv=None):
                             workers=args.workers, image_decode=args.image_decode)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    preds = runner.run(images, depths, config.test.batch_size)
+    want_stats = args.stats_output is not None
+    preds = runner.run(images, depths, config.test.batch_size, stats=want_stats)
+    if want_stats:
+        preds, frame_stats = preds
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -177,7 +196,13 @@ def main(argv=None):
         os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
         with open(args.output, "wb") as f:
             pickle.dump(preds, f)
-    return {"frames": len(preds), "mpjpe": mpjpe, "pa_mpjpe": pampjpe, "fps": len(preds) / dt, "predictions": preds}
+    result = {"frames": len(preds), "mpjpe": mpjpe, "pa_mpjpe": pampjpe, "fps": len(preds) / dt, "predictions": preds}
+    if want_stats:
+        os.makedirs(os.path.dirname(os.path.abspath(args.stats_output)), exist_ok=True)
+        with open(args.stats_output, "wb") as f:
+            pickle.dump(frame_stats, f)
+        result["stats"] = frame_stats
+    return result
 
 
 if __name__ == "__main__":

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -65,6 +65,8 @@ SIGNATURES = {
     "se_softargmax3d_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "se_softargmax3d_scratch_elems": (_ll, [_i]),
     "se_softargmax3d_finish_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "se_joint_stats_scratch_elems": (_ll, [_i]),
+    "se_joint_stats_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "se_pointwise_chain3_softargmax_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "se_conv3d_pack_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "se_conv3d_packed_elems_bf16": (_ll, [_i, _i, _i, _i]),
@@ -810,3 +812,43 @@ def softargmax3d(vol, coord, out_vol, joints, rows, voxels, mode, scratch=None):
         scratch = torch.empty(softargmax3d_scratch_elems(rows), device=vol.device, dtype=torch.float32)
     _check(load().se_softargmax3d_f32(_ptr(vol), _ptr(coord), _ptr(out_vol), _ptr(joints), _ptr(scratch), rows,
                                       voxels, mode, _stream()), "se_softargmax3d_f32")
+
+
+def joint_stats_scratch_elems(rows) -> int:
+    return int(load().se_joint_stats_scratch_elems(rows))
+
+
+JOINT_STATS_SLOTS = 12     # cxx cyy czz cxy cxz cyz entropy peak_p peak_x peak_y peak_z sigma (include/sceneego_hip.h)
+
+
+def joint_stats(prob, coord, joints, stats, peak_index, rows, voxels, scratch=None):
+    """se_joint_stats_f32: per-row covariance about ``joints``, entropy and peak of the softmaxed volumes ``prob`` [rows, voxels]
+    into ``stats`` [rows, 12] float32 and ``peak_index`` [rows] int32.  Every argument is checked here and a bad one raises
+    HipExtensionError before anything is launched: the kernel reads with 16-byte loads and trusts the sizes it is given."""
+    def bad(msg):
+        raise HipExtensionError("joint_stats: " + msg)
+    named = (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
+             ("joints", joints, torch.float32, rows * 3), ("stats", stats, torch.float32, rows * JOINT_STATS_SLOTS),
+             ("peak_index", peak_index, torch.int32, rows))
+    if rows <= 0 or voxels <= 0 or voxels % 4:
+        bad(f"rows = {rows}, voxels = {voxels}: both must be positive and voxels a multiple of 4")
+    for name, t, dtype, numel in named + ((("scratch", scratch, torch.float32, None),) if scratch is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            bad(f"{name} is not a tensor")
+        if not t.is_cuda:
+            bad(f"{name} is on {t.device}: the operator needs tensors on a HIP device")
+        if t.dtype != dtype:
+            bad(f"{name} is {t.dtype}, expected {dtype}")
+        if not t.is_contiguous():
+            bad(f"{name} is not contiguous")
+        if numel is not None and t.numel() != numel:
+            bad(f"{name} has {t.numel()} elements, expected {numel} for rows = {rows}, voxels = {voxels}")
+        if t.device != prob.device:
+            bad(f"{name} is on {t.device}, prob on {prob.device}")
+    need = joint_stats_scratch_elems(rows)
+    if scratch is None:
+        scratch = torch.empty(need, device=prob.device, dtype=torch.float32)
+    elif scratch.numel() < need:
+        bad(f"scratch has {scratch.numel()} elements, needs {need}")
+    _check(load().se_joint_stats_f32(_ptr(prob), _ptr(coord), _ptr(joints), _ptr(stats), _ptr(peak_index), _ptr(scratch), rows,
+                                     voxels, _stream()), "se_joint_stats_f32")

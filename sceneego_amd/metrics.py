@@ -86,3 +86,57 @@ def global_align_sequence(estimated, gt):
     est = np.asarray(estimated, dtype=np.float64)
     c, R, t = umeyama(est.reshape(-1, 3), np.asarray(gt, dtype=np.float64).reshape(-1, 3))
     return (c * (est.reshape(-1, 3) @ R) + t).reshape(est.shape)
+
+
+def _average_ranks(x):
+    """Ranks 1..n of a 1-D float64 array, ties sharing the mean of their ranks (what Spearman's coefficient is defined on)."""
+    order = np.argsort(x, kind="stable")
+    xs = x[order]
+    start = np.concatenate(([True], xs[1:] != xs[:-1]))          # first element of every run of equal values
+    first = np.flatnonzero(start)
+    last = np.concatenate((first[1:], [len(xs)])) - 1
+    run = np.cumsum(start) - 1
+    ranks = np.empty(len(x), dtype=np.float64)
+    ranks[order] = 0.5 * (first[run] + last[run]) + 1.0
+    return ranks
+
+
+def error_by_confidence(estimated, gt, sigma, bins: int = 4):
+    """Does the soft-argmax's own spread say where it is wrong?  ``estimated`` / ``gt`` [T,J,3], ``sigma`` [T,J] (the ``sigma`` of
+    ``op.joint_statistics``; any per-joint spread in any unit works: only its order is used).
+
+    All (frame, joint) pairs with a finite sigma are sorted by sigma (stable) and cut into ``bins`` groups of equal count (the first
+    ``n % bins`` groups hold one more): the sigma quantile bins, lowest first.  Returns a dict:
+      ``bin_mean_error`` [bins]  mean Euclidean joint error inside each bin (NaN for an empty bin)
+      ``bin_sigma_max``  [bins]  the largest sigma of each bin (its upper quantile edge)
+      ``bin_count``      [bins]
+      ``spearman``               rank correlation of error and sigma (average ranks for ties; NaN when either is constant)
+      ``pairs``                  number of pairs used
+    numpy, float64."""
+    est = np.asarray(estimated, dtype=np.float64)
+    ref = np.asarray(gt, dtype=np.float64)
+    sig = np.asarray(sigma, dtype=np.float64)
+    if est.shape != ref.shape or est.shape[-1] != 3 or sig.shape != est.shape[:-1]:
+        raise ValueError(f"shape mismatch: estimated {est.shape}, gt {ref.shape}, sigma {sig.shape}")
+    if bins < 1:
+        raise ValueError("bins must be >= 1")
+    err = np.linalg.norm(est - ref, axis=-1).reshape(-1)
+    sig = sig.reshape(-1)
+    keep = np.isfinite(sig) & np.isfinite(err)
+    err, sig = err[keep], sig[keep]
+    order = np.argsort(sig, kind="stable")
+    groups = np.array_split(order, bins)
+    nan = float("nan")
+    out = {"bin_mean_error": np.array([err[g].mean() if len(g) else nan for g in groups], dtype=np.float64),
+           "bin_sigma_max": np.array([sig[g].max() if len(g) else nan for g in groups], dtype=np.float64),
+           "bin_count": np.array([len(g) for g in groups], dtype=np.int64), "pairs": int(len(err))}
+    rho = nan
+    if len(err) >= 2:
+        re, rs = _average_ranks(err), _average_ranks(sig)
+        re -= re.mean()
+        rs -= rs.mean()
+        den = np.sqrt((re * re).sum() * (rs * rs).sum())
+        if den > 0.0:
+            rho = float((re * rs).sum() / den)
+    out["spearman"] = rho
+    return out

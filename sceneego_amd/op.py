@@ -180,3 +180,54 @@ def integrate_tensor_3d_with_coordinates(volumes, coord_volumes, softmax=True):
     joints = torch.empty((B, J, 3), device=vol.device, dtype=torch.float32)
     _lib.softargmax3d(vol, coord, out_vol, joints, B * J, X * Y * Z, 1 if softmax else 0)
     return joints, out_vol
+
+
+STAT_KEYS = ("cov", "sigma", "entropy", "peak_prob", "peak_index", "peak_coord")
+
+
+def joint_statistics(volumes, coord_volumes, joints, scratch=None):
+    """How far to trust each soft-argmax joint (no counterpart in the reference): statistics of the softmaxed ``volumes``
+    [B,J,X,Y,Z] float32 as ``integrate_tensor_3d_with_coordinates`` returns them, about the ``joints`` [B,J,3] it returned with
+    them.  ``coord_volumes`` [>=1,X,Y,Z,3]: sample 0 is used, as there.  One pass over the volumes on the device
+    (``se_joint_stats_f32``); returns a dict of device tensors:
+
+      ``cov``        [B,J,3,3]  sum_n p_n (c_n - joint)(c_n - joint)^T in m^2, symmetric
+      ``sigma``      [B,J]      sqrt(trace(cov)) in metres
+      ``entropy``    [B,J]      -sum_n p_n ln p_n in nats
+      ``peak_prob``  [B,J]      max_n p_n
+      ``peak_index`` [B,J]      int32, the lowest flat voxel index that holds it
+      ``peak_coord`` [B,J,3]    that voxel's centre
+
+    A (sample, joint) whose volume holds a NaN gets NaN in every float entry and peak_index -1.  ``scratch``: an optional float32
+    workspace of at least ``_lib.joint_stats_scratch_elems(B * J)`` elements (allocated per call otherwise)."""
+    _lib.require_hip(volumes, joints)
+    if volumes.dim() != 5 or volumes.dtype != torch.float32:
+        raise _lib.HipExtensionError("joint_statistics: volumes must be [B,J,X,Y,Z] float32, got %s %s"
+                                     % (tuple(volumes.shape), volumes.dtype))
+    B, J, X, Y, Z = volumes.shape
+    if tuple(coord_volumes.shape[1:]) != (X, Y, Z, 3) or coord_volumes.shape[0] < 1:
+        raise _lib.HipExtensionError("joint_statistics: coord_volumes %s does not match volumes %s"
+                                     % (tuple(coord_volumes.shape), tuple(volumes.shape)))
+    if tuple(joints.shape) != (B, J, 3):
+        raise _lib.HipExtensionError("joint_statistics: joints %s, expected %s" % (tuple(joints.shape), (B, J, 3)))
+    coord = coord_volumes[0].to(device=volumes.device, dtype=torch.float32).contiguous()
+    return _joint_statistics_flat(volumes.contiguous(), coord, joints.contiguous().float(), B, J, X * Y * Z, scratch)
+
+
+def _joint_statistics_flat(vol, coord, joints, B, J, N, scratch):
+    rows = B * J
+    stats = torch.empty((rows, _lib.JOINT_STATS_SLOTS), device=vol.device, dtype=torch.float32)
+    peak_index = torch.empty((rows,), device=vol.device, dtype=torch.int32)
+    _lib.joint_stats(vol, coord, joints, stats, peak_index, rows, N, scratch=scratch)
+    s = stats.view(B, J, _lib.JOINT_STATS_SLOTS)
+    #                  xx xy xz  xy yy yz  xz yz zz   from cxx cyy czz cxy cxz cyz
+    cov = s[..., [0, 3, 4, 3, 1, 5, 4, 5, 2]].view(B, J, 3, 3)
+    return {"cov": cov, "sigma": s[..., 11], "entropy": s[..., 6], "peak_prob": s[..., 7],
+            "peak_index": peak_index.view(B, J), "peak_coord": s[..., 8:11]}
+
+
+def joint_statistics_to_numpy(stats):
+    """The dict of ``joint_statistics`` as a list of per-frame dicts of numpy arrays (the keys without the batch dimension): what
+    demo.py --stats and run_sequence.py --stats_output write."""
+    host = {k: stats[k].cpu().numpy() for k in STAT_KEYS}
+    return [{k: host[k][b].copy() for k in STAT_KEYS} for b in range(host["sigma"].shape[0])]

@@ -82,6 +82,11 @@ class PipelinedForward:
     def __len__(self):
         return len(self.nets)
 
+    def next_slot(self):
+        """(module replica, stream) the NEXT call will run on: a caller that post-processes a batch's outputs on the stream that
+        produced them (run_sequence.py --stats_output) asks before the call."""
+        return self.nets[self._next], self.streams[self._next]
+
     def enable_graphs(self, flag: bool = True):
         """Replay every replica's forward as a captured hipGraph (``VoxelNetwork_depth.enable_graphs``).  At batch 1 the eager pipeline is
         bound by the host's launch rate (~175 launches per frame from one Python thread): three streams give 357 frames/s eager and 567

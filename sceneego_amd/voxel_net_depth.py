@@ -114,6 +114,7 @@ class VoxelNetwork_depth(nn.Module):
         self.planar3_input = True      # float32 V2V input in the triplet-planar layout (False: channels-last; A/B switch)
         self._graphs = {}
         self._xbuf = {}
+        self._stats_ws = {}
         # V2V storage type: "fp32" (parity path, default) or "bf16" (BASELINE config 3: bf16 activations/weights,
         # float32 accumulation; joints differ from the float32 reference by more than 1e-3)
         self.v2v_dtype = torch.bfloat16 if str(config.model.get("v2v_dtype", "fp32")).lower() in ("bf16", "bfloat16") \
@@ -148,6 +149,7 @@ class VoxelNetwork_depth(nn.Module):
         self._folded = None
         self._graphs = {}
         self._xbuf = {}
+        self._stats_ws = {}
 
     def _load_from_state_dict(self, *a, **k):
         super()._load_from_state_dict(*a, **k)
@@ -360,6 +362,39 @@ class VoxelNetwork_depth(nn.Module):
         if self.materialize_features:
             features = self.process_features[2](self.process_features[1](feat2d.float()))
         return joints, features, volumes, self.coord_volumes
+
+    @torch.no_grad()
+    def joint_statistics(self, volumes, joints):
+        """Per-joint covariance, entropy and peak of the softmaxed ``volumes`` [B,J,G,G,G] about the ``joints`` [B,J,3] that
+        ``forward()`` returned with them: ``op.joint_statistics`` with the module's own ``coord_volumes`` (the dict of device tensors
+        described there: cov, sigma, entropy, peak_prob, peak_index, peak_coord).  One pass over the volumes on the current stream;
+        the partial-record workspace is cached per (device, rows).  ``forward()`` itself is unchanged: pass what it returned.
+
+        Under ``enable_graphs(True)`` the volumes and joints are the graph's STATIC buffers, overwritten by the next replay: take the
+        statistics before the next ``forward()`` (the call is queued on the current stream, so stream order is enough).
+
+        Raises ValueError when ``config.model.volume_softmax`` is false: the ReLU volumes are not a distribution."""
+        if not self.volume_softmax:
+            raise ValueError("joint_statistics needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        _lib.require_hip(volumes, joints)
+        G = self.volume_size
+        if volumes.dim() != 5 or tuple(volumes.shape[2:]) != (G, G, G) or volumes.dtype != torch.float32:
+            raise _lib.HipExtensionError("joint_statistics: volumes must be [B,J,%d,%d,%d] float32, got %s %s"
+                                         % (G, G, G, tuple(volumes.shape), volumes.dtype))
+        B, J = int(volumes.shape[0]), int(volumes.shape[1])
+        if tuple(joints.shape) != (B, J, 3):
+            raise _lib.HipExtensionError("joint_statistics: joints %s, expected %s" % (tuple(joints.shape), (B, J, 3)))
+        dev = volumes.device
+        # the module's own grid, whatever tables the last forward was given (they are keyed on its arguments)
+        coord = self._stats_ws.get((str(dev), "coord"))
+        if coord is None:
+            coord = self._stats_ws[(str(dev), "coord")] = \
+                self.coord_volumes[0].reshape(G * G * G, 3).to(device=dev, dtype=torch.float32).contiguous()
+        key = (str(dev), B * J)
+        ws = self._stats_ws.get(key)
+        if ws is None:
+            ws = self._stats_ws[key] = torch.empty(_lib.joint_stats_scratch_elems(B * J), device=dev, dtype=torch.float32)
+        return op._joint_statistics_flat(volumes.contiguous(), coord, joints.contiguous().float(), B, J, G * G * G, ws)
 
     def _voxelise(self, x, planar3, fast_occ, prog, scene_volumes, depth_map_batch, B, G, N, C, dev, planar1=False):
         """Occupancy into the V2V input buffer ``x`` (reference ``:246-262``)."""
