@@ -9,6 +9,8 @@ Differences: ``--vis`` (open3d GUI) is out of scope; depth maps are read from ``
 scanline OpenEXR, NONE/ZIP/PIZ, decoded by ``sceneego_amd/exr.py``) or ``.npy`` / ``.npz``; ``--weights synthetic`` uses the portable seeded weights when no checkpoint exists
 (``config.test.model_path`` is loaded strictly otherwise, exactly like ``demo.py:29-31``); ``--stats true`` writes
 ``<img_name>.stats.pkl`` beside each ``<img_name>.pkl``: the per-joint statistics of ``VoxelNetwork_depth.joint_statistics``.
+``--render_dir DIR`` writes ``<img_name>.render.png`` (scene point cloud and skeleton from a third-person view) and
+``<img_name>.overlay.png`` (the skeleton in the fisheye frame) per frame, rendered on the device (``sceneego_amd/render.py``).
 """
 import argparse
 import os
@@ -29,13 +31,15 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 
 class Demo:
-    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False):
+    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
         self.config = config
         self.image_decode = image_decode
         self.stats = stats
+        self.render_dir = render_dir
+        self.renderer = None
         self.items = []
         for img_name in sorted(os.listdir(img_dir)):
             img_path = os.path.join(img_dir, img_name)
@@ -62,11 +66,14 @@ class Demo:
                 jpeg = JpegFile(img_path) if self.image_decode == "device" else None
                 if jpeg is not None and jpeg.device and (jpeg.H, jpeg.W) == full:
                     # JPEG decoded on the device (bit-identical to load_image_bgr), then se_preprocess_image_u8
-                    img = preprocess_image_device(decode_jpeg_batch([jpeg], self.device), self.config.image_shape)
+                    frame_u8 = decode_jpeg_batch([jpeg], self.device)
+                    img = preprocess_image_device(frame_u8, self.config.image_shape)
                 elif (frame := load_image_bgr(img_path)).shape[:2] == full:
                     # raw uint8 frame to the device; crop / quarter-resize / normalise there (se_preprocess_image_u8)
-                    img = preprocess_image_device(torch.from_numpy(frame).to(self.device), self.config.image_shape)
+                    frame_u8 = torch.from_numpy(frame).to(self.device)[None]
+                    img = preprocess_image_device(frame_u8, self.config.image_shape)
                 else:
+                    frame_u8 = torch.from_numpy(frame)[None]
                     img = preprocess_image(frame, self.config.image_shape)[None].to(self.device)
                 d = load_depth(depth_path)
                 if d.shape == (H // 2, W // 2):
@@ -82,7 +89,21 @@ class Demo:
                 if self.stats:
                     # the volumes are the replayed graph's static buffers: reduced here, before the next frame overwrites them
                     results[-1]["stats"] = joint_statistics_to_numpy(self.network.joint_statistics(volumes, kp))[0]
+                if self.render_dir is not None:
+                    self.render(os.path.split(img_path)[1], frame_u8, depth, kp)
         return results
+
+    def render(self, img_name, frame_u8, depth, kp):
+        """<img_name>.render.png and <img_name>.overlay.png into render_dir; reads the forward's results, changes none."""
+        from sceneego_amd.render import SceneRenderer, save_png
+        if self.renderer is None:
+            from sceneego_amd.config import resolve_calibration_path
+            calib = resolve_calibration_path(self.config.dataset.camera_calibration_path)
+            self.renderer = SceneRenderer(calib, frame_size=(self.config.dataset.image_height, self.config.dataset.image_width),
+                                          device=self.device)
+        os.makedirs(self.render_dir, exist_ok=True)
+        save_png(os.path.join(self.render_dir, img_name + ".render.png"), self.renderer.render(depth, frame_u8, kp)[0])
+        save_png(os.path.join(self.render_dir, img_name + ".overlay.png"), self.renderer.overlay(frame_u8, kp, depth=depth)[0])
 
 
 def parse_args(argv=None):
@@ -95,6 +116,8 @@ def parse_args(argv=None):
     ap.add_argument("--weights", type=str, default=None, help="checkpoint path, or 'synthetic'")
     ap.add_argument("--stats", type=str, default="false",
                     help="true: also write <img_name>.stats.pkl (per-joint cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
+    ap.add_argument("--render_dir", type=str, default=None,
+                    help="also write <img_name>.render.png and <img_name>.overlay.png here (rendered on the device; no display needed)")
     args = ap.parse_args(argv)
     if args.vis.lower() == "true":
         raise SystemExit("--vis true (open3d visualisation) is out of scope of this build")
@@ -107,7 +130,7 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     config = load_config(args.config)
-    demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats)
+    demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats, render_dir=args.render_dir)
     os.makedirs(args.output_dir, exist_ok=True)
     for r in demo.run():
         out_path = os.path.join(args.output_dir, os.path.split(r["img_path"])[1] + ".pkl")

@@ -499,6 +499,48 @@ int se_jpeg_decode_bgr_u8(const void* payload, long long payload_bytes, const in
                           int n_segs, const void* tables, const int* quant, const long long* layout, unsigned char* out, int n_out,
                           int out_h, int out_w, void* scratch, long long scratch_bytes, int* status, int rounds, void* stream);
 
+/* Headless renderer (stands in for the reference's visualize.py: utils/depth2pointcloud.py get_point_cloud_single_image +
+ * utils/skeleton.py joints_2_mesh, drawn by open3d).  All arithmetic is float64, unfused, in the order written here
+ * (tests/render_model.py restates it).  joint_rgb, bone_rgb (3 floats in [0, 1], R G B) and background (3 bytes, R G B) are HOST
+ * pointers, read during the call; every other pointer is device memory.  batch <= 65535; splat 1..4; near >= 0.
+ *
+ * se_render_splat_f64: point cloud -> z-buffer of a pinhole view.  One thread per frame pixel (y, x):
+ *   depth    [B][depth_h][depth_w] float32 metres        ray_tab [height][width][3] float64: the calibrated camera's ray of (x, y)
+ *   image    [B][height][width][3] uint8 (B, G, R)        view    [12] float64: row-major R[3][3], then t[3]
+ *   zbuf     [B][out_h][out_w] uint64, cleared to all-ones ("no point") inside, then written
+ *   1. d = depth[b][(y * depth_h) / height][(x * depth_w) / width] (integer division);  2. dropped unless d > 0 && d <= max_depth
+ *   (a NaN fails);  3. p = ray * d per component, dropped unless p.z > min_z;  4. q_i = ((R[i][0] p.x + R[i][1] p.y) + R[i][2] p.z)
+ *   + t[i], dropped unless q.z > near;  5. u = (f q.x) / q.z + cx, v = (f q.y) / q.z + cy, dropped unless u >= -4 && u < out_w + 4
+ *   && v >= -4 && v < out_h + 4 (tested on the doubles), iu = (int)floor(u), iv = (int)floor(v);  6. key = (uint64)(bits of
+ *   (float)q.z) << 32 | R << 16 | G << 8 | B;  7. for dy, dx in [0, splat): px = iu - (splat - 1) / 2 + dx, py likewise; inside the
+ *   image: zbuf[b][py][px] = min(zbuf[b][py][px], key), a 64-bit atomic minimum.  Positive floats order like their bits, so the
+ *   result is the nearest point and, at equal depth, the lowest colour word, whatever the launch order: bitwise reproducible.
+ *
+ * se_render_resolve_f64 / se_render_overlay_f64: the skeleton ray-cast along a per-pixel ray table, one thread per pixel.
+ *   rays     [h][w][3] float64, direction through the origin: ((px + 0.5 - cx) / f, (py + 0.5 - cy) / f, 1) for the pinhole view
+ *            (the hit parameter s is then view z), the calibrated camera's unit rays for the overlay (s is distance, as in a depth map)
+ *   joints   [B][15][3] float64 in the frame of `rays`; bones: Skeleton.lines (utils/skeleton.py:20-21)
+ *   With a = d.d for the ray direction d: sphere of centre c, radius r_joint: b = d.c, disc = b b - a (c.c - r r), roots
+ *   (b -+ sqrt(disc)) / a when disc >= 0.  Capless cylinder from A to B, radius r_bone, skipped when |B - A| < 1e-9: v = B - A,
+ *   e = d - (d.v / v.v) v, g = A - (A.v / v.v) v, qa = e.e (skipped unless > 0), qb = e.g, disc = qb qb - qa (g.g - r r), roots
+ *   (qb -+ sqrt(disc)) / qa kept when the axial parameter (s d.v - A.v) / v.v lies in [0, 1].  Every dot product is
+ *   (x x + y y) + z z.  The hit is the smallest root with s > near over spheres 0..14, then bones 0..14 (an equal later root does not
+ *   replace an earlier one); a non-finite joint disables its sphere and its bones.  Normal n = s d - c (sphere), s e - g (cylinder);
+ *   shade = 0.3 + 0.7 max(0, -(n.d) / (|n| |d|)); channel = (int)((255 base) shade + 0.5).
+ *   resolve: out [B][out_h][out_w][3] uint8 (R, G, B) = the skeleton colour when there is a hit and zbuf is empty or
+ *            s < (double)(float of zbuf >> 32) (strict: a tie goes to the scene), else the z-buffer's colour, else `background`.
+ *   overlay: frame [B][height][width][3] uint8 (B, G, R) -> out, same shape, (R, G, B), with the skeleton over it; depth (may be
+ *            NULL) [B][depth_h][depth_w] float32: the skeleton shows only where s < depth[b][(y depth_h) / height][(x depth_w) / width]. */
+int se_render_splat_f64(const float* depth, const double* ray_tab, const unsigned char* image, const double* view,
+                        unsigned long long* zbuf, int batch, int depth_h, int depth_w, int height, int width, int out_h, int out_w,
+                        double f, double cx, double cy, int splat, double min_z, double max_depth, double near, void* stream);
+int se_render_resolve_f64(const double* rays, const double* joints, const unsigned long long* zbuf, unsigned char* out, int batch,
+                          int out_h, int out_w, double r_joint, double r_bone, double near, const float* joint_rgb,
+                          const float* bone_rgb, const unsigned char* background, void* stream);
+int se_render_overlay_f64(const double* rays, const double* joints, const unsigned char* frame, const float* depth,
+                          unsigned char* out, int batch, int height, int width, int depth_h, int depth_w, double r_joint,
+                          double r_bone, double near, const float* joint_rgb, const float* bone_rgb, void* stream);
+
 #ifdef SE_DEVTOOLS
 /* Development builds only (csrc/build.sh --devtools; absent from the production library): A/B kernel selection for
  * tools/bench_conv.py and the cycle-stamp diagnostics.  The selector is thread-local. */

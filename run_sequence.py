@@ -5,6 +5,7 @@
     python run_sequence.py --root_dir data --seq_name new_diogo1 --estimated_depth_name matterport_green \\
                            --output out/no_body_diogo1.pkl [--weights synthetic] [--depth_decode device|host]
                            [--image_decode device|host] [--streams 2] [--stats_output out/no_body_diogo1.stats.pkl]
+                           [--render_dir out/frames [--render_every 10]]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -17,6 +18,9 @@ PIL in that pool; the image path is then demo.py's (``se_preprocess_image_u8`` f
 through ``exr.py`` + ``prepare_depth`` - the same values either way (``TestDataset.__getitem__``: nearest resize to 1280x1024, clamp
 to 10 m).  The pickle holds the list of float32 [15, 3] predictions, as ``test.py`` writes it.  ``--stats_output`` adds a second
 pickle: the per-joint statistics of every frame (``VoxelNetwork_depth.joint_statistics``), taken per batch on the stream it ran on.
+``--render_dir`` writes ``<img_name>.render.png`` and ``<img_name>.overlay.png`` (``sceneego_amd/render.py``: the scene point cloud
+with the skeleton from a third-person view, and the skeleton in the fisheye frame) for every ``--render_every``-th frame, batched
+through one ``SceneRenderer`` once the joints of the batch are final; the forward is the same with and without it.
 """
 import argparse
 import json
@@ -87,6 +91,7 @@ class SequenceRunner:
             net.load_state_dict(loads["state_dict"])
         self.net = net.to(self.device).eval()
         self.pipe = PipelinedForward(self.net, n_streams=streams) if streams > 1 else None
+        self.renderer = None
 
     def _images(self, frames):
         from sceneego_amd.preprocess import preprocess_image, preprocess_image_device, preprocess_jpeg_batch
@@ -107,9 +112,35 @@ class SequenceRunner:
             return decode_depth_exr_batch(paths, self.device, out_hw=(H, W), clamp=DEPTH_CLAMP)
         return torch.stack([prepare_depth(load_depth(p), W, H) for p in paths]).to(self.device)
 
+    def _frames_u8(self, frames):
+        """uint8 [n, H, W, 3] (B, G, R) on the device of the frames picked for rendering: a second decode of those frames only, so
+        that the image path of the forward stays exactly what it is without --render_dir."""
+        from sceneego_amd.jpeg_device import decode_jpeg_batch
+        if self.image_decode == "device":
+            if all(f.device for f in frames) and len({(f.H, f.W) for f in frames}) == 1:
+                return decode_jpeg_batch(frames, self.device)
+            frames = [f.host_decode() for f in frames]
+        return torch.from_numpy(np.stack(frames)).to(self.device)
+
+    def _render(self, job, kp):
+        """The PNG pair of every picked frame of one batch; ``kp``: the batch's final joints on the host."""
+        from sceneego_amd.config import resolve_calibration_path
+        from sceneego_amd.render import SceneRenderer, save_png
+        render_dir, pick, names, frames_u8, depth = job
+        if self.renderer is None:
+            self.renderer = SceneRenderer(resolve_calibration_path(self.config.dataset.camera_calibration_path),
+                                          frame_size=tuple(frames_u8.shape[1:3]), device=self.device)
+        joints = kp[pick]
+        scene = self.renderer.render(depth, frames_u8, joints).cpu()
+        over = self.renderer.overlay(frames_u8, joints, depth=depth).cpu()
+        for k, name in enumerate(names):
+            save_png(os.path.join(render_dir, name + ".render.png"), scene[k])
+            save_png(os.path.join(render_dir, name + ".overlay.png"), over[k])
+
     @torch.no_grad()
-    def run(self, images, depths, batch_size, stats=False):
-        """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts)."""
+    def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1):
+        """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
+        write the rendered PNG pair of every ``render_every``-th frame there."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import joint_statistics_to_numpy
         from sceneego_amd.preprocess import load_image_bgr
@@ -117,14 +148,22 @@ class SequenceRunner:
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
         preds, frame_stats, pending = [], [], []
 
+        if render_dir is not None:
+            if render_every < 1:
+                raise ValueError(f"--render_every must be >= 1, got {render_every}")
+            os.makedirs(render_dir, exist_ok=True)
+
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done = pending.pop(0)
+                kp, st, done, job = pending.pop(0)
                 if done is not None:
                     done.synchronize()
-                preds.extend(np.asarray(k, dtype=np.float32) for k in kp.cpu().numpy())
+                kp_host = kp.cpu().numpy()
+                preds.extend(np.asarray(k, dtype=np.float32) for k in kp_host)
                 if st is not None:
                     frame_stats.extend(joint_statistics_to_numpy(st))
+                if job is not None:
+                    self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             ahead = [pool.submit(load, p) for p in batches[0][0]] if batches else []
@@ -134,9 +173,15 @@ class SequenceRunner:
                     ahead = [pool.submit(load, p) for p in batches[i + 1][0]]
                 img = self._images(frames)
                 depth = self._depths(deps)
+                job = None
+                if render_dir is not None:
+                    pick = [k for k in range(len(imgs)) if (i * batch_size + k) % render_every == 0]
+                    if pick:
+                        job = (render_dir, pick, [os.path.split(imgs[k])[1] for k in pick], self._frames_u8([frames[k] for k in pick]),
+                               depth[pick])
                 if self.pipe is None:
                     kp, _, vol, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
-                    pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None))
+                    pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
@@ -148,7 +193,7 @@ class SequenceRunner:
                             st = net.joint_statistics(vol, kp)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done))
+                    pending.append((kp, st, done, job))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             drain(0)
         return (preds, frame_stats) if stats else preds
@@ -168,6 +213,8 @@ def main(argv=None):
     ap.add_argument("--streams", type=int, default=1, help="forwards in flight (PipelinedForward when > 1)")
     ap.add_argument("--workers", type=int, default=8, help=f"JPEG read / parse (host decode: decode) threads (at most {MAX_WORKERS})")
     ap.add_argument("--output", default=None, help="pickle of the predicted [15,3] joints of every frame")
+    ap.add_argument("--render_dir", default=None, help="write <img_name>.render.png and <img_name>.overlay.png of the picked frames here")
+    ap.add_argument("--render_every", type=int, default=1, help="with --render_dir: render every N-th frame (default: every frame)")
     ap.add_argument("--stats_output", default=None, help="pickle of the per-frame joint statistics (list of dicts of numpy arrays: "
                     "cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
     args = ap.parse_args(argv)
@@ -181,7 +228,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     want_stats = args.stats_output is not None
-    preds = runner.run(images, depths, config.test.batch_size, stats=want_stats)
+    preds = runner.run(images, depths, config.test.batch_size, stats=want_stats, render_dir=args.render_dir,
+                       render_every=args.render_every)
     if want_stats:
         preds, frame_stats = preds
     torch.cuda.synchronize()

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -94,6 +94,9 @@ SIGNATURES = {
     "se_exr_zip_decode_f32": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _ll, _vp, _vp]),
     "se_jpeg_scratch_bytes": (_ll, [_vp, _i, _vp, _i, _vp]),
     "se_jpeg_decode_bgr_u8": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _i, _vp]),
+    "se_render_splat_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _d, _d, _d, _vp]),
+    "se_render_resolve_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp]),
+    "se_render_overlay_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -852,3 +855,91 @@ def joint_stats(prob, coord, joints, stats, peak_index, rows, voxels, scratch=No
         bad(f"scratch has {scratch.numel()} elements, needs {need}")
     _check(load().se_joint_stats_f32(_ptr(prob), _ptr(coord), _ptr(joints), _ptr(stats), _ptr(peak_index), _ptr(scratch), rows,
                                      voxels, _stream()), "se_joint_stats_f32")
+
+
+# ---------------------------------------------------------------------------------------------
+# Headless renderer (csrc/render.hip; sceneego_amd/render.py drives it)
+RENDER_JOINTS = 15
+RENDER_R_JOINT, RENDER_R_BONE = 0.03, 0.0075                       # metres
+RENDER_JOINT_RGB, RENDER_BONE_RGB = (0.1, 0.1, 0.7), (0.1, 0.9, 0.1)  # reference utils/skeleton.py:52
+
+
+def _render_check(name, t, dtype, shape):
+    if not isinstance(t, torch.Tensor):
+        raise HipExtensionError(f"render: {name} is not a tensor")
+    if not t.is_cuda:
+        raise HipExtensionError(f"render: {name} is on {t.device}: the renderer needs tensors on a HIP device")
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise HipExtensionError(f"render: {name} is {t.dtype} {tuple(t.shape)} (contiguous: {t.is_contiguous()}), expected contiguous "
+                                f"{dtype} {tuple(shape)}")
+
+
+def render_splat(depth, ray_tab, image, view, zbuf, f, cx, cy, splat=2, min_z=0.1, max_depth=100.0, near=0.05):
+    """se_render_splat_f64: depth [B,dh,dw] float32, ray_tab [H,W,3] float64, image [B,H,W,3] uint8 (B, G, R), view [12] float64 ->
+    zbuf [B,Hout,Wout] int64 (the uint64 keys; cleared inside).  Shapes and devices are checked here, before anything is launched."""
+    for name, t in (("depth", depth), ("ray_tab", ray_tab), ("image", image), ("view", view), ("zbuf", zbuf)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise HipExtensionError(f"render_splat: {name} must be a tensor on a HIP device")
+    if depth.dim() != 3 or zbuf.dim() != 3 or ray_tab.dim() != 3:
+        raise HipExtensionError("render_splat: depth [B,dh,dw], ray_tab [H,W,3] and zbuf [B,Hout,Wout] expected")
+    B, dh, dw = depth.shape
+    H, W, _ = ray_tab.shape
+    _render_check("depth", depth, torch.float32, (B, dh, dw))
+    _render_check("ray_tab", ray_tab, torch.float64, (H, W, 3))
+    _render_check("image", image, torch.uint8, (B, H, W, 3))
+    _render_check("view", view, torch.float64, (12,))
+    _render_check("zbuf", zbuf, torch.int64, (B, zbuf.shape[1], zbuf.shape[2]))
+    _check(load().se_render_splat_f64(_ptr(depth), _ptr(ray_tab), _ptr(image), _ptr(view), _ptr(zbuf), B, dh, dw, H, W, zbuf.shape[1],
+                                      zbuf.shape[2], float(f), float(cx), float(cy), int(splat), float(min_z), float(max_depth),
+                                      float(near), _stream()), "se_render_splat_f64")
+    return zbuf
+
+
+def _rgb3(v):
+    return (ctypes.c_float * 3)(*[float(x) for x in v])
+
+
+def render_resolve(rays, joints, zbuf, out, r_joint=RENDER_R_JOINT, r_bone=RENDER_R_BONE, near=0.05, joint_rgb=RENDER_JOINT_RGB,
+                   bone_rgb=RENDER_BONE_RGB, background=(255, 255, 255)):
+    """se_render_resolve_f64: rays [Hout,Wout,3] float64, joints [B,15,3] float64 (frame of the rays), zbuf [B,Hout,Wout] int64 ->
+    out [B,Hout,Wout,3] uint8 (R, G, B)."""
+    for name, t in (("rays", rays), ("joints", joints), ("zbuf", zbuf), ("out", out)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise HipExtensionError(f"render_resolve: {name} must be a tensor on a HIP device")
+    if zbuf.dim() != 3:
+        raise HipExtensionError("render_resolve: zbuf [B,Hout,Wout] expected")
+    B, Ho, Wo = zbuf.shape
+    _render_check("rays", rays, torch.float64, (Ho, Wo, 3))
+    _render_check("joints", joints, torch.float64, (B, RENDER_JOINTS, 3))
+    _render_check("zbuf", zbuf, torch.int64, (B, Ho, Wo))
+    _render_check("out", out, torch.uint8, (B, Ho, Wo, 3))
+    bg = (ctypes.c_ubyte * 3)(*[int(x) for x in background])
+    _check(load().se_render_resolve_f64(_ptr(rays), _ptr(joints), _ptr(zbuf), _ptr(out), B, Ho, Wo, float(r_joint), float(r_bone),
+                                        float(near), _rgb3(joint_rgb), _rgb3(bone_rgb), bg, _stream()), "se_render_resolve_f64")
+    return out
+
+
+def render_overlay(rays, joints, frame, out, depth=None, r_joint=RENDER_R_JOINT, r_bone=RENDER_R_BONE, near=0.05,
+                   joint_rgb=RENDER_JOINT_RGB, bone_rgb=RENDER_BONE_RGB):
+    """se_render_overlay_f64: rays [H,W,3] float64 (the camera's unit rays), joints [B,15,3] float64 (camera frame), frame [B,H,W,3]
+    uint8 (B, G, R), depth None or [B,dh,dw] float32 -> out [B,H,W,3] uint8 (R, G, B)."""
+    for name, t in (("rays", rays), ("joints", joints), ("frame", frame), ("out", out)) + ((("depth", depth),) if depth is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise HipExtensionError(f"render_overlay: {name} must be a tensor on a HIP device")
+    if frame.dim() != 4:
+        raise HipExtensionError("render_overlay: frame [B,H,W,3] expected")
+    B, H, W, _ = frame.shape
+    _render_check("rays", rays, torch.float64, (H, W, 3))
+    _render_check("joints", joints, torch.float64, (B, RENDER_JOINTS, 3))
+    _render_check("frame", frame, torch.uint8, (B, H, W, 3))
+    _render_check("out", out, torch.uint8, (B, H, W, 3))
+    dh = dw = 0
+    if depth is not None:
+        if depth.dim() != 3:
+            raise HipExtensionError("render_overlay: depth [B,dh,dw] expected")
+        dh, dw = depth.shape[1:]
+        _render_check("depth", depth, torch.float32, (B, dh, dw))
+    _check(load().se_render_overlay_f64(_ptr(rays), _ptr(joints), _ptr(frame), _ptr(depth), _ptr(out), B, H, W, dh, dw, float(r_joint),
+                                        float(r_bone), float(near), _rgb3(joint_rgb), _rgb3(bone_rgb), _stream()),
+           "se_render_overlay_f64")
+    return out

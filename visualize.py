@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Counterpart of the reference's ``visualize.py`` (``visualize.py:12-38``) on MI355X, without a display: one frame, its depth map
+and its predicted pose -> a rendered image of the scene point cloud with the skeleton, the skeleton drawn into the fisheye frame,
+and the point cloud as a PLY file.
+
+    python visualize.py --img_path data/demo/imgs/img_001000.jpg --depth_path data/demo/depths/img_001000.jpg.exr \\
+                        --pose_path data/demo/out/img_001000.jpg.pkl [--output render.png] [--overlay overlay.png] [--ply scene.ply]
+                        [--azimuth 35 --elevation 25 --distance 3.5 --fov 50 --size 720x960 --splat 2]
+
+The reference opens an open3d window (``draw_geometries([scene, predicted_pose_mesh])``); this script renders the same two
+geometries on the device (``sceneego_amd/render.py``, ``csrc/render.hip``) and writes files.  It reads what ``demo.py`` reads and
+writes: the frame (a baseline JPEG is decoded on the device where that path takes the file, otherwise by PIL), the depth map
+(``.exr`` / ``.npy`` / ``.npz``) and the pickle of float32 [15, 3] joints.  An empty string for ``--output`` / ``--overlay`` /
+``--ply`` skips that file.
+"""
+import argparse
+import os
+import pickle
+import sys
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+CALIBRATION = os.path.join(ROOT, "sceneego_amd", "calibration", "fisheye.calibration_05_08.json")
+
+
+def _size(text):
+    try:
+        h, w = (int(v) for v in text.lower().split("x"))
+        if h <= 0 or w <= 0:
+            raise ValueError
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--size wants HxW, e.g. 720x960; got {text!r}")
+    return h, w
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--img_path", type=str, required=True)
+    ap.add_argument("--depth_path", type=str, required=True)
+    ap.add_argument("--pose_path", type=str, required=True)
+    ap.add_argument("--output", type=str, default="render.png", help="third-person view of the point cloud and the skeleton")
+    ap.add_argument("--overlay", type=str, default="overlay.png", help="the skeleton drawn into the fisheye frame")
+    ap.add_argument("--ply", type=str, default="scene.ply", help="the coloured point cloud (binary PLY)")
+    ap.add_argument("--azimuth", type=float, default=35.0, help="degrees around the cuboid centre (0, 0, 1)")
+    ap.add_argument("--elevation", type=float, default=25.0, help="degrees towards the head camera")
+    ap.add_argument("--distance", type=float, default=3.5, help="metres from the cuboid centre")
+    ap.add_argument("--fov", type=float, default=50.0, help="vertical field of view, degrees")
+    ap.add_argument("--size", type=_size, default=(720, 960), help="HxW of the rendered view")
+    ap.add_argument("--splat", type=int, default=2, choices=(1, 2, 3, 4), help="footprint of a point, pixels")
+    ap.add_argument("--calibration", type=str, default=CALIBRATION)
+    return ap.parse_args(argv)
+
+
+def load_frame(img_path, device):
+    """uint8 [1, H, W, 3] (B, G, R) on the device: decoded there when the JPEG path takes the file, else by PIL."""
+    import torch
+
+    from sceneego_amd.jpeg_device import JpegFile, decode_jpeg_batch
+    from sceneego_amd.preprocess import load_image_bgr
+    jpeg = JpegFile(img_path) if img_path.lower().endswith((".jpg", ".jpeg")) else None
+    if jpeg is not None and jpeg.device:
+        return decode_jpeg_batch([jpeg], device)
+    return torch.from_numpy(load_image_bgr(img_path))[None].to(device)
+
+
+def visualize(args):
+    import torch
+
+    from sceneego_amd.preprocess import load_depth
+    from sceneego_amd.render import SceneRenderer, orbit_view, save_png, write_ply
+    if not torch.cuda.is_available():
+        raise RuntimeError("visualize.py needs an MI355X (HIP device); the renderer has no CPU fallback")
+    device = torch.device("cuda")
+    with open(args.pose_path, "rb") as f:
+        pose = pickle.load(f)
+    frame = load_frame(args.img_path, device)
+    depth = torch.from_numpy(load_depth(args.depth_path))[None].to(device)
+    renderer = SceneRenderer(args.calibration, frame_size=tuple(frame.shape[1:3]), out_size=args.size, fov_y_deg=args.fov,
+                             splat=args.splat, device=device)
+    written = []
+    if args.output:
+        view = orbit_view(args.azimuth, args.elevation, args.distance)
+        save_png(args.output, renderer.render(depth, frame, pose, view=view)[0])
+        written.append(args.output)
+    if args.overlay:
+        save_png(args.overlay, renderer.overlay(frame, pose, depth=depth)[0])
+        written.append(args.overlay)
+    if args.ply:
+        write_ply(args.ply, *renderer.scene_points(depth, frame))
+        written.append(args.ply)
+    return written
+
+
+def main(argv=None):
+    for path in visualize(parse_args(argv)):
+        print(path)
+
+
+if __name__ == "__main__":
+    main()
