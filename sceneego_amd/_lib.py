@@ -371,7 +371,7 @@ def intersection(buf, occ, batch, voxels, channels, stride_c):
 
 
 def bias_act_nchw(x, bias, residual, relu):
-    """In place on ``x`` [N,C,H,W] (contiguous): x = relu?(x + bias[c] (+ residual))."""
+    """In place on ``x`` [N,C,H,W] (contiguous): x = relu?(x + bias[c] (+ residual)).  float32: any map size; bfloat16: H * W % 8 == 0."""
     require_hip(x, bias)
     n, c, hh, ww = x.shape
     if x.dtype == torch.bfloat16:

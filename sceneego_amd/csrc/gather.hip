@@ -204,7 +204,8 @@ extern "C" int se_intersection_f32(float* buf, const float* occ, int batch, int 
 // ------------------------------------------------------------------------------------------------
 // NCHW bias (+ residual) (+ ReLU) epilogue for the MIOpen 2D convolutions of the backbone: one pass instead of the
 // separate bias-add / add / clamp kernels PyTorch issues after F.conv2d (network/pose_resnet.py:52-90 per block).
-// x, res, out: [N][C][HW] float32 (out may alias x); bias [C].  HW % 4 == 0.
+// x, res, out: [N][C][HW] float32 (out may alias x); bias [C].  Four elements per thread where HW % 4 == 0 (every map of a 256 x 256
+// image), one per thread for the others (odd maps: 33 x 33 from a 264 x 264 image), where a row of four would cross into the next channel.
 // ------------------------------------------------------------------------------------------------
 namespace {
 __global__ __launch_bounds__(256) void bias_act_kernel(const f32x4* __restrict__ x, const float* __restrict__ bias,
@@ -218,11 +219,27 @@ __global__ __launch_bounds__(256) void bias_act_kernel(const f32x4* __restrict__
         out[i] = v;
     }
 }
+
+__global__ __launch_bounds__(256) void bias_act_scalar_kernel(const float* x, const float* __restrict__ bias, const float* res, float* out,
+                                                              long long total, int hw, int channels, int relu) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        float v = x[i] + bias[(int)((i / hw) % channels)];
+        if (res) v += res[i];
+        out[i] = relu ? fmaxf(v, 0.f) : v;
+    }
+}
 }  // namespace
 
 extern "C" int se_bias_act_nchw_f32(const float* x, const float* bias, const float* residual, float* out, int batch,
                                     int channels, int hw, int relu, void* stream) {
-    if (batch <= 0 || channels <= 0 || hw <= 0 || (hw & 3)) return SE_ERR_BAD_ARG;
+    if (batch <= 0 || channels <= 0 || hw <= 0 || !x || !bias || !out) return SE_ERR_BAD_ARG;
+    if (hw & 3) {
+        const long long total = (long long)batch * channels * hw;
+        const unsigned grid1 = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+        hipLaunchKernelGGL(bias_act_scalar_kernel, dim3(grid1), dim3(256), 0, se_stream(stream), x, bias, residual, out, total, hw, channels, relu);
+        SE_CHECK_LAUNCH();
+        return 0;
+    }
     const long long total4 = (long long)batch * channels * (hw / 4);
     const unsigned grid = (unsigned)((total4 + 255) / 256 < 4096 ? (total4 + 255) / 256 : 4096);
     hipLaunchKernelGGL(bias_act_kernel, dim3(grid), dim3(256), 0, se_stream(stream), reinterpret_cast<const f32x4*>(x), bias,

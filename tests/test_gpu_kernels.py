@@ -447,6 +447,25 @@ def test_bias_act_and_fused_backbone():
     assert float((fused - ref).abs().max()) < 1e-4 * float(ref.abs().max()) + 1e-5
 
 
+@pytest.mark.parametrize("B,C,H,W", [(2, 8, 33, 33), (1, 7, 9, 10), (2, 4, 3, 5), (3, 5, 1, 1)])
+def test_bias_act_nchw_map_area_not_a_multiple_of_4(B, C, H, W):
+    """se_bias_act_nchw_f32 on maps of 1089 / 90 / 15 / 1 pixels (area % 4 = 1 / 2 / 3 / 1: the 33 x 33 maps of layer2 for a 264 x 264 image,
+    which the MIOpen route of FoldedBackbone hands it): the float32 expression (x + bias) + residual, bit for bit, in place."""
+    g = torch.Generator().manual_seed(B * 100 + H * W)
+    x = torch.randn(B, C, H, W, generator=g).to(DEV)
+    b = torch.randn(C, generator=g).to(DEV)
+    r = torch.randn(B, C, H, W, generator=g).to(DEV)
+    for res, relu in ((r, True), (None, False), (None, True), (r, False)):
+        want = x + b.view(1, -1, 1, 1)
+        if res is not None:
+            want = want + res
+        if relu:
+            want = F.relu(want)
+        buf = x.clone()
+        got = _lib.bias_act_nchw(buf, b, res, relu)
+        assert got.data_ptr() == buf.data_ptr() and torch.equal(got, want)
+
+
 @pytest.mark.parametrize("B,cin,cout,H,residual,relu", [
     (8, 64, 256, 64, True, True), (8, 64, 64, 64, False, True), (8, 256, 128, 64, False, True), (8, 128, 512, 32, True, True),
     (8, 512, 128, 32, False, True), (8, 256, 1024, 16, True, True), (8, 512, 2048, 8, True, True), (8, 2048, 512, 8, False, True), (8, 1024, 256, 16, False, True), (8, 1024, 512, 16, False, True),
