@@ -3,7 +3,7 @@
 15x3 joints per image.
 
     python demo.py --config experiments/sceneego/test/sceneego.yaml --img_dir data/demo/imgs \\
-                   --depth_dir data/demo/depths --output_dir data/demo/out [--weights synthetic] [--stats true]
+                   --depth_dir data/demo/depths --output_dir data/demo/out [--weights synthetic] [--stats true] [--scene_check true]
 
 Differences: ``--vis`` (open3d GUI) is out of scope; depth maps are read from ``<img_name>.exr`` (the reference's format:
 scanline OpenEXR, NONE/ZIP/PIZ, decoded by ``sceneego_amd/exr.py``) or ``.npy`` / ``.npz``; ``--weights synthetic`` uses the portable seeded weights when no checkpoint exists
@@ -11,6 +11,8 @@ scanline OpenEXR, NONE/ZIP/PIZ, decoded by ``sceneego_amd/exr.py``) or ``.npy`` 
 ``<img_name>.stats.pkl`` beside each ``<img_name>.pkl``: the per-joint statistics of ``VoxelNetwork_depth.joint_statistics``.
 ``--render_dir DIR`` writes ``<img_name>.render.png`` (scene point cloud and skeleton from a third-person view) and
 ``<img_name>.overlay.png`` (the skeleton in the fisheye frame) per frame, rendered on the device (``sceneego_amd/render.py``).
+``--scene_check true`` writes ``<img_name>.scene.pkl`` beside each ``<img_name>.pkl``: collision, clearance and contact of the
+predicted skeleton against the scene of its own depth map (``sceneego_amd/scene_check.py``: ``SceneConsistency.check``).
 """
 import argparse
 import os
@@ -20,7 +22,7 @@ import torch
 
 from sceneego_amd import load_config, synth
 from sceneego_amd.jpeg_device import JpegFile, decode_jpeg_batch
-from sceneego_amd.op import joint_statistics_to_numpy
+from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy
 from sceneego_amd.preprocess import (DEPTH_CLAMP, load_depth, load_image_bgr, prepare_depth, preprocess_image,
                                      preprocess_image_device)
 from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
@@ -31,7 +33,7 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 
 class Demo:
-    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None):
+    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
@@ -40,6 +42,8 @@ class Demo:
         self.stats = stats
         self.render_dir = render_dir
         self.renderer = None
+        self.scene_check = scene_check
+        self.scene = None
         self.items = []
         for img_name in sorted(os.listdir(img_dir)):
             img_path = os.path.join(img_dir, img_name)
@@ -89,9 +93,22 @@ class Demo:
                 if self.stats:
                     # the volumes are the replayed graph's static buffers: reduced here, before the next frame overwrites them
                     results[-1]["stats"] = joint_statistics_to_numpy(self.network.joint_statistics(volumes, kp))[0]
+                if self.scene_check:
+                    results[-1]["scene"] = scene_check_to_numpy(self.check_scene(depth, kp))[0]
                 if self.render_dir is not None:
                     self.render(os.path.split(img_path)[1], frame_u8, depth, kp)
         return results
+
+    def check_scene(self, depth, kp):
+        """The scene check of one frame's joints (device tensors); reads the forward's results, changes none."""
+        if self.scene is None:
+            from sceneego_amd.config import resolve_calibration_path
+            from sceneego_amd.scene_check import SceneConsistency
+            calib = resolve_calibration_path(self.config.dataset.camera_calibration_path)
+            size = (self.config.dataset.image_height, self.config.dataset.image_width)
+            shared = self.renderer.ray_tab if self.renderer is not None else None      # one upload of the 31 MB table
+            self.scene = SceneConsistency(calib, frame_size=size, device=self.device, ray_tab=shared, config=self.config)
+        return self.scene.check(depth, kp)
 
     def render(self, img_name, frame_u8, depth, kp):
         """<img_name>.render.png and <img_name>.overlay.png into render_dir; reads the forward's results, changes none."""
@@ -101,6 +118,8 @@ class Demo:
             calib = resolve_calibration_path(self.config.dataset.camera_calibration_path)
             self.renderer = SceneRenderer(calib, frame_size=(self.config.dataset.image_height, self.config.dataset.image_width),
                                           device=self.device)
+            if self.scene is not None:
+                self.renderer.ray_tab = self.scene.ray_tab                              # the same table: keep one copy
         os.makedirs(self.render_dir, exist_ok=True)
         save_png(os.path.join(self.render_dir, img_name + ".render.png"), self.renderer.render(depth, frame_u8, kp)[0])
         save_png(os.path.join(self.render_dir, img_name + ".overlay.png"), self.renderer.overlay(frame_u8, kp, depth=depth)[0])
@@ -118,19 +137,26 @@ def parse_args(argv=None):
                     help="true: also write <img_name>.stats.pkl (per-joint cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
     ap.add_argument("--render_dir", type=str, default=None,
                     help="also write <img_name>.render.png and <img_name>.overlay.png here (rendered on the device; no display needed)")
+    ap.add_argument("--scene_check", type=str, default="false",
+                    help="true: also write <img_name>.scene.pkl (nearest_dist, clearance, bone_clearance, penetration_depth, penetrating, "
+                         "contact, ... of the skeleton against the depth map's scene)")
     args = ap.parse_args(argv)
     if args.vis.lower() == "true":
         raise SystemExit("--vis true (open3d visualisation) is out of scope of this build")
     if args.stats.lower() not in ("true", "false"):
         raise SystemExit("--stats must be true or false")
     args.stats = args.stats.lower() == "true"
+    if args.scene_check.lower() not in ("true", "false"):
+        raise SystemExit("--scene_check must be true or false")
+    args.scene_check = args.scene_check.lower() == "true"
     return args
 
 
 def main(argv=None):
     args = parse_args(argv)
     config = load_config(args.config)
-    demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats, render_dir=args.render_dir)
+    demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats, render_dir=args.render_dir,
+                scene_check=args.scene_check)
     os.makedirs(args.output_dir, exist_ok=True)
     for r in demo.run():
         out_path = os.path.join(args.output_dir, os.path.split(r["img_path"])[1] + ".pkl")
@@ -140,6 +166,9 @@ def main(argv=None):
         if args.stats:
             with open(out_path[:-4] + ".stats.pkl", "wb") as f:
                 pickle.dump(r["stats"], f)                # dict of numpy arrays, the keys of op.joint_statistics
+        if args.scene_check:
+            with open(out_path[:-4] + ".scene.pkl", "wb") as f:
+                pickle.dump(r["scene"], f)                # dict of numpy arrays, the keys of SceneConsistency.check
 
 
 if __name__ == "__main__":

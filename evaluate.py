@@ -21,7 +21,7 @@ if ROOT not in sys.path:
 
 
 def load_predictions(pred_dir):
-    names = sorted(n for n in os.listdir(pred_dir) if n.endswith(".pkl") and not n.endswith(".stats.pkl"))
+    names = sorted(n for n in os.listdir(pred_dir) if n.endswith(".pkl") and not n.endswith((".stats.pkl", ".scene.pkl")))
     if not names:
         raise SystemExit(f"no .pkl predictions in {pred_dir}")
     poses = []
@@ -51,6 +51,22 @@ def load_sigma(path, names):
     if sigma.shape != (len(names), 15):
         raise SystemExit(f"{path}: expected sigma of shape ({len(names)}, 15), got {sigma.shape}")
     return sigma
+
+
+def load_scene(path, names):
+    """The per-frame scene-check dicts of the frames behind the prediction files ``names``: from a directory of
+    ``<image name>.scene.pkl`` files (demo.py --scene_check true) or from the one pickle of run_sequence.py --scene_output."""
+    if os.path.isdir(path):
+        frames = []
+        for n in names:
+            with open(os.path.join(path, n[:-4] + ".scene.pkl"), "rb") as f:
+                frames.append(pickle.load(f))
+    else:
+        with open(path, "rb") as f:
+            frames = pickle.load(f)
+    if len(frames) != len(names):
+        raise SystemExit(f"{path}: scene checks of {len(frames)} frames for {len(names)} predictions")
+    return frames
 
 
 def match_ground_truth(gt, names):
@@ -83,6 +99,8 @@ def main(argv=None):
     ap.add_argument("--stats", default=None, help="joint statistics of the same frames: a directory of <image name>.stats.pkl files "
                     "(demo.py --stats true) or the one pickle of run_sequence.py --stats_output; adds the error per sigma quantile")
     ap.add_argument("--stats_bins", type=int, default=4, help="number of sigma quantile bins of --stats")
+    ap.add_argument("--scene", default=None, help="scene checks of the same frames: a directory of <image name>.scene.pkl files "
+                    "(demo.py --scene_check true) or the one pickle of run_sequence.py --scene_output; adds the plausibility summary")
     args = ap.parse_args(argv)
     names, pred = load_predictions(args.pred_dir)
     with open(args.gt, "rb") as f:
@@ -97,6 +115,10 @@ def main(argv=None):
         r["by_confidence"] = c
         print("error by sigma quantile (low to high): " + " ".join(f"{v:.4f}" for v in c["bin_mean_error"]) + f" {args.unit}")
         print(f"spearman(error, sigma): {c['spearman']:.4f} over {c['pairs']} joints")
+    if args.scene is not None:
+        from sceneego_amd import metrics as M
+        r["scene_summary"] = M.scene_summary(load_scene(args.scene, names))
+        print(M.format_scene_summary(r["scene_summary"], args.unit))
     return r
 
 

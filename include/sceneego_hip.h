@@ -541,6 +541,34 @@ int se_render_overlay_f64(const double* rays, const double* joints, const unsign
                           unsigned char* out, int batch, int height, int width, int depth_h, int depth_w, double r_joint,
                           double r_bone, double near, const float* joint_rgb, const float* bone_rgb, void* stream);
 
+/* Scene probe (no counterpart in the reference; sceneego_amd/scene_check.py drives it): up to 64 probe points per frame against
+ * every scene point of the frame's depth map.  All arithmetic is float64, unfused, in the order written here; every dot product
+ * is (x x + y y) + z z.  No square root and no division is computed: every value written is a correctly rounded sum or product,
+ * or a copy, so the output has one right answer bit for bit (tests/scene_model.py restates it).
+ *   depth    [B][depth_h][depth_w] float32 metres        ray_tab [height][width][3] float64: the calibrated camera's ray of (x, y)
+ *   probes   [B][P][3] float64, 1 <= P <= 64             out     [B][P][8] float64        index [B][P][2] int32
+ *   scratch  se_scene_probe_scratch_bytes(batch, height, width, P) bytes of device workspace, 8-byte aligned (-1: bad shape)
+ * Pixel n = y * width + x (steps 1-3 of se_render_splat_f64): d = depth[b][(y * depth_h) / height][(x * depth_w) / width] (integer
+ * division); the pixel has a SURFACE iff d > 0 && d <= max_depth (a NaN fails); s = ray * (double)d per component; it is a SCENE
+ * POINT iff it has a surface and s.z > min_z.  A pixel whose ray has a non-finite component takes part in nothing.
+ * Per probe c:  nearest point: e = s - c per component, q = e.e; nearest_q = the minimum of q over the scene points and
+ * nearest_index the lowest n that attains it.  Line of sight: t = ray.c over all pixels with a finite ray, whatever their depth;
+ * sight_dot = the maximum of t, sight_index the lowest n that attains it, surface = (double)d of that pixel if it has a surface,
+ * else NaN.
+ *   out row   {nearest_q, s[nearest_index].x, .y, .z, c.c, sight_dot, surface, 0.0}        index row {nearest_index, sight_index}
+ * A frame without a scene point: nearest_q = +inf, NaN in out[1..3], nearest_index = -1 (the sight half is still filled; without
+ * any finite ray sight_dot = -inf, sight_index = -1).  A probe with a non-finite component: 8 NaNs and {-1, -1}; other rows are
+ * unaffected.  Probe coordinates are assumed small enough for t not to overflow.
+ * Two launches (one workgroup per (2048-pixel tile, frame) writing (value, index) partials to scratch, then one wave per
+ * (frame, probe)); lexicographic (value, index) reductions only, no floating-point atomics: independent of the launch order,
+ * bitwise reproducible; nothing is allocated, so the call is legal under hipGraph capture.
+ * SE_ERR_BAD_ARG: batch <= 0 or > 65535, n_probes outside 1..64, a non-positive size, a null pointer, scratch_bytes too small,
+ * min_z < 0 or NaN, max_depth <= 0 or NaN. */
+long long se_scene_probe_scratch_bytes(int batch, int height, int width, int probes);
+int se_scene_probe_f64(const float* depth, const double* ray_tab, const double* probes, double* out, int* index, void* scratch,
+                       long long scratch_bytes, int batch, int depth_h, int depth_w, int height, int width, int n_probes,
+                       double min_z, double max_depth, void* stream);
+
 #ifdef SE_DEVTOOLS
 /* Development builds only (csrc/build.sh --devtools; absent from the production library): A/B kernel selection for
  * tools/bench_conv.py and the cycle-stamp diagnostics.  The selector is thread-local. */

@@ -5,7 +5,7 @@
     python run_sequence.py --root_dir data --seq_name new_diogo1 --estimated_depth_name matterport_green \\
                            --output out/no_body_diogo1.pkl [--weights synthetic] [--depth_decode device|host]
                            [--image_decode device|host] [--streams 2] [--stats_output out/no_body_diogo1.stats.pkl]
-                           [--render_dir out/frames [--render_every 10]]
+                           [--render_dir out/frames [--render_every 10]] [--scene_output out/no_body_diogo1.scene.pkl]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -21,6 +21,9 @@ pickle: the per-joint statistics of every frame (``VoxelNetwork_depth.joint_stat
 ``--render_dir`` writes ``<img_name>.render.png`` and ``<img_name>.overlay.png`` (``sceneego_amd/render.py``: the scene point cloud
 with the skeleton from a third-person view, and the skeleton in the fisheye frame) for every ``--render_every``-th frame, batched
 through one ``SceneRenderer`` once the joints of the batch are final; the forward is the same with and without it.
+``--scene_output`` adds a pickle of the per-frame scene checks (``sceneego_amd/scene_check.py``: collision, clearance and contact of
+each predicted skeleton against the scene of its own depth map), taken per batch on the stream it ran on, and prints their summary
+(``metrics.scene_summary``) at the end.
 """
 import argparse
 import json
@@ -92,6 +95,20 @@ class SequenceRunner:
         self.net = net.to(self.device).eval()
         self.pipe = PipelinedForward(self.net, n_streams=streams) if streams > 1 else None
         self.renderer = None
+        self.scenes = {}
+
+    def _scene(self, slot=0):
+        """The SceneConsistency of a stream slot: one workspace per slot, one ray table for all (and for the renderer)."""
+        from sceneego_amd.config import resolve_calibration_path
+        from sceneego_amd.scene_check import SceneConsistency
+        if slot not in self.scenes:
+            shared = next((s.ray_tab for s in self.scenes.values()), self.renderer.ray_tab if self.renderer is not None else None)
+            size = (self.config.dataset.image_height, self.config.dataset.image_width)
+            if shared is not None and tuple(shared.shape[:2]) != size:
+                shared = None
+            self.scenes[slot] = SceneConsistency(resolve_calibration_path(self.config.dataset.camera_calibration_path), frame_size=size,
+                                                 device=self.device, ray_tab=shared, config=self.config)
+        return self.scenes[slot]
 
     def _images(self, frames):
         from sceneego_amd.preprocess import preprocess_image, preprocess_image_device, preprocess_jpeg_batch
@@ -138,15 +155,16 @@ class SequenceRunner:
             save_png(os.path.join(render_dir, name + ".overlay.png"), over[k])
 
     @torch.no_grad()
-    def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1):
+    def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
-        write the rendered PNG pair of every ``render_every``-th frame there."""
+        write the rendered PNG pair of every ``render_every``-th frame there.  ``scene``: the per-frame scene-check dicts are appended
+        to what is returned (joints, [statistics,] scene checks)."""
         from sceneego_amd.jpeg_device import JpegFile
-        from sceneego_amd.op import joint_statistics_to_numpy
+        from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
-        preds, frame_stats, pending = [], [], []
+        preds, frame_stats, frame_scene, pending = [], [], [], []
 
         if render_dir is not None:
             if render_every < 1:
@@ -155,13 +173,15 @@ class SequenceRunner:
 
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done, job = pending.pop(0)
+                kp, st, done, job, sc = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 kp_host = kp.cpu().numpy()
                 preds.extend(np.asarray(k, dtype=np.float32) for k in kp_host)
                 if st is not None:
                     frame_stats.extend(joint_statistics_to_numpy(st))
+                if sc is not None:
+                    frame_scene.extend(scene_check_to_numpy(sc))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -181,22 +201,28 @@ class SequenceRunner:
                                depth[pick])
                 if self.pipe is None:
                     kp, _, vol, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
-                    pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job))
+                    pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
+                                    self._scene().check(depth, kp) if scene else None))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
-                    st = None
-                    if stats:
+                    st = sc = None
+                    if stats or scene:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
-                            st = net.joint_statistics(vol, kp)
+                            if stats:
+                                st = net.joint_statistics(vol, kp)
+                            if scene:
+                                sc = self._scene(stream.cuda_stream).check(depth, kp)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done, job))
+                    pending.append((kp, st, done, job, sc))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             drain(0)
-        return (preds, frame_stats) if stats else preds
+        if not (stats or scene):
+            return preds
+        return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ())
 
 
 def main(argv=None):
@@ -217,6 +243,8 @@ def main(argv=None):
     ap.add_argument("--render_every", type=int, default=1, help="with --render_dir: render every N-th frame (default: every frame)")
     ap.add_argument("--stats_output", default=None, help="pickle of the per-frame joint statistics (list of dicts of numpy arrays: "
                     "cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
+    ap.add_argument("--scene_output", default=None, help="pickle of the per-frame scene checks (list of dicts of numpy arrays: "
+                    "nearest_dist, clearance, bone_clearance, penetration_depth, penetrating, contact, ...); prints their summary")
     args = ap.parse_args(argv)
     config = load_config(args.config)
     images, poses, depths = frame_list(args.root_dir, args.seq_name, args.estimated_depth_name)
@@ -228,10 +256,13 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     want_stats = args.stats_output is not None
+    want_scene = args.scene_output is not None
     preds = runner.run(images, depths, config.test.batch_size, stats=want_stats, render_dir=args.render_dir,
-                       render_every=args.render_every)
-    if want_stats:
-        preds, frame_stats = preds
+                       render_every=args.render_every, scene=want_scene)
+    if want_stats or want_scene:
+        preds, *extra = preds
+        frame_stats = extra.pop(0) if want_stats else None
+        frame_scene = extra.pop(0) if want_scene else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -250,6 +281,13 @@ def main(argv=None):
         with open(args.stats_output, "wb") as f:
             pickle.dump(frame_stats, f)
         result["stats"] = frame_stats
+    if want_scene:
+        os.makedirs(os.path.dirname(os.path.abspath(args.scene_output)), exist_ok=True)
+        with open(args.scene_output, "wb") as f:
+            pickle.dump(frame_scene, f)
+        result["scene"] = frame_scene
+        result["scene_summary"] = M.scene_summary(frame_scene)
+        print(M.format_scene_summary(result["scene_summary"]))
     return result
 
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -97,6 +97,8 @@ SIGNATURES = {
     "se_render_splat_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _d, _d, _d, _vp]),
     "se_render_resolve_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "se_render_overlay_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
+    "se_scene_probe_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_scene_probe_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _d, _d, _vp]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -943,3 +945,58 @@ def render_overlay(rays, joints, frame, out, depth=None, r_joint=RENDER_R_JOINT,
                                         float(r_bone), float(near), _rgb3(joint_rgb), _rgb3(bone_rgb), _stream()),
            "se_render_overlay_f64")
     return out
+
+
+# Scene probe (csrc/scene_probe.hip; sceneego_amd/scene_check.py drives it)
+SCENE_PROBE_MAX = 64
+SCENE_PROBE_SLOTS = 8      # nearest_q, nearest point x y z, c.c, sight_dot, surface, 0 (include/sceneego_hip.h)
+# Skeleton.lines of the reference (utils/skeleton.py:20-21), the table csrc/render.hip holds as c_bones
+SKELETON_LINES = ((0, 1), (0, 4), (1, 2), (2, 3), (4, 5), (5, 6), (1, 7), (4, 11), (7, 8), (8, 9), (9, 10), (11, 12), (12, 13), (13, 14),
+                  (7, 11))
+
+
+def scene_probe_scratch_bytes(batch, height, width, probes) -> int:
+    n = int(load().se_scene_probe_scratch_bytes(int(batch), int(height), int(width), int(probes)))
+    if n < 0:
+        raise HipExtensionError(f"scene_probe: no launch for batch {batch}, {height}x{width} rays, {probes} probes")
+    return n
+
+
+def scene_probe(depth, ray_tab, probes, out, index, scratch=None, min_z=0.1, max_depth=100.0):
+    """se_scene_probe_f64: depth [B,dh,dw] float32, ray_tab [H,W,3] float64, probes [B,P,3] float64 (1 <= P <= 64) -> out [B,P,8]
+    float64, index [B,P,2] int32 (the header states every slot).  ``scratch``: an optional uint8 workspace of at least
+    ``scene_probe_scratch_bytes(B, H, W, P)`` bytes (allocated per call otherwise).  Returns (out, index)."""
+    def check(name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor):
+            raise HipExtensionError(f"scene_probe: {name} is not a tensor")
+        if t.device.type != "cuda":
+            raise HipExtensionError(f"scene_probe: {name} is on {t.device}: the scene probe needs tensors on a HIP device")
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise HipExtensionError(f"scene_probe: {name} is {t.dtype} {tuple(t.shape)} (contiguous: {t.is_contiguous()}), expected "
+                                    f"contiguous {dtype} {tuple(shape)}")
+
+    for name, t in (("depth", depth), ("ray_tab", ray_tab), ("probes", probes)):
+        if not isinstance(t, torch.Tensor):
+            raise HipExtensionError(f"scene_probe: {name} must be a tensor on a HIP device")
+    if depth.dim() != 3 or ray_tab.dim() != 3 or probes.dim() != 3:
+        raise HipExtensionError("scene_probe: depth [B,dh,dw], ray_tab [H,W,3] and probes [B,P,3] expected")
+    B, dh, dw = depth.shape
+    H, W = ray_tab.shape[:2]
+    P = probes.shape[1]
+    if not 1 <= P <= SCENE_PROBE_MAX:
+        raise HipExtensionError(f"scene_probe: {P} probes per frame, 1..{SCENE_PROBE_MAX} supported")
+    check("depth", depth, torch.float32, (B, dh, dw))
+    check("ray_tab", ray_tab, torch.float64, (H, W, 3))
+    check("probes", probes, torch.float64, (B, P, 3))
+    check("out", out, torch.float64, (B, P, SCENE_PROBE_SLOTS))
+    check("index", index, torch.int32, (B, P, 2))
+    need = scene_probe_scratch_bytes(B, H, W, P)
+    if scratch is None:
+        scratch = torch.empty((need,), device=depth.device, dtype=torch.uint8)
+    else:
+        if not isinstance(scratch, torch.Tensor) or scratch.device.type != "cuda" or scratch.dtype != torch.uint8 \
+                or not scratch.is_contiguous() or scratch.numel() < need:
+            raise HipExtensionError(f"scene_probe: scratch must be a contiguous uint8 tensor of at least {need} bytes on a HIP device")
+    _check(load().se_scene_probe_f64(_ptr(depth), _ptr(ray_tab), _ptr(probes), _ptr(out), _ptr(index), _ptr(scratch), scratch.numel(),
+                                     B, dh, dw, H, W, P, float(min_z), float(max_depth), _stream()), "se_scene_probe_f64")
+    return out, index

@@ -10,6 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 LEFT_HIP, RIGHT_HIP = 11, 7      # indices in the 15-joint order of utils/skeleton.py:17-19
+FOOT_JOINTS = (9, 10, 13, 14)    # Right_ankle, Right_foot, Left_ankle, Left_foot: the ends of the chains 7-8-9-10 and 11-12-13-14
 
 
 def umeyama(P, Q):
@@ -140,3 +141,28 @@ def error_by_confidence(estimated, gt, sigma, bins: int = 4):
             rho = float((re * rs).sum() / den)
     out["spearman"] = rho
     return out
+
+
+def scene_summary(frames):
+    """Physical plausibility of a sequence: ``frames`` is the list of per-frame dicts of ``op.scene_check_to_numpy`` (the keys
+    ``penetrating``, ``penetration_depth`` and ``contact`` [15] are used).  Returns a dict:
+      ``non_penetration_rate``    share of frames with ``penetrating == False``
+      ``mean_penetration_depth``  mean of ``penetration_depth`` over the frames (metres)
+      ``foot_contact_rate``       share of frames in which at least one ankle or foot joint (9, 10, 13, 14) is in contact
+      ``frames``                  number of frames
+    The rates are NaN for an empty list."""
+    n = len(frames)
+    if n == 0:
+        nan = float("nan")
+        return {"non_penetration_rate": nan, "mean_penetration_depth": nan, "foot_contact_rate": nan, "frames": 0}
+    pen = np.array([bool(np.asarray(f["penetrating"]).reshape(())) for f in frames])
+    depth = np.array([float(np.asarray(f["penetration_depth"]).reshape(())) for f in frames], dtype=np.float64)
+    contact = np.stack([np.asarray(f["contact"], dtype=bool).reshape(15) for f in frames])
+    return {"non_penetration_rate": float((~pen).mean()), "mean_penetration_depth": float(depth.mean()),
+            "foot_contact_rate": float(contact[:, list(FOOT_JOINTS)].any(axis=1).mean()), "frames": n}
+
+
+def format_scene_summary(s, unit="m") -> str:
+    """The one line demo / sequence / evaluation tools print for ``scene_summary``."""
+    return (f"scene check: {s['frames']} frames  non-penetration rate {s['non_penetration_rate']:.4f}  mean penetration depth "
+            f"{s['mean_penetration_depth']:.6f} {unit}  foot contact rate {s['foot_contact_rate']:.4f}")

@@ -231,3 +231,14 @@ def joint_statistics_to_numpy(stats):
     demo.py --stats and run_sequence.py --stats_output write."""
     host = {k: stats[k].cpu().numpy() for k in STAT_KEYS}
     return [{k: host[k][b].copy() for k in STAT_KEYS} for b in range(host["sigma"].shape[0])]
+
+
+SCENE_KEYS = ("nearest_dist", "nearest_point", "nearest_index", "range", "sight_index", "in_view", "clearance", "bone_clearance",
+              "penetration_depth", "penetrating", "contact")
+
+
+def scene_check_to_numpy(result):
+    """The dict of ``scene_check.SceneConsistency.check`` as a list of per-frame dicts of numpy arrays (the keys without the batch
+    dimension): what demo.py --scene_check and run_sequence.py --scene_output write."""
+    host = {k: result[k].cpu().numpy() for k in SCENE_KEYS}
+    return [{k: np.array(host[k][b]) for k in SCENE_KEYS} for b in range(host["range"].shape[0])]      # 0-d entries stay arrays
