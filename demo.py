@@ -10,7 +10,9 @@ scanline OpenEXR, NONE/ZIP/PIZ, decoded by ``sceneego_amd/exr.py``) or ``.npy`` 
 (``config.test.model_path`` is loaded strictly otherwise, exactly like ``demo.py:29-31``); ``--stats true`` writes
 ``<img_name>.stats.pkl`` beside each ``<img_name>.pkl``: the per-joint statistics of ``VoxelNetwork_depth.joint_statistics``.
 ``--render_dir DIR`` writes ``<img_name>.render.png`` (scene point cloud and skeleton from a third-person view) and
-``<img_name>.overlay.png`` (the skeleton in the fisheye frame) per frame, rendered on the device (``sceneego_amd/render.py``).
+``<img_name>.overlay.png`` (the skeleton in the fisheye frame) per frame, rendered on the device (``sceneego_amd/render.py``);
+``--render_format jpg`` writes ``.render.jpg`` / ``.overlay.jpg`` instead: quality-90 4:4:4 JPEG files encoded on the device
+(``sceneego_amd/jpeg_encode.py``), so that only compressed bytes cross to the host.
 ``--scene_check true`` writes ``<img_name>.scene.pkl`` beside each ``<img_name>.pkl``: collision, clearance and contact of the
 predicted skeleton against the scene of its own depth map (``sceneego_amd/scene_check.py``: ``SceneConsistency.check``).
 """
@@ -33,7 +35,8 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 
 class Demo:
-    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False):
+    def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False,
+                 render_format="png"):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
@@ -41,6 +44,9 @@ class Demo:
         self.image_decode = image_decode
         self.stats = stats
         self.render_dir = render_dir
+        if render_format not in ("png", "jpg"):
+            raise ValueError(f"render_format must be png or jpg, got {render_format!r}")
+        self.render_format = render_format
         self.renderer = None
         self.scene_check = scene_check
         self.scene = None
@@ -111,8 +117,8 @@ class Demo:
         return self.scene.check(depth, kp)
 
     def render(self, img_name, frame_u8, depth, kp):
-        """<img_name>.render.png and <img_name>.overlay.png into render_dir; reads the forward's results, changes none."""
-        from sceneego_amd.render import SceneRenderer, save_png
+        """<img_name>.render.png and <img_name>.overlay.png (or .jpg) into render_dir; reads the forward's results, changes none."""
+        from sceneego_amd.render import SceneRenderer, save_jpeg, save_png
         if self.renderer is None:
             from sceneego_amd.config import resolve_calibration_path
             calib = resolve_calibration_path(self.config.dataset.camera_calibration_path)
@@ -121,8 +127,10 @@ class Demo:
             if self.scene is not None:
                 self.renderer.ray_tab = self.scene.ray_tab                              # the same table: keep one copy
         os.makedirs(self.render_dir, exist_ok=True)
-        save_png(os.path.join(self.render_dir, img_name + ".render.png"), self.renderer.render(depth, frame_u8, kp)[0])
-        save_png(os.path.join(self.render_dir, img_name + ".overlay.png"), self.renderer.overlay(frame_u8, kp, depth=depth)[0])
+        save = save_jpeg if self.render_format == "jpg" else save_png
+        ext = "." + self.render_format
+        save(os.path.join(self.render_dir, img_name + ".render" + ext), self.renderer.render(depth, frame_u8, kp)[0])
+        save(os.path.join(self.render_dir, img_name + ".overlay" + ext), self.renderer.overlay(frame_u8, kp, depth=depth)[0])
 
 
 def parse_args(argv=None):
@@ -137,6 +145,8 @@ def parse_args(argv=None):
                     help="true: also write <img_name>.stats.pkl (per-joint cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
     ap.add_argument("--render_dir", type=str, default=None,
                     help="also write <img_name>.render.png and <img_name>.overlay.png here (rendered on the device; no display needed)")
+    ap.add_argument("--render_format", type=str, default="png", choices=("png", "jpg"),
+                    help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG encoded on the device)")
     ap.add_argument("--scene_check", type=str, default="false",
                     help="true: also write <img_name>.scene.pkl (nearest_dist, clearance, bone_clearance, penetration_depth, penetrating, "
                          "contact, ... of the skeleton against the depth map's scene)")
@@ -156,7 +166,7 @@ def main(argv=None):
     args = parse_args(argv)
     config = load_config(args.config)
     demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats, render_dir=args.render_dir,
-                scene_check=args.scene_check)
+                scene_check=args.scene_check, render_format=args.render_format)
     os.makedirs(args.output_dir, exist_ok=True)
     for r in demo.run():
         out_path = os.path.join(args.output_dir, os.path.split(r["img_path"])[1] + ".pkl")

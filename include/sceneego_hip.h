@@ -569,6 +569,38 @@ int se_scene_probe_f64(const float* depth, const double* ray_tab, const double* 
                        long long scratch_bytes, int batch, int depth_h, int depth_w, int height, int width, int n_probes,
                        double min_z, double max_depth, void* stream);
 
+/* Baseline JPEG encoder (no counterpart in the reference; sceneego_amd/jpeg_encode.py writes the file headers around it).
+ *   frames    uint8 [batch][height][width][3] on the device, R, G, B (bgr = 0) or B, G, R (bgr = 1); any height, width in 1..65535
+ *   quant_luma, quant_chroma   HOST pointers: unsigned short [64], natural order, every value in 1..255 (baseline tables)
+ *   subsampling   444 or 420 (chroma averaged 2x2)           restart_rows   0: no restart markers; n: a restart interval of n MCU
+ *             rows (n * MCUs per row <= 65535; n beyond the frame's MCU rows means one interval, the caller writes the DRI)
+ *   out       uint8 [batch][capacity]: per frame the entropy-coded scan, with the 00 after every FF byte, the RSTm markers between
+ *             intervals and the 1-bits that fill the last byte of every interval: what stands between the SOS header and EOI
+ *   length    int32 [batch]: bytes of the frame's scan in out, 0 when it did not fit
+ *   status    int32 [batch][2]: {0, scan bytes} or, when the scan needs more than `capacity`, {1, bytes needed}; nothing is ever
+ *             written at or beyond `capacity` bytes of a frame's slot
+ *   scratch   se_jpeg_encode_scratch_bytes(batch, height, width, subsampling) bytes of device workspace, 16-byte aligned; the
+ *             helper allocates nothing and returns SE_ERR_BAD_ARG for a bad shape (more than 2^31 / 1664 blocks in a frame included)
+ * Arithmetic (integer only, libjpeg's: jccolor.c, jcsample.c, jfdctint.c, jcdctmgr.c, jchuff.c; tests/jpeg_encode_model.py restates
+ * it and the result equals libjpeg-turbo's byte for byte):
+ *   colour    Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *             Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   edges     a plane's last column and row are replicated out to whole blocks.  4:2:0 chroma: sample (cy, cx) is
+ *             (a + b + c + d + 1 + (cx & 1)) >> 2 of the pixels (min(2 cy', H-1) | min(2 cy'+1, H-1), min(2 cx, W-1) | min(2 cx+1,
+ *             W-1)) with cy' = min(cy, ceil(H/2) - 1).  4:2:0 luma: an MCU holds 2x2 blocks; a block outside ceil(W/8) x ceil(H/8)
+ *             has all AC coefficients zero and the DC of the block before it in the MCU (left neighbour; lower row: block 1)
+ *   DCT       jfdctint.c for 8-bit samples minus 128 (CONST_BITS 13, PASS1_BITS 2, rows then columns)
+ *   quantiser sign(c) * ((|c| + (8 q >> 1)) / (8 q))
+ *   entropy   the four Annex K.3 Huffman tables; DC differences per component in MCU order, reset at every restart interval; runs of
+ *             16 zeros as ZRL, EOB unless coefficient 63 is non-zero
+ * Eight kernel launches on `stream`, nothing allocated, no memset node: legal under hipGraph capture; bitwise reproducible.
+ * SE_ERR_BAD_ARG: a null pointer, a bad shape, batch outside 1..65535, subsampling not 444 / 420, a table value outside 1..255,
+ * capacity < 0 or > 2^31-1, scratch too small or misaligned, restart_rows < 0 or an interval of more than 65535 MCUs. */
+long long se_jpeg_encode_scratch_bytes(int batch, int height, int width, int subsampling);
+int se_jpeg_encode_u8(const unsigned char* frames, int batch, int height, int width, int bgr, const unsigned short* quant_luma,
+                      const unsigned short* quant_chroma, int subsampling, int restart_rows, unsigned char* out, long long capacity,
+                      int* length, int* status, void* scratch, long long scratch_bytes, void* stream);
+
 #ifdef SE_DEVTOOLS
 /* Development builds only (csrc/build.sh --devtools; absent from the production library): A/B kernel selection for
  * tools/bench_conv.py and the cycle-stamp diagnostics.  The selector is thread-local. */

@@ -5,7 +5,9 @@
     python run_sequence.py --root_dir data --seq_name new_diogo1 --estimated_depth_name matterport_green \\
                            --output out/no_body_diogo1.pkl [--weights synthetic] [--depth_decode device|host]
                            [--image_decode device|host] [--streams 2] [--stats_output out/no_body_diogo1.stats.pkl]
-                           [--render_dir out/frames [--render_every 10]] [--scene_output out/no_body_diogo1.scene.pkl]
+                           [--render_dir out/frames [--render_every 10] [--render_format jpg]]
+                           [--render_video out/seq.avi [--render_fps 25] [--render_view render|overlay|both] [--render_quality 90]]
+                           [--scene_output out/no_body_diogo1.scene.pkl]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -18,7 +20,8 @@ PIL in that pool; the image path is then demo.py's (``se_preprocess_image_u8`` f
 through ``exr.py`` + ``prepare_depth`` - the same values either way (``TestDataset.__getitem__``: nearest resize to 1280x1024, clamp
 to 10 m).  The pickle holds the list of float32 [15, 3] predictions, as ``test.py`` writes it.  ``--stats_output`` adds a second
 pickle: the per-joint statistics of every frame (``VoxelNetwork_depth.joint_statistics``), taken per batch on the stream it ran on.
-``--render_dir`` writes ``<img_name>.render.png`` and ``<img_name>.overlay.png`` (``sceneego_amd/render.py``: the scene point cloud
+``--render_format jpg`` writes the pair as JPEG files and ``--render_video`` the picked frames as one Motion-JPEG AVI, both encoded
+on the device (``sceneego_amd/jpeg_encode.py``).  ``--render_dir`` writes ``<img_name>.render.png`` and ``<img_name>.overlay.png`` (``sceneego_amd/render.py``: the scene point cloud
 with the skeleton from a third-person view, and the skeleton in the fisheye frame) for every ``--render_every``-th frame, batched
 through one ``SceneRenderer`` once the joints of the batch are final; the forward is the same with and without it.
 ``--scene_output`` adds a pickle of the per-frame scene checks (``sceneego_amd/scene_check.py``: collision, clearance and contact of
@@ -95,6 +98,9 @@ class SequenceRunner:
         self.net = net.to(self.device).eval()
         self.pipe = PipelinedForward(self.net, n_streams=streams) if streams > 1 else None
         self.renderer = None
+        self.encoder = None
+        self.video = None
+        self.render_options = {"format": "png", "video": None, "fps": 25, "view": "render", "quality": 90, "renderer": {}}
         self.scenes = {}
 
     def _scene(self, slot=0):
@@ -140,25 +146,57 @@ class SequenceRunner:
         return torch.from_numpy(np.stack(frames)).to(self.device)
 
     def _render(self, job, kp):
-        """The PNG pair of every picked frame of one batch; ``kp``: the batch's final joints on the host."""
+        """The image pair of every picked frame of one batch and / or their video frames; ``kp``: the batch's final joints on the
+        host.  PNG files go through the host; JPEG files and video frames are encoded on the device in the batch they were
+        rendered in, and only their compressed bytes cross to the host."""
         from sceneego_amd.config import resolve_calibration_path
         from sceneego_amd.render import SceneRenderer, save_png
         render_dir, pick, names, frames_u8, depth = job
+        opt = self.render_options
         if self.renderer is None:
             self.renderer = SceneRenderer(resolve_calibration_path(self.config.dataset.camera_calibration_path),
-                                          frame_size=tuple(frames_u8.shape[1:3]), device=self.device)
+                                          frame_size=tuple(frames_u8.shape[1:3]), device=self.device, **opt["renderer"])
         joints = kp[pick]
-        scene = self.renderer.render(depth, frames_u8, joints).cpu()
-        over = self.renderer.overlay(frames_u8, joints, depth=depth).cpu()
-        for k, name in enumerate(names):
-            save_png(os.path.join(render_dir, name + ".render.png"), scene[k])
-            save_png(os.path.join(render_dir, name + ".overlay.png"), over[k])
+        scene = self.renderer.render(depth, frames_u8, joints)
+        over = self.renderer.overlay(frames_u8, joints, depth=depth)
+        if render_dir is not None and opt["format"] == "png":
+            scene_h, over_h = scene.cpu(), over.cpu()
+            for k, name in enumerate(names):
+                save_png(os.path.join(render_dir, name + ".render.png"), scene_h[k])
+                save_png(os.path.join(render_dir, name + ".overlay.png"), over_h[k])
+        elif render_dir is not None:
+            for view, images in (("render", scene), ("overlay", over)):
+                for name, data in zip(names, self._encoder().encode(images, quality=90, subsampling="444")):
+                    with open(os.path.join(render_dir, f"{name}.{view}.jpg"), "wb") as f:
+                        f.write(data)
+        if opt["video"] is not None:
+            if opt["view"] == "both":
+                if scene.shape[1] != over.shape[1]:
+                    raise ValueError(f"--render_view both puts the views side by side and needs equal heights: the rendered view is "
+                                     f"{scene.shape[1]} rows, the frame {over.shape[1]}; pass --render_size {over.shape[1]}xW")
+                images = torch.cat([scene, over], dim=2)
+            else:
+                images = scene if opt["view"] == "render" else over
+            if self.video is None:
+                from sceneego_amd.jpeg_encode import MjpegWriter
+                os.makedirs(os.path.dirname(os.path.abspath(opt["video"])), exist_ok=True)
+                self.video = MjpegWriter(opt["video"], images.shape[2], images.shape[1], opt["fps"])
+            for data in self._encoder().encode(images, quality=opt["quality"], subsampling="420"):      # what players expect of MJPG
+                self.video.write(data)
+
+    def _encoder(self):
+        if self.encoder is None:
+            from sceneego_amd.jpeg_encode import JpegEncoder
+            self.encoder = JpegEncoder(self.device)
+        return self.encoder
 
     @torch.no_grad()
-    def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False):
+    def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
+            render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
-        write the rendered PNG pair of every ``render_every``-th frame there.  ``scene``: the per-frame scene-check dicts are appended
-        to what is returned (joints, [statistics,] scene checks)."""
+        write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
+        those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
+        scene-check dicts are appended to what is returned (joints, [statistics,] scene checks)."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy
         from sceneego_amd.preprocess import load_image_bgr
@@ -166,10 +204,16 @@ class SequenceRunner:
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
         preds, frame_stats, frame_scene, pending = [], [], [], []
 
-        if render_dir is not None:
+        rendering = render_dir is not None or render_video is not None
+        if rendering:
             if render_every < 1:
                 raise ValueError(f"--render_every must be >= 1, got {render_every}")
-            os.makedirs(render_dir, exist_ok=True)
+            if render_format not in ("png", "jpg") or render_view not in ("render", "overlay", "both"):
+                raise ValueError(f"bad render_format {render_format!r} or render_view {render_view!r}")
+            if render_dir is not None:
+                os.makedirs(render_dir, exist_ok=True)
+            self.render_options = {"format": render_format, "video": render_video, "fps": render_fps, "view": render_view,
+                                   "quality": render_quality, "renderer": {} if render_size is None else {"out_size": tuple(render_size)}}
 
         def drain(keep):
             while len(pending) > keep:
@@ -194,7 +238,7 @@ class SequenceRunner:
                 img = self._images(frames)
                 depth = self._depths(deps)
                 job = None
-                if render_dir is not None:
+                if rendering:
                     pick = [k for k in range(len(imgs)) if (i * batch_size + k) % render_every == 0]
                     if pick:
                         job = (render_dir, pick, [os.path.split(imgs[k])[1] for k in pick], self._frames_u8([frames[k] for k in pick]),
@@ -219,15 +263,42 @@ class SequenceRunner:
                             done.record(stream)
                     pending.append((kp, st, done, job, sc))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
-            drain(0)
+            try:
+                drain(0)
+            finally:
+                if self.video is not None:
+                    self.video.close()
+                    self.video = None
         if not (stats or scene):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ())
 
 
-def main(argv=None):
-    from sceneego_amd import load_config
-    from sceneego_amd import metrics as M
+def _size(text):
+    try:
+        h, w = (int(v) for v in text.lower().split("x"))
+        if h <= 0 or w <= 0:
+            raise ValueError
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"HxW expected, e.g. 720x960; got {text!r}")
+    return h, w
+
+
+def _quality(text):
+    q = int(text)
+    if not 1 <= q <= 100:
+        raise argparse.ArgumentTypeError(f"1..100 expected, got {text!r}")
+    return q
+
+
+def _fps(text):
+    v = float(text)
+    if not v > 0:
+        raise argparse.ArgumentTypeError(f"a positive rate expected, got {text!r}")
+    return int(v) if v == int(v) else v
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--config", default=os.path.join(ROOT, "experiments", "sceneego", "test", "sceneego.yaml"))
     ap.add_argument("--root_dir", required=True, help="directory holding the sequence directories")
@@ -245,7 +316,21 @@ def main(argv=None):
                     "cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
     ap.add_argument("--scene_output", default=None, help="pickle of the per-frame scene checks (list of dicts of numpy arrays: "
                     "nearest_dist, clearance, bone_clearance, penetration_depth, penetrating, contact, ...); prints their summary")
-    args = ap.parse_args(argv)
+    ap.add_argument("--render_format", default="png", choices=("png", "jpg"),
+                    help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG files encoded on the device)")
+    ap.add_argument("--render_video", default=None, help="write the picked frames as one Motion-JPEG AVI (4:2:0, encoded on the device)")
+    ap.add_argument("--render_fps", type=_fps, default=25, help="with --render_video: frames per second of the file")
+    ap.add_argument("--render_view", default="render", choices=("render", "overlay", "both"),
+                    help="with --render_video: the third-person view, the fisheye overlay, or both side by side (equal heights only)")
+    ap.add_argument("--render_quality", type=_quality, default=90, help="with --render_video: JPEG quality, 1..100")
+    ap.add_argument("--render_size", type=_size, default=None, help="HxW of the third-person view (default: 720x960)")
+    return ap
+
+
+def main(argv=None):
+    from sceneego_amd import load_config
+    from sceneego_amd import metrics as M
+    args = build_parser().parse_args(argv)
     config = load_config(args.config)
     images, poses, depths = frame_list(args.root_dir, args.seq_name, args.estimated_depth_name)
     if not images:
@@ -258,7 +343,9 @@ def main(argv=None):
     want_stats = args.stats_output is not None
     want_scene = args.scene_output is not None
     preds = runner.run(images, depths, config.test.batch_size, stats=want_stats, render_dir=args.render_dir,
-                       render_every=args.render_every, scene=want_scene)
+                       render_every=args.render_every, scene=want_scene, render_format=args.render_format,
+                       render_video=args.render_video, render_fps=args.render_fps, render_view=args.render_view,
+                       render_quality=args.render_quality, render_size=args.render_size)
     if want_stats or want_scene:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -94,6 +94,8 @@ SIGNATURES = {
     "se_exr_zip_decode_f32": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _ll, _vp, _vp]),
     "se_jpeg_scratch_bytes": (_ll, [_vp, _i, _vp, _i, _vp]),
     "se_jpeg_decode_bgr_u8": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _i, _vp]),
+    "se_jpeg_encode_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_jpeg_encode_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _ll, _vp, _vp, _vp, _ll, _vp]),
     "se_render_splat_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _d, _d, _d, _vp]),
     "se_render_resolve_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "se_render_overlay_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
@@ -1000,3 +1002,35 @@ def scene_probe(depth, ray_tab, probes, out, index, scratch=None, min_z=0.1, max
     _check(load().se_scene_probe_f64(_ptr(depth), _ptr(ray_tab), _ptr(probes), _ptr(out), _ptr(index), _ptr(scratch), scratch.numel(),
                                      B, dh, dw, H, W, P, float(min_z), float(max_depth), _stream()), "se_scene_probe_f64")
     return out, index
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Baseline JPEG encoder (csrc/jpeg_enc.hip; sceneego_amd/jpeg_encode.py drives it)
+def jpeg_encode_scratch_bytes(batch, height, width, subsampling) -> int:
+    """se_jpeg_encode_scratch_bytes: device workspace of one encode call; ``subsampling`` is 444 or 420."""
+    n = load().se_jpeg_encode_scratch_bytes(int(batch), int(height), int(width), int(subsampling))
+    if n < 0:
+        raise HipExtensionError(f"se_jpeg_encode_scratch_bytes: bad shape (batch {batch}, {height}x{width}, subsampling {subsampling})")
+    return int(n)
+
+
+def jpeg_encode(frames, quant_luma, quant_chroma, subsampling, restart_rows, out, length, status, scratch, bgr=False):
+    """se_jpeg_encode_u8: frames uint8 [B,H,W,3] -> out uint8 [B,capacity] (the scan of every frame), length int32 [B], status int32
+    [B,2]; ``quant_*``: numpy uint16 [64], natural order.  Runs on the current stream."""
+    import numpy as np
+    for name, t, dtype in (("frames", frames, torch.uint8), ("out", out, torch.uint8), ("length", length, torch.int32),
+                           ("status", status, torch.int32), ("scratch", scratch, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise HipExtensionError(f"jpeg_encode: {name} must be a tensor on a HIP device (the encoder has no CPU fallback)")
+        if t.dtype != dtype or not t.is_contiguous():
+            raise HipExtensionError(f"jpeg_encode: {name} is {t.dtype} (contiguous: {t.is_contiguous()}), expected contiguous {dtype}")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise HipExtensionError(f"jpeg_encode: frames [B,H,W,3] expected, got {tuple(frames.shape)}")
+    B, H, W = frames.shape[:3]
+    if out.dim() != 2 or out.shape[0] != B or length.numel() != B or tuple(status.shape) != (B, 2):
+        raise HipExtensionError("jpeg_encode: out [B,capacity], length [B] and status [B,2] expected")
+    ql = np.ascontiguousarray(quant_luma, dtype=np.uint16).reshape(64)
+    qc = np.ascontiguousarray(quant_chroma, dtype=np.uint16).reshape(64)
+    _check(load().se_jpeg_encode_u8(_ptr(frames), B, H, W, 1 if bgr else 0, ql.ctypes.data, qc.ctypes.data, int(subsampling),
+                                    int(restart_rows), _ptr(out), out.shape[1], _ptr(length), _ptr(status), _ptr(scratch),
+                                    scratch.numel(), _stream()), "se_jpeg_encode_u8")

@@ -201,3 +201,10 @@ def save_png(path, rgb) -> None:
     """uint8 [H,W,3] (R, G, B), tensor or array -> PNG (PIL, on the host)."""
     from PIL import Image
     Image.fromarray(np.ascontiguousarray(torch.as_tensor(rgb).cpu().numpy())).save(path, format="PNG")
+
+
+def save_jpeg(path, rgb, quality=90, subsampling="444") -> None:
+    """uint8 [H,W,3] (R, G, B), tensor or array -> baseline JPEG encoded on the device (``sceneego_amd/jpeg_encode.py``); only the
+    compressed bytes cross to the host."""
+    from .jpeg_encode import save_jpeg as _save
+    _save(path, rgb, quality=quality, subsampling=subsampling)

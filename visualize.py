@@ -5,13 +5,14 @@ and the point cloud as a PLY file.
 
     python visualize.py --img_path data/demo/imgs/img_001000.jpg --depth_path data/demo/depths/img_001000.jpg.exr \\
                         --pose_path data/demo/out/img_001000.jpg.pkl [--output render.png] [--overlay overlay.png] [--ply scene.ply]
-                        [--azimuth 35 --elevation 25 --distance 3.5 --fov 50 --size 720x960 --splat 2]
+                        [--azimuth 35 --elevation 25 --distance 3.5 --fov 50 --size 720x960 --splat 2] [--format png|jpg]
 
 The reference opens an open3d window (``draw_geometries([scene, predicted_pose_mesh])``); this script renders the same two
 geometries on the device (``sceneego_amd/render.py``, ``csrc/render.hip``) and writes files.  It reads what ``demo.py`` reads and
 writes: the frame (a baseline JPEG is decoded on the device where that path takes the file, otherwise by PIL), the depth map
 (``.exr`` / ``.npy`` / ``.npz``) and the pickle of float32 [15, 3] joints.  An empty string for ``--output`` / ``--overlay`` /
-``--ply`` skips that file.
+``--ply`` skips that file.  ``--format jpg`` writes the two images as quality-90 4:4:4 JPEG files encoded on the device
+(``sceneego_amd/jpeg_encode.py``); their default names become ``render.jpg`` and ``overlay.jpg``.
 """
 import argparse
 import os
@@ -40,8 +41,12 @@ def parse_args(argv=None):
     ap.add_argument("--img_path", type=str, required=True)
     ap.add_argument("--depth_path", type=str, required=True)
     ap.add_argument("--pose_path", type=str, required=True)
-    ap.add_argument("--output", type=str, default="render.png", help="third-person view of the point cloud and the skeleton")
-    ap.add_argument("--overlay", type=str, default="overlay.png", help="the skeleton drawn into the fisheye frame")
+    ap.add_argument("--output", type=str, default=None,
+                    help="third-person view of the point cloud and the skeleton (default: render.png, or render.jpg with --format jpg)")
+    ap.add_argument("--overlay", type=str, default=None,
+                    help="the skeleton drawn into the fisheye frame (default: overlay.png, or overlay.jpg with --format jpg)")
+    ap.add_argument("--format", type=str, default="png", choices=("png", "jpg"),
+                    help="png (PIL on the host) or jpg (quality-90 4:4:4 JPEG encoded on the device)")
     ap.add_argument("--ply", type=str, default="scene.ply", help="the coloured point cloud (binary PLY)")
     ap.add_argument("--azimuth", type=float, default=35.0, help="degrees around the cuboid centre (0, 0, 1)")
     ap.add_argument("--elevation", type=float, default=25.0, help="degrees towards the head camera")
@@ -50,7 +55,12 @@ def parse_args(argv=None):
     ap.add_argument("--size", type=_size, default=(720, 960), help="HxW of the rendered view")
     ap.add_argument("--splat", type=int, default=2, choices=(1, 2, 3, 4), help="footprint of a point, pixels")
     ap.add_argument("--calibration", type=str, default=CALIBRATION)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.output is None:
+        args.output = "render." + args.format
+    if args.overlay is None:
+        args.overlay = "overlay." + args.format
+    return args
 
 
 def load_frame(img_path, device):
@@ -69,7 +79,7 @@ def visualize(args):
     import torch
 
     from sceneego_amd.preprocess import load_depth
-    from sceneego_amd.render import SceneRenderer, orbit_view, save_png, write_ply
+    from sceneego_amd.render import SceneRenderer, orbit_view, save_jpeg, save_png, write_ply
     if not torch.cuda.is_available():
         raise RuntimeError("visualize.py needs an MI355X (HIP device); the renderer has no CPU fallback")
     device = torch.device("cuda")
@@ -79,13 +89,14 @@ def visualize(args):
     depth = torch.from_numpy(load_depth(args.depth_path))[None].to(device)
     renderer = SceneRenderer(args.calibration, frame_size=tuple(frame.shape[1:3]), out_size=args.size, fov_y_deg=args.fov,
                              splat=args.splat, device=device)
+    save = save_jpeg if getattr(args, "format", "png") == "jpg" else save_png
     written = []
     if args.output:
         view = orbit_view(args.azimuth, args.elevation, args.distance)
-        save_png(args.output, renderer.render(depth, frame, pose, view=view)[0])
+        save(args.output, renderer.render(depth, frame, pose, view=view)[0])
         written.append(args.output)
     if args.overlay:
-        save_png(args.overlay, renderer.overlay(frame, pose, depth=depth)[0])
+        save(args.overlay, renderer.overlay(frame, pose, depth=depth)[0])
         written.append(args.overlay)
     if args.ply:
         write_ply(args.ply, *renderer.scene_points(depth, frame))
