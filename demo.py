@@ -13,6 +13,11 @@ scanline OpenEXR, NONE/ZIP/PIZ, decoded by ``sceneego_amd/exr.py``) or ``.npy`` 
 ``<img_name>.overlay.png`` (the skeleton in the fisheye frame) per frame, rendered on the device (``sceneego_amd/render.py``);
 ``--render_format jpg`` writes ``.render.jpg`` / ``.overlay.jpg`` instead: quality-90 4:4:4 JPEG files encoded on the device
 (``sceneego_amd/jpeg_encode.py``), so that only compressed bytes cross to the host.
+``--render_volumes true`` (with ``--render_dir``) also writes ``<img_name>.volumes.render.*`` and ``<img_name>.volumes.overlay.*``: the same
+two pictures with the joint probability volumes drawn over them as a maximum-intensity projection in per-joint colours
+(``SceneRenderer.render_volumes`` / ``overlay_volumes``); ``--volume_joints 9,10,13,14`` draws only those joints.
+``--save_volumes true`` writes ``<img_name>.volumes.npy`` (float32 [15, G, G, G]) beside each ``<img_name>.pkl``, the file
+``visualize.py --volumes_path`` reads.
 ``--scene_check true`` writes ``<img_name>.scene.pkl`` beside each ``<img_name>.pkl``: collision, clearance and contact of the
 predicted skeleton against the scene of its own depth map (``sceneego_amd/scene_check.py``: ``SceneConsistency.check``).
 """
@@ -20,6 +25,7 @@ import argparse
 import os
 import pickle
 
+import numpy as np
 import torch
 
 from sceneego_amd import load_config, synth
@@ -36,7 +42,7 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 class Demo:
     def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False,
-                 render_format="png"):
+                 render_format="png", render_volumes=False, volume_joints=None, save_volumes=None):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
@@ -48,6 +54,9 @@ class Demo:
             raise ValueError(f"render_format must be png or jpg, got {render_format!r}")
         self.render_format = render_format
         self.renderer = None
+        self.render_volumes = render_volumes
+        self.volume_joints = volume_joints
+        self.save_volumes = save_volumes
         self.scene_check = scene_check
         self.scene = None
         self.items = []
@@ -101,8 +110,12 @@ class Demo:
                     results[-1]["stats"] = joint_statistics_to_numpy(self.network.joint_statistics(volumes, kp))[0]
                 if self.scene_check:
                     results[-1]["scene"] = scene_check_to_numpy(self.check_scene(depth, kp))[0]
+                if self.save_volumes is not None:
+                    # written frame by frame: a frame's volumes are 15.7 MB, too much to keep for a whole directory
+                    os.makedirs(self.save_volumes, exist_ok=True)
+                    np.save(os.path.join(self.save_volumes, os.path.split(img_path)[1] + ".volumes.npy"), volumes[0].cpu().numpy())
                 if self.render_dir is not None:
-                    self.render(os.path.split(img_path)[1], frame_u8, depth, kp)
+                    self.render(os.path.split(img_path)[1], frame_u8, depth, kp, volumes if self.render_volumes else None)
         return results
 
     def check_scene(self, depth, kp):
@@ -116,8 +129,10 @@ class Demo:
             self.scene = SceneConsistency(calib, frame_size=size, device=self.device, ray_tab=shared, config=self.config)
         return self.scene.check(depth, kp)
 
-    def render(self, img_name, frame_u8, depth, kp):
-        """<img_name>.render.png and <img_name>.overlay.png (or .jpg) into render_dir; reads the forward's results, changes none."""
+    def render(self, img_name, frame_u8, depth, kp, volumes=None):
+        """<img_name>.render.png and <img_name>.overlay.png (or .jpg) into render_dir, with ``volumes`` also <img_name>.volumes.render.*
+        and <img_name>.volumes.overlay.*; reads the forward's results (the volumes before the next forward overwrites them), changes
+        none."""
         from sceneego_amd.render import SceneRenderer, save_jpeg, save_png
         if self.renderer is None:
             from sceneego_amd.config import resolve_calibration_path
@@ -131,6 +146,12 @@ class Demo:
         ext = "." + self.render_format
         save(os.path.join(self.render_dir, img_name + ".render" + ext), self.renderer.render(depth, frame_u8, kp)[0])
         save(os.path.join(self.render_dir, img_name + ".overlay" + ext), self.renderer.overlay(frame_u8, kp, depth=depth)[0])
+        if volumes is not None:
+            side = self.network.cuboid_side
+            save(os.path.join(self.render_dir, img_name + ".volumes.render" + ext),
+                 self.renderer.render_volumes(depth, frame_u8, kp, volumes, side, joint_mask=self.volume_joints)[0])
+            save(os.path.join(self.render_dir, img_name + ".volumes.overlay" + ext),
+                 self.renderer.overlay_volumes(frame_u8, kp, volumes, side, depth=depth, joint_mask=self.volume_joints)[0])
 
 
 def parse_args(argv=None):
@@ -147,6 +168,13 @@ def parse_args(argv=None):
                     help="also write <img_name>.render.png and <img_name>.overlay.png here (rendered on the device; no display needed)")
     ap.add_argument("--render_format", type=str, default="png", choices=("png", "jpg"),
                     help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG encoded on the device)")
+    ap.add_argument("--render_volumes", type=str, default="false",
+                    help="true (with --render_dir): also write <img_name>.volumes.render.* and <img_name>.volumes.overlay.*, the two "
+                         "pictures with the joint probability volumes drawn over them")
+    ap.add_argument("--volume_joints", type=str, default=None,
+                    help="with --render_volumes true: the joints to draw, e.g. 9,10,13,14 (default: all 15)")
+    ap.add_argument("--save_volumes", type=str, default="false",
+                    help="true: also write <img_name>.volumes.npy (float32 [15,G,G,G]; visualize.py --volumes_path reads it)")
     ap.add_argument("--scene_check", type=str, default="false",
                     help="true: also write <img_name>.scene.pkl (nearest_dist, clearance, bone_clearance, penetration_depth, penetrating, "
                          "contact, ... of the skeleton against the depth map's scene)")
@@ -159,6 +187,19 @@ def parse_args(argv=None):
     if args.scene_check.lower() not in ("true", "false"):
         raise SystemExit("--scene_check must be true or false")
     args.scene_check = args.scene_check.lower() == "true"
+    for flag in ("render_volumes", "save_volumes"):
+        if getattr(args, flag).lower() not in ("true", "false"):
+            raise SystemExit(f"--{flag} must be true or false")
+        setattr(args, flag, getattr(args, flag).lower() == "true")
+    if args.render_volumes and args.render_dir is None:
+        raise SystemExit("--render_volumes true needs --render_dir")
+    if args.volume_joints is not None and not args.render_volumes:
+        raise SystemExit("--volume_joints needs --render_volumes true")
+    from sceneego_amd.render import parse_joint_list
+    try:
+        args.volume_joints = parse_joint_list(args.volume_joints)
+    except ValueError as e:
+        raise SystemExit(str(e))
     return args
 
 
@@ -166,7 +207,8 @@ def main(argv=None):
     args = parse_args(argv)
     config = load_config(args.config)
     demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats, render_dir=args.render_dir,
-                scene_check=args.scene_check, render_format=args.render_format)
+                scene_check=args.scene_check, render_format=args.render_format, render_volumes=args.render_volumes,
+                volume_joints=args.volume_joints, save_volumes=args.output_dir if args.save_volumes else None)
     os.makedirs(args.output_dir, exist_ok=True)
     for r in demo.run():
         out_path = os.path.join(args.output_dir, os.path.split(r["img_path"])[1] + ".pkl")

@@ -601,6 +601,59 @@ int se_jpeg_encode_u8(const unsigned char* frames, int batch, int height, int wi
                       const unsigned short* quant_chroma, int subsampling, int restart_rows, unsigned char* out, long long capacity,
                       int* length, int* status, void* scratch, long long scratch_bytes, void* stream);
 
+/* Volume renderer (no counterpart in the reference; sceneego_amd/render.py: SceneRenderer.render_volumes / overlay_volumes): a
+ * maximum-intensity projection of the 15 per-joint volumes along every pixel's ray, composited joint by joint over a picture
+ * se_render_resolve_f64 / se_render_overlay_f64 made.  All arithmetic is float64, unfused, in the order written here
+ * (tests/volume_render_model.py restates it).  `view` is a HOST pointer, read during the call; every other pointer is device memory.
+ *   volumes  [B][15][G][G][G] float32 (x, y, z; z fastest), softmaxed or ReLU        packed  [B][G^3][16] float32, 16-byte aligned,
+ *            se_render_volume_packed_bytes(batch, grid) bytes (-1: bad shape): cell-interleaved copy written by
+ *            se_render_volume_pack_f32 (slot 15 is 0); the two marches read it, not `volumes`
+ *   scale    [B][15] float64        joint_mask  bit j set: joint j is drawn.  Joint j of frame b is OFF when its bit is clear or
+ *            scale[b][j] is not finite or <= 0
+ *   rays     as for se_render_resolve_f64 (view: pinhole table, out_h x out_w) / se_render_overlay_f64 (overlay: the calibrated unit rays)
+ *   base     the picture to draw over, uint8 (R, G, B), shape of out; may be `out` itself (in place)
+ * Grid (op.build_coord_volume(G, S), camera frame): pos = (-(S / 2), -(S / 2), 0), h = S / (double)(G - 1); boundary k of axis a is
+ *   bnd_a(k) = pos_a + ((double)k - 0.5) * h, cell i covers [bnd_a(i), bnd_a(i + 1)), the box is [bnd_a(0), bnd_a(G)) per axis.
+ * Ray o + s d.  Overlay: o = 0, d = rays[y][x] (s is distance).  View, with R = view[0..8] row-major and t = view[9..11] (q = R p + t):
+ *   o_i = -((R[0][i] t[0] + R[1][i] t[1]) + R[2][i] t[2]), d_i = (R[0][i] p.x + R[1][i] p.y) + R[2][i] p.z for the pinhole ray p (s is
+ *   view-space z, the quantity in the z-buffer key).  A ray with a non-finite component misses.
+ * Limit: +inf; view with zbuf != NULL: (double)(float of zbuf >> 32) unless the key is all-ones ("no point"); overlay with depth !=
+ *   NULL: (double)depth[b][(y depth_h) / height][(x depth_w) / width]; a NaN limit misses (the rule of se_render_overlay_f64: shown
+ *   only where s < depth).
+ * Range: s0 = near, s1 = limit; per axis a = x, y, z: if d_a == 0 the ray misses unless bnd_a(0) <= o_a < bnd_a(G) (no division);
+ *   else inv_a = 1 / d_a, ta = (bnd_a(0) - o_a) * inv_a, tb = (bnd_a(G) - o_a) * inv_a, tn = ta < tb ? ta : tb, tf = the other;
+ *   if tn > s0: s0 = tn; if tf < s1: s1 = tf.  The ray misses unless s0 < s1.
+ * Walk (Amanatides-Woo): start index i_a = floor(u) clamped into 0..G-1 with u = ((o_a + s0 * d_a) - pos_a) / h + 0.5 (a NaN: 0);
+ *   step_a = sign(d_a); next_a = (bnd_a(i_a + (step_a > 0 ? 1 : 0)) - o_a) * inv_a, +inf when d_a == 0, recomputed from the index after
+ *   every step (no running sum).  The start cell counts.  Then repeatedly: a = x; if next_y < next_a: a = y; if next_z < next_a: a = z
+ *   (strict: of equal ones the first); stop unless next_a < s1 (the next cell's entry parameter); i_a += step_a; stop when it leaves
+ *   0..G-1; the cell counts.
+ * Maximum: m_j = max over the counted cells of (double)p_j[cell] * scale_j, taken as v > m from m = 0 (a NaN never wins; the kernel
+ *   takes the float32 maximum and multiplies once, which is the same number for a scale > 0).
+ * Composite: c = (double)base channel; for j = 0..14 ascending, joints that are not off: g = gain * m_j, a = (g < 1 ? g : 1) *
+ *   opacity, c = c + a * ((double)palette[j][channel] - c); out = (uint8)floor(c + 0.5).  A miss, an all-zero volume and a zero mask
+ *   leave the base picture byte for byte.
+ * One launch each, nothing allocated, no memset node: legal under hipGraph capture; bitwise reproducible.
+ * SE_ERR_BAD_ARG: a null pointer (zbuf / depth may be NULL: no occlusion), batch outside 1..65535, grid outside 2..1024, a
+ *   non-positive size, packed misaligned or packed_bytes too small, cuboid_side <= 0, > 1e6 or NaN, near < 0, > 1e6 or NaN, gain < 0,
+ *   > 1e30 or NaN,
+ *   opacity outside [0, 1], a mask bit above 14, a non-finite view. */
+/* per joint (R, G, B): the neck neutral, right-side joints (1-3, 7-10) warm, left-side joints (4-6, 11-14) cold */
+#define SE_RENDER_VOLUME_PALETTE                                                                                                  \
+    {{235, 235, 235}, {255, 60, 30}, {255, 120, 20}, {255, 185, 10}, {30, 90, 255}, {20, 160, 255}, {10, 225, 255}, {200, 20, 60}, \
+     {230, 40, 120}, {250, 80, 170}, {255, 140, 210}, {70, 40, 210}, {40, 70, 160}, {20, 150, 150}, {40, 210, 130}}
+void se_render_volume_palette(unsigned char* rgb /* HOST, 45 bytes */);
+long long se_render_volume_packed_bytes(int batch, int grid);
+int se_render_volume_pack_f32(const float* volumes, float* packed, long long packed_bytes, int batch, int grid, void* stream);
+int se_render_volume_view_f64(const float* packed, const double* scale, const double* rays, const double* view,
+                              const unsigned long long* zbuf, const unsigned char* base, unsigned char* out, int batch, int out_h,
+                              int out_w, int grid, double cuboid_side, double near, unsigned int joint_mask, double gain,
+                              double opacity, void* stream);
+int se_render_volume_overlay_f64(const float* packed, const double* scale, const double* rays, const float* depth,
+                                 const unsigned char* base, unsigned char* out, int batch, int height, int width, int depth_h,
+                                 int depth_w, int grid, double cuboid_side, double near, unsigned int joint_mask, double gain,
+                                 double opacity, void* stream);
+
 #ifdef SE_DEVTOOLS
 /* Development builds only (csrc/build.sh --devtools; absent from the production library): A/B kernel selection for
  * tools/bench_conv.py and the cycle-stamp diagnostics.  The selector is thread-local. */

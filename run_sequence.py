@@ -151,24 +151,38 @@ class SequenceRunner:
         rendered in, and only their compressed bytes cross to the host."""
         from sceneego_amd.config import resolve_calibration_path
         from sceneego_amd.render import SceneRenderer, save_png
-        render_dir, pick, names, frames_u8, depth = job
+        render_dir, pick, names, frames_u8, depth, vol = job
         opt = self.render_options
         if self.renderer is None:
             self.renderer = SceneRenderer(resolve_calibration_path(self.config.dataset.camera_calibration_path),
                                           frame_size=tuple(frames_u8.shape[1:3]), device=self.device, **opt["renderer"])
         joints = kp[pick]
-        scene = self.renderer.render(depth, frames_u8, joints)
-        over = self.renderer.overlay(frames_u8, joints, depth=depth)
-        if render_dir is not None and opt["format"] == "png":
-            scene_h, over_h = scene.cpu(), over.cpu()
-            for k, name in enumerate(names):
-                save_png(os.path.join(render_dir, name + ".render.png"), scene_h[k])
-                save_png(os.path.join(render_dir, name + ".overlay.png"), over_h[k])
-        elif render_dir is not None:
-            for view, images in (("render", scene), ("overlay", over)):
+
+        def write(view, images):
+            if render_dir is None:
+                return
+            if opt["format"] == "png":
+                images_h = images.cpu()
+                for k, name in enumerate(names):
+                    save_png(os.path.join(render_dir, f"{name}.{view}.png"), images_h[k])
+            else:
                 for name, data in zip(names, self._encoder().encode(images, quality=90, subsampling="444")):
                     with open(os.path.join(render_dir, f"{name}.{view}.jpg"), "wb") as f:
                         f.write(data)
+
+        volumes = bool(opt.get("volumes"))
+        if not volumes or render_dir is not None:           # with volumes and a video only, nobody looks at the plain pair
+            scene = self.renderer.render(depth, frames_u8, joints)
+            over = self.renderer.overlay(frames_u8, joints, depth=depth)
+            write("render", scene)
+            write("overlay", over)
+        if volumes:
+            # drawn into the buffers the plain pair was in: that pair has been written by now
+            side, which = self.net.cuboid_side, opt.get("volume_joints")
+            scene = self.renderer.render_volumes(depth, frames_u8, joints, vol[pick], side, joint_mask=which)
+            over = self.renderer.overlay_volumes(frames_u8, joints, vol[pick], side, depth=depth, joint_mask=which)
+            write("volumes.render", scene)
+            write("volumes.overlay", over)
         if opt["video"] is not None:
             if opt["view"] == "both":
                 if scene.shape[1] != over.shape[1]:
@@ -192,11 +206,14 @@ class SequenceRunner:
 
     @torch.no_grad()
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
-            render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None):
+            render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
+            volume_joints=None):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
-        scene-check dicts are appended to what is returned (joints, [statistics,] scene checks)."""
+        scene-check dicts are appended to what is returned (joints, [statistics,] scene checks).  ``render_volumes``: also write
+        ``<img_name>.volumes.render.*`` / ``.volumes.overlay.*`` (the joint probability volumes of ``volume_joints``, default all, drawn
+        over the pair), and the video shows those views."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy
         from sceneego_amd.preprocess import load_image_bgr
@@ -213,7 +230,8 @@ class SequenceRunner:
             if render_dir is not None:
                 os.makedirs(render_dir, exist_ok=True)
             self.render_options = {"format": render_format, "video": render_video, "fps": render_fps, "view": render_view,
-                                   "quality": render_quality, "renderer": {} if render_size is None else {"out_size": tuple(render_size)}}
+                                   "quality": render_quality, "renderer": {} if render_size is None else {"out_size": tuple(render_size)},
+                                   "volumes": bool(render_volumes), "volume_joints": volume_joints}
 
         def drain(keep):
             while len(pending) > keep:
@@ -245,11 +263,13 @@ class SequenceRunner:
                                depth[pick])
                 if self.pipe is None:
                     kp, _, vol, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
+                    job = job + (vol,) if job is not None else None       # drained before the next forward overwrites the volumes
                     pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
                                     self._scene().check(depth, kp) if scene else None))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
+                    job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
                     st = sc = None
                     if stats or scene:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
@@ -324,13 +344,34 @@ def build_parser():
                     help="with --render_video: the third-person view, the fisheye overlay, or both side by side (equal heights only)")
     ap.add_argument("--render_quality", type=_quality, default=90, help="with --render_video: JPEG quality, 1..100")
     ap.add_argument("--render_size", type=_size, default=None, help="HxW of the third-person view (default: 720x960)")
+    ap.add_argument("--render_volumes", default="false",
+                    help="true (with --render_dir / --render_video): also write <img_name>.volumes.render.* and .volumes.overlay.* (the "
+                         "joint probability volumes drawn over the pair); the video shows the volume views")
+    ap.add_argument("--volume_joints", default=None, help="with --render_volumes true: the joints to draw, e.g. 9,10,13,14 (default: all)")
     return ap
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.render_volumes.lower() not in ("true", "false"):
+        raise SystemExit("--render_volumes must be true or false")
+    args.render_volumes = args.render_volumes.lower() == "true"
+    if args.render_volumes and args.render_dir is None and args.render_video is None:
+        raise SystemExit("--render_volumes true needs --render_dir or --render_video")
+    if args.volume_joints is not None and not args.render_volumes:
+        raise SystemExit("--volume_joints needs --render_volumes true")
+    from sceneego_amd.render import parse_joint_list
+    try:
+        args.volume_joints = parse_joint_list(args.volume_joints)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return args
 
 
 def main(argv=None):
     from sceneego_amd import load_config
     from sceneego_amd import metrics as M
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     config = load_config(args.config)
     images, poses, depths = frame_list(args.root_dir, args.seq_name, args.estimated_depth_name)
     if not images:
@@ -345,7 +386,8 @@ def main(argv=None):
     preds = runner.run(images, depths, config.test.batch_size, stats=want_stats, render_dir=args.render_dir,
                        render_every=args.render_every, scene=want_scene, render_format=args.render_format,
                        render_video=args.render_video, render_fps=args.render_fps, render_view=args.render_view,
-                       render_quality=args.render_quality, render_size=args.render_size)
+                       render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
+                       volume_joints=args.volume_joints)
     if want_stats or want_scene:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -99,6 +99,11 @@ SIGNATURES = {
     "se_render_splat_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _d, _d, _d, _vp]),
     "se_render_resolve_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "se_render_overlay_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
+    "se_render_volume_palette": (None, [_vp]),
+    "se_render_volume_packed_bytes": (_ll, [_i, _i]),
+    "se_render_volume_pack_f32": (_i, [_vp, _vp, _ll, _i, _i, _vp]),
+    "se_render_volume_view_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, ctypes.c_uint, _d, _d, _vp]),
+    "se_render_volume_overlay_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, ctypes.c_uint, _d, _d, _vp]),
     "se_scene_probe_scratch_bytes": (_ll, [_i, _i, _i, _i]),
     "se_scene_probe_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _d, _d, _vp]),
 }
@@ -946,6 +951,106 @@ def render_overlay(rays, joints, frame, out, depth=None, r_joint=RENDER_R_JOINT,
     _check(load().se_render_overlay_f64(_ptr(rays), _ptr(joints), _ptr(frame), _ptr(depth), _ptr(out), B, H, W, dh, dw, float(r_joint),
                                         float(r_bone), float(near), _rgb3(joint_rgb), _rgb3(bone_rgb), _stream()),
            "se_render_overlay_f64")
+    return out
+
+
+# Volume renderer (csrc/render_volume.hip; SceneRenderer.render_volumes / overlay_volumes drive it)
+RENDER_VOLUME_SLOTS = 16           # floats per cell of the packed copy: 15 joints and a zero
+RENDER_VOLUME_ALL = (1 << RENDER_JOINTS) - 1
+
+
+def render_volume_palette():
+    """The 15 per-joint colours (R, G, B) of include/sceneego_hip.h, read from the library (host only: no device needed)."""
+    buf = (ctypes.c_ubyte * (3 * RENDER_JOINTS))()
+    load().se_render_volume_palette(ctypes.cast(buf, ctypes.c_void_p))
+    return tuple(tuple(int(buf[3 * j + k]) for k in range(3)) for j in range(RENDER_JOINTS))
+
+
+def render_volume_packed_elems(batch, grid):
+    """float32 elements of the packed copy of ``batch`` frames of ``grid``^3 cells."""
+    n = int(load().se_render_volume_packed_bytes(int(batch), int(grid)))
+    if n < 0:
+        raise HipExtensionError(f"render_volume: batch = {batch}, grid = {grid}: batch must be 1..65535 and grid 2..1024")
+    return n // 4
+
+
+def render_volume_pack(volumes, packed):
+    """se_render_volume_pack_f32: volumes [B,15,G,G,G] float32 -> packed, float32 with at least B * G^3 * 16 elements."""
+    for name, t in (("volumes", volumes), ("packed", packed)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise HipExtensionError(f"render_volume_pack: {name} must be a tensor on a HIP device")
+    if volumes.dim() != 5 or volumes.shape[1] != RENDER_JOINTS or not volumes.shape[2] == volumes.shape[3] == volumes.shape[4]:
+        raise HipExtensionError(f"render_volume_pack: volumes [B,15,G,G,G] expected, got {tuple(volumes.shape)}")
+    B, G = volumes.shape[0], volumes.shape[2]
+    _render_check("volumes", volumes, torch.float32, (B, RENDER_JOINTS, G, G, G))
+    need = render_volume_packed_elems(B, G)
+    if packed.dtype != torch.float32 or not packed.is_contiguous() or packed.numel() < need:
+        raise HipExtensionError(f"render: packed is {packed.dtype} with {packed.numel()} elements (contiguous: {packed.is_contiguous()}), "
+                                f"expected contiguous torch.float32 with at least {need}")
+    _check(load().se_render_volume_pack_f32(_ptr(volumes), _ptr(packed), packed.numel() * 4, B, G, _stream()), "se_render_volume_pack_f32")
+    return packed
+
+
+def _render_volume_common(who, packed, scale, B, grid):
+    for name, t in (("packed", packed), ("scale", scale)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise HipExtensionError(f"{who}: {name} must be a tensor on a HIP device")
+    need = render_volume_packed_elems(B, grid)
+    if packed.dtype != torch.float32 or not packed.is_contiguous() or packed.numel() < need:
+        raise HipExtensionError(f"render: packed is {packed.dtype} with {packed.numel()} elements (contiguous: {packed.is_contiguous()}), "
+                                f"expected contiguous torch.float32 with at least {need}")
+    _render_check("scale", scale, torch.float64, (B, RENDER_JOINTS))
+
+
+def render_volume_view(packed, scale, rays, view, zbuf, out, grid, cuboid_side, base=None, near=0.05, joint_mask=RENDER_VOLUME_ALL,
+                       gain=1.0, opacity=0.8):
+    """se_render_volume_view_f64: packed (render_volume_pack), scale [B,15] float64, rays [Hout,Wout,3] float64 (pinhole table), view
+    12 floats on the host, zbuf None (no occlusion) or [B,Hout,Wout] int64 -> out [B,Hout,Wout,3] uint8 (R, G, B), drawn over
+    ``base`` (default: over ``out`` itself, in place)."""
+    base = out if base is None else base
+    for name, t in (("rays", rays), ("out", out), ("base", base)) + ((("zbuf", zbuf),) if zbuf is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise HipExtensionError(f"render_volume_view: {name} must be a tensor on a HIP device")
+    if out.dim() != 4:
+        raise HipExtensionError("render_volume_view: out [B,Hout,Wout,3] expected")
+    B, Ho, Wo, _ = out.shape
+    _render_volume_common("render_volume_view", packed, scale, B, grid)
+    _render_check("rays", rays, torch.float64, (Ho, Wo, 3))
+    _render_check("out", out, torch.uint8, (B, Ho, Wo, 3))
+    _render_check("base", base, torch.uint8, (B, Ho, Wo, 3))
+    if zbuf is not None:
+        _render_check("zbuf", zbuf, torch.int64, (B, Ho, Wo))
+    v = (ctypes.c_double * 12)(*[float(x) for x in view])
+    _check(load().se_render_volume_view_f64(_ptr(packed), _ptr(scale), _ptr(rays), ctypes.cast(v, ctypes.c_void_p), _ptr(zbuf),
+                                            _ptr(base), _ptr(out), B, Ho, Wo, int(grid), float(cuboid_side), float(near),
+                                            int(joint_mask), float(gain), float(opacity), _stream()), "se_render_volume_view_f64")
+    return out
+
+
+def render_volume_overlay(packed, scale, rays, out, grid, cuboid_side, base=None, depth=None, near=0.05,
+                          joint_mask=RENDER_VOLUME_ALL, gain=1.0, opacity=0.8):
+    """se_render_volume_overlay_f64: packed, scale [B,15] float64, rays [H,W,3] float64 (the camera's unit rays), depth None (no
+    occlusion) or [B,dh,dw] float32 -> out [B,H,W,3] uint8 (R, G, B), drawn over ``base`` (default: ``out`` itself, in place)."""
+    base = out if base is None else base
+    for name, t in (("rays", rays), ("out", out), ("base", base)) + ((("depth", depth),) if depth is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise HipExtensionError(f"render_volume_overlay: {name} must be a tensor on a HIP device")
+    if out.dim() != 4:
+        raise HipExtensionError("render_volume_overlay: out [B,H,W,3] expected")
+    B, H, W, _ = out.shape
+    _render_volume_common("render_volume_overlay", packed, scale, B, grid)
+    _render_check("rays", rays, torch.float64, (H, W, 3))
+    _render_check("out", out, torch.uint8, (B, H, W, 3))
+    _render_check("base", base, torch.uint8, (B, H, W, 3))
+    dh = dw = 0
+    if depth is not None:
+        if depth.dim() != 3:
+            raise HipExtensionError("render_volume_overlay: depth [B,dh,dw] expected")
+        dh, dw = depth.shape[1:]
+        _render_check("depth", depth, torch.float32, (B, dh, dw))
+    _check(load().se_render_volume_overlay_f64(_ptr(packed), _ptr(scale), _ptr(rays), _ptr(depth), _ptr(base), _ptr(out), B, H, W, dh, dw,
+                                               int(grid), float(cuboid_side), float(near), int(joint_mask), float(gain), float(opacity),
+                                               _stream()), "se_render_volume_overlay_f64")
     return out
 
 

@@ -69,6 +69,20 @@ def pinhole_ray_table(out_h, out_w, f, cx, cy) -> np.ndarray:
     return rays
 
 
+def parse_joint_list(text):
+    """"9,10,13,14" -> (9, 10, 13, 14), the form of the tools' ``--volume_joints``; None stays None (all joints).  ValueError with
+    the message the tools print for anything else."""
+    if text is None:
+        return None
+    try:
+        joints = tuple(int(t) for t in str(text).split(","))
+    except ValueError:
+        raise ValueError(f"--volume_joints wants joint indices separated by commas, e.g. 9,10,13,14; got {text!r}") from None
+    if not joints or any(not 0 <= j < _lib.RENDER_JOINTS for j in joints):
+        raise ValueError(f"--volume_joints wants joint indices 0..{_lib.RENDER_JOINTS - 1}; got {text!r}")
+    return joints
+
+
 class SceneRenderer:
     """Owns the two ray tables (built and uploaded once), the z-buffer and the output images.  The arrays ``render`` / ``overlay``
     return are the renderer's own buffers: the next call with the same batch size overwrites them."""
@@ -147,6 +161,99 @@ class SceneRenderer:
         j = self._joints(joints, B).contiguous()
         d = None if depth is None else self._depth(depth, B)
         return _lib.render_overlay(self.ray_tab, j, img, self._buffers(B)[2], depth=d, near=NEAR)
+
+    # -------------------------------------------------------------------------------------------- the joint probability volumes
+    @staticmethod
+    def _joint_mask(joint_mask) -> int:
+        """None (all joints) or an iterable of joint indices -> the bit mask of se_render_volume_*_f64."""
+        if joint_mask is None:
+            return _lib.RENDER_VOLUME_ALL
+        if isinstance(joint_mask, (str, bytes)) or not hasattr(joint_mask, "__iter__"):
+            raise ValueError(f"joint_mask must be None or an iterable of joint indices 0..14, got {joint_mask!r}")
+        mask = 0
+        for j in joint_mask:
+            if isinstance(j, bool) or int(j) != j or not 0 <= int(j) < _lib.RENDER_JOINTS:
+                raise ValueError(f"joint_mask must hold joint indices 0..14, got {j!r}")
+            mask |= 1 << int(j)
+        return mask
+
+    @staticmethod
+    def _volume_options(cuboid_side, gain, opacity):
+        side, gain, opacity = float(cuboid_side), float(gain), float(opacity)
+        if not (math.isfinite(side) and side > 0):
+            raise ValueError(f"cuboid_side must be a positive number of metres, got {cuboid_side}")
+        if not 0 <= gain <= 1e30:
+            raise ValueError(f"gain must lie in [0, 1e30], got {gain}")
+        if not 0 <= opacity <= 1:
+            raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
+        return side, gain, opacity
+
+    def _volumes(self, volumes, B):
+        v = volumes if isinstance(volumes, torch.Tensor) else torch.as_tensor(volumes)
+        if v.dim() == 4:
+            v = v[None]
+        if v.dtype != torch.float32 or v.dim() != 5 or v.shape[1] != _lib.RENDER_JOINTS or not v.shape[2] == v.shape[3] == v.shape[4]:
+            raise ValueError(f"volumes must be float32 [B,15,G,G,G], got {v.dtype} {tuple(v.shape)}")
+        if v.shape[0] != B:
+            raise ValueError(f"volumes must be [B,15,G,G,G] with B = {B}, got {tuple(v.shape)}")
+        if v.shape[2] < 2:
+            raise ValueError(f"volumes need a grid of at least 2 cells per axis, got {tuple(v.shape)}")
+        return v.to(self.device).contiguous()
+
+    def _scale(self, scale, vol):
+        B = vol.shape[0]
+        if scale is None:
+            # the brightest finite cell of every joint maps to 1 (a NaN or infinite cell counts as 0 here, as a NaN cell never wins
+            # in the march); a joint without a positive cell gets an infinite scale, which switches it off
+            return 1.0 / torch.nan_to_num(vol, nan=0.0, posinf=0.0, neginf=0.0).amax(dim=(2, 3, 4)).double()
+        s = torch.as_tensor(scale)
+        if s.dim() == 1:
+            s = s[None]
+        if tuple(s.shape) != (B, _lib.RENDER_JOINTS):
+            raise ValueError(f"scale must be [B,15] with B = {B}, got {tuple(s.shape)}")
+        return s.to(self.device, torch.float64).contiguous()
+
+    def _packed(self, vol):
+        """The cell-interleaved copy of ``vol`` (se_render_volume_pack_f32) in a buffer the renderer keeps per (B, G)."""
+        B, G = vol.shape[0], vol.shape[2]
+        key = ("packed", B, G)
+        if key not in self._buf:
+            self._buf[key] = torch.empty(_lib.render_volume_packed_elems(B, G), device=self.device, dtype=torch.float32)
+        return _lib.render_volume_pack(vol, self._buf[key])
+
+    def render_volumes(self, depth, image_bgr_u8, joints, volumes, cuboid_side, view=None, joint_mask=None, scale=None, gain=1.0,
+                       opacity=0.8, occlude=True) -> torch.Tensor:
+        """``render`` with the maximum of every joint's volume along each pixel's ray drawn over it in the joint's colour
+        (include/sceneego_hip.h: se_render_volume_view_f64).  ``volumes``: the float32 [B,15,G,G,G] device tensor ``forward()`` returns,
+        over a cuboid of ``cuboid_side`` metres; ``scale`` [B,15] (default 1 / the joint's largest finite value: its brightest cell maps to 1, a NaN cell is passed over);
+        ``joint_mask``: an iterable of joint indices (default all); ``occlude``: hidden behind the point cloud.  Under
+        ``enable_graphs(True)`` the volumes are the graph's static buffers: render before the next forward."""
+        side, gain, opacity = self._volume_options(cuboid_side, gain, opacity)
+        mask = self._joint_mask(joint_mask)
+        img = self._frames(image_bgr_u8)
+        B = img.shape[0]
+        vol = self._volumes(volumes, B)
+        sc = self._scale(scale, vol)
+        v = np.asarray(orbit_view() if view is None else view, dtype=np.float64).reshape(12)
+        out = self.render(depth, img, joints, view=v)
+        zbuf = self._buffers(B)[0]
+        return _lib.render_volume_view(self._packed(vol), sc, self.pinhole, v, zbuf if occlude else None, out, vol.shape[2], side,
+                                       near=NEAR, joint_mask=mask, gain=gain, opacity=opacity)
+
+    def overlay_volumes(self, image_bgr_u8, joints, volumes, cuboid_side, depth=None, joint_mask=None, scale=None, gain=1.0,
+                        opacity=0.8, occlude=True) -> torch.Tensor:
+        """``overlay`` with the volumes drawn into the fisheye frame (se_render_volume_overlay_f64); with ``depth`` and ``occlude`` the
+        skeleton and the volumes are hidden where the depth map is nearer.  Arguments as for ``render_volumes``."""
+        side, gain, opacity = self._volume_options(cuboid_side, gain, opacity)
+        mask = self._joint_mask(joint_mask)
+        img = self._frames(image_bgr_u8)
+        B = img.shape[0]
+        vol = self._volumes(volumes, B)
+        sc = self._scale(scale, vol)
+        d = None if depth is None else self._depth(depth, B)
+        out = self.overlay(img, joints, depth=d)
+        return _lib.render_volume_overlay(self._packed(vol), sc, self.ray_tab, out, vol.shape[2], side, depth=d if occlude else None,
+                                          near=NEAR, joint_mask=mask, gain=gain, opacity=opacity)
 
     def scene_points(self, depth, image_bgr_u8):
         """(points float32 [n,3], rgb uint8 [n,3]) on the device: the reference's ``get_point_cloud_single_image`` with

@@ -6,13 +6,16 @@ and the point cloud as a PLY file.
     python visualize.py --img_path data/demo/imgs/img_001000.jpg --depth_path data/demo/depths/img_001000.jpg.exr \\
                         --pose_path data/demo/out/img_001000.jpg.pkl [--output render.png] [--overlay overlay.png] [--ply scene.ply]
                         [--azimuth 35 --elevation 25 --distance 3.5 --fov 50 --size 720x960 --splat 2] [--format png|jpg]
+                        [--volumes_path img_001000.jpg.volumes.npy [--volume_joints 9,10,13,14] [--cuboid_side 2]]
 
 The reference opens an open3d window (``draw_geometries([scene, predicted_pose_mesh])``); this script renders the same two
 geometries on the device (``sceneego_amd/render.py``, ``csrc/render.hip``) and writes files.  It reads what ``demo.py`` reads and
 writes: the frame (a baseline JPEG is decoded on the device where that path takes the file, otherwise by PIL), the depth map
 (``.exr`` / ``.npy`` / ``.npz``) and the pickle of float32 [15, 3] joints.  An empty string for ``--output`` / ``--overlay`` /
 ``--ply`` skips that file.  ``--format jpg`` writes the two images as quality-90 4:4:4 JPEG files encoded on the device
-(``sceneego_amd/jpeg_encode.py``); their default names become ``render.jpg`` and ``overlay.jpg``.
+(``sceneego_amd/jpeg_encode.py``); their default names become ``render.jpg`` and ``overlay.jpg``.  ``--volumes_path`` takes the
+float32 [15, G, G, G] file ``demo.py --save_volumes true`` writes and draws the joint probability volumes over both images
+(``SceneRenderer.render_volumes`` / ``overlay_volumes``).
 """
 import argparse
 import os
@@ -55,7 +58,18 @@ def parse_args(argv=None):
     ap.add_argument("--size", type=_size, default=(720, 960), help="HxW of the rendered view")
     ap.add_argument("--splat", type=int, default=2, choices=(1, 2, 3, 4), help="footprint of a point, pixels")
     ap.add_argument("--calibration", type=str, default=CALIBRATION)
+    ap.add_argument("--volumes_path", type=str, default=None,
+                    help="float32 [15,G,G,G] .npy of demo.py --save_volumes true: draw the joint probability volumes over both images")
+    ap.add_argument("--volume_joints", type=str, default=None, help="with --volumes_path: the joints to draw, e.g. 9,10,13,14 (default: all)")
+    ap.add_argument("--cuboid_side", type=float, default=2.0, help="with --volumes_path: side of the volume's cuboid, metres")
     args = ap.parse_args(argv)
+    if args.volume_joints is not None and args.volumes_path is None:
+        ap.error("--volume_joints needs --volumes_path")
+    from sceneego_amd.render import parse_joint_list
+    try:
+        args.volume_joints = parse_joint_list(args.volume_joints)
+    except ValueError as e:
+        ap.error(str(e))
     if args.output is None:
         args.output = "render." + args.format
     if args.overlay is None:
@@ -90,13 +104,24 @@ def visualize(args):
     renderer = SceneRenderer(args.calibration, frame_size=tuple(frame.shape[1:3]), out_size=args.size, fov_y_deg=args.fov,
                              splat=args.splat, device=device)
     save = save_jpeg if getattr(args, "format", "png") == "jpg" else save_png
+    volumes = None
+    if getattr(args, "volumes_path", None):
+        import numpy as np
+        volumes = torch.from_numpy(np.ascontiguousarray(np.load(args.volumes_path), dtype=np.float32)).to(device)
+        which, side = getattr(args, "volume_joints", None), getattr(args, "cuboid_side", 2.0)
     written = []
     if args.output:
         view = orbit_view(args.azimuth, args.elevation, args.distance)
-        save(args.output, renderer.render(depth, frame, pose, view=view)[0])
+        if volumes is None:
+            save(args.output, renderer.render(depth, frame, pose, view=view)[0])
+        else:
+            save(args.output, renderer.render_volumes(depth, frame, pose, volumes, side, view=view, joint_mask=which)[0])
         written.append(args.output)
     if args.overlay:
-        save(args.overlay, renderer.overlay(frame, pose, depth=depth)[0])
+        if volumes is None:
+            save(args.overlay, renderer.overlay(frame, pose, depth=depth)[0])
+        else:
+            save(args.overlay, renderer.overlay_volumes(frame, pose, volumes, side, depth=depth, joint_mask=which)[0])
         written.append(args.overlay)
     if args.ply:
         write_ply(args.ply, *renderer.scene_points(depth, frame))
