@@ -659,28 +659,23 @@ def conv3d(inp, wpack, bpack, residual, out, batch, dim, cin, cin_pad, cout, ksi
     Winograd layer sums a frame in a different float32 order at batch 1 than at batch > 1; the frequency-domain front
     layer (conv3d_k7_fft, the production path since round 6) is batch-invariant bit for bit."""
     require_hip(inp, out)
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if inp.dtype == torch.bfloat16:
-        assert wpack.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
-        assert inp.shape[-1] == (8 if ksize == 7 else cin_pad)       # the 7^3 layer reads octet-planar input
-        assert residual is None or residual.dtype == torch.bfloat16
-        _check(load().se_conv3d_bf16(_ptr(inp), _ptr(wpack), _ptr(bpack), _ptr(residual), _ptr(out), batch, dim,
-                                     cin_pad, cout, ksize, flags, _stream()), "se_conv3d_bf16")
-    elif pool_out is not None:
-        require_hip(pool_out)
-        assert pool_out.dtype == torch.float32 and pool_out.numel() == batch * (dim // 2) ** 3 * cout and pool_out.is_contiguous()
-        _check(load().se_conv3d_pool_f32(_ptr(inp), _ptr(wpack), _ptr(bpack), _ptr(residual), _ptr(out), _ptr(pool_out), batch,
-                                         dim, cin, cin_pad, cout, ksize, flags, _ptr(workspace),
-                                         0 if workspace is None else workspace.numel(), _stream()), "se_conv3d_pool_f32")
-    else:
-        _check(load().se_conv3d_f32(_ptr(inp), _ptr(wpack), _ptr(bpack), _ptr(residual), _ptr(out), batch, dim, cin,
-                                    cin_pad, cout, ksize, flags, _ptr(workspace),
-                                    0 if workspace is None else workspace.numel(), _stream()), "se_conv3d_f32")
-    if _prof is not None:
-        e1.record()
-        _prof.append((("conv3d" if inp.dtype == torch.float32 else "conv3d_bf16", ksize, cin_pad, cout, dim), e0, e1, flags))
+    with _timed(("conv3d" + _tag(inp), ksize, cin_pad, cout, dim), flags):
+        if inp.dtype == torch.bfloat16:
+            assert wpack.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
+            assert inp.shape[-1] == (8 if ksize == 7 else cin_pad)       # the 7^3 layer reads octet-planar input
+            assert residual is None or residual.dtype == torch.bfloat16
+            _check(load().se_conv3d_bf16(_ptr(inp), _ptr(wpack), _ptr(bpack), _ptr(residual), _ptr(out), batch, dim,
+                                         cin_pad, cout, ksize, flags, _stream()), "se_conv3d_bf16")
+        elif pool_out is not None:
+            require_hip(pool_out)
+            assert pool_out.dtype == torch.float32 and pool_out.numel() == batch * (dim // 2) ** 3 * cout and pool_out.is_contiguous()
+            _check(load().se_conv3d_pool_f32(_ptr(inp), _ptr(wpack), _ptr(bpack), _ptr(residual), _ptr(out), _ptr(pool_out), batch,
+                                             dim, cin, cin_pad, cout, ksize, flags, _ptr(workspace),
+                                             0 if workspace is None else workspace.numel(), _stream()), "se_conv3d_pool_f32")
+        else:
+            _check(load().se_conv3d_f32(_ptr(inp), _ptr(wpack), _ptr(bpack), _ptr(residual), _ptr(out), batch, dim, cin,
+                                        cin_pad, cout, ksize, flags, _ptr(workspace),
+                                        0 if workspace is None else workspace.numel(), _stream()), "se_conv3d_f32")
 
 
 def conv3d_k7_fft_supported(dim, cin, cout) -> bool:

@@ -10,13 +10,17 @@ Two layers:
   published checkpoint loads strictly.  The modules own no arithmetic.
 * ``V2VProgram`` is what runs: built once from the tree (``V2VModel.compile``), it folds every eval-mode
   BatchNorm3d into its convolution, re-orders the weights into MFMA fragment order on the device
-  (``se_conv3d_pack_f32``) and replays a fixed launch list over channels-last ``[B,Z,Y,X,C]`` buffers:
-  one kernel per Conv3d+BN(+ReLU)(+residual) / ConvTranspose3d+BN+ReLU(+skip) / max-pool.  There is no
-  ATen fallback: without ``libsceneego_hip.so`` or off a HIP device it raises.
+  (``se_conv3d_pack_f32``) and walks the network's fixed structure, one kernel per Conv3d+BN(+ReLU)(+residual) /
+  ConvTranspose3d+BN+ReLU(+skip) / max-pool.  What each launch looks like - tensor layouts (channels-last, quad- or
+  octet-planar), flag words, fused skip / pooled / tail forms - is decided once per (batch, grid, input form, fused
+  soft-argmax, fork set) by the pure function ``v2v_route`` and cached; ``run()`` only reads that table and launches.
+  There is no ATen fallback: without ``libsceneego_hip.so`` or off a HIP device it raises.
 """
 from __future__ import annotations
 
 import os
+from types import MappingProxyType
+from typing import Mapping, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -165,6 +169,151 @@ def channels_last_to_octet_planar(x):
 
 
 # ------------------------------------------------------------------------------------------------
+# the route: every layout and fused-form decision of one forward, made before anything is launched
+# ------------------------------------------------------------------------------------------------
+class FrontRoute(NamedTuple):
+    fft: bool                   # front_layers.0 in the frequency domain (se_conv3d_k7_fft_f32) or on se_conv3d_f32
+    flags: int
+    lay_out: Optional[str]      # "quad" / None = channels-last
+
+
+class BlockRoute(NamedTuple):
+    """One Res3DBlock.  Layouts: "quad" [B][C/4][D][D][D][4], "oct" [B][C/8][D][D][D][8], None = channels-last."""
+    dim: int
+    cin: int
+    cout: int
+    lay_in: Optional[str]
+    lay_out: Optional[str]
+    flags1: int                 # complete flag words of the two 3x3x3 launches
+    flags2: int
+    skip: str                   # "identity" | "conv" (1x1x1 launch) | "skip16" (inside the second launch: se_conv3d_skip16_f32)
+    pools: bool                 # the second launch also writes the block's 2x max-pool (se_conv3d_pool_f32)
+    variants: Tuple[Optional[int], Optional[int]]   # se_conv3d_f32_variant of both launches (None: bf16 / split-bf16 kernel)
+
+
+class TailRoute(NamedTuple):
+    fused: bool                 # back_layers.1 / .2 / output_layer in one launch, else three se_conv3d_f32 launches
+    in_quad: bool
+    softargmax: bool            # pass 1 of the soft-argmax rides in the fused launch
+
+
+class V2VRoute(NamedTuple):
+    front0: FrontRoute
+    blocks: Mapping[str, BlockRoute]    # front1..3, skip1..5, enc1..5, mid, decres1..5, back0 (the reference's names)
+    up: Tuple[int, ...]                 # flag words of decoder_upsample1..5
+    fork: frozenset                     # levels (0 = G^3) whose skip block runs on the side stream
+    tail: TailRoute
+
+
+_BLOCKS = {"front1": (16, 32), "front2": (32, 32), "front3": (32, 32), "mid": (128, 128), "back0": (32, 32)}
+for _k in range(5):
+    _BLOCKS[f"skip{_k + 1}"] = (_SKIP[_k], _SKIP[_k])
+    _BLOCKS[f"enc{_k + 1}"] = _ENC[_k]
+    _BLOCKS[f"decres{_k + 1}"] = (_DEC_RES[_k], _DEC_RES[_k])
+_LAY = {"quad": (_lib.IN_QUAD, _lib.OUT_QUAD, _lib.RES_QUAD), "oct": (_lib.IN_OCTET, _lib.OUT_OCTET, _lib.RES_OCTET), None: (0, 0, 0)}
+
+
+def v2v_route(cout, dtype, split3, B, G, input_form="cl", fused_softargmax=False, fork=frozenset()) -> V2VRoute:
+    """Layouts, flag words and fused forms of one forward of the V2V program: a pure function of these integers and of the library's
+    kernel choice (``_lib.conv3d_variant``, a host function).  Nothing is allocated or launched.  ``input_form``: "planar1"
+    [B,cin,G,G,G] (frequency-domain front layer), "planar3" (triplet-planar) or "cl" (channels-last; bf16: octet-planar).
+
+    Tensor layouts of the float32 program: a Res3DBlock output that is read only by 2-D Winograd convolutions of the same kernel
+    family (as input or as skip tensor) and by a max-pool is kept in that family's planar layout (quad-planar at 64^3 / 32^3,
+    octet-planar at 16^3); what the deconvolutions' inputs, the 1x1x1 convolutions and the unfused tail read stays channels-last.
+    The invariants the walk relies on are established here: a violation raises before run() launches anything."""
+    if G % 32:
+        raise ValueError("volume_size must be a multiple of 32 (five 2x max-pools), got %d" % G)
+    f32 = dtype == torch.float32
+    split3 = bool(split3) and f32
+    # bf16 storage: everything channels-last.  Split-bf16 arithmetic: octet-planar where its kernel runs (D % 16 == 0).  Neither has
+    # quad-planar, pooled or fused-skip forms (`forms`); only the plain float32 program asks the library for its layouts.
+    forms = f32 and not split3
+    R, PRE, POST = _lib.EPI_RELU, _lib.EPI_RES_PRE_RELU, _lib.EPI_RES_POST_RELU
+
+    def variant(ci, co, dim, flags):
+        if not f32 or (split3 and dim % 16 == 0):      # a bf16 / split-bf16 kernel runs the launch: not se_conv3d_f32's choice
+            return None
+        return _lib.conv3d_variant(B, dim, ci, co, 3, flags)
+
+    def kind(name, dim):
+        """Planar hand-over layout of a block at this (batch, level): "quad" when both 3x3x3 convolutions run on the F(4,3) x F(4,3)
+        kernel (variant 3 with quad flags), "oct" when they run on the F(4,3) x F(2,3) one or on the split-bf16 kernel, None for a
+        level with so few voxels that the plain split-K kernel is faster (16^3 at batch 1) and for the levels below."""
+        ci, co = _BLOCKS[name]
+        if not forms:
+            return "oct" if split3 and dim % 16 == 0 else None
+        if variant(ci, co, dim, _lib.IN_QUAD) == 3 and variant(co, co, dim, _lib.IN_QUAD) == 3:
+            return "quad"
+        if variant(ci, co, dim, 0) in (2, 3) and variant(co, co, dim, 0) in (2, 3):
+            return "oct"
+        return None
+
+    blocks = {}
+
+    def block(name, dim, lay_in, out_planar, pool=False):
+        """``out_planar``: the output in the block's own planar layout (if it has one); ``pool``: an encoder max-pool reads it."""
+        ci, co = _BLOCKS[name]
+        k = kind(name, dim)
+        if lay_in not in (None, k):
+            raise RuntimeError(f"{name}: {lay_in}-planar input, but its convolutions at {dim}^3, batch {B} take {k or 'channels-last'}")
+        IN, OUT, RES = _LAY[k]
+        lay_out = k if out_planar else None
+        pools = bool(pool and k and forms)
+        # the fused 16-channel skip convolution reads channels-last or, in the quad family, the quad-planar tensor the
+        # frequency-domain front layer writes (SE_RES_QUAD of se_conv3d_skip16_f32)
+        fuse = bool(ci == 16 and forms and k and lay_out and not pools and lay_in in (None, "quad"))
+        if ci != co and lay_in and not fuse:
+            raise RuntimeError(f"{name}: a 1x1x1 skip convolution reads channels-last, got {lay_in}-planar")
+        flags1 = R | OUT | (IN if lay_in else 0)
+        if fuse:
+            flags2 = R | IN | OUT | (RES if lay_in else 0)
+        else:
+            flags2 = R | PRE | IN | (RES if lay_in and ci == co else 0) | (OUT if lay_out else 0)
+        blocks[name] = BlockRoute(dim, ci, co, lay_in, lay_out, flags1, flags2,
+                                  "skip16" if fuse else "conv" if ci != co else "identity", pools,
+                                  (variant(ci, co, dim, flags1), variant(co, co, dim, flags2)))
+        return blocks[name]
+
+    if input_form == "planar1":
+        # quad-planar hand-over when front_layers.1 takes it: both its 3^3 convolutions on the F(4,3) x F(4,3) kernel and the fused
+        # 16-channel skip convolution (which then reads the quad-planar tensor too)
+        q = kind("front1", G) == "quad"
+        front0 = FrontRoute(True, R | (_lib.OUT_QUAD if q else 0), "quad" if q else None)
+    else:
+        front0 = FrontRoute(False, R | (_lib.IN_PLANAR3 if input_form == "planar3" else 0), None)
+    # A block whose output goes to an encoder max-pool writes the pooled tensor from its last convolution's epilogue when that
+    # convolution runs on a 2-D Winograd kernel; the pool kernel is then not launched.
+    src = front0
+    for i in (1, 2, 3):
+        src = block(f"front{i}", G, src.lay_out, True, pool=i == 3)
+    # Which transposed convolutions write (and read their skip tensor) quad-planar: those in front of a block whose convolutions
+    # run on the F(4,3) x F(4,3) kernel (decoder_res1 at 32^3, back_layers.0 at 64^3) and whose shape has that form in
+    # se_deconv3d_k2s2_f32; the skip block of that level then writes its output quad-planar as well - whole 16-byte records
+    # instead of 64 of every 128 bytes of a channels-last record.
+    up_quad = [kind(f"decres{k}" if k else "back0", G >> k) == "quad" and kind(f"skip{k + 1}", G >> k) == "quad"
+               and (G >> (k + 1)) % 16 == 0 and _DEC_UP[k] in ((64, 32), (128, 64)) for k in range(5)]
+    for k in range(5):
+        block(f"skip{k + 1}", G >> k, src.lay_out, up_quad[k])
+        if src.lay_out == "quad" and not src.pools:       # there is no quad-planar pool kernel (the octet one: se_maxpool3d_2_octin_f32)
+            raise RuntimeError("a quad-planar block output is always pooled by its producer")
+        src = block(f"enc{k + 1}", G >> (k + 1), None, True, pool=k < 4)
+    if src.lay_out:    # cannot happen: the deepest levels are too small for the 2-D kernels
+        raise RuntimeError("planar tensor reached the middle block")
+    block("mid", G >> 5, None, False)
+    # A decoder / back block whose convolutions run on the F(4,3) x F(4,3) kernel gets its input quad-planar straight from the
+    # transposed convolution in front of it; a transposed convolution itself reads channels-last.
+    for k in range(5, 0, -1):
+        block(f"decres{k}", G >> k, "quad" if k < 5 and up_quad[k] else None, False)
+    # the fused tail with the soft-argmax pass reads a quad-planar tensor as well: back_layers.0 then writes whole records
+    sa = bool(cout <= 16 and fused_softargmax)
+    tail = TailRoute(cout <= 16, sa and kind("back0", G) == "quad", sa)
+    block("back0", G, "quad" if up_quad[0] else None, tail.in_quad)
+    up = tuple(R | POST | (_lib.OUT_QUAD | _lib.RES_QUAD if q else 0) for q in up_quad)
+    return V2VRoute(front0, MappingProxyType(blocks), up, frozenset(fork), tail)
+
+
+# ------------------------------------------------------------------------------------------------
 # the launch program
 # ------------------------------------------------------------------------------------------------
 class _PackedConv:
@@ -256,6 +405,9 @@ class V2VProgram:
         # skip_res{k+1} of the levels in fork_levels run on a side stream beside the encoder chain (reference network/v2v.py:104-119:
         # skip_x_k = skip_res_k(x) is not read before decoder_upsample_k).  None = decide per batch in run().
         self.fork_levels = None
+        # (B, G, input form, fused soft-argmax, fork set) -> V2VRoute.  A route holds the library's kernel choices: a development-library
+        # tool that changes the kernel selector under a program that has run must clear this.
+        self._routes = {}
 
     def _pack_res(self, m):
         c1 = _PackedConv(m.res_branch[0], m.res_branch[1], None, self.dtype, split3=self.split3)
@@ -282,55 +434,18 @@ class V2VProgram:
         _lib.conv3d(x, pc.w, pc.b, residual, out, B, dim, pc.cin, pc.cin_pad, pc.cout, pc.k, flags, self._ws, pool_out=pool_out)
         return out
 
-    _LAY = {"quad": (_lib.IN_QUAD, _lib.OUT_QUAD, _lib.RES_QUAD), "oct": (_lib.IN_OCTET, _lib.OUT_OCTET, _lib.RES_OCTET)}
-
-    def _res(self, x, blk, B, dim, x_lay=None, out_planar=False, pool_out=None):
-        """Res3DBlock (v2v.py:40-43): relu(bn(conv(relu(bn(conv(x))))) + skip(x)).
-
-        Layouts (float32 program, blocks whose two 3x3x3 convolutions run on a 2-D Winograd kernel): the tensor between the two
-        convolutions is always in the block's planar layout (``_planar``: quad-planar [B][C/4][D][D][D][4] on the F(4,3) x F(4,3) kernel,
-        octet-planar [B][C/8][D][D][D][8] on the F(4,3) x F(2,3) one); ``x_lay`` names the layout of the block input (None =
-        channels-last), ``out_planar`` asks for the block output in the block's planar layout (see run() for who reads what)."""
+    def _res(self, x, blk, r, B, pool_out=None):
+        """Res3DBlock (v2v.py:40-43): relu(bn(conv(relu(bn(conv(x))))) + skip(x)), launched as its route entry ``r`` says.  The tensor
+        between the two convolutions is in the block's planar layout whenever it has one; ``pool_out`` (``r.pools``) receives the
+        block's 2x max-pool from the second launch."""
         c1, c2, sk = blk
-        kind = self._planar(blk, dim, B)    # both convolutions take the planar / pooled / fused-skip forms of this kernel family
-        assert kind or not (x_lay or out_planar)
-        assert x_lay in (None, kind)
-        fused = sk.fused if sk is not None else None
-        fuse = fused is not None and kind and not self.split3 and out_planar and pool_out is None and (not x_lay or x_lay == "quad")
-        # a 1x1x1 skip convolution reads channels-last - except the fused 16-channel one of the quad family, which also takes the
-        # quad-planar tensor the frequency-domain front layer writes (SE_RES_QUAD of se_conv3d_skip16_f32)
-        assert sk is None or not x_lay or fuse
-        IN, OUT, RES = self._LAY[kind] if kind else (0, 0, 0)
-        a = self._conv(x, c1, B, dim, _lib.EPI_RELU | OUT | (IN if x_lay else 0))
-        if fuse:
-            out = torch.empty((B, dim, dim, dim, c2.cout), device=self.device, dtype=self.dtype)
-            _lib.conv3d_skip16(a, c2.w, fused[1], x, fused[0], out, B, dim, c2.cin, c2.cout,
-                               _lib.EPI_RELU | IN | OUT | (RES if x_lay == "quad" else 0))
+        a = self._conv(x, c1, B, r.dim, r.flags1)
+        if r.skip == "skip16":
+            out = self._new(B, r.dim, c2.cout)
+            _lib.conv3d_skip16(a, c2.w, sk.fused[1], x, sk.fused[0], out, B, r.dim, c2.cin, c2.cout, r.flags2)
             return out
-        s = x if sk is None else self._conv(x, sk, B, dim, 0)
-        f2 = _lib.EPI_RELU | _lib.EPI_RES_PRE_RELU | IN
-        if x_lay and sk is None:
-            f2 |= RES
-        if out_planar:
-            f2 |= OUT
-        return self._conv(a, c2, B, dim, f2, residual=s, pool_out=pool_out)      # pool_out: the block's 2x max-pool, written by the same launch
-
-    def _planar(self, blk, dim, B):
-        """Planar hand-over layout of a block at this (batch, level): "quad" when both 3x3x3 convolutions run on the F(4,3) x F(4,3)
-        kernel (variant 3 with quad flags: the 64^3 / 32^3 levels), "oct" when they run on the F(4,3) x F(2,3) kernel (the 16^3
-        level) or on the split-bf16 kernel, None for a level with so few voxels that the plain split-K kernel is faster (16^3 at batch
-        1: it stays channels-last) and for the levels below."""
-        c1, c2, _ = blk
-        if self.dtype != torch.float32:
-            return None
-        if self.split3:
-            return "oct" if c1.w_split is not None and c2.w_split is not None and dim % 16 == 0 else None
-        var = lambda c, fl: _lib.conv3d_variant(B, dim, c.cin_pad, c.cout, 3, fl)
-        if var(c1, _lib.IN_QUAD) == 3 and var(c2, _lib.IN_QUAD) == 3:
-            return "quad"
-        if var(c1, 0) in (2, 3) and var(c2, 0) in (2, 3):
-            return "oct"
-        return None
+        s = self._conv(x, sk, B, r.dim, 0) if r.skip == "conv" else x
+        return self._conv(a, c2, B, r.dim, r.flags2, residual=s, pool_out=pool_out)
 
     def _fork_set(self, B, G):
         """Levels (0 = G^3 ... 4 = (G/16)^3) whose skip block runs on the side stream: ``fork_levels`` if set, else the levels
@@ -355,41 +470,43 @@ class V2VProgram:
         _lib.maxpool3d_2(x, out, B, dim, c, in_octet=x_oct)
         return out
 
-    def _up(self, x, pc, skip, B, dim, out_quad=False, res_quad=False):
-        """Upsample3DBlock + decoder add (v2v.py:64-67,124-137): relu(bn(convT(x))) + skip.  ``out_quad``: the output is written
-        quad-planar [B][C/4][2D][2D][2D][4] for a block behind it whose convolutions run on the F(4,3) x F(4,3) kernel;
-        ``res_quad`` (with it): ``skip`` is quad-planar too (the skip block wrote whole records)."""
+    def _up(self, x, pc, skip, B, dim, flags):
+        """Upsample3DBlock + decoder add (v2v.py:64-67,124-137): relu(bn(convT(x))) + skip.  With OUT_QUAD | RES_QUAD in ``flags``
+        the output is written quad-planar [B][C/4][2D][2D][2D][4] for a block behind it whose convolutions run on the
+        F(4,3) x F(4,3) kernel, and ``skip`` is quad-planar too (the skip block wrote whole records)."""
         out = self._new(B, dim * 2, pc.cout)
-        _lib.deconv3d_k2s2(x, pc.w, pc.b, skip, out, B, dim, pc.cin_pad, pc.cout,
-                           _lib.EPI_RELU | _lib.EPI_RES_POST_RELU | (_lib.OUT_QUAD if out_quad else 0) | (_lib.RES_QUAD if res_quad else 0))
+        _lib.deconv3d_k2s2(x, pc.w, pc.b, skip, out, B, dim, pc.cin_pad, pc.cout, flags)
         return out
-
-    @staticmethod
-    def _up_quad_ok(pc, dim):
-        """Shapes whose transposed convolution has the quad-planar output form (se_deconv3d_k2s2_f32 with SE_OUT_QUAD)."""
-        return dim % 16 == 0 and (pc.cin_pad, pc.cout) in ((64, 32), (128, 64))
 
     # -- the network -------------------------------------------------------------------------
     def fft7_ready(self, G):
         """True when run(..., planar1=True) can take the planar input [B, cin, G, G, G] (the frequency-domain front layer covers it)."""
         return self.front0_fft is not None and G >= 16 and G % 16 == 0
 
-    def _front0_fft(self, x, B, G, out_quad):
-        """front_layers.0 in the frequency domain (se_conv3d_k7_fft_f32): planar x [B,cin,G,G,G] -> 16 channels, channels-last or quad-planar.
-        The spectra of up to 8 samples live in a workspace owned by the program (1.5 GB at 64^3; larger batches walk it in chunks)."""
+    def _front0_fft(self, x, B, G, flags):
+        """front_layers.0 in the frequency domain (se_conv3d_k7_fft_f32): planar x [B,cin,G,G,G] -> 16 channels, channels-last or (OUT_QUAD)
+        quad-planar.  The spectra of up to 8 samples live in a workspace owned by the program (1.5 GB at 64^3; larger batches walk it in
+        chunks)."""
         need = _lib.conv3d_k7_fft_workspace_elems(min(B, 8), G, self.cin)
         if self._fft_ws is None or self._fft_ws.numel() < need:
             self._fft_ws = torch.empty(need, device=self.device, dtype=torch.float32)
         out = self._new(B, G, self.front0.cout)
-        _lib.conv3d_k7_fft(x, self.front0_fft, self.front0.b, out, B, G, self.cin, self.front0.cout,
-                           _lib.EPI_RELU | (_lib.OUT_QUAD if out_quad else 0), self._fft_ws)
+        _lib.conv3d_k7_fft(x, self.front0_fft, self.front0.b, out, B, G, self.cin, self.front0.cout, flags, self._fft_ws)
         return out
+
+    def _route(self, B, G, form, fused_softargmax):
+        key = (B, G, form, fused_softargmax, self._fork_set(B, G))
+        route = self._routes.get(key)
+        if route is None:
+            route = self._routes[key] = v2v_route(self.cout, self.dtype, self.split3, *key)
+        return route
 
     def run(self, x, B, G, out=None, softargmax=None, scaled=False, planar1=False):
         """x: [B,G,G,G,cin_pad] channels-last (channels >= cin zero; bf16: octet-planar [B,cin_pad/8,G,G,G,8]; float32 may
         also be triplet-planar [B,ceil(cin/3),G,G,G,3], which the 7^3 Winograd front layer reads with ~5x fewer cache-line requests,
         or - ``planar1`` - fully planar [B,cin,G,G,G] for the frequency-domain front layer, see fft7_ready())
-        -> planar logits [B,cout,G^3] (``scaled``: times ``output_scale``)."""
+        -> planar logits [B,cout,G^3] (``scaled``: times ``output_scale``).
+        ``softargmax`` = (coord, scratch): pass 1 of the soft-argmax rides in the fused tail launch."""
         assert x.is_contiguous() and x.dtype == self.dtype
         outc = self.out_scaled if scaled else self.out
         planar3 = self.dtype == torch.float32 and x.dim() == 6       # float32 triplet-planar [B,ceil(cin/3),G,G,G,3]
@@ -399,51 +516,31 @@ class V2VProgram:
             assert tuple(x.shape) == (B, (self.cin + 2) // 3, G, G, G, 3)
         else:
             assert tuple(x.shape) == ((B, self.cin_pad // 8, G, G, G, 8) if self.dtype == torch.bfloat16 else (B, G, G, G, self.cin_pad))
-        if G % 32:
-            raise ValueError("volume_size must be a multiple of 32 (five 2x max-pools), got %d" % G)
-        x_lay = None
-        if planar1:
-            # quad-planar hand-over when front_layers.1 takes it: both its 3^3 convolutions on the F(4,3) x F(4,3) kernel and the fused
-            # 16-channel skip convolution (which then reads the quad-planar tensor too)
-            blk0 = self.front_res[0]
-            q = (not self.split3 and self._planar(blk0, G, B) == "quad" and blk0[2] is not None and blk0[2].fused is not None
-                 and len(self.front_res) > 1)
-            x = self._front0_fft(x, B, G, q)
-            x_lay = "quad" if q else None
+        # every layout, flag word and fused form of this forward (v2v_route): below, only launches
+        route = self._route(B, G, "planar1" if planar1 else "planar3" if planar3 else "cl", softargmax is not None)
+
+        def res(name, blk, x):
+            r = route.blocks[name]
+            pooled = self._new(B, r.dim // 2, r.cout) if r.pools else None
+            return self._res(x, blk, r, B, pool_out=pooled), pooled
+
+        if route.front0.fft:
+            x = self._front0_fft(x, B, G, route.front0.flags)
         else:
-            x = self._conv(x, self.front0, B, G, _lib.EPI_RELU | (_lib.IN_PLANAR3 if planar3 else 0))
-        # Tensor layouts of the float32 program: a Res3DBlock output that is read only by 2-D Winograd convolutions of the same kernel
-        # family (as input or as skip tensor) and by a max-pool is kept in that family's planar layout (_planar: quad-planar at 64^3 /
-        # 32^3, octet-planar at 16^3); what the deconvolutions, the 1x1x1 convolutions and the fused tail read stays channels-last.
-        # x_lay tracks the layout of the running tensor.
-        # A block whose output goes to an encoder max-pool writes the pooled tensor from its last convolution's epilogue when
-        # that convolution runs on a 2-D Winograd kernel (`pooled`); the pool kernel is then not launched.
-        pooled = None
+            x = self._conv(x, self.front0, B, G, route.front0.flags)
         for i, blk in enumerate(self.front_res):
-            kind = self._planar(blk, G, B)
-            if kind and not self.split3 and i == len(self.front_res) - 1:      # (the split-bf16 kernel has no pooled form)
-                pooled = self._new(B, G // 2, blk[1].cout)
-            x = self._res(x, blk, B, G, x_lay=x_lay, out_planar=bool(kind), pool_out=pooled)
-            x_lay = kind
+            x, pooled = res(f"front{i + 1}", blk, x)
         # encoder (v2v.py:104-119).  skip_res_k(x) is not read before decoder_upsample_k: the skip blocks of the levels in `fork` are
         # issued on a side stream (event fork behind the producer of x, event join in front of the deconvolution that reads the
         # result) and run beside the encoder / middle / decoder chain, which at small batches leaves most of the chip idle
         # (16^3 at batch 1: 32 work units on 256 CUs).  Inside a hipGraph capture the fork and the joins become graph edges.
-        # Which transposed convolutions write (and read their skip tensor) quad-planar: those in front of a block whose convolutions
-        # run on the F(4,3) x F(4,3) kernel (decoder_res1 at 32^3, back_layers.0 at 64^3); the skip block of that level then writes its
-        # output quad-planar as well - whole 16-byte records instead of 64 of every 128 bytes of a channels-last record.
-        up_quad = [False] * 5
-        for k in range(5):
-            nxt = self.dec[k - 1] if k > 0 else self.back_res
-            up_quad[k] = (not self.split3 and self._planar(nxt, G >> k, B) == "quad" and self._up_quad_ok(self.up[k], G >> (k + 1))
-                          and self._planar(self.skip[k], G >> k, B) == "quad")
         skips = []
         joins = [None] * 5
-        fork = self._fork_set(B, G)
-        main = torch.cuda.current_stream(self.device) if fork else None
+        main = torch.cuda.current_stream(self.device) if route.fork else None
         dim = G
+        lay = route.blocks["front3"].lay_out
         for k in range(5):
-            if k in fork:
+            if k in route.fork:
                 side = self._side(main)
                 ev = torch.cuda.Event()
                 ev.record(main)
@@ -452,7 +549,7 @@ class V2VProgram:
                 with torch.cuda.stream(side):
                     self._ws = self.workspace_side
                     try:
-                        sk = self._res(x, self.skip[k], B, dim, x_lay=x_lay, out_planar=up_quad[k])
+                        sk = res(f"skip{k + 1}", self.skip[k], x)[0]
                     finally:
                         self._ws = self.workspace
                     joins[k] = torch.cuda.Event()
@@ -460,46 +557,29 @@ class V2VProgram:
                 sk.record_stream(main)
                 skips.append(sk)
             else:
-                skips.append(self._res(x, self.skip[k], B, dim, x_lay=x_lay, out_planar=up_quad[k]))    # read by the decoder's deconvolution
-            if pooled is None and x_lay == "quad":
-                raise RuntimeError("a quad-planar block output is always pooled by its producer")
-            x = pooled if pooled is not None else self._pool(x, B, dim, x.numel() // (B * dim ** 3), x_oct=x_lay == "oct")
-            pooled = None
+                skips.append(res(f"skip{k + 1}", self.skip[k], x)[0])    # read by the decoder's deconvolution
+            # the producer of x wrote its max-pool from its epilogue, or the pool kernel runs (which also reads octet-planar)
+            x = pooled if pooled is not None else self._pool(x, B, dim, x.numel() // (B * dim ** 3), x_oct=lay == "oct")
             dim //= 2
-            kind = self._planar(self.enc[k], dim, B)
-            if kind and not self.split3 and k < 4:
-                pooled = self._new(B, dim // 2, self.enc[k][1].cout)
-            x = self._res(x, self.enc[k], B, dim, x_lay=None, out_planar=bool(kind), pool_out=pooled)
-            x_lay = kind
-        if x_lay:    # cannot happen: the deepest levels are too small for the 2-D kernels
-            raise RuntimeError("planar tensor reached the middle block")
-        x = self._res(x, self.mid, B, dim)
+            x, pooled = res(f"enc{k + 1}", self.enc[k], x)
+            lay = route.blocks[f"enc{k + 1}"].lay_out
+        x = res("mid", self.mid, x)[0]
         # decoder (v2v.py:121-137)
-        # A decoder / back block whose convolutions run on the F(4,3) x F(4,3) kernel gets its input quad-planar straight from the
-        # transposed convolution in front of it (round 5; rounds 2-4: channels-last, which kept the block's first convolution on the
-        # F(4,3) x F(2,3) kernel - 0.41 ms against 0.32 for back_layers.0's).
-        x_lay = None
         for k in range(4, -1, -1):
-            x = self._res(x, self.dec[k], B, dim, x_lay=x_lay)
+            x = res(f"decres{k + 1}", self.dec[k], x)[0]
             if joins[k] is not None:
                 main.wait_event(joins[k])
-            quad = up_quad[k]
-            x = self._up(x, self.up[k], skips[k], B, dim, out_quad=quad, res_quad=quad)
-            x_lay = "quad" if quad else None
+            x = self._up(x, self.up[k], skips[k], B, dim, route.up[k])
             skips[k] = None
             dim *= 2
         # back layers + output (v2v.py:155-161)
-        # the fused tail with the soft-argmax pass reads a quad-planar tensor as well: back_layers.0 then writes whole records
-        sa = softargmax            # (coord, scratch): pass 1 of the soft-argmax rides in the tail launch (float32 since round 4, bf16 since round 6)
-        tail_quad = (self.dtype == torch.float32 and self.cout <= 16 and sa is not None and not self.split3
-                     and self._planar(self.back_res, G, B) == "quad")
-        x = self._res(x, self.back_res, B, G, x_lay=x_lay, out_planar=tail_quad)
+        x = res("back0", self.back_res, x)[0]
         if out is None:
             out = torch.empty((B, self.cout, G * G * G), device=self.device, dtype=torch.float32)
-        if self.cout <= 16:
+        if route.tail.fused:
             # back_layers.1 / .2 / output_layer fused: one read of x, one planar write of the logits
-            # ``softargmax`` = (coord, scratch): float32 program only - pass 1 of the soft-argmax rides in the same launch
-            _lib.pointwise_chain3(x, self.back1, self.back2, outc, out, B, G, softargmax=sa, in_quad=tail_quad)
+            _lib.pointwise_chain3(x, self.back1, self.back2, outc, out, B, G, softargmax=softargmax if route.tail.softargmax else None,
+                                  in_quad=route.tail.in_quad)
             return out
         x = self._conv(x, self.back1, B, G, _lib.EPI_RELU)
         x = self._conv(x, self.back2, B, G, _lib.EPI_RELU)

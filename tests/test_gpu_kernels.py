@@ -1562,7 +1562,7 @@ def test_conv3d_pyramid_edge_dims_vs_float64(B, dim, cin, cout, residual):
         errs.append(err)
         assert err <= tol, (err, tol, workspace is not None, _lib.conv3d_variant(B, dim, cin, cout, 3, 0))
     if dim == 48:
-        # the forms V2VProgram._planar picks at 48^3 (octet-planar at these unit counts) and the pooled epilogue of an encoder input
+        # the forms v2v_route picks at 48^3 (octet-planar at these unit counts) and the pooled epilogue of an encoder input
         kind = "quad" if _lib.conv3d_variant(B, dim, cin, cout, 3, _lib.IN_QUAD) == 3 else "oct"
         assert _lib.conv3d_variant(B, dim, cin, cout, 3, _lib.IN_OCTET | _lib.OUT_OCTET) == 2
         to_pl, from_pl, _, IN, OUT, RES = _lay(kind)
@@ -1584,7 +1584,7 @@ def test_conv3d_pyramid_edge_dims_vs_float64(B, dim, cin, cout, residual):
     (1, 3, 128, 128),     # G=96 decoder_upsample5: 3^3 -> 6^3, odd input
     (3, 6, 128, 128),     # G=96 decoder_upsample4
     (2, 12, 128, 128),    # G=96 decoder_upsample3
-    (1, 24, 128, 64),     # G=96 decoder_upsample2: 24^3 -> 48^3 (24 % 16 != 0: no quad-planar output form, _up_quad_ok)
+    (1, 24, 128, 64),     # G=96 decoder_upsample2: 24^3 -> 48^3 (24 % 16 != 0: no quad-planar output form, v2v_route's up_quad)
     (2, 24, 128, 64),
 ])
 def test_deconv_pyramid_edge_dims_vs_float64(B, dim, cin, cout):

@@ -1,6 +1,6 @@
 """Per-block float64 parity of the whole V2V program over the batch / grid routes it can take.
 
-``V2VProgram.run`` picks, block by block, the kernel (``conv3d_variant``: 0 direct / split-K, 1 1-D F(4,3), 2 F(4,3) x F(2,3),
+``v2v_route`` picks, block by block, the kernel (``conv3d_variant``: 0 direct / split-K, 1 1-D F(4,3), 2 F(4,3) x F(2,3),
 3 F(4,3) x F(4,3) ping-pong) and the hand-over layout (channels-last, quad-planar, octet-planar) from the batch and the level size.
 The kernel tests check each kernel alone; this module checks what the program composes from them.  A recorder wraps
 ``_front0_fft`` / ``_conv`` (front layer), ``_res``, ``_up`` and ``run`` with ``monkeypatch`` and keeps, for the checked samples,
@@ -165,29 +165,22 @@ class Recorder:
         orig_res, orig_up, orig_fft, orig_conv, orig_run = (V2VProgram._res, V2VProgram._up, V2VProgram._front0_fft,
                                                             V2VProgram._conv, V2VProgram.run)
 
-        def _res(prog, x, blk, B, dim, x_lay=None, out_planar=False, pool_out=None):
-            out = orig_res(prog, x, blk, B, dim, x_lay=x_lay, out_planar=out_planar, pool_out=pool_out)
+        def _res(prog, x, blk, r, B, pool_out=None):
+            out = orig_res(prog, x, blk, r, B, pool_out=pool_out)
             name = rec._name(prog, blk)
-            kind = prog._planar(blk, dim, B)
-            lay = kind if out_planar else None
-            c1, c2, sk = blk
-            IN, OUT, RES = prog._LAY[kind] if kind else (0, 0, 0)
-            f1 = OUT | (IN if x_lay else 0)
-            f2 = IN | (OUT if out_planar else 0) | (RES if x_lay and sk is None else 0)
-            var = (_lib.conv3d_variant(B, dim, c1.cin_pad, c1.cout, 3, f1), _lib.conv3d_variant(B, dim, c2.cin_pad, c2.cout, 3, f2))
-            rec._put(name, out, lay, dim, c2.cout, var)
+            rec._put(name, out, r.lay_out, r.dim, r.cout, r.variants)       # layout and kernels: the route entry the executor was given
             if pool_out is not None:
-                rec._put(name + ".pool", pool_out, None, dim // 2, c2.cout, var)
+                rec._put(name + ".pool", pool_out, None, r.dim // 2, r.cout, r.variants)
             return out
 
-        def _up(prog, x, pc, skip, B, dim, out_quad=False, res_quad=False):
-            out = orig_up(prog, x, pc, skip, B, dim, out_quad=out_quad, res_quad=res_quad)
-            rec._put(rec._name(prog, pc), out, "quad" if out_quad else None, 2 * dim, pc.cout, ())
+        def _up(prog, x, pc, skip, B, dim, flags):
+            out = orig_up(prog, x, pc, skip, B, dim, flags)
+            rec._put(rec._name(prog, pc), out, "quad" if flags & _lib.OUT_QUAD else None, 2 * dim, pc.cout, ())
             return out
 
-        def _front0_fft(prog, x, B, G, out_quad):
-            out = orig_fft(prog, x, B, G, out_quad)
-            rec._put("front0", out, "quad" if out_quad else None, G, prog.front0.cout, ("fft",))
+        def _front0_fft(prog, x, B, G, flags):
+            out = orig_fft(prog, x, B, G, flags)
+            rec._put("front0", out, "quad" if flags & _lib.OUT_QUAD else None, G, prog.front0.cout, ("fft",))
             return out
 
         def _conv(prog, x, pc, B, dim, flags, residual=None, out=None, pool_out=None):
@@ -335,7 +328,7 @@ def _forward_point(monkeypatch, G, B, sel, seed):
 
 # Route matrix (G, B, checked samples).  Which kernel / layout each level takes follows se_conv3d_f32_variant,
 # se_conv3d_wino44pp_shape (units = B * (D/16) * (D/8)^2 * cout/32 against the CU count, or D >= 64), se_conv3d_small_volume
-# (B * D^3 <= 4096), the 2048..8192-voxel window of the split-K kernels and V2VProgram._planar / _up_quad_ok / tail_quad.
+# (B * D^3 <= 4096), the 2048..8192-voxel window of the split-K kernels and sceneego_amd.v2v.v2v_route.
 ROUTES = [
     # G=64: 64^3 quad everywhere; 32^3 octet (64 units < 256 CUs); 16^3 channels-last split-K (4096 voxels) + halo; 8^3 grid split-K
     pytest.param(64, 1, (0,), id="G64-B1"),
