@@ -20,6 +20,9 @@ two pictures with the joint probability volumes drawn over them as a maximum-int
 ``visualize.py --volumes_path`` reads.
 ``--scene_check true`` writes ``<img_name>.scene.pkl`` beside each ``<img_name>.pkl``: collision, clearance and contact of the
 predicted skeleton against the scene of its own depth map (``sceneego_amd/scene_check.py``: ``SceneConsistency.check``).
+``--constrained_dir DIR`` writes ``DIR/<img_name>.pkl``: the joints re-estimated over the free space in front of the depth surface
+(``VoxelNetwork_depth.constrain_to_scene``), float32 [15,3] like the prediction, so ``evaluate.py --pred_dir DIR`` reads them; and
+``DIR/<img_name>.constraint.pkl``: free_mass, moved, constrained, the free peak, ... of every joint.
 """
 import argparse
 import os
@@ -30,7 +33,7 @@ import torch
 
 from sceneego_amd import load_config, synth
 from sceneego_amd.jpeg_device import JpegFile, decode_jpeg_batch
-from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy
+from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy
 from sceneego_amd.preprocess import (DEPTH_CLAMP, load_depth, load_image_bgr, prepare_depth, preprocess_image,
                                      preprocess_image_device)
 from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
@@ -42,7 +45,7 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 class Demo:
     def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False,
-                 render_format="png", render_volumes=False, volume_joints=None, save_volumes=None):
+                 render_format="png", render_volumes=False, volume_joints=None, save_volumes=None, constrain=False):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
@@ -58,6 +61,7 @@ class Demo:
         self.volume_joints = volume_joints
         self.save_volumes = save_volumes
         self.scene_check = scene_check
+        self.constrain = constrain
         self.scene = None
         self.items = []
         for img_name in sorted(os.listdir(img_dir)):
@@ -108,6 +112,9 @@ class Demo:
                 if self.stats:
                     # the volumes are the replayed graph's static buffers: reduced here, before the next frame overwrites them
                     results[-1]["stats"] = joint_statistics_to_numpy(self.network.joint_statistics(volumes, kp))[0]
+                if self.constrain:
+                    # likewise before the next frame: the volumes are the graph's static buffers
+                    results[-1]["constraint"] = scene_constraint_to_numpy(self.network.constrain_to_scene(volumes, kp, depth))[0]
                 if self.scene_check:
                     results[-1]["scene"] = scene_check_to_numpy(self.check_scene(depth, kp))[0]
                 if self.save_volumes is not None:
@@ -178,6 +185,9 @@ def parse_args(argv=None):
     ap.add_argument("--scene_check", type=str, default="false",
                     help="true: also write <img_name>.scene.pkl (nearest_dist, clearance, bone_clearance, penetration_depth, penetrating, "
                          "contact, ... of the skeleton against the depth map's scene)")
+    ap.add_argument("--constrained_dir", type=str, default=None,
+                    help="also write <img_name>.pkl here: the joints re-estimated over the free space in front of the depth surface "
+                         "(float32 [15,3], readable by evaluate.py --pred_dir), and <img_name>.constraint.pkl (free_mass, moved, ...)")
     args = ap.parse_args(argv)
     if args.vis.lower() == "true":
         raise SystemExit("--vis true (open3d visualisation) is out of scope of this build")
@@ -208,8 +218,11 @@ def main(argv=None):
     config = load_config(args.config)
     demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats, render_dir=args.render_dir,
                 scene_check=args.scene_check, render_format=args.render_format, render_volumes=args.render_volumes,
-                volume_joints=args.volume_joints, save_volumes=args.output_dir if args.save_volumes else None)
+                volume_joints=args.volume_joints, save_volumes=args.output_dir if args.save_volumes else None,
+                constrain=args.constrained_dir is not None)
     os.makedirs(args.output_dir, exist_ok=True)
+    if args.constrained_dir is not None:
+        os.makedirs(args.constrained_dir, exist_ok=True)
     for r in demo.run():
         out_path = os.path.join(args.output_dir, os.path.split(r["img_path"])[1] + ".pkl")
         with open(out_path, "wb") as f:
@@ -221,6 +234,13 @@ def main(argv=None):
         if args.scene_check:
             with open(out_path[:-4] + ".scene.pkl", "wb") as f:
                 pickle.dump(r["scene"], f)                # dict of numpy arrays, the keys of SceneConsistency.check
+        if args.constrained_dir is not None:
+            c = dict(r["constraint"])
+            name = os.path.join(args.constrained_dir, os.path.split(r["img_path"])[1])
+            with open(name + ".pkl", "wb") as f:
+                pickle.dump(np.asarray(c.pop("joints"), dtype=np.float32), f)      # [15,3], the format of the prediction
+            with open(name + ".constraint.pkl", "wb") as f:
+                pickle.dump(c, f)                         # dict of numpy arrays, the other keys of op.CONSTRAINT_KEYS
 
 
 if __name__ == "__main__":

@@ -21,7 +21,7 @@ if ROOT not in sys.path:
 
 
 def load_predictions(pred_dir):
-    names = sorted(n for n in os.listdir(pred_dir) if n.endswith(".pkl") and not n.endswith((".stats.pkl", ".scene.pkl")))
+    names = sorted(n for n in os.listdir(pred_dir) if n.endswith(".pkl") and not n.endswith((".stats.pkl", ".scene.pkl", ".constraint.pkl")))
     if not names:
         raise SystemExit(f"no .pkl predictions in {pred_dir}")
     poses = []

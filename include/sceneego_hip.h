@@ -569,6 +569,45 @@ int se_scene_probe_f64(const float* depth, const double* ray_tab, const double* 
                        long long scratch_bytes, int batch, int depth_h, int depth_w, int height, int width, int n_probes,
                        double min_z, double max_depth, void* stream);
 
+/* Scene-constrained joints (no counterpart in the reference; sceneego_amd/op.py: build_sight_table, scene_free_mask,
+ * constrained_joints; VoxelNetwork_depth.constrain_to_scene drives them): the soft-argmax taken over the part of the voxel grid that
+ * lies in front of the depth surface.
+ *
+ * SIGHT TABLE, built once on the host per (grid, frame size).  For voxel n with the float32 centre c_n (build_coord_volume) and its
+ * float32 projection (u, v) (grid_coord_proj):  x = floor((double)u + 0.5), y = floor((double)v + 0.5);
+ *   pix[n] = y * width + x (int32) when u, v are finite and 0 <= x < width, 0 <= y < height, else -1;
+ *   rng[n] = (float)sqrt(((double)cx cx + (double)cy cy) + (double)cz cz), the voxel's distance from the camera.
+ *
+ * FREE MASK, se_scene_free_mask_u8, per frame b and voxel n:
+ *   depth [B][depth_h][depth_w] float32 metres     pix [voxels] int32     rng [voxels] float32     free_mask [B][voxels] uint8
+ *   pix[n] < 0 (or >= height * width): free, there is no evidence against the voxel.  Otherwise y = pix[n] / width,
+ *   x = pix[n] - y * width, d = depth[b][(y * depth_h) / height][(x * depth_w) / width] (the integer division of se_scene_probe_f64);
+ *   the pixel has a SURFACE iff d > 0 && d <= max_depth (a NaN fails); the voxel is BLOCKED iff it has a surface and
+ *   (double)d + margin < (double)rng[n]: one correctly rounded float64 sum and one comparison (equality counts as free).
+ *   free_mask[b][n] = 1 free, 0 blocked.  One right answer, bit for bit (tests/scene_constraint_model.py restates it).
+ * One launch, nothing allocated.  SE_ERR_BAD_ARG: a null pointer, batch outside 1..65535, a non-positive size, height * width above
+ * 0x7fff0000, voxels & 3, a free_mask that is not 4-byte aligned, margin NaN, max_depth <= 0 or NaN.
+ *
+ * MASKED REDUCTION, se_softargmax3d_masked_f32, per row r = b * rows_per_frame + j:
+ *   prob  [rows][voxels] float32 probabilities, as se_softargmax3d_f32 writes them in mode 1       coord [voxels][3] float32
+ *   free_mask [rows / rows_per_frame][voxels] uint8 (any non-zero byte is free); f_n = free_mask[r / rows_per_frame][n]
+ *   out [rows][8]: 0     free_mass = sum_n f_n p_n
+ *                  1..3  sum_n f_n p_n c_n for x, y, z (NOT divided: the kernel does no division; the caller divides by slot 0)
+ *                  4     free_peak_p = the largest p_n over the free voxels
+ *                  5..7  coord[peak_index]
+ *   peak_index [rows] int32: the LOWEST free index with p_n == free_peak_p
+ *   scratch: se_softargmax3d_masked_scratch_elems(rows) floats of workspace.
+ * A row without a free voxel: slots 0..4 are 0, slots 5..7 NaN, peak_index -1.  A row that holds a NaN probability (free or blocked)
+ * gets 8 NaNs and peak_index -1; other rows are unaffected.  Two launches on `stream` (se_sa_splits(rows) chunks per row as the
+ * soft-argmax, then one wave per row), a fixed reduction order and no atomics: bitwise identical from run to run.  Allocates nothing
+ * (legal inside hipGraph capture).  rows <= 0, rows > 65535, rows_per_frame <= 0, rows % rows_per_frame, voxels <= 0, voxels & 3, a
+ * null pointer, a prob / coord that is not 16-byte aligned or a free_mask that is not 4-byte aligned -> SE_ERR_BAD_ARG.              */
+int se_scene_free_mask_u8(const float* depth, const int* pix, const float* rng, unsigned char* free_mask, int batch, int depth_h,
+                          int depth_w, int height, int width, int voxels, double margin, double max_depth, void* stream);
+int se_softargmax3d_masked_f32(const float* prob, const float* coord, const unsigned char* free_mask, float* out, int* peak_index,
+                               float* scratch, int rows, int rows_per_frame, int voxels, void* stream);
+long long se_softargmax3d_masked_scratch_elems(int rows);
+
 /* Baseline JPEG encoder (no counterpart in the reference; sceneego_amd/jpeg_encode.py writes the file headers around it).
  *   frames    uint8 [batch][height][width][3] on the device, R, G, B (bgr = 0) or B, G, R (bgr = 1); any height, width in 1..65535
  *   quant_luma, quant_chroma   HOST pointers: unsigned short [64], natural order, every value in 1..255 (baseline tables)

@@ -7,7 +7,7 @@
                            [--image_decode device|host] [--streams 2] [--stats_output out/no_body_diogo1.stats.pkl]
                            [--render_dir out/frames [--render_every 10] [--render_format jpg]]
                            [--render_video out/seq.avi [--render_fps 25] [--render_view render|overlay|both] [--render_quality 90]]
-                           [--scene_output out/no_body_diogo1.scene.pkl]
+                           [--scene_output out/no_body_diogo1.scene.pkl] [--constrain_output out/no_body_diogo1.constraint.pkl]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -27,6 +27,9 @@ through one ``SceneRenderer`` once the joints of the batch are final; the forwar
 ``--scene_output`` adds a pickle of the per-frame scene checks (``sceneego_amd/scene_check.py``: collision, clearance and contact of
 each predicted skeleton against the scene of its own depth map), taken per batch on the stream it ran on, and prints their summary
 (``metrics.scene_summary``) at the end.
+``--constrain_output`` adds a pickle of the per-frame scene constraints (``VoxelNetwork_depth.constrain_to_scene``: the joints
+re-estimated over the free space in front of the depth surface, free_mass, moved, ...), taken per batch on the stream it ran on; with
+``--scene_output`` the scene check also runs on the constrained joints and both summaries are printed.
 """
 import argparse
 import json
@@ -207,19 +210,21 @@ class SequenceRunner:
     @torch.no_grad()
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
-            volume_joints=None):
+            volume_joints=None, constrain=False):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
         scene-check dicts are appended to what is returned (joints, [statistics,] scene checks).  ``render_volumes``: also write
         ``<img_name>.volumes.render.*`` / ``.volumes.overlay.*`` (the joint probability volumes of ``volume_joints``, default all, drawn
-        over the pair), and the video shows those views."""
+        over the pair), and the video shows those views.  ``constrain``: the per-frame scene-constraint dicts are appended after
+        those, and with ``scene`` the scene checks of the constrained joints after them."""
         from sceneego_amd.jpeg_device import JpegFile
-        from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy
+        from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
         preds, frame_stats, frame_scene, pending = [], [], [], []
+        frame_constraint, frame_scene_constrained = [], []
 
         rendering = render_dir is not None or render_video is not None
         if rendering:
@@ -235,7 +240,7 @@ class SequenceRunner:
 
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done, job, sc = pending.pop(0)
+                kp, st, done, job, sc, con = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 kp_host = kp.cpu().numpy()
@@ -244,6 +249,10 @@ class SequenceRunner:
                     frame_stats.extend(joint_statistics_to_numpy(st))
                 if sc is not None:
                     frame_scene.extend(scene_check_to_numpy(sc))
+                if con is not None:
+                    frame_constraint.extend(scene_constraint_to_numpy(con[0]))
+                    if con[1] is not None:
+                        frame_scene_constrained.extend(scene_check_to_numpy(con[1]))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -264,14 +273,18 @@ class SequenceRunner:
                 if self.pipe is None:
                     kp, _, vol, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # drained before the next forward overwrites the volumes
+                    con = None
+                    if constrain:
+                        c = self.net.constrain_to_scene(vol, kp, depth)
+                        con = (c, self._scene().check(depth, c["joints"]) if scene else None)
                     pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
-                                    self._scene().check(depth, kp) if scene else None))
+                                    self._scene().check(depth, kp) if scene else None, con))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
-                    st = sc = None
-                    if stats or scene:
+                    st = sc = con = None
+                    if stats or scene or constrain:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
@@ -279,9 +292,12 @@ class SequenceRunner:
                                 st = net.joint_statistics(vol, kp)
                             if scene:
                                 sc = self._scene(stream.cuda_stream).check(depth, kp)
+                            if constrain:
+                                c = net.constrain_to_scene(vol, kp, depth)
+                                con = (c, self._scene(stream.cuda_stream).check(depth, c["joints"]) if scene else None)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done, job, sc))
+                    pending.append((kp, st, done, job, sc, con))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             try:
                 drain(0)
@@ -289,9 +305,10 @@ class SequenceRunner:
                 if self.video is not None:
                     self.video.close()
                     self.video = None
-        if not (stats or scene):
+        if not (stats or scene or constrain):
             return preds
-        return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ())
+        return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
+            + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ())
 
 
 def _size(text):
@@ -336,6 +353,9 @@ def build_parser():
                     "cov, sigma, entropy, peak_prob, peak_index, peak_coord)")
     ap.add_argument("--scene_output", default=None, help="pickle of the per-frame scene checks (list of dicts of numpy arrays: "
                     "nearest_dist, clearance, bone_clearance, penetration_depth, penetrating, contact, ...); prints their summary")
+    ap.add_argument("--constrain_output", default=None, help="pickle of the per-frame scene constraints (list of dicts of numpy arrays: "
+                    "joints, constrained, free_mass, moved, free_peak_prob, free_peak_index, free_peak_coord); with --scene_output the "
+                    "scene check also runs on the constrained joints and both summaries are printed")
     ap.add_argument("--render_format", default="png", choices=("png", "jpg"),
                     help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG files encoded on the device)")
     ap.add_argument("--render_video", default=None, help="write the picked frames as one Motion-JPEG AVI (4:2:0, encoded on the device)")
@@ -383,15 +403,18 @@ def main(argv=None):
     t0 = time.perf_counter()
     want_stats = args.stats_output is not None
     want_scene = args.scene_output is not None
+    want_constraint = args.constrain_output is not None
     preds = runner.run(images, depths, config.test.batch_size, stats=want_stats, render_dir=args.render_dir,
                        render_every=args.render_every, scene=want_scene, render_format=args.render_format,
                        render_video=args.render_video, render_fps=args.render_fps, render_view=args.render_view,
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
-                       volume_joints=args.volume_joints)
-    if want_stats or want_scene:
+                       volume_joints=args.volume_joints, constrain=want_constraint)
+    if want_stats or want_scene or want_constraint:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
         frame_scene = extra.pop(0) if want_scene else None
+        frame_constraint = extra.pop(0) if want_constraint else None
+        frame_scene_constrained = extra.pop(0) if want_constraint and want_scene else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -417,6 +440,15 @@ def main(argv=None):
         result["scene"] = frame_scene
         result["scene_summary"] = M.scene_summary(frame_scene)
         print(M.format_scene_summary(result["scene_summary"]))
+    if want_constraint:
+        os.makedirs(os.path.dirname(os.path.abspath(args.constrain_output)), exist_ok=True)
+        with open(args.constrain_output, "wb") as f:
+            pickle.dump(frame_constraint, f)
+        result["constraint"] = frame_constraint
+        if want_scene:
+            result["scene_constrained"] = frame_scene_constrained
+            result["scene_summary_constrained"] = M.scene_summary(frame_scene_constrained)
+            print("constrained joints: " + M.format_scene_summary(result["scene_summary_constrained"]))
     return result
 
 

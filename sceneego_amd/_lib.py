@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -106,6 +106,9 @@ SIGNATURES = {
     "se_render_volume_overlay_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, ctypes.c_uint, _d, _d, _vp]),
     "se_scene_probe_scratch_bytes": (_ll, [_i, _i, _i, _i]),
     "se_scene_probe_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _d, _d, _vp]),
+    "se_scene_free_mask_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _vp]),
+    "se_softargmax3d_masked_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "se_softargmax3d_masked_scratch_elems": (_ll, [_i]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -1102,6 +1105,84 @@ def scene_probe(depth, ray_tab, probes, out, index, scratch=None, min_z=0.1, max
     _check(load().se_scene_probe_f64(_ptr(depth), _ptr(ray_tab), _ptr(probes), _ptr(out), _ptr(index), _ptr(scratch), scratch.numel(),
                                      B, dh, dw, H, W, P, float(min_z), float(max_depth), _stream()), "se_scene_probe_f64")
     return out, index
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Scene-constrained joints (csrc/scene_constraint.hip; sceneego_amd/op.py and VoxelNetwork_depth.constrain_to_scene drive them)
+MASKED_SLOTS = 8           # free_mass, sum f p c (x y z), free_peak_p, free peak coordinate x y z (include/sceneego_hip.h)
+
+
+def _sc_check(what, named, ref_device):
+    """Every tensor of ``named`` = (name, tensor, dtype, numel or None) is a contiguous tensor of that type on one HIP device."""
+    for name, t, dtype, numel in named:
+        if not isinstance(t, torch.Tensor):
+            raise HipExtensionError(f"{what}: {name} is not a tensor")
+        if not t.is_cuda:
+            raise HipExtensionError(f"{what}: {name} is on {t.device}: the operator needs tensors on a HIP device")
+        if t.dtype != dtype:
+            raise HipExtensionError(f"{what}: {name} is {t.dtype}, expected {dtype}")
+        if not t.is_contiguous():
+            raise HipExtensionError(f"{what}: {name} is not contiguous")
+        if numel is not None and t.numel() != numel:
+            raise HipExtensionError(f"{what}: {name} has {t.numel()} elements, expected {numel}")
+        if ref_device is not None and t.device != ref_device:
+            raise HipExtensionError(f"{what}: {name} is on {t.device}, expected {ref_device}")
+
+
+def scene_free_mask(depth, pix, rng, free, height, width, margin, max_depth):
+    """se_scene_free_mask_u8: depth [B,dh,dw] float32, the sight table pix [voxels] int32 / rng [voxels] float32 of a ``height`` x
+    ``width`` frame -> free [B,voxels] uint8 (1 free, 0 blocked; the header states the rule).  Every argument is checked here and a
+    bad one raises HipExtensionError before anything is launched.  Returns ``free``."""
+    what = "scene_free_mask"
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise HipExtensionError(f"{what}: depth [B,dh,dw] expected")
+    if not isinstance(pix, torch.Tensor) or pix.dim() != 1:
+        raise HipExtensionError(f"{what}: pix [voxels] expected")
+    B, dh, dw = (int(v) for v in depth.shape)
+    voxels = int(pix.numel())
+    height, width = int(height), int(width)
+    _sc_check(what, (("depth", depth, torch.float32, None), ("pix", pix, torch.int32, voxels), ("rng", rng, torch.float32, voxels),
+                     ("free", free, torch.uint8, B * voxels)), depth.device if depth.is_cuda else None)
+    if B <= 0 or B > 65535 or dh <= 0 or dw <= 0 or height <= 0 or width <= 0 or height * width > 0x7fff0000:
+        raise HipExtensionError(f"{what}: batch {B}, depth {dh}x{dw}, frame {height}x{width} not supported")
+    if voxels <= 0 or voxels % 4:
+        raise HipExtensionError(f"{what}: voxels = {voxels} must be a positive multiple of 4")
+    margin, max_depth = float(margin), float(max_depth)
+    if margin != margin or not max_depth > 0.0:
+        raise HipExtensionError(f"{what}: margin {margin} must not be NaN and max_depth {max_depth} must be positive")
+    _check(load().se_scene_free_mask_u8(_ptr(depth), _ptr(pix), _ptr(rng), _ptr(free), B, dh, dw, height, width, voxels, margin,
+                                        max_depth, _stream()), "se_scene_free_mask_u8")
+    return free
+
+
+def softargmax3d_masked_scratch_elems(rows) -> int:
+    return int(load().se_softargmax3d_masked_scratch_elems(int(rows)))
+
+
+def softargmax3d_masked(prob, coord, free, out, peak_index, rows, rows_per_frame, voxels, scratch=None):
+    """se_softargmax3d_masked_f32: the soft-argmax sums and the peak of ``prob`` [rows, voxels] over the voxels that ``free``
+    [rows / rows_per_frame, voxels] uint8 marks free, into ``out`` [rows, 8] float32 and ``peak_index`` [rows] int32.  Every argument
+    is checked here and a bad one raises HipExtensionError before anything is launched: the kernel reads with 16-byte loads and trusts
+    the sizes it is given."""
+    what = "softargmax3d_masked"
+    rows, rows_per_frame, voxels = int(rows), int(rows_per_frame), int(voxels)
+    if rows <= 0 or rows > 65535 or rows_per_frame <= 0 or rows % rows_per_frame or voxels <= 0 or voxels % 4:
+        raise HipExtensionError(f"{what}: rows = {rows} (1..65535, a multiple of rows_per_frame = {rows_per_frame}), voxels = {voxels} "
+                                "(a positive multiple of 4) expected")
+    named = (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
+             ("free", free, torch.uint8, rows // rows_per_frame * voxels), ("out", out, torch.float32, rows * MASKED_SLOTS),
+             ("peak_index", peak_index, torch.int32, rows))
+    if scratch is not None:
+        named += (("scratch", scratch, torch.float32, None),)
+    _sc_check(what, named, prob.device if isinstance(prob, torch.Tensor) and prob.is_cuda else None)
+    need = softargmax3d_masked_scratch_elems(rows)
+    if scratch is None:
+        scratch = torch.empty(need, device=prob.device, dtype=torch.float32)
+    elif scratch.numel() < need:
+        raise HipExtensionError(f"{what}: scratch has {scratch.numel()} elements, needs {need}")
+    _check(load().se_softargmax3d_masked_f32(_ptr(prob), _ptr(coord), _ptr(free), _ptr(out), _ptr(peak_index), _ptr(scratch), rows,
+                                             rows_per_frame, voxels, _stream()), "se_softargmax3d_masked_f32")
+    return out, peak_index
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -242,3 +242,105 @@ def scene_check_to_numpy(result):
     dimension): what demo.py --scene_check and run_sequence.py --scene_output write."""
     host = {k: result[k].cpu().numpy() for k in SCENE_KEYS}
     return [{k: np.array(host[k][b]) for k in SCENE_KEYS} for b in range(host["range"].shape[0])]      # 0-d entries stay arrays
+
+
+# ----------------------------------------------------------------------------------------------
+# scene-constrained joints (csrc/scene_constraint.hip; no counterpart in the reference)
+# ----------------------------------------------------------------------------------------------
+CONSTRAINT_KEYS = ("joints", "constrained", "free_mass", "moved", "free_peak_prob", "free_peak_index", "free_peak_coord")
+
+
+def build_sight_table(grid_coord_proj, coord_volume, height, width):
+    """The sight table of ``include/sceneego_hip.h`` (host, once per grid and frame size): for every voxel the pixel its centre
+    projects to and its distance from the camera.  ``grid_coord_proj`` [N,2] float32 (u, v) as the module holds it, ``coord_volume``
+    [..., 3] float32 voxel centres with N rows in all.  Returns CPU tensors (pix int32 [N], rng float32 [N]):
+    x = floor((double)u + 0.5), y = floor((double)v + 0.5); pix = y * width + x when u, v are finite and the pixel lies in the
+    ``height`` x ``width`` frame, else -1; rng = (float)sqrt(((double)cx cx + (double)cy cy) + (double)cz cz)."""
+    height, width = int(height), int(width)
+    if height <= 0 or width <= 0 or height * width > 0x7fff0000:
+        raise ValueError(f"sight table: frame {height}x{width} not representable")
+    uv = grid_coord_proj.detach().to(torch.float32).cpu().numpy().reshape(-1, 2).astype(np.float64)
+    c = coord_volume.detach().to(torch.float32).cpu().numpy().reshape(-1, 3).astype(np.float64)
+    if uv.shape[0] != c.shape[0]:
+        raise ValueError(f"sight table: {uv.shape[0]} projections for {c.shape[0]} voxel centres")
+    finite = np.isfinite(uv).all(axis=1)
+    with np.errstate(invalid="ignore"):
+        x = np.floor(np.where(finite, uv[:, 0], -1.0) + 0.5)
+        y = np.floor(np.where(finite, uv[:, 1], -1.0) + 0.5)
+    inside = finite & (x >= 0) & (x < width) & (y >= 0) & (y < height)
+    pix = np.where(inside, np.where(inside, y, 0.0) * width + np.where(inside, x, 0.0), -1.0).astype(np.int32)
+    rng = np.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]).astype(np.float32)
+    return torch.from_numpy(pix), torch.from_numpy(rng)
+
+
+def scene_free_mask(depth, pix, rng, height, width, margin, max_depth, out=None):
+    """The free space of the voxel grid, per frame (``se_scene_free_mask_u8``): ``depth`` [B,dh,dw] float32 on the device, the sight
+    table ``pix`` / ``rng`` of ``build_sight_table`` on the same device -> uint8 [B,N], 1 where the voxel is free: it projects outside
+    the frame, its pixel has no surface (depth <= 0, > ``max_depth`` or NaN), or it is no more than ``margin`` metres behind the
+    surface: blocked iff (double)d + margin < (double)rng.  ``out``: an optional uint8 [B,N] buffer."""
+    _lib.require_hip(depth, pix, rng)
+    if depth.dim() != 3:
+        raise _lib.HipExtensionError("scene_free_mask: depth [B,dh,dw] expected, got %s" % (tuple(depth.shape),))
+    if out is None:
+        out = torch.empty((depth.shape[0], pix.numel()), device=depth.device, dtype=torch.uint8)
+    return _lib.scene_free_mask(depth, pix, rng, out, height, width, margin, max_depth)
+
+
+def constrained_joints(volumes, coord_volumes, free, joints=None, scratch=None):
+    """The soft-argmax over the free voxels alone (``se_softargmax3d_masked_f32``; one pass over the volumes on the device).
+    ``volumes`` [B,J,X,Y,Z] float32 softmaxed, as ``integrate_tensor_3d_with_coordinates`` returns them; ``coord_volumes``
+    [>=1,X,Y,Z,3] (sample 0 is used); ``free`` uint8 [B,X,Y,Z] (or [B,N]) of ``scene_free_mask``; ``joints`` [B,J,3]: the unconstrained
+    joints, kept where a row cannot be constrained (NaN there without them).  Returns a dict of device tensors:
+
+      ``joints``          [B,J,3]  sum_n f_n p_n c_n / sum_n f_n p_n (float32 division), or the input joint where free_mass is 0 or NaN
+      ``constrained``     [B,J]    bool: the masked expectation was used
+      ``free_mass``       [B,J]    sum_n f_n p_n: the probability in front of the depth surface
+      ``moved``           [B,J]    metres between the input and the returned joint (NaN without ``joints``)
+      ``free_peak_prob``  [B,J]    the largest p_n over the free voxels (0 without a free voxel)
+      ``free_peak_index`` [B,J]    int32, the lowest free flat index that holds it (-1 without one)
+      ``free_peak_coord`` [B,J,3]  that voxel's centre (NaN without one): the one output that is guaranteed to be free
+
+    Masking and renormalising is a convention, not validated against annotated data, and the mean of a masked distribution is not
+    itself guaranteed to lie in free space.  A (sample, joint) whose volume holds a NaN keeps its input joint, with NaN in free_mass,
+    free_peak_prob and free_peak_coord and index -1."""
+    _lib.require_hip(volumes, free, joints)
+    if volumes.dim() != 5 or volumes.dtype != torch.float32:
+        raise _lib.HipExtensionError("constrained_joints: volumes must be [B,J,X,Y,Z] float32, got %s %s"
+                                     % (tuple(volumes.shape), volumes.dtype))
+    B, J, X, Y, Z = volumes.shape
+    N = X * Y * Z
+    if tuple(coord_volumes.shape[1:]) != (X, Y, Z, 3) or coord_volumes.shape[0] < 1:
+        raise _lib.HipExtensionError("constrained_joints: coord_volumes %s does not match volumes %s"
+                                     % (tuple(coord_volumes.shape), tuple(volumes.shape)))
+    if free.dtype != torch.uint8 or free.shape[0] != B or free.numel() != B * N:
+        raise _lib.HipExtensionError("constrained_joints: free must be uint8 [%d,%d,%d,%d], got %s %s"
+                                     % (B, X, Y, Z, tuple(free.shape), free.dtype))
+    if joints is not None and tuple(joints.shape) != (B, J, 3):
+        raise _lib.HipExtensionError("constrained_joints: joints %s, expected %s" % (tuple(joints.shape), (B, J, 3)))
+    coord = coord_volumes[0].to(device=volumes.device, dtype=torch.float32).contiguous()
+    return _constrained_joints_flat(volumes.contiguous(), coord, free.contiguous(),
+                                    None if joints is None else joints.contiguous().float(), B, J, N, scratch)
+
+
+def _constrained_joints_flat(vol, coord, free, joints, B, J, N, scratch):
+    rows = B * J
+    out = torch.empty((rows, _lib.MASKED_SLOTS), device=vol.device, dtype=torch.float32)
+    peak_index = torch.empty((rows,), device=vol.device, dtype=torch.int32)
+    _lib.softargmax3d_masked(vol, coord, free, out, peak_index, rows, J, N, scratch=scratch)
+    o = out.view(B, J, _lib.MASKED_SLOTS)
+    mass = o[..., 0]
+    constrained = mass > 0                                   # false for an empty row (0) and for a NaN row
+    before = joints if joints is not None else torch.full((B, J, 3), float("nan"), device=vol.device, dtype=torch.float32)
+    after = torch.where(constrained[..., None], o[..., 1:4] / mass[..., None], before)
+    d = after - before
+    moved = torch.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+    return {"joints": after, "constrained": constrained, "free_mass": mass, "moved": moved, "free_peak_prob": o[..., 4],
+            "free_peak_index": peak_index.view(B, J), "free_peak_coord": o[..., 5:8]}
+
+
+def scene_constraint_to_numpy(result):
+    """The dict of ``VoxelNetwork_depth.constrain_to_scene`` / ``constrained_joints`` as a list of per-frame dicts of numpy arrays (the
+    keys without the batch dimension and without the ``free`` mask): what demo.py --constrained_dir and run_sequence.py
+    --constrain_output write."""
+    host = {k: result[k].cpu().numpy() for k in CONSTRAINT_KEYS}
+    return [{k: host[k][b].copy() for k in CONSTRAINT_KEYS} for b in range(host["free_mass"].shape[0])]

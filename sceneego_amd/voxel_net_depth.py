@@ -115,6 +115,7 @@ class VoxelNetwork_depth(nn.Module):
         self._graphs = {}
         self._xbuf = {}
         self._stats_ws = {}
+        self._scene_ws = {}
         # V2V storage type: "fp32" (parity path, default) or "bf16" (BASELINE config 3: bf16 activations/weights,
         # float32 accumulation; joints differ from the float32 reference by more than 1e-3)
         self.v2v_dtype = torch.bfloat16 if str(config.model.get("v2v_dtype", "fp32")).lower() in ("bf16", "bfloat16") \
@@ -150,6 +151,7 @@ class VoxelNetwork_depth(nn.Module):
         self._graphs = {}
         self._xbuf = {}
         self._stats_ws = {}
+        self._scene_ws = {}
 
     def _load_from_state_dict(self, *a, **k):
         super()._load_from_state_dict(*a, **k)
@@ -395,6 +397,59 @@ class VoxelNetwork_depth(nn.Module):
         if ws is None:
             ws = self._stats_ws[key] = torch.empty(_lib.joint_stats_scratch_elems(B * J), device=dev, dtype=torch.float32)
         return op._joint_statistics_flat(volumes.contiguous(), coord, joints.contiguous().float(), B, J, G * G * G, ws)
+
+    @torch.no_grad()
+    def constrain_to_scene(self, volumes, joints, depth, margin=None):
+        """The joints re-estimated over the free space of the scene: the soft-argmax of the softmaxed ``volumes`` [B,J,G,G,G] taken
+        over only the voxels that lie in front of the depth surface of ``depth`` [B,dh,dw] (or [B,1,dh,dw]; metres, any size: it is
+        looked up by nearest index like the scene check does), beside the ``joints`` [B,J,3] that ``forward()`` returned with them.
+        ``op.scene_free_mask`` + ``op.constrained_joints`` with the module's own ``grid_coord_proj`` and ``coord_volumes`` and the
+        frame ``config.dataset.image_height`` x ``image_width``; ``margin`` (metres a voxel may lie behind the surface and still
+        count as free) defaults to one voxel edge, ``cuboid_side / volume_size``, the tolerance ``SceneConsistency`` calls
+        penetrating: a convention, not calibrated.  Returns the dict of device tensors ``op.constrained_joints`` describes (joints,
+        constrained, free_mass, moved, free_peak_prob, free_peak_index, free_peak_coord) plus ``free`` [B,G,G,G] uint8.  Two small
+        launches and one pass over the volumes on the current stream; the sight table is cached per device, the mask and the
+        partial-record workspace per (device, rows), so ``free`` is overwritten by the next call with the same batch.
+        ``forward()`` itself is unchanged: pass what it returned.
+
+        Under ``enable_graphs(True)`` the volumes and joints are the graph's STATIC buffers, overwritten by the next replay: call this
+        before the next ``forward()`` (the call is queued on the current stream, so stream order is enough).
+
+        Raises ValueError when ``config.model.volume_softmax`` is false: the ReLU volumes are not a distribution."""
+        if not self.volume_softmax:
+            raise ValueError("constrain_to_scene needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        _lib.require_hip(volumes, joints, depth)
+        G = self.volume_size
+        if volumes.dim() != 5 or tuple(volumes.shape[2:]) != (G, G, G) or volumes.dtype != torch.float32:
+            raise _lib.HipExtensionError("constrain_to_scene: volumes must be [B,J,%d,%d,%d] float32, got %s %s"
+                                         % (G, G, G, tuple(volumes.shape), volumes.dtype))
+        B, J = int(volumes.shape[0]), int(volumes.shape[1])
+        if tuple(joints.shape) != (B, J, 3):
+            raise _lib.HipExtensionError("constrain_to_scene: joints %s, expected %s" % (tuple(joints.shape), (B, J, 3)))
+        if depth.dim() not in (3, 4) or depth.shape[0] != B or depth.numel() != B * depth.shape[-2] * depth.shape[-1]:
+            raise _lib.HipExtensionError("constrain_to_scene: depth [%d,dh,dw] expected, got %s" % (B, tuple(depth.shape)))
+        dev = volumes.device
+        N = G * G * G
+        tab = self._scene_ws.get((str(dev), "sight"))
+        if tab is None:
+            # the module's own grid, whatever tables the last forward was given
+            pix, rng = op.build_sight_table(self.grid_coord_proj, self.coord_volume, self.image_height, self.image_width)
+            coord = self.coord_volumes[0].reshape(N, 3).to(device=dev, dtype=torch.float32).contiguous()
+            tab = self._scene_ws[(str(dev), "sight")] = (pix.to(dev), rng.to(dev), coord)
+        pix, rng, coord = tab
+        ws = self._scene_ws.get((str(dev), B * J))
+        if ws is None:
+            ws = self._scene_ws[(str(dev), B * J)] = (
+                torch.empty((B, N), device=dev, dtype=torch.uint8),
+                torch.empty(_lib.softargmax3d_masked_scratch_elems(B * J), device=dev, dtype=torch.float32))
+        free, scratch = ws
+        from .render import MAX_DEPTH
+        d = depth.reshape(B, depth.shape[-2], depth.shape[-1]).float().contiguous()
+        op.scene_free_mask(d, pix, rng, self.image_height, self.image_width,
+                           self.cuboid_side / self.volume_size if margin is None else float(margin), MAX_DEPTH, out=free)
+        out = op._constrained_joints_flat(volumes.contiguous(), coord, free, joints.contiguous().float(), B, J, N, scratch)
+        out["free"] = free.view(B, G, G, G)
+        return out
 
     def _voxelise(self, x, planar3, fast_occ, prog, scene_volumes, depth_map_batch, B, G, N, C, dev, planar1=False):
         """Occupancy into the V2V input buffer ``x`` (reference ``:246-262``)."""
