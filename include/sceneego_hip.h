@@ -246,7 +246,10 @@ int se_maxpool3d_2_octin_f32(const float* in, float* out, int batch, int dim, in
  *   coord  [voxels][3] float32 voxel-centre coordinates
  *   out_vol[rows][voxels] softmax(vol) (mode 1) or relu(vol) (mode 0)
  *   joints [rows][3] = sum_n out_vol[n] * coord[n]
- *   scratch: se_softargmax3d_scratch_elems(rows) floats of workspace.                              */
+ *   scratch: se_softargmax3d_scratch_elems(rows) floats of workspace.
+ * Mode 1 treats non-finite logits as torch.softmax does: a -inf logit has probability exactly 0 and leaves the rest of its row
+ * finite (also where it fills a whole chunk of the split row); a row of nothing but -inf, or one that holds a NaN, is NaN
+ * throughout, joints included.                                                                      */
 int se_softargmax3d_f32(const float* vol, const float* coord, float* out_vol, float* joints,
                         float* scratch, int rows, int voxels, int mode, void* stream);
 

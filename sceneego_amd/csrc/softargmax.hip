@@ -58,7 +58,11 @@ __global__ __launch_bounds__(256) void softargmax_partial_kernel(const float* __
         const f32x4 c_c = *reinterpret_cast<const f32x4*>(coord + (size_t)i * 3 + 8);
         float e0, e1, e2, e3;
         if (mode == 1) {
-            e0 = expf(x.x - m); e1 = expf(x.y - m); e2 = expf(x.z - m); e3 = expf(x.w - m);
+            // A -inf logit contributes exactly 0, whatever m is: in a chunk of nothing but -inf, m is -inf too and expf(-inf - -inf) would be
+            // NaN, which the fold's 0 weight for that chunk does not remove (NaN * 0).  m itself is not special-cased: a NaN among -inf
+            // logits (fmaxf drops it from m) must still come out of expf(NaN - m) and reach L.
+            e0 = x.x == -INFINITY ? 0.f : expf(x.x - m); e1 = x.y == -INFINITY ? 0.f : expf(x.y - m);
+            e2 = x.z == -INFINITY ? 0.f : expf(x.z - m); e3 = x.w == -INFINITY ? 0.f : expf(x.w - m);
         } else {
             e0 = fmaxf(x.x, 0.f); e1 = fmaxf(x.y, 0.f); e2 = fmaxf(x.z, 0.f); e3 = fmaxf(x.w, 0.f);
         }
