@@ -23,6 +23,8 @@ predicted skeleton against the scene of its own depth map (``sceneego_amd/scene_
 ``--constrained_dir DIR`` writes ``DIR/<img_name>.pkl``: the joints re-estimated over the free space in front of the depth surface
 (``VoxelNetwork_depth.constrain_to_scene``), float32 [15,3] like the prediction, so ``evaluate.py --pred_dir DIR`` reads them; and
 ``DIR/<img_name>.constraint.pkl``: free_mass, moved, constrained, the free peak, ... of every joint.
+``--modes true [--modes_k 4]`` writes ``<img_name>.modes.pkl`` beside each ``<img_name>.pkl``: the strongest peaks of every joint's
+volume with their mass and sub-voxel centroid (``VoxelNetwork_depth.joint_modes``); ``evaluate.py --modes`` reads them.
 """
 import argparse
 import os
@@ -33,7 +35,7 @@ import torch
 
 from sceneego_amd import load_config, synth
 from sceneego_amd.jpeg_device import JpegFile, decode_jpeg_batch
-from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy
+from sceneego_amd.op import joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy
 from sceneego_amd.preprocess import (DEPTH_CLAMP, load_depth, load_image_bgr, prepare_depth, preprocess_image,
                                      preprocess_image_device)
 from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
@@ -45,7 +47,7 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 class Demo:
     def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False,
-                 render_format="png", render_volumes=False, volume_joints=None, save_volumes=None, constrain=False):
+                 render_format="png", render_volumes=False, volume_joints=None, save_volumes=None, constrain=False, modes=0):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
@@ -62,6 +64,7 @@ class Demo:
         self.save_volumes = save_volumes
         self.scene_check = scene_check
         self.constrain = constrain
+        self.modes = int(modes)                # modes kept per joint; 0: off
         self.scene = None
         self.items = []
         for img_name in sorted(os.listdir(img_dir)):
@@ -115,6 +118,9 @@ class Demo:
                 if self.constrain:
                     # likewise before the next frame: the volumes are the graph's static buffers
                     results[-1]["constraint"] = scene_constraint_to_numpy(self.network.constrain_to_scene(volumes, kp, depth))[0]
+                if self.modes:
+                    # likewise before the next frame
+                    results[-1]["modes"] = joint_modes_to_numpy(self.network.joint_modes(volumes, k=self.modes))[0]
                 if self.scene_check:
                     results[-1]["scene"] = scene_check_to_numpy(self.check_scene(depth, kp))[0]
                 if self.save_volumes is not None:
@@ -188,6 +194,10 @@ def parse_args(argv=None):
     ap.add_argument("--constrained_dir", type=str, default=None,
                     help="also write <img_name>.pkl here: the joints re-estimated over the free space in front of the depth surface "
                          "(float32 [15,3], readable by evaluate.py --pred_dir), and <img_name>.constraint.pkl (free_mass, moved, ...)")
+    ap.add_argument("--modes", type=str, default="false",
+                    help="true: also write <img_name>.modes.pkl (the strongest peaks of every joint's volume: coord, peak_coord, "
+                         "peak_prob, mass, index, count, total, valid)")
+    ap.add_argument("--modes_k", type=int, default=4, help="with --modes true: modes kept per joint, 1..16")
     args = ap.parse_args(argv)
     if args.vis.lower() == "true":
         raise SystemExit("--vis true (open3d visualisation) is out of scope of this build")
@@ -197,7 +207,9 @@ def parse_args(argv=None):
     if args.scene_check.lower() not in ("true", "false"):
         raise SystemExit("--scene_check must be true or false")
     args.scene_check = args.scene_check.lower() == "true"
-    for flag in ("render_volumes", "save_volumes"):
+    if not 1 <= args.modes_k <= 16:
+        raise SystemExit("--modes_k must be in 1..16")
+    for flag in ("render_volumes", "save_volumes", "modes"):
         if getattr(args, flag).lower() not in ("true", "false"):
             raise SystemExit(f"--{flag} must be true or false")
         setattr(args, flag, getattr(args, flag).lower() == "true")
@@ -219,7 +231,7 @@ def main(argv=None):
     demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats, render_dir=args.render_dir,
                 scene_check=args.scene_check, render_format=args.render_format, render_volumes=args.render_volumes,
                 volume_joints=args.volume_joints, save_volumes=args.output_dir if args.save_volumes else None,
-                constrain=args.constrained_dir is not None)
+                constrain=args.constrained_dir is not None, modes=args.modes_k if args.modes else 0)
     os.makedirs(args.output_dir, exist_ok=True)
     if args.constrained_dir is not None:
         os.makedirs(args.constrained_dir, exist_ok=True)
@@ -231,6 +243,9 @@ def main(argv=None):
         if args.stats:
             with open(out_path[:-4] + ".stats.pkl", "wb") as f:
                 pickle.dump(r["stats"], f)                # dict of numpy arrays, the keys of op.joint_statistics
+        if args.modes:
+            with open(out_path[:-4] + ".modes.pkl", "wb") as f:
+                pickle.dump(r["modes"], f)                # dict of numpy arrays, the keys of op.MODES_KEYS
         if args.scene_check:
             with open(out_path[:-4] + ".scene.pkl", "wb") as f:
                 pickle.dump(r["scene"], f)                # dict of numpy arrays, the keys of SceneConsistency.check

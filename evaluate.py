@@ -21,7 +21,14 @@ if ROOT not in sys.path:
 
 
 def load_predictions(pred_dir):
-    names = sorted(n for n in os.listdir(pred_dir) if n.endswith(".pkl") and not n.endswith((".stats.pkl", ".scene.pkl", ".constraint.pkl")))
+    if os.path.isfile(pred_dir):                             # the one pickle of run_sequence.py --output / --track_output
+        with open(pred_dir, "rb") as f:
+            poses = np.asarray(pickle.load(f), dtype=np.float64)
+        if poses.ndim != 3 or poses.shape[1:] != (15, 3):
+            raise SystemExit(f"{pred_dir}: expected a list of [15,3] poses, got {poses.shape}")
+        return ["%06d.pkl" % t for t in range(poses.shape[0])], poses
+    names = sorted(n for n in os.listdir(pred_dir)
+                   if n.endswith(".pkl") and not n.endswith((".stats.pkl", ".scene.pkl", ".constraint.pkl", ".modes.pkl")))
     if not names:
         raise SystemExit(f"no .pkl predictions in {pred_dir}")
     poses = []
@@ -69,6 +76,42 @@ def load_scene(path, names):
     return frames
 
 
+def load_modes(path, names):
+    """The per-frame joint-mode dicts of the frames behind the prediction files ``names``: from a directory of
+    ``<image name>.modes.pkl`` files (demo.py --modes true) or from the one pickle of run_sequence.py --modes_output."""
+    if os.path.isdir(path):
+        frames = []
+        for n in names:
+            with open(os.path.join(path, n[:-4] + ".modes.pkl"), "rb") as f:
+                frames.append(pickle.load(f))
+    else:
+        with open(path, "rb") as f:
+            frames = pickle.load(f)
+    if len(frames) != len(names):
+        raise SystemExit(f"{path}: modes of {len(frames)} frames for {len(names)} predictions")
+    return frames
+
+
+def best_of_k(frames, pred, gt):
+    """The usual multi-hypothesis figure: per joint the smallest distance to the ground truth over its VALID modes (their ``coord``;
+    the prediction itself where a joint has no valid mode), averaged over joints and frames; and the share of the joints that have
+    a valid mode whose best mode is not mode 0.  No alignment: the distances are in the frame of the predictions, as MPJPE."""
+    best, not_first, have = [], 0, 0
+    for fr, p, g in zip(frames, pred, gt):
+        valid = np.asarray(fr["valid"]).astype(bool)                                            # [15,K]
+        with np.errstate(invalid="ignore"):
+            d = np.sqrt(((np.asarray(fr["coord"], dtype=np.float64) - g[:, None, :]) ** 2).sum(axis=2))
+        d = np.where(valid, d, np.inf)
+        k = d.argmin(axis=1)                                                                    # the lowest slot of the minimum
+        any_valid = valid.any(axis=1)
+        fallback = np.sqrt(((p - g) ** 2).sum(axis=1))
+        best.append(np.where(any_valid, d[np.arange(d.shape[0]), k], fallback))
+        not_first += int((any_valid & (k != 0)).sum())
+        have += int(any_valid.sum())
+    return {"best_of_k_mpjpe": float(np.mean(best)), "best_not_first_share": not_first / have if have else 0.0,
+            "joints_with_modes": have}
+
+
 def match_ground_truth(gt, names):
     if isinstance(gt, dict):
         def find(n):
@@ -92,7 +135,8 @@ def evaluate(pred, gt, scale=True):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--pred_dir", required=True, help="directory of <image name>.pkl files written by demo.py")
+    ap.add_argument("--pred_dir", required=True, help="directory of <image name>.pkl files written by demo.py, or the one pickle of "
+                    "run_sequence.py --output / --track_output")
     ap.add_argument("--gt", required=True, help="pickle: dict name -> [15,3], or [T,15,3] in sorted file order")
     ap.add_argument("--no-scale", action="store_true", help="rigid instead of similarity alignment (align_skeleton(scale=False))")
     ap.add_argument("--unit", default="m", help="label only; the numbers are in the unit of the inputs")
@@ -101,6 +145,8 @@ def main(argv=None):
     ap.add_argument("--stats_bins", type=int, default=4, help="number of sigma quantile bins of --stats")
     ap.add_argument("--scene", default=None, help="scene checks of the same frames: a directory of <image name>.scene.pkl files "
                     "(demo.py --scene_check true) or the one pickle of run_sequence.py --scene_output; adds the plausibility summary")
+    ap.add_argument("--modes", default=None, help="joint modes of the same frames: a directory of <image name>.modes.pkl files "
+                    "(demo.py --modes true) or the one pickle of run_sequence.py --modes_output; adds the best-of-K MPJPE")
     args = ap.parse_args(argv)
     names, pred = load_predictions(args.pred_dir)
     with open(args.gt, "rb") as f:
@@ -119,6 +165,10 @@ def main(argv=None):
         from sceneego_amd import metrics as M
         r["scene_summary"] = M.scene_summary(load_scene(args.scene, names))
         print(M.format_scene_summary(r["scene_summary"], args.unit))
+    if args.modes is not None:
+        r.update(best_of_k(load_modes(args.modes, names), pred, gt))
+        print(f"best-of-K MPJPE {r['best_of_k_mpjpe']:.6f} {args.unit} (the closest valid mode of every joint); the best mode is not "
+              f"mode 0 in {r['best_not_first_share']:.1%} of {r['joints_with_modes']} joints")
     return r
 
 

@@ -611,6 +611,38 @@ int se_softargmax3d_masked_f32(const float* prob, const float* coord, const unsi
                                float* scratch, int rows, int rows_per_frame, int voxels, void* stream);
 long long se_softargmax3d_masked_scratch_elems(int rows);
 
+/* Multi-hypothesis joints (no counterpart in the reference; sceneego_amd/op.py: joint_modes; VoxelNetwork_depth.joint_modes drives
+ * it): the K strongest local maxima (modes) of every softmaxed joint volume, each with the mass and the first moments of its
+ * neighbourhood.  One right answer, bit for bit (tests/joint_modes_model.py restates it).
+ *   prob   [rows][voxels] float32 probabilities, as se_softargmax3d_f32 writes them in mode 1; voxels = G^3, flat index
+ *          n = (i G + j) G + k                                   coord  [voxels][3] float32 voxel-centre coordinates
+ *   K in 1..16     radius in 0..3     min_prob >= 0
+ * KEY        voxel n has the key (p_n, -n), compared lexicographically: a strict total order.
+ * MODE       voxel n is a mode iff p_n > 0, p_n >= min_prob (equality counts) and its key is greater than the key of every
+ *            neighbour: the up to 26 voxels with |di|, |dj|, |dk| <= 1 that lie inside the grid (nothing wraps from one row of the
+ *            grid into the next).  Two equal adjacent voxels give one mode, the lower index; two equal voxels that are not adjacent
+ *            are both modes; the zero tail of an underflowed softmax gives none.
+ * SELECTION  the row's modes sorted by descending key (p descending, then index ascending); the first min(K, total) are selected.
+ * WINDOW     of a selected mode at (i, j, k): every voxel m with |d| <= radius on each axis, clipped to the grid.
+ *            mass = sum_m p_m, mom_a = sum_m p_m c_m,a (a = x, y, z): each sum accumulated in float64 in ASCENDING flat index m from
+ *            the float32 values (the products are exact in float64) and rounded to float32 once at the end.  NOT divided: the kernel
+ *            does no division; the caller divides by the mass.
+ *   modes [rows][K][8] float32: 0 p_peak, 1 mass, 2..4 mom_x mom_y mom_z, 5..7 coord[index]
+ *   index [rows][K] int32: the mode's flat index
+ *   count [rows] int32: the number of selected modes, min(K, total)
+ *   total [rows] int32: the number of modes in the row, uncapped (an exact integer)
+ *   scratch: se_joint_modes_scratch_bytes(rows, G, K) bytes of workspace, 4-byte aligned (0 for rows <= 0 or a G / K out of range).
+ * An unfilled record (slot >= count) has index -1, slots 0..4 equal to +0 and slots 5..7 NaN.  A row that holds a NaN probability
+ * anywhere gets NaN in all its K x 8 slots, every index -1 and count = total = -1; other rows are unaffected.  Two launches on
+ * `stream` (one workgroup per (row, tile of 4 i-planes x up to 256 / ceil(G / 4) j-rows) staged in LDS with a one-voxel halo, then
+ * one wave per row), no atomics, selections under the total order and sums in a fixed order: bitwise identical from run to run.
+ * Allocates nothing (legal inside hipGraph capture).  SE_ERR_BAD_ARG, with nothing launched: a null pointer, rows outside 1..65535,
+ * G < 2, voxels != G^3, voxels & 3, K outside 1..16, radius outside 0..3, min_prob negative or NaN, a prob / coord that is not
+ * 16-byte aligned, a scratch that is not 4-byte aligned or scratch_bytes below se_joint_modes_scratch_bytes(rows, G, K).           */
+int se_joint_modes_f32(const float* prob, const float* coord, float* modes, int* index, int* count, int* total, void* scratch,
+                       long long scratch_bytes, int rows, int voxels, int G, int K, int radius, float min_prob, void* stream);
+long long se_joint_modes_scratch_bytes(int rows, int G, int K);
+
 /* Baseline JPEG encoder (no counterpart in the reference; sceneego_amd/jpeg_encode.py writes the file headers around it).
  *   frames    uint8 [batch][height][width][3] on the device, R, G, B (bgr = 0) or B, G, R (bgr = 1); any height, width in 1..65535
  *   quant_luma, quant_chroma   HOST pointers: unsigned short [64], natural order, every value in 1..255 (baseline tables)

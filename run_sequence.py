@@ -8,6 +8,7 @@
                            [--render_dir out/frames [--render_every 10] [--render_format jpg]]
                            [--render_video out/seq.avi [--render_fps 25] [--render_view render|overlay|both] [--render_quality 90]]
                            [--scene_output out/no_body_diogo1.scene.pkl] [--constrain_output out/no_body_diogo1.constraint.pkl]
+                           [--modes_output out/no_body_diogo1.modes.pkl [--modes_k 4] [--track_output out/tracked.pkl [--track_sigma 0.1]]]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -30,6 +31,11 @@ each predicted skeleton against the scene of its own depth map), taken per batch
 ``--constrain_output`` adds a pickle of the per-frame scene constraints (``VoxelNetwork_depth.constrain_to_scene``: the joints
 re-estimated over the free space in front of the depth surface, free_mass, moved, ...), taken per batch on the stream it ran on; with
 ``--scene_output`` the scene check also runs on the constrained joints and both summaries are printed.
+``--modes_output`` adds a pickle of the per-frame joint modes (``VoxelNetwork_depth.joint_modes``: the ``--modes_k`` strongest peaks of
+every joint's volume with their mass and sub-voxel centroid), taken per batch on the stream it ran on.  ``--track_output`` then writes
+a pickle in the format of ``--output`` whose joints are one mode per joint and frame, picked over the whole sequence by
+``sceneego_amd.track.select_modes`` (``--track_sigma`` metres per frame; the soft-argmax joint where a frame has no valid mode), and
+prints its MPJPE beside the soft-argmax's: mass as likelihood and a Gaussian step are a convention, not calibrated.
 """
 import argparse
 import json
@@ -210,21 +216,22 @@ class SequenceRunner:
     @torch.no_grad()
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
-            volume_joints=None, constrain=False):
+            volume_joints=None, constrain=False, modes=0):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
         scene-check dicts are appended to what is returned (joints, [statistics,] scene checks).  ``render_volumes``: also write
         ``<img_name>.volumes.render.*`` / ``.volumes.overlay.*`` (the joint probability volumes of ``volume_joints``, default all, drawn
         over the pair), and the video shows those views.  ``constrain``: the per-frame scene-constraint dicts are appended after
-        those, and with ``scene`` the scene checks of the constrained joints after them."""
+        those, and with ``scene`` the scene checks of the constrained joints after them.  ``modes`` = k > 0: the per-frame joint-mode
+        dicts (``VoxelNetwork_depth.joint_modes(k=modes)``) are appended last."""
         from sceneego_amd.jpeg_device import JpegFile
-        from sceneego_amd.op import joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy
+        from sceneego_amd.op import joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
         preds, frame_stats, frame_scene, pending = [], [], [], []
-        frame_constraint, frame_scene_constrained = [], []
+        frame_constraint, frame_scene_constrained, frame_modes = [], [], []
 
         rendering = render_dir is not None or render_video is not None
         if rendering:
@@ -240,7 +247,7 @@ class SequenceRunner:
 
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done, job, sc, con = pending.pop(0)
+                kp, st, done, job, sc, con, md = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 kp_host = kp.cpu().numpy()
@@ -253,6 +260,8 @@ class SequenceRunner:
                     frame_constraint.extend(scene_constraint_to_numpy(con[0]))
                     if con[1] is not None:
                         frame_scene_constrained.extend(scene_check_to_numpy(con[1]))
+                if md is not None:
+                    frame_modes.extend(joint_modes_to_numpy(md))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -278,13 +287,14 @@ class SequenceRunner:
                         c = self.net.constrain_to_scene(vol, kp, depth)
                         con = (c, self._scene().check(depth, c["joints"]) if scene else None)
                     pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
-                                    self._scene().check(depth, kp) if scene else None, con))
+                                    self._scene().check(depth, kp) if scene else None, con,
+                                    self.net.joint_modes(vol, k=modes) if modes else None))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
-                    st = sc = con = None
-                    if stats or scene or constrain:
+                    st = sc = con = md = None
+                    if stats or scene or constrain or modes:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
@@ -295,9 +305,11 @@ class SequenceRunner:
                             if constrain:
                                 c = net.constrain_to_scene(vol, kp, depth)
                                 con = (c, self._scene(stream.cuda_stream).check(depth, c["joints"]) if scene else None)
+                            if modes:
+                                md = net.joint_modes(vol, k=modes)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done, job, sc, con))
+                    pending.append((kp, st, done, job, sc, con, md))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             try:
                 drain(0)
@@ -305,10 +317,11 @@ class SequenceRunner:
                 if self.video is not None:
                     self.video.close()
                     self.video = None
-        if not (stats or scene or constrain):
+        if not (stats or scene or constrain or modes):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
-            + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ())
+            + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
+            + ((frame_modes,) if modes else ())
 
 
 def _size(text):
@@ -356,6 +369,12 @@ def build_parser():
     ap.add_argument("--constrain_output", default=None, help="pickle of the per-frame scene constraints (list of dicts of numpy arrays: "
                     "joints, constrained, free_mass, moved, free_peak_prob, free_peak_index, free_peak_coord); with --scene_output the "
                     "scene check also runs on the constrained joints and both summaries are printed")
+    ap.add_argument("--modes_output", default=None, help="pickle of the per-frame joint modes (list of dicts of numpy arrays: coord, "
+                    "peak_coord, peak_prob, mass, index, count, total, valid)")
+    ap.add_argument("--modes_k", type=int, default=4, help="with --modes_output: modes kept per joint, 1..16")
+    ap.add_argument("--track_output", default=None, help="with --modes_output: pickle in the format of --output holding one mode per "
+                    "joint and frame, picked over the sequence (sceneego_amd/track.py: a convention, not calibrated)")
+    ap.add_argument("--track_sigma", type=float, default=0.1, help="with --track_output: metres a joint is assumed to move per frame")
     ap.add_argument("--render_format", default="png", choices=("png", "jpg"),
                     help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG files encoded on the device)")
     ap.add_argument("--render_video", default=None, help="write the picked frames as one Motion-JPEG AVI (4:2:0, encoded on the device)")
@@ -380,6 +399,12 @@ def parse_args(argv=None):
         raise SystemExit("--render_volumes true needs --render_dir or --render_video")
     if args.volume_joints is not None and not args.render_volumes:
         raise SystemExit("--volume_joints needs --render_volumes true")
+    if args.track_output is not None and args.modes_output is None:
+        raise SystemExit("--track_output needs --modes_output")
+    if not 1 <= args.modes_k <= 16:
+        raise SystemExit("--modes_k must be in 1..16")
+    if not args.track_sigma > 0:
+        raise SystemExit("--track_sigma must be positive")
     from sceneego_amd.render import parse_joint_list
     try:
         args.volume_joints = parse_joint_list(args.volume_joints)
@@ -404,17 +429,19 @@ def main(argv=None):
     want_stats = args.stats_output is not None
     want_scene = args.scene_output is not None
     want_constraint = args.constrain_output is not None
+    want_modes = args.modes_output is not None
     preds = runner.run(images, depths, config.test.batch_size, stats=want_stats, render_dir=args.render_dir,
                        render_every=args.render_every, scene=want_scene, render_format=args.render_format,
                        render_video=args.render_video, render_fps=args.render_fps, render_view=args.render_view,
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
-                       volume_joints=args.volume_joints, constrain=want_constraint)
-    if want_stats or want_scene or want_constraint:
+                       volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0)
+    if want_stats or want_scene or want_constraint or want_modes:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
         frame_scene = extra.pop(0) if want_scene else None
         frame_constraint = extra.pop(0) if want_constraint else None
         frame_scene_constrained = extra.pop(0) if want_constraint and want_scene else None
+        frame_modes = extra.pop(0) if want_modes else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -449,6 +476,22 @@ def main(argv=None):
             result["scene_constrained"] = frame_scene_constrained
             result["scene_summary_constrained"] = M.scene_summary(frame_scene_constrained)
             print("constrained joints: " + M.format_scene_summary(result["scene_summary_constrained"]))
+    if want_modes:
+        os.makedirs(os.path.dirname(os.path.abspath(args.modes_output)), exist_ok=True)
+        with open(args.modes_output, "wb") as f:
+            pickle.dump(frame_modes, f)
+        result["modes"] = frame_modes
+        if args.track_output is not None:
+            from sceneego_amd.track import select_modes
+            joints, choice = select_modes(frame_modes, sigma=args.track_sigma, fallback=np.stack(preds))
+            tracked = [np.asarray(j, dtype=np.float32) for j in joints]
+            os.makedirs(os.path.dirname(os.path.abspath(args.track_output)), exist_ok=True)
+            with open(args.track_output, "wb") as f:
+                pickle.dump(tracked, f)
+            result["tracked"], result["track_choice"] = tracked, choice
+            result["tracked_mpjpe"] = M.mpjpe(joints.astype(np.float64), gt)
+            print("tracked modes (a convention, not calibrated): mpjpe: {}, mode 0 in {:.1%} of the joints, fallback in {:.1%}".format(
+                result["tracked_mpjpe"], float((choice == 0).mean()), float((choice < 0).mean())))
     return result
 
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -109,6 +109,8 @@ SIGNATURES = {
     "se_scene_free_mask_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _vp]),
     "se_softargmax3d_masked_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "se_softargmax3d_masked_scratch_elems": (_ll, [_i]),
+    "se_joint_modes_scratch_bytes": (_ll, [_i, _i, _i]),
+    "se_joint_modes_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -1183,6 +1185,48 @@ def softargmax3d_masked(prob, coord, free, out, peak_index, rows, rows_per_frame
     _check(load().se_softargmax3d_masked_f32(_ptr(prob), _ptr(coord), _ptr(free), _ptr(out), _ptr(peak_index), _ptr(scratch), rows,
                                              rows_per_frame, voxels, _stream()), "se_softargmax3d_masked_f32")
     return out, peak_index
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Multi-hypothesis joints (csrc/joint_modes.hip; sceneego_amd/op.py and VoxelNetwork_depth.joint_modes drive it)
+MODES_SLOTS = 8            # p_peak, mass, mom_x mom_y mom_z, peak coordinate x y z (include/sceneego_hip.h)
+MODES_MAX_K, MODES_MAX_RADIUS = 16, 3
+
+
+def joint_modes_scratch_bytes(rows, grid, k) -> int:
+    return int(load().se_joint_modes_scratch_bytes(int(rows), int(grid), int(k)))
+
+
+def joint_modes(prob, coord, modes, index, count, total, rows, voxels, grid, k, radius, min_prob, scratch=None):
+    """se_joint_modes_f32: the ``k`` strongest local maxima of every row of ``prob`` [rows, voxels] (voxels = grid^3) into ``modes``
+    [rows, k, 8] float32, ``index`` [rows, k] int32, ``count`` / ``total`` [rows] int32 (the header states the definition).
+    ``scratch``: an optional uint8 workspace of at least ``joint_modes_scratch_bytes(rows, grid, k)`` bytes.  Every argument is checked
+    here and a bad one raises HipExtensionError before anything is launched: the kernel trusts the sizes it is given."""
+    what = "joint_modes"
+    rows, voxels, grid, k, radius, min_prob = int(rows), int(voxels), int(grid), int(k), int(radius), float(min_prob)
+    if rows <= 0 or rows > 65535 or grid < 2 or voxels != grid ** 3 or voxels % 4:
+        raise HipExtensionError(f"{what}: rows = {rows} (1..65535), grid = {grid} (>= 2), voxels = {voxels} (grid^3, a multiple of 4) "
+                                "expected")
+    if not 1 <= k <= MODES_MAX_K or not 0 <= radius <= MODES_MAX_RADIUS:
+        raise HipExtensionError(f"{what}: k = {k} (1..{MODES_MAX_K}) and radius = {radius} (0..{MODES_MAX_RADIUS}) expected")
+    if not min_prob >= 0.0:
+        raise HipExtensionError(f"{what}: min_prob = {min_prob} must be >= 0 and not NaN")
+    named = (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
+             ("modes", modes, torch.float32, rows * k * MODES_SLOTS), ("index", index, torch.int32, rows * k),
+             ("count", count, torch.int32, rows), ("total", total, torch.int32, rows))
+    if scratch is not None:
+        named += (("scratch", scratch, torch.uint8, None),)
+    _sc_check(what, named, prob.device if isinstance(prob, torch.Tensor) and prob.is_cuda else None)
+    need = joint_modes_scratch_bytes(rows, grid, k)
+    if need <= 0:
+        raise HipExtensionError(f"{what}: grid = {grid} is not supported")
+    if scratch is None:
+        scratch = torch.empty(need, device=prob.device, dtype=torch.uint8)
+    elif scratch.numel() < need:
+        raise HipExtensionError(f"{what}: scratch has {scratch.numel()} bytes, needs {need}")
+    _check(load().se_joint_modes_f32(_ptr(prob), _ptr(coord), _ptr(modes), _ptr(index), _ptr(count), _ptr(total), _ptr(scratch),
+                                     scratch.numel(), rows, voxels, grid, k, radius, min_prob, _stream()), "se_joint_modes_f32")
+    return modes, index, count, total
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

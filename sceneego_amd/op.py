@@ -344,3 +344,68 @@ def scene_constraint_to_numpy(result):
     --constrain_output write."""
     host = {k: result[k].cpu().numpy() for k in CONSTRAINT_KEYS}
     return [{k: host[k][b].copy() for k in CONSTRAINT_KEYS} for b in range(host["free_mass"].shape[0])]
+
+
+# ----------------------------------------------------------------------------------------------
+# multi-hypothesis joints (csrc/joint_modes.hip; no counterpart in the reference)
+# ----------------------------------------------------------------------------------------------
+MODES_KEYS = ("coord", "peak_coord", "peak_prob", "mass", "index", "count", "total", "valid")
+
+
+def joint_modes(volumes, coord_volumes, k=4, radius=2, min_prob=0.0, min_rel=0.02, scratch=None):
+    """Where the peaks of each joint's distribution are and how much probability each holds (``se_joint_modes_f32``; one pass over
+    the volumes on the device).  ``volumes`` [B,J,G,G,G] float32 softmaxed, as ``integrate_tensor_3d_with_coordinates`` returns them;
+    ``coord_volumes`` [>=1,G,G,G,3] (sample 0 is used).  A mode is a voxel with p > 0 and p >= ``min_prob`` whose key (p, -index) is
+    greater than that of each of its up to 26 neighbours; the ``k`` (1..16) strongest are returned, strongest first, each with the sums
+    over its window of ``radius`` (0..3) voxels each way, clipped to the grid.  Returns a dict of device tensors (``MODES_KEYS``):
+
+      ``coord``      [B,J,K,3]  the window's centroid sum p c / sum p (float32 division): the sub-voxel position of the mode; NaN
+                                where the record is unfilled.  With ``radius`` 0 the window is the mode's voxel: its centre is returned
+      ``peak_coord`` [B,J,K,3]  the mode voxel's centre (NaN where unfilled)
+      ``peak_prob``  [B,J,K]    its probability (0 where unfilled)
+      ``mass``       [B,J,K]    the probability inside the window (0 where unfilled); windows of close modes overlap
+      ``index``      [B,J,K]    int32 flat voxel index (-1 where unfilled)
+      ``count``      [B,J]      int32, the number of filled records, min(K, total)
+      ``total``      [B,J]      int32, the number of modes in the volume, uncapped: how multi-modal it is
+      ``valid``      [B,J,K]    bool: the record is filled and peak_prob >= ``min_rel`` * peak_prob of mode 0
+
+    A (sample, joint) whose volume holds a NaN gets NaN in every float entry, index -1, count = total = -1 and no valid mode.
+    ``scratch``: an optional uint8 workspace of at least ``_lib.joint_modes_scratch_bytes(B * J, G, k)`` bytes."""
+    _lib.require_hip(volumes)
+    if volumes.dim() != 5 or volumes.dtype != torch.float32 or not volumes.shape[2] == volumes.shape[3] == volumes.shape[4]:
+        raise _lib.HipExtensionError("joint_modes: volumes must be [B,J,G,G,G] float32, got %s %s"
+                                     % (tuple(volumes.shape), volumes.dtype))
+    B, J, G = int(volumes.shape[0]), int(volumes.shape[1]), int(volumes.shape[2])
+    if tuple(coord_volumes.shape[1:]) != (G, G, G, 3) or coord_volumes.shape[0] < 1:
+        raise _lib.HipExtensionError("joint_modes: coord_volumes %s does not match volumes %s"
+                                     % (tuple(coord_volumes.shape), tuple(volumes.shape)))
+    coord = coord_volumes[0].to(device=volumes.device, dtype=torch.float32).contiguous()
+    return _joint_modes_flat(volumes.contiguous(), coord, B, J, G, k, radius, min_prob, min_rel, scratch)
+
+
+def _joint_modes_flat(vol, coord, B, J, G, k, radius, min_prob, min_rel, scratch):
+    rows, k = B * J, int(k)
+    if not 1 <= k <= _lib.MODES_MAX_K:
+        raise _lib.HipExtensionError(f"joint_modes: k = {k} (1..{_lib.MODES_MAX_K}) expected")
+    modes = torch.empty((rows, k, _lib.MODES_SLOTS), device=vol.device, dtype=torch.float32)
+    index = torch.empty((rows, k), device=vol.device, dtype=torch.int32)
+    count = torch.empty((rows,), device=vol.device, dtype=torch.int32)
+    total = torch.empty((rows,), device=vol.device, dtype=torch.int32)
+    _lib.joint_modes(vol, coord, modes, index, count, total, rows, G ** 3, G, k, radius, min_prob, scratch=scratch)
+    m = modes.view(B, J, k, _lib.MODES_SLOTS)
+    index = index.view(B, J, k)
+    peak, mass = m[..., 0], m[..., 1]
+    filled = index >= 0
+    nan = torch.full((), float("nan"), device=vol.device, dtype=torch.float32)
+    # radius 0: the window is the mode's own voxel and its centroid that voxel's centre; fl(fl(p c) / p) would only add rounding to it
+    centroid = torch.where(filled[..., None], m[..., 5:8] if int(radius) == 0 else m[..., 2:5] / mass[..., None], nan)
+    valid = filled & (peak >= float(min_rel) * peak[..., :1])
+    return {"coord": centroid, "peak_coord": m[..., 5:8], "peak_prob": peak, "mass": mass, "index": index,
+            "count": count.view(B, J), "total": total.view(B, J), "valid": valid}
+
+
+def joint_modes_to_numpy(result):
+    """The dict of ``joint_modes`` / ``VoxelNetwork_depth.joint_modes`` as a list of per-frame dicts of numpy arrays (the keys without
+    the batch dimension): what demo.py --modes and run_sequence.py --modes_output write."""
+    host = {k: result[k].cpu().numpy() for k in MODES_KEYS}
+    return [{k: host[k][b].copy() for k in MODES_KEYS} for b in range(host["mass"].shape[0])]

@@ -116,6 +116,7 @@ class VoxelNetwork_depth(nn.Module):
         self._xbuf = {}
         self._stats_ws = {}
         self._scene_ws = {}
+        self._modes_ws = {}
         # V2V storage type: "fp32" (parity path, default) or "bf16" (BASELINE config 3: bf16 activations/weights,
         # float32 accumulation; joints differ from the float32 reference by more than 1e-3)
         self.v2v_dtype = torch.bfloat16 if str(config.model.get("v2v_dtype", "fp32")).lower() in ("bf16", "bfloat16") \
@@ -152,6 +153,7 @@ class VoxelNetwork_depth(nn.Module):
         self._xbuf = {}
         self._stats_ws = {}
         self._scene_ws = {}
+        self._modes_ws = {}
 
     def _load_from_state_dict(self, *a, **k):
         super()._load_from_state_dict(*a, **k)
@@ -450,6 +452,38 @@ class VoxelNetwork_depth(nn.Module):
         out = op._constrained_joints_flat(volumes.contiguous(), coord, free, joints.contiguous().float(), B, J, N, scratch)
         out["free"] = free.view(B, G, G, G)
         return out
+
+    @torch.no_grad()
+    def joint_modes(self, volumes, k=4, radius=2, min_prob=0.0, min_rel=0.02):
+        """The ``k`` strongest modes of every joint's softmaxed volume [B,J,G,G,G]: where the peaks are, how much probability each
+        holds within ``radius`` voxels and the sub-voxel centroid of that window: ``op.joint_modes`` with the module's own
+        ``coord_volumes`` (the dict of device tensors described there: coord, peak_coord, peak_prob, mass, index, count, total,
+        valid).  One pass over the volumes on the current stream; the workspace is cached per (device, rows, k).  ``forward()`` itself
+        is unchanged: pass the volumes it returned.  ``sceneego_amd.track.select_modes`` picks one mode per joint over a sequence.
+
+        Under ``enable_graphs(True)`` the volumes are the graph's STATIC buffer, overwritten by the next replay: call this before the
+        next ``forward()`` (the call is queued on the current stream, so stream order is enough).
+
+        Raises ValueError when ``config.model.volume_softmax`` is false: the ReLU volumes are not a distribution."""
+        if not self.volume_softmax:
+            raise ValueError("joint_modes needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        _lib.require_hip(volumes)
+        G = self.volume_size
+        if volumes.dim() != 5 or tuple(volumes.shape[2:]) != (G, G, G) or volumes.dtype != torch.float32:
+            raise _lib.HipExtensionError("joint_modes: volumes must be [B,J,%d,%d,%d] float32, got %s %s"
+                                         % (G, G, G, tuple(volumes.shape), volumes.dtype))
+        B, J, k = int(volumes.shape[0]), int(volumes.shape[1]), int(k)
+        dev = volumes.device
+        # the module's own grid, whatever tables the last forward was given (they are keyed on its arguments)
+        coord = self._modes_ws.get((str(dev), "coord"))
+        if coord is None:
+            coord = self._modes_ws[(str(dev), "coord")] = \
+                self.coord_volumes[0].reshape(G * G * G, 3).to(device=dev, dtype=torch.float32).contiguous()
+        key = (str(dev), B * J, k)
+        ws = self._modes_ws.get(key)
+        if ws is None and 1 <= k <= _lib.MODES_MAX_K:
+            ws = self._modes_ws[key] = torch.empty(_lib.joint_modes_scratch_bytes(B * J, G, k), device=dev, dtype=torch.uint8)
+        return op._joint_modes_flat(volumes.contiguous(), coord, B, J, G, k, radius, min_prob, min_rel, ws)
 
     def _voxelise(self, x, planar3, fast_occ, prog, scene_volumes, depth_map_batch, B, G, N, C, dev, planar1=False):
         """Occupancy into the V2V input buffer ``x`` (reference ``:246-262``)."""
