@@ -313,14 +313,19 @@ __global__ __launch_bounds__(256) void maxpool2_bf16_kernel(const unsigned short
 // fused tail: 1x1x1 32->32 (+ReLU), 32->32 (+ReLU), 32->cout3 (<=16) -> float32 planar logits.  One k step per layer; the D
 // fragments of a tile pair ARE the next layer's B fragment (channels 8g..8g+7), so the chain stays in registers.
 // ------------------------------------------------------------------------------------------------
+// ReLU of the hidden layers.  NOT fmaxf: fmaxf(NaN, 0) = 0 would turn a NaN voxel of this launch's input into an ordinary logit, and the
+// soft-argmax behind this kernel would return plausible joints for it; torch's relu (reference network/v2v.py:17) keeps the NaN, and so
+// does this.  (The convolution epilogues in bf16_common.h still use fmaxf: a NaN further up the program is flushed there.)
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+
 __device__ __forceinline__ u16x8 relu_pack(f32x4 lo, f32x4 hi, const float* __restrict__ bias, int g) {
     const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + 8 * g);
     const f32x4 b1 = *reinterpret_cast<const f32x4*>(bias + 8 * g + 4);
     u16x8 o;
-    o[0] = f2bf(fmaxf(lo.x + b0.x, 0.f)); o[1] = f2bf(fmaxf(lo.y + b0.y, 0.f));
-    o[2] = f2bf(fmaxf(lo.z + b0.z, 0.f)); o[3] = f2bf(fmaxf(lo.w + b0.w, 0.f));
-    o[4] = f2bf(fmaxf(hi.x + b1.x, 0.f)); o[5] = f2bf(fmaxf(hi.y + b1.y, 0.f));
-    o[6] = f2bf(fmaxf(hi.z + b1.z, 0.f)); o[7] = f2bf(fmaxf(hi.w + b1.w, 0.f));
+    o[0] = f2bf(relu_keep_nan(lo.x + b0.x)); o[1] = f2bf(relu_keep_nan(lo.y + b0.y));
+    o[2] = f2bf(relu_keep_nan(lo.z + b0.z)); o[3] = f2bf(relu_keep_nan(lo.w + b0.w));
+    o[4] = f2bf(relu_keep_nan(hi.x + b1.x)); o[5] = f2bf(relu_keep_nan(hi.y + b1.y));
+    o[6] = f2bf(relu_keep_nan(hi.z + b1.z)); o[7] = f2bf(relu_keep_nan(hi.w + b1.w));
     return o;
 }
 
