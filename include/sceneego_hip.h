@@ -643,6 +643,45 @@ int se_joint_modes_f32(const float* prob, const float* coord, float* modes, int*
                        long long scratch_bytes, int rows, int voxels, int G, int K, int radius, float min_prob, void* stream);
 long long se_joint_modes_scratch_bytes(int rows, int G, int K);
 
+/* Grid Bayes filter over the joint volumes of a sequence (no counterpart in the reference; sceneego_amd/volume_filter.py:
+ * VolumeFilter; VoxelNetwork_depth.volume_filter returns one).  A convention, not a calibrated model: the softmaxed volume is read as
+ * the likelihood of the frame, a truncated Gaussian step as the motion model and a uniform floor as the chance of a jump.  The beliefs
+ * have the shape and the meaning of the volumes.  tests/volume_filter_model.py restates the definition in float64.
+ *   prob       [frames][rows][voxels] float32 probabilities, as se_softargmax3d_f32 writes them in mode 1; a row is one joint of one
+ *              track, the frames are consecutive; voxels = G^3, flat index n = (i G + j) G + k
+ *   coord      [voxels][3] float32 voxel-centre coordinates
+ *   taps       [2 radius + 1] float32 on the DEVICE: w[d], d = -radius..radius, non-negative.  The caller computes them (float64
+ *              exp(-(d h)^2 / (2 sigma^2)), h the voxel edge, normalised to sum 1, rounded to float32; sigma = 0 or radius = 0: {1}).
+ *   state      [rows][voxels] float32.  In: the belief before the first frame of the call, read only for rows that have a prior.
+ *              Out: the belief after the last frame.
+ *   have_prior NULL (no row has a prior: the first call of a track) or int32 [rows] on the device: non-zero where `state` holds the
+ *              row's prior.  It is read, never written; after any call every row has a prior.
+ *   G in 2..128     radius in 0..min(16, G - 1)     floor in [0, 1]     rows in 1..65535     frames >= 1
+ * PREDICT    q = blur3(b): the separable convolution with w along k, then j, then i, zero-padded (probability that leaves the grid is
+ *            lost), then u = (1 - floor) q + floor / voxels.
+ * UPDATE     a = p u,  Z = sum a,  b' = a / Z  (float32 division).
+ * RESTART    a row restarts when it has no prior or when Z is not a finite number > 0.  Then b' = p, copied bit for bit whatever it
+ *            holds: a row whose p holds a NaN restarts at this frame and again at the next.  Other rows are unaffected.
+ *   belief_out NULL or [frames][rows][voxels] float32: b' of every frame
+ *   joints     [frames][rows][3] float32: sum_n b'_n coord_n (computed as (sum a c) / Z; on a restart sum p c)
+ *   evidence   [frames][rows] float32: Z, the predictive likelihood of the frame (1 / voxels is chance); NaN where the row had no
+ *              prior; on a Z restart the offending value
+ *   restarted  [frames][rows] int32: 1 where the row restarted
+ *   scratch    se_volume_filter_scratch_bytes(rows, G, radius) bytes of workspace, 4-byte aligned (16-byte for the fast finish pass);
+ *              0 for a shape out of range.  rows (G^3 + 8 G) floats.
+ * The frames are processed in order inside the call: three launches per frame on `stream` (k- and j-blur of one i-plane per
+ * workgroup in LDS; i-blur of one j-slab fused with the floor, the product and the partial sums; a finish pass that folds the partial
+ * sums, decides the restart and writes b').  No atomics; every sum is taken in an order fixed by the shape alone, at most 80
+ * sequential float32 additions on the longest path (volume_filter.hip states the order): bitwise identical from run to run and
+ * independent of how the frames of a sequence are cut into calls.  Allocates nothing (legal inside hipGraph capture).
+ * SE_ERR_BAD_ARG, with nothing launched: a null pointer other than belief_out / have_prior, a pointer that is not 4-byte aligned,
+ * frames < 1, rows outside 1..65535, G outside 2..128, voxels != G^3, radius outside 0..min(16, G - 1), floor outside [0, 1] or NaN,
+ * scratch_bytes below se_volume_filter_scratch_bytes(rows, G, radius).                                                              */
+int se_volume_filter_f32(const float* prob, const float* coord, const float* taps, float* state, float* belief_out, float* joints,
+                         float* evidence, int* restarted, void* scratch, long long scratch_bytes, int frames, int rows, int voxels,
+                         int G, int radius, float floor, const int* have_prior, void* stream);
+long long se_volume_filter_scratch_bytes(int rows, int G, int radius);
+
 /* Baseline JPEG encoder (no counterpart in the reference; sceneego_amd/jpeg_encode.py writes the file headers around it).
  *   frames    uint8 [batch][height][width][3] on the device, R, G, B (bgr = 0) or B, G, R (bgr = 1); any height, width in 1..65535
  *   quant_luma, quant_chroma   HOST pointers: unsigned short [64], natural order, every value in 1..255 (baseline tables)

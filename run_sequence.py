@@ -9,6 +9,8 @@
                            [--render_video out/seq.avi [--render_fps 25] [--render_view render|overlay|both] [--render_quality 90]]
                            [--scene_output out/no_body_diogo1.scene.pkl] [--constrain_output out/no_body_diogo1.constraint.pkl]
                            [--modes_output out/no_body_diogo1.modes.pkl [--modes_k 4] [--track_output out/tracked.pkl [--track_sigma 0.1]]]
+                           [--filter_output out/filtered.pkl [--filter_info_output out/filter.pkl] [--filter_sigma 0.1]
+                            [--filter_radius R] [--filter_floor 1e-3]] [--render_volumes filtered]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -36,6 +38,13 @@ every joint's volume with their mass and sub-voxel centroid), taken per batch on
 a pickle in the format of ``--output`` whose joints are one mode per joint and frame, picked over the whole sequence by
 ``sceneego_amd.track.select_modes`` (``--track_sigma`` metres per frame; the soft-argmax joint where a frame has no valid mode), and
 prints its MPJPE beside the soft-argmax's: mass as likelihood and a Gaussian step are a convention, not calibrated.
+``--filter_output`` writes a pickle in the format of ``--output`` whose joints are those of a grid Bayes filter run over the volumes of
+the sequence on the device (``VoxelNetwork_depth.volume_filter``, ``sceneego_amd/volume_filter.py``: the whole [15,G,G,G] belief is
+blurred by a Gaussian step of ``--filter_sigma`` metres truncated at ``--filter_radius`` voxels, mixed with a uniform floor
+``--filter_floor`` and multiplied by the next frame's volumes), once per batch on the stream the batch ran on and in frame order
+across the pipelined streams; ``--filter_info_output`` adds the per-frame dicts (joints, evidence, restarted, shift) and
+``--render_volumes filtered`` draws the beliefs instead of the raw volumes.  It prints its MPJPE beside the soft-argmax's: the volume
+as likelihood, the Gaussian step and the floor are a convention, not calibrated.
 """
 import argparse
 import json
@@ -216,7 +225,7 @@ class SequenceRunner:
     @torch.no_grad()
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
-            volume_joints=None, constrain=False, modes=0):
+            volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -224,14 +233,21 @@ class SequenceRunner:
         ``<img_name>.volumes.render.*`` / ``.volumes.overlay.*`` (the joint probability volumes of ``volume_joints``, default all, drawn
         over the pair), and the video shows those views.  ``constrain``: the per-frame scene-constraint dicts are appended after
         those, and with ``scene`` the scene checks of the constrained joints after them.  ``modes`` = k > 0: the per-frame joint-mode
-        dicts (``VoxelNetwork_depth.joint_modes(k=modes)``) are appended last."""
+        dicts (``VoxelNetwork_depth.joint_modes(k=modes)``) are appended after those.  ``filter``: a dict of ``sigma`` / ``radius`` /
+        ``floor`` for ``VoxelNetwork_depth.volume_filter``: the whole sequence is one track, filtered batch by batch in frame order on
+        the stream each batch ran on, and the per-frame filter dicts are appended last; ``render_filtered`` (with ``render_volumes``)
+        draws its beliefs instead of the raw volumes."""
         from sceneego_amd.jpeg_device import JpegFile
-        from sceneego_amd.op import joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy
+        from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
+                                     volume_filter_to_numpy)
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
         preds, frame_stats, frame_scene, pending = [], [], [], []
-        frame_constraint, frame_scene_constrained, frame_modes = [], [], []
+        frame_constraint, frame_scene_constrained, frame_modes, frame_filter = [], [], [], []
+        if render_filtered and (filter is None or not render_volumes):
+            raise ValueError("render_filtered needs filter and render_volumes")
+        vf = self.net.volume_filter(**filter) if filter is not None else None
 
         rendering = render_dir is not None or render_video is not None
         if rendering:
@@ -247,7 +263,7 @@ class SequenceRunner:
 
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done, job, sc, con, md = pending.pop(0)
+                kp, st, done, job, sc, con, md, fr = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 kp_host = kp.cpu().numpy()
@@ -262,6 +278,8 @@ class SequenceRunner:
                         frame_scene_constrained.extend(scene_check_to_numpy(con[1]))
                 if md is not None:
                     frame_modes.extend(joint_modes_to_numpy(md))
+                if fr is not None:
+                    frame_filter.extend(volume_filter_to_numpy(fr))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -286,15 +304,20 @@ class SequenceRunner:
                     if constrain:
                         c = self.net.constrain_to_scene(vol, kp, depth)
                         con = (c, self._scene().check(depth, c["joints"]) if scene else None)
+                    fr = None
+                    if vf is not None:                                    # before the next forward overwrites the volumes
+                        fr = vf.step(vol, joints=kp, return_beliefs=render_filtered and job is not None)
+                        if "beliefs" in fr:
+                            job = job[:-1] + (fr["beliefs"],)
                     pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
                                     self._scene().check(depth, kp) if scene else None, con,
-                                    self.net.joint_modes(vol, k=modes) if modes else None))
+                                    self.net.joint_modes(vol, k=modes) if modes else None, fr))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
-                    st = sc = con = md = None
-                    if stats or scene or constrain or modes:
+                    st = sc = con = md = fr = None
+                    if stats or scene or constrain or modes or vf is not None:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
@@ -307,9 +330,14 @@ class SequenceRunner:
                                 con = (c, self._scene(stream.cuda_stream).check(depth, c["joints"]) if scene else None)
                             if modes:
                                 md = net.joint_modes(vol, k=modes)
+                            if vf is not None:
+                                # one filter for all slots: its own event chain makes this stream wait for the step of the batch before
+                                fr = vf.step(vol, joints=kp, return_beliefs=render_filtered and job is not None, stream=stream)
+                                if "beliefs" in fr:
+                                    job = job[:-1] + (fr["beliefs"],)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done, job, sc, con, md))
+                    pending.append((kp, st, done, job, sc, con, md, fr))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             try:
                 drain(0)
@@ -317,11 +345,11 @@ class SequenceRunner:
                 if self.video is not None:
                     self.video.close()
                     self.video = None
-        if not (stats or scene or constrain or modes):
+        if not (stats or scene or constrain or modes or vf is not None):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
             + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
-            + ((frame_modes,) if modes else ())
+            + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ())
 
 
 def _size(text):
@@ -375,6 +403,14 @@ def build_parser():
     ap.add_argument("--track_output", default=None, help="with --modes_output: pickle in the format of --output holding one mode per "
                     "joint and frame, picked over the sequence (sceneego_amd/track.py: a convention, not calibrated)")
     ap.add_argument("--track_sigma", type=float, default=0.1, help="with --track_output: metres a joint is assumed to move per frame")
+    ap.add_argument("--filter_output", default=None, help="pickle in the format of --output holding the joints of a grid Bayes filter "
+                    "over the sequence's volumes (sceneego_amd/volume_filter.py: a convention, not calibrated)")
+    ap.add_argument("--filter_info_output", default=None, help="pickle of the per-frame filter dicts (list of dicts of numpy arrays: "
+                    "joints, evidence, restarted, shift)")
+    ap.add_argument("--filter_sigma", type=float, default=0.1, help="the filter's motion model: metres a joint is assumed to move per frame")
+    ap.add_argument("--filter_radius", type=int, default=None, help="voxels the Gaussian step is truncated at, 0..16 "
+                    "(default: min(16, G - 1, ceil(3 sigma / voxel edge)))")
+    ap.add_argument("--filter_floor", type=float, default=1e-3, help="the filter's uniform floor in [0, 1]: the chance of a jump")
     ap.add_argument("--render_format", default="png", choices=("png", "jpg"),
                     help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG files encoded on the device)")
     ap.add_argument("--render_video", default=None, help="write the picked frames as one Motion-JPEG AVI (4:2:0, encoded on the device)")
@@ -385,20 +421,31 @@ def build_parser():
     ap.add_argument("--render_size", type=_size, default=None, help="HxW of the third-person view (default: 720x960)")
     ap.add_argument("--render_volumes", default="false",
                     help="true (with --render_dir / --render_video): also write <img_name>.volumes.render.* and .volumes.overlay.* (the "
-                         "joint probability volumes drawn over the pair); the video shows the volume views")
+                         "joint probability volumes drawn over the pair); the video shows the volume views.  filtered: the same with the "
+                         "beliefs of the grid Bayes filter (--filter_sigma, --filter_radius, --filter_floor) instead of the raw volumes")
     ap.add_argument("--volume_joints", default=None, help="with --render_volumes true: the joints to draw, e.g. 9,10,13,14 (default: all)")
     return ap
 
 
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
-    if args.render_volumes.lower() not in ("true", "false"):
-        raise SystemExit("--render_volumes must be true or false")
-    args.render_volumes = args.render_volumes.lower() == "true"
+    if args.render_volumes.lower() not in ("true", "false", "filtered"):
+        raise SystemExit("--render_volumes must be true, false or filtered")
+    args.render_filtered = args.render_volumes.lower() == "filtered"
+    args.render_volumes = args.render_volumes.lower() in ("true", "filtered")
     if args.render_volumes and args.render_dir is None and args.render_video is None:
-        raise SystemExit("--render_volumes true needs --render_dir or --render_video")
+        raise SystemExit("--render_volumes true / filtered needs --render_dir or --render_video")
     if args.volume_joints is not None and not args.render_volumes:
-        raise SystemExit("--volume_joints needs --render_volumes true")
+        raise SystemExit("--volume_joints needs --render_volumes true or filtered")
+    if not args.filter_sigma >= 0 or args.filter_sigma == float("inf"):
+        raise SystemExit("--filter_sigma must be a finite number >= 0")
+    if not 0.0 <= args.filter_floor <= 1.0:
+        raise SystemExit("--filter_floor must lie in [0, 1]")
+    if args.filter_radius is not None and not 0 <= args.filter_radius <= 16:
+        raise SystemExit("--filter_radius must be in 0..16")
+    args.filter = None
+    if args.filter_output is not None or args.filter_info_output is not None or args.render_filtered:
+        args.filter = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor}
     if args.track_output is not None and args.modes_output is None:
         raise SystemExit("--track_output needs --modes_output")
     if not 1 <= args.modes_k <= 16:
@@ -430,18 +477,21 @@ def main(argv=None):
     want_scene = args.scene_output is not None
     want_constraint = args.constrain_output is not None
     want_modes = args.modes_output is not None
+    want_filter = args.filter is not None
     preds = runner.run(images, depths, config.test.batch_size, stats=want_stats, render_dir=args.render_dir,
                        render_every=args.render_every, scene=want_scene, render_format=args.render_format,
                        render_video=args.render_video, render_fps=args.render_fps, render_view=args.render_view,
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
-                       volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0)
-    if want_stats or want_scene or want_constraint or want_modes:
+                       volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
+                       filter=args.filter, render_filtered=args.render_filtered)
+    if want_stats or want_scene or want_constraint or want_modes or want_filter:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
         frame_scene = extra.pop(0) if want_scene else None
         frame_constraint = extra.pop(0) if want_constraint else None
         frame_scene_constrained = extra.pop(0) if want_constraint and want_scene else None
         frame_modes = extra.pop(0) if want_modes else None
+        frame_filter = extra.pop(0) if want_filter else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -492,6 +542,18 @@ def main(argv=None):
             result["tracked_mpjpe"] = M.mpjpe(joints.astype(np.float64), gt)
             print("tracked modes (a convention, not calibrated): mpjpe: {}, mode 0 in {:.1%} of the joints, fallback in {:.1%}".format(
                 result["tracked_mpjpe"], float((choice == 0).mean()), float((choice < 0).mean())))
+    if want_filter:
+        filtered = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_filter]
+        for path, obj in ((args.filter_output, filtered), (args.filter_info_output, frame_filter)):
+            if path is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "wb") as f:
+                    pickle.dump(obj, f)
+        result["filtered"], result["filter"] = filtered, frame_filter
+        result["filtered_mpjpe"] = M.mpjpe(np.stack(filtered).astype(np.float64), gt)
+        print("filtered volumes (a convention, not calibrated): mpjpe: {}, mean shift {:.4f} m, {} restarts after the first frame".format(
+            result["filtered_mpjpe"], float(np.mean([fr["shift"] for fr in frame_filter])),
+            int(sum(fr["restarted"].sum() for fr in frame_filter[1:]))))
     return result
 
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -111,6 +111,8 @@ SIGNATURES = {
     "se_softargmax3d_masked_scratch_elems": (_ll, [_i]),
     "se_joint_modes_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_joint_modes_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
+    "se_volume_filter_scratch_bytes": (_ll, [_i, _i, _i]),
+    "se_volume_filter_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -1227,6 +1229,59 @@ def joint_modes(prob, coord, modes, index, count, total, rows, voxels, grid, k, 
     _check(load().se_joint_modes_f32(_ptr(prob), _ptr(coord), _ptr(modes), _ptr(index), _ptr(count), _ptr(total), _ptr(scratch),
                                      scratch.numel(), rows, voxels, grid, k, radius, min_prob, _stream()), "se_joint_modes_f32")
     return modes, index, count, total
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Grid Bayes filter over the joint volumes of a sequence (csrc/volume_filter.hip; sceneego_amd/volume_filter.py drives it)
+FILTER_MAX_GRID, FILTER_MAX_RADIUS = 128, 16
+FILTER_CHAIN = 80          # sequential float32 additions on the longest path of Z and of the joint sums (csrc/volume_filter.hip: L)
+
+
+def volume_filter_scratch_bytes(rows, grid, radius) -> int:
+    return int(load().se_volume_filter_scratch_bytes(int(rows), int(grid), int(radius)))
+
+
+def volume_filter(prob, coord, taps, state, belief_out, joints, evidence, restarted, frames, rows, voxels, grid, radius, floor,
+                  have_prior=None, scratch=None):
+    """se_volume_filter_f32: ``frames`` consecutive steps of the grid Bayes filter on ``prob`` [frames, rows, voxels] (voxels =
+    grid^3) from the belief in ``state`` [rows, voxels], which is updated in place (the header states the definition).  ``taps``
+    [2 radius + 1] float32 on the device; ``have_prior`` None (no row has a prior) or int32 [rows]; ``belief_out`` None or [frames,
+    rows, voxels]; ``joints`` [frames, rows, 3], ``evidence`` [frames, rows] float32 and ``restarted`` [frames, rows] int32 are written.
+    ``scratch``: an optional uint8 workspace of at least ``volume_filter_scratch_bytes(rows, grid, radius)`` bytes.  Every argument
+    is checked here and a bad one raises HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
+    what = "volume_filter"
+    frames, rows, voxels, grid, radius, floor = int(frames), int(rows), int(voxels), int(grid), int(radius), float(floor)
+    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
+                                f"voxels = {voxels} (grid^3) expected")
+    if not 0 <= radius <= min(FILTER_MAX_RADIUS, grid - 1):
+        raise HipExtensionError(f"{what}: radius = {radius} (0..{min(FILTER_MAX_RADIUS, grid - 1)}) expected")
+    if not 0.0 <= floor <= 1.0:
+        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    named = (("prob", prob, torch.float32, frames * rows * voxels), ("coord", coord, torch.float32, voxels * 3),
+             ("taps", taps, torch.float32, 2 * radius + 1), ("state", state, torch.float32, rows * voxels),
+             ("joints", joints, torch.float32, frames * rows * 3), ("evidence", evidence, torch.float32, frames * rows),
+             ("restarted", restarted, torch.int32, frames * rows))
+    if belief_out is not None:
+        named += (("belief_out", belief_out, torch.float32, frames * rows * voxels),)
+    if have_prior is not None:
+        named += (("have_prior", have_prior, torch.int32, rows),)
+    if scratch is not None:
+        named += (("scratch", scratch, torch.uint8, None),)
+    _sc_check(what, named, prob.device if isinstance(prob, torch.Tensor) and prob.is_cuda else None)
+    if belief_out is not None and belief_out.data_ptr() in (prob.data_ptr(), state.data_ptr()):
+        raise HipExtensionError(f"{what}: belief_out must not alias prob or state")
+    need = volume_filter_scratch_bytes(rows, grid, radius)
+    if need <= 0:
+        raise HipExtensionError(f"{what}: rows = {rows}, grid = {grid}, radius = {radius} is not supported")
+    if scratch is None:
+        scratch = torch.empty(need, device=prob.device, dtype=torch.uint8)
+    elif scratch.numel() < need:
+        raise HipExtensionError(f"{what}: scratch has {scratch.numel()} bytes, needs {need}")
+    _check(load().se_volume_filter_f32(_ptr(prob), _ptr(coord), _ptr(taps), _ptr(state), _ptr(belief_out), _ptr(joints),
+                                       _ptr(evidence), _ptr(restarted), _ptr(scratch), scratch.numel(), frames, rows, voxels, grid,
+                                       radius, floor, _ptr(have_prior), _stream()), "se_volume_filter_f32")
+    return joints, evidence, restarted
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,255 @@
+// Grid Bayes filter over the softmaxed joint volumes of a sequence (sceneego_amd/volume_filter.py: VolumeFilter;
+// VoxelNetwork_depth.volume_filter returns one).  No counterpart in the reference.  include/sceneego_hip.h states the definition;
+// tests/volume_filter_model.py restates it in float64.
+//
+// Per frame and row (one joint of one track), with the belief b of the frame before in `state`:
+//     q = blur3(b)                    separable, taps w[-R..R], along k, then j, then i; zero-padded
+//     u = (1 - floor) q + floor / N
+//     a = p u,  Z = sum a,  b' = a / Z          or, without a prior or with a Z that is not a finite number > 0:  b' = p (restart)
+// The frames of a call run one after the other on the stream: three launches per frame.
+//   vf_blur_kj_kernel   grid (G, rows), block 256: one i-plane [G j][G k] of b staged in LDS, blurred along k into a second LDS
+//                       plane, blurred along j from there and written to q (scratch).  2 G^2 floats of LDS: 32 KB at 64^3, 128 KB at 128^3.
+//   vf_update_kernel    grid (G, rows), block 256: the slab [G i][G k] of q at one j staged in LDS (G^2 floats), blurred along i, then the
+//                       floor and the product with p; a overwrites q in place (a workgroup writes only what it staged itself).  The
+//                       workgroup's sums Z, sum a c (3) and sum p c (3, the joint of a restart) go to one record of 8 floats.
+//   vf_finish_kernel    grid (chunks, rows), block 256: every workgroup folds the row's G records in the same fixed order (so all of them
+//                       hold the same Z, bit for bit), decides the restart and writes its share of b' = a / Z, or of the copy of p,
+//                       to `state` and `belief_out`; chunk 0 also writes joints, evidence and restarted.
+// A thread owns column k of the staged plane and every (256 / W)-th row of it, W the power of two >= G: any G in 2..128, no vector access
+// in the two plane kernels (rows of G floats are read whole by neighbouring lanes).  The finish pass moves 16 bytes per lane when
+// voxels is a multiple of 4 and one float otherwise.
+//
+// BYTE MODEL per frame, row and voxel (float32): blur_kj reads b and writes q (8 B); update reads q and p and writes a (12 B; the
+// coordinates, 12 B per voxel, are shared by all rows and stay in L2); finish reads a and writes b' (8 B): 28 B, and 4 B more when
+// the beliefs are returned.  The records are G x 32 B per row.  At 64^3 and 15 rows that is 110 MB per frame over a working set
+// (b, q, p: 47 MB) that does not fit the L2 but largely fits the Infinity Cache.  A restarted row reads p instead of a in the finish pass.
+//
+// SUMMATION ORDER.  No atomics.  A thread adds its voxels in ascending row order (G W / 256 <= 64 terms), the wave folds by a butterfly
+// (6), the four waves as (0 + 1) + (2 + 3) (2); the finish pass gives lane l the records l and l + 64 (2) and folds the lanes by a
+// butterfly (6).  L = 64 + 6 + 2 + 2 + 6 = 80 sequential float32 additions on the longest path of Z and of the joint sums
+// (SE_VF_CHAIN; G = 128).  Every order depends on the shape alone: the results are bitwise identical from run to run, and since a frame
+// sees only `state` and its own p they do not depend on how the frames are cut into calls.
+#include <float.h>
+
+#include "common.h"
+
+#define SE_VF_THREADS 256
+#define SE_VF_MAX_G 128
+#define SE_VF_MAX_R 16
+#define SE_VF_PART 8              // Z, sum a c (x y z), sum p c (x y z), pad
+#define SE_VF_MAX_CHUNKS 64
+#define SE_VF_CHAIN 80            // L of the header comment
+
+namespace {
+
+__device__ __forceinline__ bool vf_has_prior(const int* __restrict__ have_prior, int prior_all, int row) {
+    return prior_all || (have_prior != nullptr && have_prior[row] != 0);
+}
+
+// grid (G, rows), block 256, dynamic LDS 2 G^2 floats
+__global__ __launch_bounds__(SE_VF_THREADS) void vf_blur_kj_kernel(const float* __restrict__ state, const float* __restrict__ taps,
+                                                                   const int* __restrict__ have_prior, int prior_all,
+                                                                   float* __restrict__ q, int G, int voxels, int R, int wshift) {
+    extern __shared__ __align__(16) float lds[];
+    __shared__ float w[2 * SE_VF_MAX_R + 1];
+    const int t = threadIdx.x, i = blockIdx.x, row = blockIdx.y;
+    if (!vf_has_prior(have_prior, prior_all, row)) return;          // uniform: the row restarts, q is not read
+    const int GG = G * G;
+    float* A = lds;
+    float* Bk = lds + GG;
+    const size_t base = (size_t)row * voxels + (size_t)i * GG;
+    for (int e = t; e < GG; e += SE_VF_THREADS) A[e] = state[base + e];
+    if (t <= 2 * R) w[t] = taps[t];
+    __syncthreads();
+    const int k = t & ((1 << wshift) - 1), jr = t >> wshift, RP = SE_VF_THREADS >> wshift;
+    if (k < G) {
+        const int lo = max(-R, -k), hi = min(R, G - 1 - k);         // the taps that stay inside the row
+        for (int j = jr; j < G; j += RP) {
+            const float* a = A + j * G + k;
+            float acc = 0.f;
+            for (int d = lo; d <= hi; ++d) acc = fmaf(w[d + R], a[d], acc);
+            Bk[j * G + k] = acc;
+        }
+    }
+    __syncthreads();
+    if (k < G) {
+        for (int j = jr; j < G; j += RP) {
+            const int lo = max(-R, -j), hi = min(R, G - 1 - j);
+            const float* b = Bk + j * G + k;
+            float acc = 0.f;
+            for (int d = lo; d <= hi; ++d) acc = fmaf(w[d + R], b[d * G], acc);
+            q[base + j * G + k] = acc;
+        }
+    }
+}
+
+// grid (G, rows), block 256, dynamic LDS G^2 floats
+__global__ __launch_bounds__(SE_VF_THREADS) void vf_update_kernel(const float* __restrict__ prob, const float* __restrict__ coord,
+                                                                  const float* __restrict__ taps, const int* __restrict__ have_prior,
+                                                                  int prior_all, float* __restrict__ q, float* __restrict__ part,
+                                                                  int G, int voxels, int R, int wshift, float keep, float uniform) {
+    extern __shared__ __align__(16) float lds[];
+    __shared__ float w[2 * SE_VF_MAX_R + 1];
+    __shared__ float sm[4][SE_VF_PART];
+    const int t = threadIdx.x, j = blockIdx.x, row = blockIdx.y;
+    const bool prior = vf_has_prior(have_prior, prior_all, row);    // uniform
+    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VF_THREADS >> wshift;
+    const size_t base = (size_t)row * voxels;
+    if (prior) {
+        if (k < G)
+            for (int i = ir; i < G; i += RP) lds[i * G + k] = q[base + ((size_t)i * G + j) * G + k];
+        if (t <= 2 * R) w[t] = taps[t];
+    }
+    __syncthreads();
+    float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};            // Z, sum a c, sum p c
+    if (k < G) {
+        for (int i = ir; i < G; i += RP) {
+            const size_t n = ((size_t)i * G + j) * G + k;
+            const float p = prob[base + n];
+            const float cx = coord[n * 3 + 0], cy = coord[n * 3 + 1], cz = coord[n * 3 + 2];
+            acc[4] += p * cx; acc[5] += p * cy; acc[6] += p * cz;
+            if (prior) {
+                const int lo = max(-R, -i), hi = min(R, G - 1 - i);
+                const float* s = lds + i * G + k;
+                float u = 0.f;
+                for (int d = lo; d <= hi; ++d) u = fmaf(w[d + R], s[d * G], u);
+                u = fmaf(keep, u, uniform);
+                const float a = p * u;
+                q[base + n] = a;                                    // staged by this workgroup, read by no other
+                acc[0] += a;
+                acc[1] += a * cx; acc[2] += a * cy; acc[3] += a * cz;
+            }
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < 7; ++x) acc[x] = wave_reduce_sum(acc[x]);
+    const int wid = t >> 6;
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int x = 0; x < 7; ++x) sm[wid][x] = acc[x];
+    }
+    __syncthreads();
+    if (t < 7) part[((size_t)row * G + j) * SE_VF_PART + t] = (sm[0][t] + sm[1][t]) + (sm[2][t] + sm[3][t]);
+}
+
+// grid (chunks, rows), block 256
+template <bool VEC>
+__global__ __launch_bounds__(SE_VF_THREADS) void vf_finish_kernel(const float* __restrict__ prob, const float* __restrict__ q,
+                                                                  const float* __restrict__ part, const int* __restrict__ have_prior,
+                                                                  int prior_all, float* __restrict__ state,
+                                                                  float* __restrict__ belief_out, float* __restrict__ joints,
+                                                                  float* __restrict__ evidence, int* __restrict__ restarted, int G,
+                                                                  int voxels) {
+    __shared__ float fin[SE_VF_PART];
+    const int t = threadIdx.x, row = blockIdx.y;
+    if (t < 64) {
+        float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int j = t; j < G; j += 64) {
+            const float* p = part + ((size_t)row * G + j) * SE_VF_PART;
+#pragma unroll
+            for (int x = 0; x < 7; ++x) acc[x] += p[x];
+        }
+#pragma unroll
+        for (int x = 0; x < 7; ++x) acc[x] = wave_reduce_sum(acc[x]);
+        if (t == 0) {
+#pragma unroll
+            for (int x = 0; x < 7; ++x) fin[x] = acc[x];
+        }
+    }
+    __syncthreads();
+    const bool prior = vf_has_prior(have_prior, prior_all, row);
+    const float Z = fin[0];
+    const bool restart = !prior || !(Z > 0.f && Z <= FLT_MAX);      // a NaN fails both comparisons
+    if (blockIdx.x == 0 && t == 0) {
+        float* o = joints + (size_t)row * 3;
+        if (restart) { o[0] = fin[4]; o[1] = fin[5]; o[2] = fin[6]; }
+        else { o[0] = fin[1] / Z; o[1] = fin[2] / Z; o[2] = fin[3] / Z; }
+        evidence[row] = prior ? Z : __int_as_float(0x7fc00000);
+        restarted[row] = restart ? 1 : 0;
+    }
+    const size_t base = (size_t)row * voxels;
+    const float* src = (restart ? prob : q) + base;                 // the copy of p is bit for bit
+    float* dst = state + base;
+    float* out = belief_out ? belief_out + base : nullptr;
+    for (int n = (blockIdx.x * SE_VF_THREADS + t) * 4; n < voxels; n += gridDim.x * SE_VF_THREADS * 4) {
+        if (VEC) {
+            f32x4 x = *reinterpret_cast<const f32x4*>(src + n);
+            if (!restart) { x.x = x.x / Z; x.y = x.y / Z; x.z = x.z / Z; x.w = x.w / Z; }
+            *reinterpret_cast<f32x4*>(dst + n) = x;
+            if (out) *reinterpret_cast<f32x4*>(out + n) = x;
+        } else {
+            for (int e = n; e < min(n + 4, voxels); ++e) {
+                float x = src[e];
+                if (!restart) x = x / Z;
+                dst[e] = x;
+                if (out) out[e] = x;
+            }
+        }
+    }
+}
+
+inline bool vf_shape_ok(int rows, int G, int R) {
+    return rows >= 1 && rows <= 65535 && G >= 2 && G <= SE_VF_MAX_G && R >= 0 && R <= SE_VF_MAX_R && R <= G - 1;
+}
+inline long long vf_q_elems(int rows, int G) { return (long long)rows * G * G * G; }
+
+}  // namespace
+
+extern "C" long long se_volume_filter_scratch_bytes(int rows, int G, int radius) {
+    if (!vf_shape_ok(rows, G, radius)) return 0;
+    return (vf_q_elems(rows, G) + (long long)rows * G * SE_VF_PART) * 4;
+}
+
+extern "C" int se_volume_filter_f32(const float* prob, const float* coord, const float* taps, float* state, float* belief_out,
+                                    float* joints, float* evidence, int* restarted, void* scratch, long long scratch_bytes,
+                                    int frames, int rows, int voxels, int G, int radius, float floor, const int* have_prior,
+                                    void* stream) {
+    if (!prob || !coord || !taps || !state || !joints || !evidence || !restarted || !scratch) return SE_ERR_BAD_ARG;
+    if (frames < 1 || !vf_shape_ok(rows, G, radius)) return SE_ERR_BAD_ARG;
+    if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
+    if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
+    const uintptr_t all = reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(coord) | reinterpret_cast<uintptr_t>(taps) |
+                          reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(belief_out) |
+                          reinterpret_cast<uintptr_t>(joints) | reinterpret_cast<uintptr_t>(evidence) |
+                          reinterpret_cast<uintptr_t>(restarted) | reinterpret_cast<uintptr_t>(scratch) |
+                          reinterpret_cast<uintptr_t>(have_prior);
+    if (all & 3) return SE_ERR_BAD_ARG;
+    if (scratch_bytes < se_volume_filter_scratch_bytes(rows, G, radius)) return SE_ERR_BAD_ARG;
+    hipStream_t s = se_stream(stream);
+    float* q = reinterpret_cast<float*>(scratch);
+    float* part = q + vf_q_elems(rows, G);
+    int wshift = 0;
+    while ((1 << wshift) < G) ++wshift;                                                   // W = 1 << wshift <= 128
+    const int plane_bytes = G * G * 4;
+    SE_ENSURE_LDS(vf_blur_kj_kernel, 2 * SE_VF_MAX_G * SE_VF_MAX_G * 4);
+    SE_ENSURE_LDS(vf_update_kernel, SE_VF_MAX_G * SE_VF_MAX_G * 4);
+    // 16-byte moves in the finish pass: whole quads per row and every base it touches aligned
+    const bool vec = (voxels & 3) == 0 && !((reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(state) |
+                                             reinterpret_cast<uintptr_t>(belief_out) | reinterpret_cast<uintptr_t>(scratch)) & 15);
+    const int chunks = min(SE_VF_MAX_CHUNKS, (voxels + SE_VF_THREADS * 4 - 1) / (SE_VF_THREADS * 4));
+    const float keep = 1.0f - floor, uniform = floor / (float)voxels;
+    const size_t frame_elems = (size_t)rows * voxels;
+    for (int f = 0; f < frames; ++f) {
+        const float* p = prob + f * frame_elems;
+        const int prior_all = f > 0;
+        if (prior_all || have_prior) {
+            hipLaunchKernelGGL(vf_blur_kj_kernel, dim3(G, rows), dim3(SE_VF_THREADS), 2 * plane_bytes, s, state, taps, have_prior,
+                               prior_all, q, G, voxels, radius, wshift);
+            SE_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(vf_update_kernel, dim3(G, rows), dim3(SE_VF_THREADS), plane_bytes, s, p, coord, taps, have_prior, prior_all,
+                           q, part, G, voxels, radius, wshift, keep, uniform);
+        SE_CHECK_LAUNCH();
+        float* bo = belief_out ? belief_out + f * frame_elems : nullptr;
+        if (vec)
+            hipLaunchKernelGGL(vf_finish_kernel<true>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, q, part, have_prior, prior_all,
+                               state, bo, joints + (size_t)f * rows * 3, evidence + (size_t)f * rows, restarted + (size_t)f * rows, G,
+                               voxels);
+        else
+            hipLaunchKernelGGL(vf_finish_kernel<false>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, q, part, have_prior,
+                               prior_all, state, bo, joints + (size_t)f * rows * 3, evidence + (size_t)f * rows,
+                               restarted + (size_t)f * rows, G, voxels);
+        SE_CHECK_LAUNCH();
+    }
+    return 0;
+}

@@ -409,3 +409,17 @@ def joint_modes_to_numpy(result):
     the batch dimension): what demo.py --modes and run_sequence.py --modes_output write."""
     host = {k: result[k].cpu().numpy() for k in MODES_KEYS}
     return [{k: host[k][b].copy() for k in MODES_KEYS} for b in range(host["mass"].shape[0])]
+
+
+# ----------------------------------------------------------------------------------------------
+# grid Bayes filter over a sequence (csrc/volume_filter.hip; sceneego_amd/volume_filter.py; no counterpart in the reference)
+# ----------------------------------------------------------------------------------------------
+FILTER_KEYS = ("joints", "evidence", "restarted")
+
+
+def volume_filter_to_numpy(result):
+    """The dict of ``VolumeFilter.step`` as a list of per-frame dicts of numpy arrays (the keys without the batch dimension and
+    without the ``beliefs``; ``shift`` when the step was given joints): what run_sequence.py --filter_info_output writes."""
+    keys = FILTER_KEYS + (("shift",) if "shift" in result else ())
+    host = {k: result[k].cpu().numpy() for k in keys}
+    return [{k: host[k][b].copy() for k in keys} for b in range(host["evidence"].shape[0])]

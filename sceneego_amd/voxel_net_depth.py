@@ -485,6 +485,25 @@ class VoxelNetwork_depth(nn.Module):
             ws = self._modes_ws[key] = torch.empty(_lib.joint_modes_scratch_bytes(B * J, G, k), device=dev, dtype=torch.uint8)
         return op._joint_modes_flat(volumes.contiguous(), coord, B, J, G, k, radius, min_prob, min_rel, ws)
 
+    def volume_filter(self, sigma=0.10, radius=None, floor=1e-3):
+        """A ``sceneego_amd.volume_filter.VolumeFilter`` bound to the module's own ``coord_volumes``, grid and cuboid side: a
+        recursive Bayes filter over the whole [J,G,G,G] grid for ONE track.  ``f = net.volume_filter(); f.step(volumes)`` per batch
+        of consecutive frames, with the volumes ``forward()`` returned, gives the filtered joints, the evidence of every frame and,
+        when asked for, the beliefs: tensors of the shape and meaning of the volumes, which ``joint_statistics``, ``joint_modes``,
+        ``constrain_to_scene`` and the volume renderer take unchanged.  ``sigma`` (metres a joint is assumed to move per frame),
+        ``radius`` (voxels; default min(16, G - 1, ceil(3 sigma / voxel edge))) and ``floor`` (the chance of a jump) are a
+        convention, not calibrated.  ``forward()`` itself is unchanged.
+
+        Under ``enable_graphs(True)`` the volumes are the graph's STATIC buffer, overwritten by the next replay: call ``step`` before
+        the next ``forward()`` (the call is queued on the current stream, so stream order is enough).
+
+        Raises ValueError when ``config.model.volume_softmax`` is false (the ReLU volumes are not a distribution) or a parameter is
+        out of range; nothing touches the device before the first ``step``."""
+        if not self.volume_softmax:
+            raise ValueError("volume_filter needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        from .volume_filter import VolumeFilter
+        return VolumeFilter(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor)
+
     def _voxelise(self, x, planar3, fast_occ, prog, scene_volumes, depth_map_batch, B, G, N, C, dev, planar1=False):
         """Occupancy into the V2V input buffer ``x`` (reference ``:246-262``)."""
         if planar1 and self.with_scene is not True:
