@@ -205,6 +205,39 @@ def _chk_f32(*ts):
 
 
 # ---------------------------------------------------------------------------------------------
+def _check_args(what, named, optional=(), device=None):
+    """Every entry (name, tensor, dtype, size) of ``named``, and every entry of ``optional`` whose tensor is not None, is a contiguous
+    tensor of that dtype on one HIP device (``device``, or the first entry's), else HipExtensionError naming the operator and the
+    argument: the kernels trust what they are given, so this runs before anything is launched.  ``size``: None (any), an int (the
+    number of elements) or a shape, in which None stands for any extent.  Returns the device."""
+    for name, t, dtype, size in tuple(named) + tuple(e for e in optional if e[1] is not None):
+        if not isinstance(t, torch.Tensor):
+            raise HipExtensionError(f"{what}: {name} is not a tensor")
+        if not t.is_cuda:
+            raise HipExtensionError(f"{what}: {name} is on {t.device}: the operator needs tensors on a HIP device (there is no CPU fallback)")
+        if t.dtype != dtype or not t.is_contiguous():
+            raise HipExtensionError(f"{what}: {name} is {t.dtype} (contiguous: {t.is_contiguous()}), expected contiguous {dtype}")
+        if isinstance(size, tuple):
+            if t.dim() != len(size) or any(want is not None and have != want for have, want in zip(t.shape, size)):
+                raise HipExtensionError(f"{what}: {name} has shape {tuple(t.shape)}, expected {size}")
+        elif size is not None and t.numel() != size:
+            raise HipExtensionError(f"{what}: {name} has {t.numel()} elements, expected {size}")
+        if device is None:
+            device = t.device
+        if t.device != device:
+            raise HipExtensionError(f"{what}: {name} is on {t.device}, expected {device}")
+    return device
+
+
+def _scratch(what, scratch, need, dtype, device):
+    """The optional workspace of an operator: allocated per call when None, else (type and device checked by _check_args) big enough."""
+    if scratch is None:
+        return torch.empty(need, device=device, dtype=dtype)
+    if scratch.numel() < need:
+        raise HipExtensionError(f"{what}: scratch has {scratch.numel()} elements of {dtype}, needs {need}")
+    return scratch
+
+
 def voxelize(depth, ray_tab, occ, batch, depth_h, depth_w, up, pad_x, volume_size, cuboid_side):
     require_hip(depth, ray_tab, occ)
     _chk_f32(depth, occ)
@@ -271,54 +304,47 @@ def preprocess_image_u8(img_u8, out, crop_x, mean3, std3):
 
 
 
-def exr_piz_scratch_bytes(chunk_desc, channel_desc) -> int:
-    """chunk_desc int64 [n, 16] and channel_desc int32 [files, 8] (HOST numpy arrays, include/sceneego_hip.h): fills the scratch
-    offset / record capacity columns of chunk_desc in place and returns the scratch bytes of se_exr_piz_decode_f32."""
+def _exr_scratch_bytes(codec, chunk_desc, channel_desc) -> int:
     import numpy as np
     assert chunk_desc.dtype == np.int64 and chunk_desc.flags.c_contiguous and chunk_desc.shape[1:] == (16,)
     assert channel_desc.dtype == np.int32 and channel_desc.flags.c_contiguous and channel_desc.shape[1:] == (8,)
-    n = load().se_exr_piz_scratch_bytes(chunk_desc.ctypes.data_as(_vp), chunk_desc.shape[0], channel_desc.ctypes.data_as(_vp),
-                                        channel_desc.shape[0])
+    name = f"se_exr_{codec}_scratch_bytes"
+    n = getattr(load(), name)(chunk_desc.ctypes.data_as(_vp), chunk_desc.shape[0], channel_desc.ctypes.data_as(_vp), channel_desc.shape[0])
     if n < 0:
-        raise HipExtensionError(f"se_exr_piz_scratch_bytes failed with code {n} (bad argument)")
+        raise HipExtensionError(f"{name} failed with code {n} (bad argument)")
     return int(n)
+
+
+def _exr_decode(codec, payload_ptr, payload_bytes, desc_ptr, n_chunks, chan_ptr, n_files, out, clamp, scratch, status):
+    require_hip(out, scratch, status)
+    _chk_f32(out)
+    assert out.dim() == 3 and out.shape[0] == n_files and status.dtype == torch.int32 and status.shape == (n_chunks, 2)
+    assert scratch.dtype == torch.uint8 and status.is_contiguous()
+    name = f"se_exr_{codec}_decode_f32"
+    _check(getattr(load(), name)(_vp(payload_ptr), int(payload_bytes), _vp(desc_ptr), n_chunks, _vp(chan_ptr), n_files, _ptr(out),
+                                 out.shape[1], out.shape[2], float(clamp), _ptr(scratch), scratch.numel(), _ptr(status), _stream()), name)
+
+
+def exr_piz_scratch_bytes(chunk_desc, channel_desc) -> int:
+    """chunk_desc int64 [n, 16] and channel_desc int32 [files, 8] (HOST numpy arrays, include/sceneego_hip.h): fills the scratch
+    offset / record capacity columns of chunk_desc in place and returns the scratch bytes of se_exr_piz_decode_f32."""
+    return _exr_scratch_bytes("piz", chunk_desc, channel_desc)
 
 
 def exr_piz_decode(payload_ptr, payload_bytes, desc_ptr, n_chunks, chan_ptr, n_files, out, clamp, scratch, status):
     """PIZ chunks -> out float32 [n_files, H_out, W_out] on the current stream.  payload_ptr / desc_ptr / chan_ptr: device addresses
     (ints) inside a buffer the caller keeps alive; status int32 [n_chunks, 2]."""
-    require_hip(out, scratch, status)
-    _chk_f32(out)
-    assert out.dim() == 3 and out.shape[0] == n_files and status.dtype == torch.int32 and status.shape == (n_chunks, 2)
-    assert scratch.dtype == torch.uint8 and status.is_contiguous()
-    _check(load().se_exr_piz_decode_f32(_vp(payload_ptr), int(payload_bytes), _vp(desc_ptr), n_chunks, _vp(chan_ptr), n_files,
-                                        _ptr(out), out.shape[1], out.shape[2], float(clamp), _ptr(scratch), scratch.numel(),
-                                        _ptr(status), _stream()), "se_exr_piz_decode_f32")
+    _exr_decode("piz", payload_ptr, payload_bytes, desc_ptr, n_chunks, chan_ptr, n_files, out, clamp, scratch, status)
 
 
 def exr_zip_scratch_bytes(chunk_desc, channel_desc) -> int:
-    """chunk_desc int64 [n, 16] and channel_desc int32 [files, 8] (HOST numpy arrays, include/sceneego_hip.h): fills the scratch
-    offset / bytes columns of chunk_desc in place and returns the scratch bytes of se_exr_zip_decode_f32."""
-    import numpy as np
-    assert chunk_desc.dtype == np.int64 and chunk_desc.flags.c_contiguous and chunk_desc.shape[1:] == (16,)
-    assert channel_desc.dtype == np.int32 and channel_desc.flags.c_contiguous and channel_desc.shape[1:] == (8,)
-    n = load().se_exr_zip_scratch_bytes(chunk_desc.ctypes.data_as(_vp), chunk_desc.shape[0], channel_desc.ctypes.data_as(_vp),
-                                        channel_desc.shape[0])
-    if n < 0:
-        raise HipExtensionError(f"se_exr_zip_scratch_bytes failed with code {n} (bad argument)")
-    return int(n)
+    """As exr_piz_scratch_bytes (the columns are scratch offset / bytes), for se_exr_zip_decode_f32."""
+    return _exr_scratch_bytes("zip", chunk_desc, channel_desc)
 
 
 def exr_zip_decode(payload_ptr, payload_bytes, desc_ptr, n_chunks, chan_ptr, n_files, out, clamp, scratch, status):
-    """ZIP / ZIPS / NONE chunks -> out float32 [n_files, H_out, W_out] on the current stream.  payload_ptr / desc_ptr / chan_ptr:
-    device addresses (ints) inside a buffer the caller keeps alive; status int32 [n_chunks, 2]."""
-    require_hip(out, scratch, status)
-    _chk_f32(out)
-    assert out.dim() == 3 and out.shape[0] == n_files and status.dtype == torch.int32 and status.shape == (n_chunks, 2)
-    assert scratch.dtype == torch.uint8 and status.is_contiguous()
-    _check(load().se_exr_zip_decode_f32(_vp(payload_ptr), int(payload_bytes), _vp(desc_ptr), n_chunks, _vp(chan_ptr), n_files,
-                                        _ptr(out), out.shape[1], out.shape[2], float(clamp), _ptr(scratch), scratch.numel(),
-                                        _ptr(status), _stream()), "se_exr_zip_decode_f32")
+    """As exr_piz_decode, for ZIP / ZIPS / NONE chunks."""
+    _exr_decode("zip", payload_ptr, payload_bytes, desc_ptr, n_chunks, chan_ptr, n_files, out, clamp, scratch, status)
 
 
 def jpeg_scratch_bytes(img_desc, seg_desc, layout) -> int:
@@ -839,31 +865,13 @@ def joint_stats(prob, coord, joints, stats, peak_index, rows, voxels, scratch=No
     """se_joint_stats_f32: per-row covariance about ``joints``, entropy and peak of the softmaxed volumes ``prob`` [rows, voxels]
     into ``stats`` [rows, 12] float32 and ``peak_index`` [rows] int32.  Every argument is checked here and a bad one raises
     HipExtensionError before anything is launched: the kernel reads with 16-byte loads and trusts the sizes it is given."""
-    def bad(msg):
-        raise HipExtensionError("joint_stats: " + msg)
-    named = (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
-             ("joints", joints, torch.float32, rows * 3), ("stats", stats, torch.float32, rows * JOINT_STATS_SLOTS),
-             ("peak_index", peak_index, torch.int32, rows))
+    what = "joint_stats"
     if rows <= 0 or voxels <= 0 or voxels % 4:
-        bad(f"rows = {rows}, voxels = {voxels}: both must be positive and voxels a multiple of 4")
-    for name, t, dtype, numel in named + ((("scratch", scratch, torch.float32, None),) if scratch is not None else ()):
-        if not isinstance(t, torch.Tensor):
-            bad(f"{name} is not a tensor")
-        if not t.is_cuda:
-            bad(f"{name} is on {t.device}: the operator needs tensors on a HIP device")
-        if t.dtype != dtype:
-            bad(f"{name} is {t.dtype}, expected {dtype}")
-        if not t.is_contiguous():
-            bad(f"{name} is not contiguous")
-        if numel is not None and t.numel() != numel:
-            bad(f"{name} has {t.numel()} elements, expected {numel} for rows = {rows}, voxels = {voxels}")
-        if t.device != prob.device:
-            bad(f"{name} is on {t.device}, prob on {prob.device}")
-    need = joint_stats_scratch_elems(rows)
-    if scratch is None:
-        scratch = torch.empty(need, device=prob.device, dtype=torch.float32)
-    elif scratch.numel() < need:
-        bad(f"scratch has {scratch.numel()} elements, needs {need}")
+        raise HipExtensionError(f"{what}: rows = {rows}, voxels = {voxels}: both must be positive and voxels a multiple of 4")
+    dev = _check_args(what, (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
+                             ("joints", joints, torch.float32, rows * 3), ("stats", stats, torch.float32, rows * JOINT_STATS_SLOTS),
+                             ("peak_index", peak_index, torch.int32, rows)), (("scratch", scratch, torch.float32, None),))
+    scratch = _scratch(what, scratch, joint_stats_scratch_elems(rows), torch.float32, dev)
     _check(load().se_joint_stats_f32(_ptr(prob), _ptr(coord), _ptr(joints), _ptr(stats), _ptr(peak_index), _ptr(scratch), rows,
                                      voxels, _stream()), "se_joint_stats_f32")
 
@@ -875,31 +883,16 @@ RENDER_R_JOINT, RENDER_R_BONE = 0.03, 0.0075                       # metres
 RENDER_JOINT_RGB, RENDER_BONE_RGB = (0.1, 0.1, 0.7), (0.1, 0.9, 0.1)  # reference utils/skeleton.py:52
 
 
-def _render_check(name, t, dtype, shape):
-    if not isinstance(t, torch.Tensor):
-        raise HipExtensionError(f"render: {name} is not a tensor")
-    if not t.is_cuda:
-        raise HipExtensionError(f"render: {name} is on {t.device}: the renderer needs tensors on a HIP device")
-    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise HipExtensionError(f"render: {name} is {t.dtype} {tuple(t.shape)} (contiguous: {t.is_contiguous()}), expected contiguous "
-                                f"{dtype} {tuple(shape)}")
-
-
 def render_splat(depth, ray_tab, image, view, zbuf, f, cx, cy, splat=2, min_z=0.1, max_depth=100.0, near=0.05):
     """se_render_splat_f64: depth [B,dh,dw] float32, ray_tab [H,W,3] float64, image [B,H,W,3] uint8 (B, G, R), view [12] float64 ->
     zbuf [B,Hout,Wout] int64 (the uint64 keys; cleared inside).  Shapes and devices are checked here, before anything is launched."""
-    for name, t in (("depth", depth), ("ray_tab", ray_tab), ("image", image), ("view", view), ("zbuf", zbuf)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise HipExtensionError(f"render_splat: {name} must be a tensor on a HIP device")
-    if depth.dim() != 3 or zbuf.dim() != 3 or ray_tab.dim() != 3:
-        raise HipExtensionError("render_splat: depth [B,dh,dw], ray_tab [H,W,3] and zbuf [B,Hout,Wout] expected")
+    what = "render_splat"
+    _check_args(what, (("depth", depth, torch.float32, (None, None, None)), ("ray_tab", ray_tab, torch.float64, (None, None, 3)),
+                       ("zbuf", zbuf, torch.int64, (None, None, None))))
     B, dh, dw = depth.shape
     H, W, _ = ray_tab.shape
-    _render_check("depth", depth, torch.float32, (B, dh, dw))
-    _render_check("ray_tab", ray_tab, torch.float64, (H, W, 3))
-    _render_check("image", image, torch.uint8, (B, H, W, 3))
-    _render_check("view", view, torch.float64, (12,))
-    _render_check("zbuf", zbuf, torch.int64, (B, zbuf.shape[1], zbuf.shape[2]))
+    _check_args(what, (("image", image, torch.uint8, (B, H, W, 3)), ("view", view, torch.float64, (12,)),
+                       ("zbuf", zbuf, torch.int64, (B, None, None))), device=depth.device)
     _check(load().se_render_splat_f64(_ptr(depth), _ptr(ray_tab), _ptr(image), _ptr(view), _ptr(zbuf), B, dh, dw, H, W, zbuf.shape[1],
                                       zbuf.shape[2], float(f), float(cx), float(cy), int(splat), float(min_z), float(max_depth),
                                       float(near), _stream()), "se_render_splat_f64")
@@ -914,16 +907,11 @@ def render_resolve(rays, joints, zbuf, out, r_joint=RENDER_R_JOINT, r_bone=RENDE
                    bone_rgb=RENDER_BONE_RGB, background=(255, 255, 255)):
     """se_render_resolve_f64: rays [Hout,Wout,3] float64, joints [B,15,3] float64 (frame of the rays), zbuf [B,Hout,Wout] int64 ->
     out [B,Hout,Wout,3] uint8 (R, G, B)."""
-    for name, t in (("rays", rays), ("joints", joints), ("zbuf", zbuf), ("out", out)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise HipExtensionError(f"render_resolve: {name} must be a tensor on a HIP device")
-    if zbuf.dim() != 3:
-        raise HipExtensionError("render_resolve: zbuf [B,Hout,Wout] expected")
+    what = "render_resolve"
+    _check_args(what, (("zbuf", zbuf, torch.int64, (None, None, None)),))
     B, Ho, Wo = zbuf.shape
-    _render_check("rays", rays, torch.float64, (Ho, Wo, 3))
-    _render_check("joints", joints, torch.float64, (B, RENDER_JOINTS, 3))
-    _render_check("zbuf", zbuf, torch.int64, (B, Ho, Wo))
-    _render_check("out", out, torch.uint8, (B, Ho, Wo, 3))
+    _check_args(what, (("rays", rays, torch.float64, (Ho, Wo, 3)), ("joints", joints, torch.float64, (B, RENDER_JOINTS, 3)),
+                       ("out", out, torch.uint8, (B, Ho, Wo, 3))), device=zbuf.device)
     bg = (ctypes.c_ubyte * 3)(*[int(x) for x in background])
     _check(load().se_render_resolve_f64(_ptr(rays), _ptr(joints), _ptr(zbuf), _ptr(out), B, Ho, Wo, float(r_joint), float(r_bone),
                                         float(near), _rgb3(joint_rgb), _rgb3(bone_rgb), bg, _stream()), "se_render_resolve_f64")
@@ -934,22 +922,12 @@ def render_overlay(rays, joints, frame, out, depth=None, r_joint=RENDER_R_JOINT,
                    joint_rgb=RENDER_JOINT_RGB, bone_rgb=RENDER_BONE_RGB):
     """se_render_overlay_f64: rays [H,W,3] float64 (the camera's unit rays), joints [B,15,3] float64 (camera frame), frame [B,H,W,3]
     uint8 (B, G, R), depth None or [B,dh,dw] float32 -> out [B,H,W,3] uint8 (R, G, B)."""
-    for name, t in (("rays", rays), ("joints", joints), ("frame", frame), ("out", out)) + ((("depth", depth),) if depth is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise HipExtensionError(f"render_overlay: {name} must be a tensor on a HIP device")
-    if frame.dim() != 4:
-        raise HipExtensionError("render_overlay: frame [B,H,W,3] expected")
+    what = "render_overlay"
+    _check_args(what, (("frame", frame, torch.uint8, (None, None, None, 3)),))
     B, H, W, _ = frame.shape
-    _render_check("rays", rays, torch.float64, (H, W, 3))
-    _render_check("joints", joints, torch.float64, (B, RENDER_JOINTS, 3))
-    _render_check("frame", frame, torch.uint8, (B, H, W, 3))
-    _render_check("out", out, torch.uint8, (B, H, W, 3))
-    dh = dw = 0
-    if depth is not None:
-        if depth.dim() != 3:
-            raise HipExtensionError("render_overlay: depth [B,dh,dw] expected")
-        dh, dw = depth.shape[1:]
-        _render_check("depth", depth, torch.float32, (B, dh, dw))
+    _check_args(what, (("rays", rays, torch.float64, (H, W, 3)), ("joints", joints, torch.float64, (B, RENDER_JOINTS, 3)),
+                       ("out", out, torch.uint8, (B, H, W, 3))), (("depth", depth, torch.float32, (B, None, None)),), device=frame.device)
+    dh, dw = depth.shape[1:] if depth is not None else (0, 0)
     _check(load().se_render_overlay_f64(_ptr(rays), _ptr(joints), _ptr(frame), _ptr(depth), _ptr(out), B, H, W, dh, dw, float(r_joint),
                                         float(r_bone), float(near), _rgb3(joint_rgb), _rgb3(bone_rgb), _stream()),
            "se_render_overlay_f64")
@@ -978,30 +956,22 @@ def render_volume_packed_elems(batch, grid):
 
 def render_volume_pack(volumes, packed):
     """se_render_volume_pack_f32: volumes [B,15,G,G,G] float32 -> packed, float32 with at least B * G^3 * 16 elements."""
-    for name, t in (("volumes", volumes), ("packed", packed)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise HipExtensionError(f"render_volume_pack: {name} must be a tensor on a HIP device")
-    if volumes.dim() != 5 or volumes.shape[1] != RENDER_JOINTS or not volumes.shape[2] == volumes.shape[3] == volumes.shape[4]:
-        raise HipExtensionError(f"render_volume_pack: volumes [B,15,G,G,G] expected, got {tuple(volumes.shape)}")
+    what = "render_volume_pack"
+    _check_args(what, (("volumes", volumes, torch.float32, (None, RENDER_JOINTS, None, None, None)),))
     B, G = volumes.shape[0], volumes.shape[2]
-    _render_check("volumes", volumes, torch.float32, (B, RENDER_JOINTS, G, G, G))
-    need = render_volume_packed_elems(B, G)
-    if packed.dtype != torch.float32 or not packed.is_contiguous() or packed.numel() < need:
-        raise HipExtensionError(f"render: packed is {packed.dtype} with {packed.numel()} elements (contiguous: {packed.is_contiguous()}), "
-                                f"expected contiguous torch.float32 with at least {need}")
+    if not volumes.shape[2] == volumes.shape[3] == volumes.shape[4]:
+        raise HipExtensionError(f"{what}: volumes [B,15,G,G,G] expected, got {tuple(volumes.shape)}")
+    _render_packed(what, packed, B, G, volumes.device)
     _check(load().se_render_volume_pack_f32(_ptr(volumes), _ptr(packed), packed.numel() * 4, B, G, _stream()), "se_render_volume_pack_f32")
     return packed
 
 
-def _render_volume_common(who, packed, scale, B, grid):
-    for name, t in (("packed", packed), ("scale", scale)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise HipExtensionError(f"{who}: {name} must be a tensor on a HIP device")
+def _render_packed(what, packed, B, grid, device):
+    """``packed`` is the float32 buffer render_volume_pack fills: at least render_volume_packed_elems(B, grid) elements."""
     need = render_volume_packed_elems(B, grid)
-    if packed.dtype != torch.float32 or not packed.is_contiguous() or packed.numel() < need:
-        raise HipExtensionError(f"render: packed is {packed.dtype} with {packed.numel()} elements (contiguous: {packed.is_contiguous()}), "
-                                f"expected contiguous torch.float32 with at least {need}")
-    _render_check("scale", scale, torch.float64, (B, RENDER_JOINTS))
+    _check_args(what, (("packed", packed, torch.float32, None),), device=device)
+    if packed.numel() < need:
+        raise HipExtensionError(f"{what}: packed has {packed.numel()} elements, needs at least {need}")
 
 
 def render_volume_view(packed, scale, rays, view, zbuf, out, grid, cuboid_side, base=None, near=0.05, joint_mask=RENDER_VOLUME_ALL,
@@ -1010,18 +980,12 @@ def render_volume_view(packed, scale, rays, view, zbuf, out, grid, cuboid_side, 
     12 floats on the host, zbuf None (no occlusion) or [B,Hout,Wout] int64 -> out [B,Hout,Wout,3] uint8 (R, G, B), drawn over
     ``base`` (default: over ``out`` itself, in place)."""
     base = out if base is None else base
-    for name, t in (("rays", rays), ("out", out), ("base", base)) + ((("zbuf", zbuf),) if zbuf is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise HipExtensionError(f"render_volume_view: {name} must be a tensor on a HIP device")
-    if out.dim() != 4:
-        raise HipExtensionError("render_volume_view: out [B,Hout,Wout,3] expected")
+    what = "render_volume_view"
+    _check_args(what, (("out", out, torch.uint8, (None, None, None, 3)),))
     B, Ho, Wo, _ = out.shape
-    _render_volume_common("render_volume_view", packed, scale, B, grid)
-    _render_check("rays", rays, torch.float64, (Ho, Wo, 3))
-    _render_check("out", out, torch.uint8, (B, Ho, Wo, 3))
-    _render_check("base", base, torch.uint8, (B, Ho, Wo, 3))
-    if zbuf is not None:
-        _render_check("zbuf", zbuf, torch.int64, (B, Ho, Wo))
+    _render_packed(what, packed, B, grid, out.device)
+    _check_args(what, (("scale", scale, torch.float64, (B, RENDER_JOINTS)), ("rays", rays, torch.float64, (Ho, Wo, 3)),
+                       ("base", base, torch.uint8, (B, Ho, Wo, 3))), (("zbuf", zbuf, torch.int64, (B, Ho, Wo)),), device=out.device)
     v = (ctypes.c_double * 12)(*[float(x) for x in view])
     _check(load().se_render_volume_view_f64(_ptr(packed), _ptr(scale), _ptr(rays), ctypes.cast(v, ctypes.c_void_p), _ptr(zbuf),
                                             _ptr(base), _ptr(out), B, Ho, Wo, int(grid), float(cuboid_side), float(near),
@@ -1034,22 +998,13 @@ def render_volume_overlay(packed, scale, rays, out, grid, cuboid_side, base=None
     """se_render_volume_overlay_f64: packed, scale [B,15] float64, rays [H,W,3] float64 (the camera's unit rays), depth None (no
     occlusion) or [B,dh,dw] float32 -> out [B,H,W,3] uint8 (R, G, B), drawn over ``base`` (default: ``out`` itself, in place)."""
     base = out if base is None else base
-    for name, t in (("rays", rays), ("out", out), ("base", base)) + ((("depth", depth),) if depth is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise HipExtensionError(f"render_volume_overlay: {name} must be a tensor on a HIP device")
-    if out.dim() != 4:
-        raise HipExtensionError("render_volume_overlay: out [B,H,W,3] expected")
+    what = "render_volume_overlay"
+    _check_args(what, (("out", out, torch.uint8, (None, None, None, 3)),))
     B, H, W, _ = out.shape
-    _render_volume_common("render_volume_overlay", packed, scale, B, grid)
-    _render_check("rays", rays, torch.float64, (H, W, 3))
-    _render_check("out", out, torch.uint8, (B, H, W, 3))
-    _render_check("base", base, torch.uint8, (B, H, W, 3))
-    dh = dw = 0
-    if depth is not None:
-        if depth.dim() != 3:
-            raise HipExtensionError("render_volume_overlay: depth [B,dh,dw] expected")
-        dh, dw = depth.shape[1:]
-        _render_check("depth", depth, torch.float32, (B, dh, dw))
+    _render_packed(what, packed, B, grid, out.device)
+    _check_args(what, (("scale", scale, torch.float64, (B, RENDER_JOINTS)), ("rays", rays, torch.float64, (H, W, 3)),
+                       ("base", base, torch.uint8, (B, H, W, 3))), (("depth", depth, torch.float32, (B, None, None)),), device=out.device)
+    dh, dw = depth.shape[1:] if depth is not None else (0, 0)
     _check(load().se_render_volume_overlay_f64(_ptr(packed), _ptr(scale), _ptr(rays), _ptr(depth), _ptr(base), _ptr(out), B, H, W, dh, dw,
                                                int(grid), float(cuboid_side), float(near), int(joint_mask), float(gain), float(opacity),
                                                _stream()), "se_render_volume_overlay_f64")
@@ -1075,37 +1030,17 @@ def scene_probe(depth, ray_tab, probes, out, index, scratch=None, min_z=0.1, max
     """se_scene_probe_f64: depth [B,dh,dw] float32, ray_tab [H,W,3] float64, probes [B,P,3] float64 (1 <= P <= 64) -> out [B,P,8]
     float64, index [B,P,2] int32 (the header states every slot).  ``scratch``: an optional uint8 workspace of at least
     ``scene_probe_scratch_bytes(B, H, W, P)`` bytes (allocated per call otherwise).  Returns (out, index)."""
-    def check(name, t, dtype, shape):
-        if not isinstance(t, torch.Tensor):
-            raise HipExtensionError(f"scene_probe: {name} is not a tensor")
-        if t.device.type != "cuda":
-            raise HipExtensionError(f"scene_probe: {name} is on {t.device}: the scene probe needs tensors on a HIP device")
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-            raise HipExtensionError(f"scene_probe: {name} is {t.dtype} {tuple(t.shape)} (contiguous: {t.is_contiguous()}), expected "
-                                    f"contiguous {dtype} {tuple(shape)}")
-
-    for name, t in (("depth", depth), ("ray_tab", ray_tab), ("probes", probes)):
-        if not isinstance(t, torch.Tensor):
-            raise HipExtensionError(f"scene_probe: {name} must be a tensor on a HIP device")
-    if depth.dim() != 3 or ray_tab.dim() != 3 or probes.dim() != 3:
-        raise HipExtensionError("scene_probe: depth [B,dh,dw], ray_tab [H,W,3] and probes [B,P,3] expected")
+    what = "scene_probe"
+    _check_args(what, (("depth", depth, torch.float32, (None, None, None)), ("ray_tab", ray_tab, torch.float64, (None, None, 3)),
+                       ("probes", probes, torch.float64, (None, None, 3))))
     B, dh, dw = depth.shape
     H, W = ray_tab.shape[:2]
     P = probes.shape[1]
     if not 1 <= P <= SCENE_PROBE_MAX:
-        raise HipExtensionError(f"scene_probe: {P} probes per frame, 1..{SCENE_PROBE_MAX} supported")
-    check("depth", depth, torch.float32, (B, dh, dw))
-    check("ray_tab", ray_tab, torch.float64, (H, W, 3))
-    check("probes", probes, torch.float64, (B, P, 3))
-    check("out", out, torch.float64, (B, P, SCENE_PROBE_SLOTS))
-    check("index", index, torch.int32, (B, P, 2))
-    need = scene_probe_scratch_bytes(B, H, W, P)
-    if scratch is None:
-        scratch = torch.empty((need,), device=depth.device, dtype=torch.uint8)
-    else:
-        if not isinstance(scratch, torch.Tensor) or scratch.device.type != "cuda" or scratch.dtype != torch.uint8 \
-                or not scratch.is_contiguous() or scratch.numel() < need:
-            raise HipExtensionError(f"scene_probe: scratch must be a contiguous uint8 tensor of at least {need} bytes on a HIP device")
+        raise HipExtensionError(f"{what}: {P} probes per frame, 1..{SCENE_PROBE_MAX} supported")
+    _check_args(what, (("probes", probes, torch.float64, (B, P, 3)), ("out", out, torch.float64, (B, P, SCENE_PROBE_SLOTS)),
+                       ("index", index, torch.int32, (B, P, 2))), (("scratch", scratch, torch.uint8, None),), device=depth.device)
+    scratch = _scratch(what, scratch, scene_probe_scratch_bytes(B, H, W, P), torch.uint8, depth.device)
     _check(load().se_scene_probe_f64(_ptr(depth), _ptr(ray_tab), _ptr(probes), _ptr(out), _ptr(index), _ptr(scratch), scratch.numel(),
                                      B, dh, dw, H, W, P, float(min_z), float(max_depth), _stream()), "se_scene_probe_f64")
     return out, index
@@ -1116,37 +1051,16 @@ def scene_probe(depth, ray_tab, probes, out, index, scratch=None, min_z=0.1, max
 MASKED_SLOTS = 8           # free_mass, sum f p c (x y z), free_peak_p, free peak coordinate x y z (include/sceneego_hip.h)
 
 
-def _sc_check(what, named, ref_device):
-    """Every tensor of ``named`` = (name, tensor, dtype, numel or None) is a contiguous tensor of that type on one HIP device."""
-    for name, t, dtype, numel in named:
-        if not isinstance(t, torch.Tensor):
-            raise HipExtensionError(f"{what}: {name} is not a tensor")
-        if not t.is_cuda:
-            raise HipExtensionError(f"{what}: {name} is on {t.device}: the operator needs tensors on a HIP device")
-        if t.dtype != dtype:
-            raise HipExtensionError(f"{what}: {name} is {t.dtype}, expected {dtype}")
-        if not t.is_contiguous():
-            raise HipExtensionError(f"{what}: {name} is not contiguous")
-        if numel is not None and t.numel() != numel:
-            raise HipExtensionError(f"{what}: {name} has {t.numel()} elements, expected {numel}")
-        if ref_device is not None and t.device != ref_device:
-            raise HipExtensionError(f"{what}: {name} is on {t.device}, expected {ref_device}")
-
-
 def scene_free_mask(depth, pix, rng, free, height, width, margin, max_depth):
     """se_scene_free_mask_u8: depth [B,dh,dw] float32, the sight table pix [voxels] int32 / rng [voxels] float32 of a ``height`` x
     ``width`` frame -> free [B,voxels] uint8 (1 free, 0 blocked; the header states the rule).  Every argument is checked here and a
     bad one raises HipExtensionError before anything is launched.  Returns ``free``."""
     what = "scene_free_mask"
-    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
-        raise HipExtensionError(f"{what}: depth [B,dh,dw] expected")
-    if not isinstance(pix, torch.Tensor) or pix.dim() != 1:
-        raise HipExtensionError(f"{what}: pix [voxels] expected")
+    _check_args(what, (("depth", depth, torch.float32, (None, None, None)), ("pix", pix, torch.int32, (None,))))
     B, dh, dw = (int(v) for v in depth.shape)
     voxels = int(pix.numel())
     height, width = int(height), int(width)
-    _sc_check(what, (("depth", depth, torch.float32, None), ("pix", pix, torch.int32, voxels), ("rng", rng, torch.float32, voxels),
-                     ("free", free, torch.uint8, B * voxels)), depth.device if depth.is_cuda else None)
+    _check_args(what, (("rng", rng, torch.float32, voxels), ("free", free, torch.uint8, B * voxels)), device=depth.device)
     if B <= 0 or B > 65535 or dh <= 0 or dw <= 0 or height <= 0 or width <= 0 or height * width > 0x7fff0000:
         raise HipExtensionError(f"{what}: batch {B}, depth {dh}x{dw}, frame {height}x{width} not supported")
     if voxels <= 0 or voxels % 4:
@@ -1173,17 +1087,11 @@ def softargmax3d_masked(prob, coord, free, out, peak_index, rows, rows_per_frame
     if rows <= 0 or rows > 65535 or rows_per_frame <= 0 or rows % rows_per_frame or voxels <= 0 or voxels % 4:
         raise HipExtensionError(f"{what}: rows = {rows} (1..65535, a multiple of rows_per_frame = {rows_per_frame}), voxels = {voxels} "
                                 "(a positive multiple of 4) expected")
-    named = (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
-             ("free", free, torch.uint8, rows // rows_per_frame * voxels), ("out", out, torch.float32, rows * MASKED_SLOTS),
-             ("peak_index", peak_index, torch.int32, rows))
-    if scratch is not None:
-        named += (("scratch", scratch, torch.float32, None),)
-    _sc_check(what, named, prob.device if isinstance(prob, torch.Tensor) and prob.is_cuda else None)
-    need = softargmax3d_masked_scratch_elems(rows)
-    if scratch is None:
-        scratch = torch.empty(need, device=prob.device, dtype=torch.float32)
-    elif scratch.numel() < need:
-        raise HipExtensionError(f"{what}: scratch has {scratch.numel()} elements, needs {need}")
+    dev = _check_args(what, (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
+                             ("free", free, torch.uint8, rows // rows_per_frame * voxels),
+                             ("out", out, torch.float32, rows * MASKED_SLOTS), ("peak_index", peak_index, torch.int32, rows)),
+                      (("scratch", scratch, torch.float32, None),))
+    scratch = _scratch(what, scratch, softargmax3d_masked_scratch_elems(rows), torch.float32, dev)
     _check(load().se_softargmax3d_masked_f32(_ptr(prob), _ptr(coord), _ptr(free), _ptr(out), _ptr(peak_index), _ptr(scratch), rows,
                                              rows_per_frame, voxels, _stream()), "se_softargmax3d_masked_f32")
     return out, peak_index
@@ -1213,19 +1121,14 @@ def joint_modes(prob, coord, modes, index, count, total, rows, voxels, grid, k, 
         raise HipExtensionError(f"{what}: k = {k} (1..{MODES_MAX_K}) and radius = {radius} (0..{MODES_MAX_RADIUS}) expected")
     if not min_prob >= 0.0:
         raise HipExtensionError(f"{what}: min_prob = {min_prob} must be >= 0 and not NaN")
-    named = (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
-             ("modes", modes, torch.float32, rows * k * MODES_SLOTS), ("index", index, torch.int32, rows * k),
-             ("count", count, torch.int32, rows), ("total", total, torch.int32, rows))
-    if scratch is not None:
-        named += (("scratch", scratch, torch.uint8, None),)
-    _sc_check(what, named, prob.device if isinstance(prob, torch.Tensor) and prob.is_cuda else None)
+    dev = _check_args(what, (("prob", prob, torch.float32, rows * voxels), ("coord", coord, torch.float32, voxels * 3),
+                             ("modes", modes, torch.float32, rows * k * MODES_SLOTS), ("index", index, torch.int32, rows * k),
+                             ("count", count, torch.int32, rows), ("total", total, torch.int32, rows)),
+                      (("scratch", scratch, torch.uint8, None),))
     need = joint_modes_scratch_bytes(rows, grid, k)
     if need <= 0:
         raise HipExtensionError(f"{what}: grid = {grid} is not supported")
-    if scratch is None:
-        scratch = torch.empty(need, device=prob.device, dtype=torch.uint8)
-    elif scratch.numel() < need:
-        raise HipExtensionError(f"{what}: scratch has {scratch.numel()} bytes, needs {need}")
+    scratch = _scratch(what, scratch, need, torch.uint8, dev)
     _check(load().se_joint_modes_f32(_ptr(prob), _ptr(coord), _ptr(modes), _ptr(index), _ptr(count), _ptr(total), _ptr(scratch),
                                      scratch.numel(), rows, voxels, grid, k, radius, min_prob, _stream()), "se_joint_modes_f32")
     return modes, index, count, total
@@ -1258,26 +1161,18 @@ def volume_filter(prob, coord, taps, state, belief_out, joints, evidence, restar
         raise HipExtensionError(f"{what}: radius = {radius} (0..{min(FILTER_MAX_RADIUS, grid - 1)}) expected")
     if not 0.0 <= floor <= 1.0:
         raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
-    named = (("prob", prob, torch.float32, frames * rows * voxels), ("coord", coord, torch.float32, voxels * 3),
-             ("taps", taps, torch.float32, 2 * radius + 1), ("state", state, torch.float32, rows * voxels),
-             ("joints", joints, torch.float32, frames * rows * 3), ("evidence", evidence, torch.float32, frames * rows),
-             ("restarted", restarted, torch.int32, frames * rows))
-    if belief_out is not None:
-        named += (("belief_out", belief_out, torch.float32, frames * rows * voxels),)
-    if have_prior is not None:
-        named += (("have_prior", have_prior, torch.int32, rows),)
-    if scratch is not None:
-        named += (("scratch", scratch, torch.uint8, None),)
-    _sc_check(what, named, prob.device if isinstance(prob, torch.Tensor) and prob.is_cuda else None)
+    dev = _check_args(what, (("prob", prob, torch.float32, frames * rows * voxels), ("coord", coord, torch.float32, voxels * 3),
+                             ("taps", taps, torch.float32, 2 * radius + 1), ("state", state, torch.float32, rows * voxels),
+                             ("joints", joints, torch.float32, frames * rows * 3), ("evidence", evidence, torch.float32, frames * rows),
+                             ("restarted", restarted, torch.int32, frames * rows)),
+                      (("belief_out", belief_out, torch.float32, frames * rows * voxels), ("have_prior", have_prior, torch.int32, rows),
+                       ("scratch", scratch, torch.uint8, None)))
     if belief_out is not None and belief_out.data_ptr() in (prob.data_ptr(), state.data_ptr()):
         raise HipExtensionError(f"{what}: belief_out must not alias prob or state")
     need = volume_filter_scratch_bytes(rows, grid, radius)
     if need <= 0:
         raise HipExtensionError(f"{what}: rows = {rows}, grid = {grid}, radius = {radius} is not supported")
-    if scratch is None:
-        scratch = torch.empty(need, device=prob.device, dtype=torch.uint8)
-    elif scratch.numel() < need:
-        raise HipExtensionError(f"{what}: scratch has {scratch.numel()} bytes, needs {need}")
+    scratch = _scratch(what, scratch, need, torch.uint8, dev)
     _check(load().se_volume_filter_f32(_ptr(prob), _ptr(coord), _ptr(taps), _ptr(state), _ptr(belief_out), _ptr(joints),
                                        _ptr(evidence), _ptr(restarted), _ptr(scratch), scratch.numel(), frames, rows, voxels, grid,
                                        radius, floor, _ptr(have_prior), _stream()), "se_volume_filter_f32")
@@ -1298,17 +1193,11 @@ def jpeg_encode(frames, quant_luma, quant_chroma, subsampling, restart_rows, out
     """se_jpeg_encode_u8: frames uint8 [B,H,W,3] -> out uint8 [B,capacity] (the scan of every frame), length int32 [B], status int32
     [B,2]; ``quant_*``: numpy uint16 [64], natural order.  Runs on the current stream."""
     import numpy as np
-    for name, t, dtype in (("frames", frames, torch.uint8), ("out", out, torch.uint8), ("length", length, torch.int32),
-                           ("status", status, torch.int32), ("scratch", scratch, torch.uint8)):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise HipExtensionError(f"jpeg_encode: {name} must be a tensor on a HIP device (the encoder has no CPU fallback)")
-        if t.dtype != dtype or not t.is_contiguous():
-            raise HipExtensionError(f"jpeg_encode: {name} is {t.dtype} (contiguous: {t.is_contiguous()}), expected contiguous {dtype}")
-    if frames.dim() != 4 or frames.shape[3] != 3:
-        raise HipExtensionError(f"jpeg_encode: frames [B,H,W,3] expected, got {tuple(frames.shape)}")
+    what = "jpeg_encode"
+    _check_args(what, (("frames", frames, torch.uint8, (None, None, None, 3)),))
     B, H, W = frames.shape[:3]
-    if out.dim() != 2 or out.shape[0] != B or length.numel() != B or tuple(status.shape) != (B, 2):
-        raise HipExtensionError("jpeg_encode: out [B,capacity], length [B] and status [B,2] expected")
+    _check_args(what, (("out", out, torch.uint8, (B, None)), ("length", length, torch.int32, B), ("status", status, torch.int32, (B, 2)),
+                       ("scratch", scratch, torch.uint8, None)), device=frames.device)
     ql = np.ascontiguousarray(quant_luma, dtype=np.uint16).reshape(64)
     qc = np.ascontiguousarray(quant_chroma, dtype=np.uint16).reshape(64)
     _check(load().se_jpeg_encode_u8(_ptr(frames), B, H, W, 1 if bgr else 0, ql.ctypes.data, qc.ctypes.data, int(subsampling),

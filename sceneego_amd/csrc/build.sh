@@ -16,7 +16,7 @@ OBJ=_obj/$KEY
 mkdir -p "$OBJ"
 pids=()
 newer() {  # source $1, a shared header or (development builds) a devtools/ include newer than object $2
-  [ ! -f "$2" ] || [ "$1" -nt "$2" ] || [ common.h -nt "$2" ] || [ conv_common.h -nt "$2" ] || [ conv3d_plan.h -nt "$2" ] || [ bf16_common.h -nt "$2" ] || [ wino67_matrices.h -nt "$2" ] || [ fft24.h -nt "$2" ] || [ ../../include/sceneego_hip.h -nt "$2" ] && return 0
+  [ ! -f "$2" ] || [ "$1" -nt "$2" ] || [ common.h -nt "$2" ] || [ row_reduce.h -nt "$2" ] || [ conv_common.h -nt "$2" ] || [ conv3d_plan.h -nt "$2" ] || [ bf16_common.h -nt "$2" ] || [ wino67_matrices.h -nt "$2" ] || [ fft24.h -nt "$2" ] || [ ../../include/sceneego_hip.h -nt "$2" ] && return 0
   if [ -n "$DEV" ]; then for i in devtools/*.inc; do [ "$i" -nt "$2" ] && return 0; done; fi
   return 1
 }

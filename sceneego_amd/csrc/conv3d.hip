@@ -20,6 +20,7 @@
 #include "common.h"
 
 #include "conv3d_plan.h"
+#include "row_reduce.h"   // se_sa_splits, se_row_chunk, SE_SA_PART: the fused tail writes the soft-argmax's pass-1 records
 #include "wino47_matrices.h"
 #include "wino67_matrices.h"
 
@@ -1497,7 +1498,7 @@ extern "C" int se_pointwise_chain3_softargmax_f32(const float* in, const float* 
     const long long vox_per_b = (long long)dim * dim * dim;
     if (vox_per_b >= (1LL << 31) || (vox_per_b & 3)) return SE_ERR_BAD_ARG;
     const int splits = se_sa_splits(batch * cout3);                                               // as softargmax.hip
-    const int chunk = (int)((((vox_per_b + splits - 1) / splits) + 3) & ~3LL);
+    const int chunk = se_row_chunk((int)vox_per_b, splits);
     if (chunk & 15) return SE_ERR_BAD_ARG;                                                       // whole 16-voxel tiles per chunk
     constexpr int LDS = PW_SA_WAVES * 64 * 20 * 4;
     SE_ENSURE_LDS(pointwise_chain3_sa_kernel, LDS);

@@ -3,6 +3,7 @@
 // The LDS-tiled 3^3 / 7^3 kernels for the large levels are in conv3d_bf16_tiled.hip.
 // Reference call sites: network/v2v.py:8-43 (Basic3DBlock / Res3DBlock), :46-67 (pool / upsample), :155-161 (tail).
 #include "bf16_common.h"
+#include "row_reduce.h"   // se_sa_splits, se_row_chunk, SE_SA_PART: the fused tail writes the soft-argmax's pass-1 records
 
 namespace {
 
@@ -603,7 +604,7 @@ extern "C" int se_pointwise_chain3_softargmax_bf16(const se_bf16* in, const se_b
     const long long vox_per_b = (long long)dim * dim * dim;
     if (vox_per_b >= (1LL << 31) || (vox_per_b & 3)) return SE_ERR_BAD_ARG;
     const int splits = se_sa_splits(batch * cout3);                                               // as softargmax.hip
-    const int chunk = (int)((((vox_per_b + splits - 1) / splits) + 3) & ~3LL);
+    const int chunk = se_row_chunk((int)vox_per_b, splits);
     if (chunk & 15) return SE_ERR_BAD_ARG;                                                       // whole 16-voxel tiles per chunk
     constexpr int LDS = PWB_SA_WAVES * 64 * 20 * 4;
     SE_ENSURE_LDS(pointwise_chain3_sa_bf16_kernel, LDS);

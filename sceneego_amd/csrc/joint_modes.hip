@@ -25,9 +25,7 @@
 //                               the window of mode r serially: float64 sums in ascending flat index, one rounding each.
 // No atomics; every result is either an exact integer, a selection under a total order or a sum in a fixed order: bitwise identical
 // from run to run.  No division of floats anywhere.
-#include <limits.h>
-
-#include "common.h"
+#include "row_reduce.h"   // Peak, peak_combine, wave_reduce_peak
 
 #pragma clang fp contract(off)
 
@@ -40,26 +38,8 @@
 
 namespace {
 
-struct Peak {
-    float p;
-    int idx;
-};
-__device__ __forceinline__ Peak peak_combine(Peak a, Peak b) {
-    const bool take_b = b.p > a.p || (b.p == a.p && b.idx < a.idx);
-    return take_b ? b : a;
-}
 // key(a) < key(b) under the order (p, -n)
 __device__ __forceinline__ bool key_less(Peak a, Peak b) { return a.p < b.p || (a.p == b.p && a.idx > b.idx); }
-__device__ __forceinline__ Peak wave_reduce_peak(Peak v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Peak o;
-        o.p = __shfl_xor(v.p, off, 64);
-        o.idx = __shfl_xor(v.idx, off, 64);
-        v = peak_combine(v, o);
-    }
-    return v;
-}
 __device__ __forceinline__ int wave_reduce_add_int(int v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

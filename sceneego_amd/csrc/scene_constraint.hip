@@ -6,48 +6,20 @@
 //                              depth there, one float64 sum and one comparison per voxel; the four uint8 results leave as one 32-bit
 //                              vector store.  Built with -ffp-contract=off: the mask has one right answer, bit for bit
 //                              (tests/scene_constraint_model.py restates it).
-//   masked_partial_kernel      grid (splits, rows), block 256, split-row exactly as joint_stats.hip (se_sa_splits(rows) chunks per row,
-//                              the same chunk rule): every workgroup reduces its chunk to one record of SE_SC_PART floats in scratch.
+//   masked_partial_kernel      pass 1 of a split-row reduction with a peak (row_reduce.h states the scheme, the peak's order and NaN
+//                              marker, and why the result is bitwise deterministic): one record of SE_SC_PART floats per chunk.
 //                              HBM/MALL-bound: 4 B/voxel/row of probabilities read once; the [voxels][3] coordinates and the frame's
-//                              mask (1 B/voxel, shared by the frame's rows) stay cache-resident.  f32x4 loads for the probabilities and
-//                              the coordinates, one 32-bit load for the four mask bytes.
-//   masked_fold_kernel         one wave per row folds the row's records in a fixed order (lane k takes chunks k, k + 64, ... in
-//                              sequence, then a butterfly over the lanes) and writes out[row][8] and peak_index[row].
-// No atomics: every sum is taken in an order that depends on the shape alone, so the result is bitwise identical from run to run.
-// An empty chunk (k * chunk >= voxels) is skipped by its position, never by the value of its record.  No division anywhere.
-//
-// The free peak is the pair (p, index) over the FREE voxels under the order "larger p first, then lower index": commutative and
-// associative, so any reduction tree gives the same pair; (-inf, INT_MAX) is its neutral element and survives only in a row without a
-// free voxel.  A NaN probability (free or blocked) is carried in the same pair as (+inf, -1), which wins every combine: a row whose
-// folded index is negative held a NaN, and all 8 floats of that row are written as NaN.
-#include <limits.h>
-
-#include "common.h"
+//                              mask (1 B/voxel, shared by the frame's rows) stay cache-resident; one 32-bit load for four mask bytes.
+//   masked_fold_kernel         pass 2: folds the row's records and writes out[row][8] and peak_index[row].  The peak is taken over the
+//                              FREE voxels alone, so its neutral element survives in a row without a free voxel; a NaN probability
+//                              (free or blocked) marks the row, and all 8 floats of that row are written as NaN.  No division anywhere.
+#include "row_reduce.h"
 
 #pragma clang fp contract(off)
 
 #define SE_SC_PART 8   // free_mass sx sy sz peak_p peak_index(int bits) pad pad
 
 namespace {
-
-struct Peak {
-    float p;
-    int idx;
-};
-__device__ __forceinline__ Peak peak_combine(Peak a, Peak b) {
-    const bool take_b = b.p > a.p || (b.p == a.p && b.idx < a.idx);
-    return take_b ? b : a;
-}
-__device__ __forceinline__ Peak wave_reduce_peak(Peak v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Peak o;
-        o.p = __shfl_xor(v.p, off, 64);
-        o.idx = __shfl_xor(v.idx, off, 64);
-        v = peak_combine(v, o);
-    }
-    return v;
-}
 
 // grid (ceil(voxels / 1024), B), block 256: thread t of block g owns the voxels 4 (256 g + t) .. + 3 of frame blockIdx.y
 __global__ __launch_bounds__(256) void scene_free_mask_kernel(const float* __restrict__ depth, const int* __restrict__ pix,
@@ -81,58 +53,31 @@ __global__ __launch_bounds__(256) void masked_partial_kernel(const float* __rest
                                                              int voxels, int splits, int rows_per_frame) {
     __shared__ float sm[4][SE_SC_PART];
     const int row = blockIdx.y, s = blockIdx.x;
-    const int chunk = (((voxels + splits - 1) / splits) + 3) & ~3;
+    const int chunk = se_row_chunk(voxels, splits);
     const int c0 = s * chunk;
     const int c1 = min(c0 + chunk, voxels);
     const float* v = prob + (size_t)row * voxels;
     const unsigned char* fm = free_mask + (size_t)(row / rows_per_frame) * voxels;
 
     float acc[4] = {0.f, 0.f, 0.f, 0.f};   // free_mass sx sy sz
-    Peak pk = {-INFINITY, INT_MAX};
+    Peak pk = PEAK_NONE;
     bool nan = false;
     for (int i = c0 + threadIdx.x * 4; i < c1; i += 1024) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(v + i);
         const unsigned fw = *reinterpret_cast<const unsigned*>(fm + i);
-        const f32x4 c_a = *reinterpret_cast<const f32x4*>(coord + (size_t)i * 3);
-        const f32x4 c_b = *reinterpret_cast<const f32x4*>(coord + (size_t)i * 3 + 4);
-        const f32x4 c_c = *reinterpret_cast<const f32x4*>(coord + (size_t)i * 3 + 8);
-        const float p[4] = {x.x, x.y, x.z, x.w};
-        const float cx[4] = {c_a.x, c_a.w, c_b.z, c_c.y};
-        const float cy[4] = {c_a.y, c_b.x, c_b.w, c_c.z};
-        const float cz[4] = {c_a.z, c_b.y, c_c.x, c_c.w};
+        const Quad q = load_quad(v, coord, i);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            nan |= p[k] != p[k];
+            const float p = q.p[k];
+            nan |= p != p;
             if ((fw >> (8 * k)) & 0xffu) {
-                acc[0] += p[k];
-                acc[1] += p[k] * cx[k]; acc[2] += p[k] * cy[k]; acc[3] += p[k] * cz[k];
-                if (p[k] > pk.p) { pk.p = p[k]; pk.idx = i + k; }   // indices ascend within a lane: strict > keeps the lowest
+                acc[0] += p;
+                acc[1] += p * q.cx[k]; acc[2] += p * q.cy[k]; acc[3] += p * q.cz[k];
+                if (p > pk.p) { pk.p = p; pk.idx = i + k; }   // indices ascend within a lane: strict > keeps the lowest
             }
         }
     }
-    if (nan) { pk.p = INFINITY; pk.idx = -1; }
-
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] = wave_reduce_sum(acc[k]);
-    pk = wave_reduce_peak(pk);
-    const int wid = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sm[wid][k] = acc[k];
-        sm[wid][4] = pk.p;
-        sm[wid][5] = __int_as_float(pk.idx);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float* out = scratch + ((size_t)row * splits + s) * SE_SC_PART;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) out[k] = (sm[0][k] + sm[1][k]) + (sm[2][k] + sm[3][k]);
-        Peak r = {sm[0][4], __float_as_int(sm[0][5])};
-#pragma unroll
-        for (int w = 1; w < 4; ++w) r = peak_combine(r, Peak{sm[w][4], __float_as_int(sm[w][5])});
-        out[4] = r.p;
-        out[5] = __int_as_float(r.idx);
-    }
+    if (nan) pk = PEAK_NAN;
+    block_fold_record<4, SE_SC_PART>(acc, pk, sm, scratch + ((size_t)row * splits + s) * SE_SC_PART);
 }
 
 // grid (rows), block 64: one wave per row
@@ -141,19 +86,8 @@ __global__ __launch_bounds__(64) void masked_fold_kernel(const float* __restrict
                                                          int splits) {
     const int row = blockIdx.x, lane = threadIdx.x;
     const float* part = scratch + (size_t)row * splits * SE_SC_PART;
-    const int chunk = (((voxels + splits - 1) / splits) + 3) & ~3;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    Peak pk = {-INFINITY, INT_MAX};
-    for (int k = lane; k < splits; k += 64) {
-        if (k * chunk >= voxels) continue;   // empty chunk: its record holds the neutral element, skipped by position all the same
-        const float* p = part + k * SE_SC_PART;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) acc[a] += p[a];
-        pk = peak_combine(pk, Peak{p[4], __float_as_int(p[5])});
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) acc[a] = wave_reduce_sum(acc[a]);
-    pk = wave_reduce_peak(pk);
+    float acc[4];
+    const Peak pk = wave_fold_chunks<4, SE_SC_PART>(part, splits, voxels, lane, acc);
     if (lane != 0) return;
     float* o = out + (size_t)row * 8;
     const float q = __int_as_float(0x7fc00000);

@@ -2,33 +2,13 @@
 // expectation of the voxel-centre coordinates.  HBM-bound: 4 B/voxel/row read (twice, second pass is
 // L2/MALL resident at 64^3) + 4 B written (the softmaxed volumes are part of forward()'s return value).
 //
-// Two launches, split-row so that B*15 rows x se_sa_splits(rows) chunks fill the 256 CUs:
-//   pass 1: per chunk  m = max v, l = sum exp(v-m), s = sum exp(v-m) * coord      -> scratch
-//   pass 2: every chunk re-derives the row's (M, L) from the row's partials in a fixed order
-//           (bitwise deterministic), writes exp(v-M)/L; chunk 0 also writes the joint.
-#include "common.h"
-
-// se_sa_splits() / SE_SA_PART (chunks per row, floats per partial record: m, l, sx, sy, sz, pad): common.h - the fused V2V tail
-// (pointwise_chain3_sa_kernel in conv3d.hip) writes the same records
+// Two launches, split-row (row_reduce.h states the scheme, the record and why the result is bitwise deterministic):
+//   pass 1: per chunk  m = max v, l = sum exp(v-m), s = sum exp(v-m) * coord      -> one SE_SA_PART record (m, l, sx, sy, sz) in scratch;
+//           the fused V2V tails (pointwise_chain3_sa_kernel in conv3d.hip, its bf16 twin) write the same records
+//   pass 2: every chunk re-derives the row's (M, L) from the row's records, writes exp(v-M)/L; chunk 0 also writes the joint.
+#include "row_reduce.h"
 
 namespace {
-
-__device__ __forceinline__ float block_reduce_max(float v, float* sm) {
-    v = wave_reduce_max(v);
-    const int wid = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[wid] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-}
-__device__ __forceinline__ float block_reduce_sum(float v, float* sm) {
-    v = wave_reduce_sum(v);
-    const int wid = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[wid] = v;
-    __syncthreads();
-    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
-}
 
 // grid (splits, rows), block 256
 __global__ __launch_bounds__(256) void softargmax_partial_kernel(const float* __restrict__ vol,
@@ -37,7 +17,7 @@ __global__ __launch_bounds__(256) void softargmax_partial_kernel(const float* __
                                                                  int mode, int splits) {
     __shared__ float sm[4];
     const int row = blockIdx.y, s = blockIdx.x;
-    const int chunk = (((voxels + splits - 1) / splits) + 3) & ~3;
+    const int chunk = se_row_chunk(voxels, splits);
     const int c0 = s * chunk;
     const int c1 = min(c0 + chunk, voxels);
     const float* v = vol + (size_t)row * voxels;
@@ -52,24 +32,21 @@ __global__ __launch_bounds__(256) void softargmax_partial_kernel(const float* __
     }
     float l = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
     for (int i = c0 + threadIdx.x * 4; i < c1; i += 1024) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(v + i);
-        const f32x4 c_a = *reinterpret_cast<const f32x4*>(coord + (size_t)i * 3);
-        const f32x4 c_b = *reinterpret_cast<const f32x4*>(coord + (size_t)i * 3 + 4);
-        const f32x4 c_c = *reinterpret_cast<const f32x4*>(coord + (size_t)i * 3 + 8);
+        const Quad q = load_quad(v, coord, i);
         float e0, e1, e2, e3;
         if (mode == 1) {
             // A -inf logit contributes exactly 0, whatever m is: in a chunk of nothing but -inf, m is -inf too and expf(-inf - -inf) would be
             // NaN, which the fold's 0 weight for that chunk does not remove (NaN * 0).  m itself is not special-cased: a NaN among -inf
             // logits (fmaxf drops it from m) must still come out of expf(NaN - m) and reach L.
-            e0 = x.x == -INFINITY ? 0.f : expf(x.x - m); e1 = x.y == -INFINITY ? 0.f : expf(x.y - m);
-            e2 = x.z == -INFINITY ? 0.f : expf(x.z - m); e3 = x.w == -INFINITY ? 0.f : expf(x.w - m);
+            e0 = q.p[0] == -INFINITY ? 0.f : expf(q.p[0] - m); e1 = q.p[1] == -INFINITY ? 0.f : expf(q.p[1] - m);
+            e2 = q.p[2] == -INFINITY ? 0.f : expf(q.p[2] - m); e3 = q.p[3] == -INFINITY ? 0.f : expf(q.p[3] - m);
         } else {
-            e0 = fmaxf(x.x, 0.f); e1 = fmaxf(x.y, 0.f); e2 = fmaxf(x.z, 0.f); e3 = fmaxf(x.w, 0.f);
+            e0 = fmaxf(q.p[0], 0.f); e1 = fmaxf(q.p[1], 0.f); e2 = fmaxf(q.p[2], 0.f); e3 = fmaxf(q.p[3], 0.f);
         }
         l += (e0 + e1) + (e2 + e3);
-        sx += e0 * c_a.x + e1 * c_a.w + e2 * c_b.z + e3 * c_c.y;
-        sy += e0 * c_a.y + e1 * c_b.x + e2 * c_b.w + e3 * c_c.z;
-        sz += e0 * c_a.z + e1 * c_b.y + e2 * c_c.x + e3 * c_c.w;
+        sx += e0 * q.cx[0] + e1 * q.cx[1] + e2 * q.cx[2] + e3 * q.cx[3];
+        sy += e0 * q.cy[0] + e1 * q.cy[1] + e2 * q.cy[2] + e3 * q.cy[3];
+        sz += e0 * q.cz[0] + e1 * q.cz[1] + e2 * q.cz[2] + e3 * q.cz[3];
     }
     l = block_reduce_sum(l, sm);
     sx = block_reduce_sum(sx, sm);
@@ -88,25 +65,24 @@ __global__ __launch_bounds__(256) void softargmax_finish_kernel(const float* __r
                                                                 float* __restrict__ joints, int voxels, int mode, int splits) {
     const int row = blockIdx.y, s = blockIdx.x;
     const float* part = scratch + (size_t)row * splits * SE_SA_PART;
-    // The first wave folds the row's partials ONCE per workgroup, in a fixed order (lane k takes chunks k, k + 64, ... in sequence, then
-    // a butterfly over the lanes): bitwise deterministic, every workgroup of the row gets the identical (M, L).  (Until round 4 every
-    // thread folded all partials itself: with 256 chunks per row - batch 1 - that was 256 expf per thread, 214 us per launch.)
-    // A chunk is skipped only when it is EMPTY (k * chunk >= voxels), never for the value of its partial sums: a NaN logit makes its
-    // chunk's l NaN, and that must reach L, the joints and the whole row of volumes as it does through torch.softmax + einsum in
-    // the reference (utils/op.py:83-96)
+    // The first wave folds the row's records ONCE per workgroup in the order of row_reduce.h, rescaling each by expf(m - M): every
+    // workgroup of the row gets the identical (M, L).  (Until round 4 every thread folded all partials itself: with 256 chunks per
+    // row - batch 1 - that was 256 expf per thread, 214 us per launch.)  An empty chunk is skipped by position, never for the value
+    // of its sums: a NaN logit makes its chunk's l NaN, and that must reach L, the joints and the whole row of volumes as it does
+    // through torch.softmax + einsum in the reference (utils/op.py:83-96)
     __shared__ float fold[5];
-    const int chunk = (((voxels + splits - 1) / splits) + 3) & ~3;
+    const int chunk = se_row_chunk(voxels, splits);
     if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
         float M = -INFINITY;
         if (mode == 1) {
             for (int k = lane; k < splits; k += 64)
-                if (k * chunk < voxels) M = fmaxf(M, part[k * SE_SA_PART + 0]);
+                if (!SE_CHUNK_EMPTY(k, chunk, voxels)) M = fmaxf(M, part[k * SE_SA_PART + 0]);
             M = wave_reduce_max(M);
         }
         float L = 0.f, SX = 0.f, SY = 0.f, SZ = 0.f;
         for (int k = lane; k < splits; k += 64) {
-            if (k * chunk >= voxels) continue;
+            if (SE_CHUNK_EMPTY(k, chunk, voxels)) continue;
             const float* p = part + k * SE_SA_PART;
             const float f = (mode == 1) ? expf(p[0] - M) : 1.f;
             L += p[1] * f; SX += p[2] * f; SY += p[3] * f; SZ += p[4] * f;

@@ -24,14 +24,15 @@
 // the beliefs are returned.  The records are G x 32 B per row.  At 64^3 and 15 rows that is 110 MB per frame over a working set
 // (b, q, p: 47 MB) that does not fit the L2 but largely fits the Infinity Cache.  A restarted row reads p instead of a in the finish pass.
 //
-// SUMMATION ORDER.  No atomics.  A thread adds its voxels in ascending row order (G W / 256 <= 64 terms), the wave folds by a butterfly
-// (6), the four waves as (0 + 1) + (2 + 3) (2); the finish pass gives lane l the records l and l + 64 (2) and folds the lanes by a
-// butterfly (6).  L = 64 + 6 + 2 + 2 + 6 = 80 sequential float32 additions on the longest path of Z and of the joint sums
-// (SE_VF_CHAIN; G = 128).  Every order depends on the shape alone: the results are bitwise identical from run to run, and since a frame
-// sees only `state` and its own p they do not depend on how the frames are cut into calls.
+// SUMMATION ORDER.  No atomics.  A thread adds its voxels in ascending row order (G W / 256 <= 64 terms); the workgroup fold and the
+// record fold are those of row_reduce.h: the wave folds by a butterfly (6), the four waves as (0 + 1) + (2 + 3) (2); the finish pass
+// gives lane l the records l and l + 64 (2) and folds the lanes by a butterfly (6).  L = 64 + 6 + 2 + 2 + 6 = 80 sequential float32
+// additions on the longest path of Z and of the joint sums (SE_VF_CHAIN; G = 128).  Every order depends on the shape alone: the
+// results are bitwise identical from run to run, and since a frame sees only `state` and its own p they do not depend on how the
+// frames are cut into calls.
 #include <float.h>
 
-#include "common.h"
+#include "row_reduce.h"
 
 #define SE_VF_THREADS 256
 #define SE_VF_MAX_G 128
@@ -121,15 +122,8 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vf_update_kernel(const float* _
             }
         }
     }
-#pragma unroll
-    for (int x = 0; x < 7; ++x) acc[x] = wave_reduce_sum(acc[x]);
-    const int wid = t >> 6;
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int x = 0; x < 7; ++x) sm[wid][x] = acc[x];
-    }
-    __syncthreads();
-    if (t < 7) part[((size_t)row * G + j) * SE_VF_PART + t] = (sm[0][t] + sm[1][t]) + (sm[2][t] + sm[3][t]);
+    block_fold_stage<7, SE_VF_PART>(acc, sm);
+    if (t < 7) part[((size_t)row * G + j) * SE_VF_PART + t] = block_fold_sum<SE_VF_PART>(sm, t);
 }
 
 // grid (chunks, rows), block 256
@@ -144,13 +138,7 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vf_finish_kernel(const float* _
     const int t = threadIdx.x, row = blockIdx.y;
     if (t < 64) {
         float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int j = t; j < G; j += 64) {
-            const float* p = part + ((size_t)row * G + j) * SE_VF_PART;
-#pragma unroll
-            for (int x = 0; x < 7; ++x) acc[x] += p[x];
-        }
-#pragma unroll
-        for (int x = 0; x < 7; ++x) acc[x] = wave_reduce_sum(acc[x]);
+        wave_fold_records<7, SE_VF_PART>(part, (size_t)row * G, G, t, acc);
         if (t == 0) {
 #pragma unroll
             for (int x = 0; x < 7; ++x) fin[x] = acc[x];

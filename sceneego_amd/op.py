@@ -182,6 +182,31 @@ def integrate_tensor_3d_with_coordinates(volumes, coord_volumes, softmax=True):
     return joints, out_vol
 
 
+def _volume_args(what, volumes, coord_volumes, joints=None, cubic=False):
+    """What the operators over the softmaxed volumes check alike: ``volumes`` [B,J,X,Y,Z] float32 on a HIP device (X = Y = Z when
+    ``cubic``), ``coord_volumes`` [>=1,X,Y,Z,3], ``joints`` None or [B,J,3] on a HIP device.  Returns B, J, (X, Y, Z) and the flat
+    float32 [X Y Z, 3] coordinates of sample 0 on the device of the volumes."""
+    _lib.require_hip(volumes, joints)
+    if volumes.dim() != 5 or volumes.dtype != torch.float32 or (cubic and not volumes.shape[2] == volumes.shape[3] == volumes.shape[4]):
+        raise _lib.HipExtensionError("%s: volumes must be [B,J,%s] float32, got %s %s"
+                                     % (what, "G,G,G" if cubic else "X,Y,Z", tuple(volumes.shape), volumes.dtype))
+    B, J = int(volumes.shape[0]), int(volumes.shape[1])
+    shape = tuple(int(v) for v in volumes.shape[2:])
+    if tuple(coord_volumes.shape[1:]) != shape + (3,) or coord_volumes.shape[0] < 1:
+        raise _lib.HipExtensionError("%s: coord_volumes %s does not match volumes %s"
+                                     % (what, tuple(coord_volumes.shape), tuple(volumes.shape)))
+    if joints is not None and tuple(joints.shape) != (B, J, 3):
+        raise _lib.HipExtensionError("%s: joints %s, expected %s" % (what, tuple(joints.shape), (B, J, 3)))
+    return B, J, shape, coord_volumes[0].to(device=volumes.device, dtype=torch.float32).contiguous()
+
+
+def _per_frame(result, keys, size_key):
+    """A dict of device tensors with a leading batch dimension as a list of per-frame dicts of numpy arrays (``keys`` without the
+    batch dimension; ``size_key`` names the entry whose length is the batch)."""
+    host = {k: result[k].cpu().numpy() for k in keys}
+    return [{k: host[k][b].copy() for k in keys} for b in range(host[size_key].shape[0])]
+
+
 STAT_KEYS = ("cov", "sigma", "entropy", "peak_prob", "peak_index", "peak_coord")
 
 
@@ -200,17 +225,7 @@ def joint_statistics(volumes, coord_volumes, joints, scratch=None):
 
     A (sample, joint) whose volume holds a NaN gets NaN in every float entry and peak_index -1.  ``scratch``: an optional float32
     workspace of at least ``_lib.joint_stats_scratch_elems(B * J)`` elements (allocated per call otherwise)."""
-    _lib.require_hip(volumes, joints)
-    if volumes.dim() != 5 or volumes.dtype != torch.float32:
-        raise _lib.HipExtensionError("joint_statistics: volumes must be [B,J,X,Y,Z] float32, got %s %s"
-                                     % (tuple(volumes.shape), volumes.dtype))
-    B, J, X, Y, Z = volumes.shape
-    if tuple(coord_volumes.shape[1:]) != (X, Y, Z, 3) or coord_volumes.shape[0] < 1:
-        raise _lib.HipExtensionError("joint_statistics: coord_volumes %s does not match volumes %s"
-                                     % (tuple(coord_volumes.shape), tuple(volumes.shape)))
-    if tuple(joints.shape) != (B, J, 3):
-        raise _lib.HipExtensionError("joint_statistics: joints %s, expected %s" % (tuple(joints.shape), (B, J, 3)))
-    coord = coord_volumes[0].to(device=volumes.device, dtype=torch.float32).contiguous()
+    B, J, (X, Y, Z), coord = _volume_args("joint_statistics", volumes, coord_volumes, joints)
     return _joint_statistics_flat(volumes.contiguous(), coord, joints.contiguous().float(), B, J, X * Y * Z, scratch)
 
 
@@ -229,8 +244,7 @@ def _joint_statistics_flat(vol, coord, joints, B, J, N, scratch):
 def joint_statistics_to_numpy(stats):
     """The dict of ``joint_statistics`` as a list of per-frame dicts of numpy arrays (the keys without the batch dimension): what
     demo.py --stats and run_sequence.py --stats_output write."""
-    host = {k: stats[k].cpu().numpy() for k in STAT_KEYS}
-    return [{k: host[k][b].copy() for k in STAT_KEYS} for b in range(host["sigma"].shape[0])]
+    return _per_frame(stats, STAT_KEYS, "sigma")
 
 
 SCENE_KEYS = ("nearest_dist", "nearest_point", "nearest_index", "range", "sight_index", "in_view", "clearance", "bone_clearance",
@@ -303,21 +317,12 @@ def constrained_joints(volumes, coord_volumes, free, joints=None, scratch=None):
     Masking and renormalising is a convention, not validated against annotated data, and the mean of a masked distribution is not
     itself guaranteed to lie in free space.  A (sample, joint) whose volume holds a NaN keeps its input joint, with NaN in free_mass,
     free_peak_prob and free_peak_coord and index -1."""
-    _lib.require_hip(volumes, free, joints)
-    if volumes.dim() != 5 or volumes.dtype != torch.float32:
-        raise _lib.HipExtensionError("constrained_joints: volumes must be [B,J,X,Y,Z] float32, got %s %s"
-                                     % (tuple(volumes.shape), volumes.dtype))
-    B, J, X, Y, Z = volumes.shape
+    _lib.require_hip(free)
+    B, J, (X, Y, Z), coord = _volume_args("constrained_joints", volumes, coord_volumes, joints)
     N = X * Y * Z
-    if tuple(coord_volumes.shape[1:]) != (X, Y, Z, 3) or coord_volumes.shape[0] < 1:
-        raise _lib.HipExtensionError("constrained_joints: coord_volumes %s does not match volumes %s"
-                                     % (tuple(coord_volumes.shape), tuple(volumes.shape)))
     if free.dtype != torch.uint8 or free.shape[0] != B or free.numel() != B * N:
         raise _lib.HipExtensionError("constrained_joints: free must be uint8 [%d,%d,%d,%d], got %s %s"
                                      % (B, X, Y, Z, tuple(free.shape), free.dtype))
-    if joints is not None and tuple(joints.shape) != (B, J, 3):
-        raise _lib.HipExtensionError("constrained_joints: joints %s, expected %s" % (tuple(joints.shape), (B, J, 3)))
-    coord = coord_volumes[0].to(device=volumes.device, dtype=torch.float32).contiguous()
     return _constrained_joints_flat(volumes.contiguous(), coord, free.contiguous(),
                                     None if joints is None else joints.contiguous().float(), B, J, N, scratch)
 
@@ -342,8 +347,7 @@ def scene_constraint_to_numpy(result):
     """The dict of ``VoxelNetwork_depth.constrain_to_scene`` / ``constrained_joints`` as a list of per-frame dicts of numpy arrays (the
     keys without the batch dimension and without the ``free`` mask): what demo.py --constrained_dir and run_sequence.py
     --constrain_output write."""
-    host = {k: result[k].cpu().numpy() for k in CONSTRAINT_KEYS}
-    return [{k: host[k][b].copy() for k in CONSTRAINT_KEYS} for b in range(host["free_mass"].shape[0])]
+    return _per_frame(result, CONSTRAINT_KEYS, "free_mass")
 
 
 # ----------------------------------------------------------------------------------------------
@@ -371,15 +375,7 @@ def joint_modes(volumes, coord_volumes, k=4, radius=2, min_prob=0.0, min_rel=0.0
 
     A (sample, joint) whose volume holds a NaN gets NaN in every float entry, index -1, count = total = -1 and no valid mode.
     ``scratch``: an optional uint8 workspace of at least ``_lib.joint_modes_scratch_bytes(B * J, G, k)`` bytes."""
-    _lib.require_hip(volumes)
-    if volumes.dim() != 5 or volumes.dtype != torch.float32 or not volumes.shape[2] == volumes.shape[3] == volumes.shape[4]:
-        raise _lib.HipExtensionError("joint_modes: volumes must be [B,J,G,G,G] float32, got %s %s"
-                                     % (tuple(volumes.shape), volumes.dtype))
-    B, J, G = int(volumes.shape[0]), int(volumes.shape[1]), int(volumes.shape[2])
-    if tuple(coord_volumes.shape[1:]) != (G, G, G, 3) or coord_volumes.shape[0] < 1:
-        raise _lib.HipExtensionError("joint_modes: coord_volumes %s does not match volumes %s"
-                                     % (tuple(coord_volumes.shape), tuple(volumes.shape)))
-    coord = coord_volumes[0].to(device=volumes.device, dtype=torch.float32).contiguous()
+    B, J, (G, _, _), coord = _volume_args("joint_modes", volumes, coord_volumes, cubic=True)
     return _joint_modes_flat(volumes.contiguous(), coord, B, J, G, k, radius, min_prob, min_rel, scratch)
 
 
@@ -407,8 +403,7 @@ def _joint_modes_flat(vol, coord, B, J, G, k, radius, min_prob, min_rel, scratch
 def joint_modes_to_numpy(result):
     """The dict of ``joint_modes`` / ``VoxelNetwork_depth.joint_modes`` as a list of per-frame dicts of numpy arrays (the keys without
     the batch dimension): what demo.py --modes and run_sequence.py --modes_output write."""
-    host = {k: result[k].cpu().numpy() for k in MODES_KEYS}
-    return [{k: host[k][b].copy() for k in MODES_KEYS} for b in range(host["mass"].shape[0])]
+    return _per_frame(result, MODES_KEYS, "mass")
 
 
 # ----------------------------------------------------------------------------------------------
@@ -420,6 +415,4 @@ FILTER_KEYS = ("joints", "evidence", "restarted")
 def volume_filter_to_numpy(result):
     """The dict of ``VolumeFilter.step`` as a list of per-frame dicts of numpy arrays (the keys without the batch dimension and
     without the ``beliefs``; ``shift`` when the step was given joints): what run_sequence.py --filter_info_output writes."""
-    keys = FILTER_KEYS + (("shift",) if "shift" in result else ())
-    host = {k: result[k].cpu().numpy() for k in keys}
-    return [{k: host[k][b].copy() for k in keys} for b in range(host["evidence"].shape[0])]
+    return _per_frame(result, FILTER_KEYS + (("shift",) if "shift" in result else ()), "evidence")
