@@ -166,7 +166,8 @@ int se_deconv2d_k4s2_assemble_f32(const float* z, const float* bias, float* out,
  *   gamma,beta,mean,var  BatchNorm3d weight/bias/running_mean/running_var [cout], or all NULL (no BN)
  *   wpack  out, se_conv3d_packed_elems(...) floats;  bpack out, cout_pad floats (cout rounded up to 16)
  * cin_pad >= cin is the channel count of the activation tensor the conv will read (multiple of 16;
- * extra channels get zero weights).                                                               */
+ * extra channels get zero weights).  The buffer's sections, their sizes and the value of every element:
+ * csrc/conv3d_pack.h; the kernels that write it: csrc/conv3d_pack.hip.                             */
 int se_conv3d_pack_f32(const float* w, const float* b, const float* gamma, const float* beta,
                        const float* mean, const float* var, float eps,
                        float* wpack, float* bpack,

@@ -600,6 +600,8 @@ def conv3d_algo(dim, cin, cout, ksize) -> int:
 
 
 def conv3d_pack(w, b, gamma, beta, mean, var, eps, wpack, bpack, cout, cin, cin_pad, ksize, transposed):
+    """Fold BatchNorm into the convolution and write the packed weights and bias (float32 format: csrc/conv3d_pack.h, written by
+    csrc/conv3d_pack.hip; bfloat16: csrc/conv3d_bf16.hip)."""
     require_hip(w, wpack, bpack)
     _chk_f32(w, b, gamma, beta, mean, var, bpack)
     if wpack.dtype == torch.bfloat16:

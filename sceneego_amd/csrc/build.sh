@@ -4,7 +4,7 @@
 #   --devtools  builds ../libsceneego_hip_dev.so instead (tools/ load it through SCENEEGO_HIP_LIB) with -DSE_DEVTOOLS: the A/B kernel selector (se_debug_set_variant), the retired kernel variants it selects
 #               (devtools/*.inc, included only under SE_DEVTOOLS) and the cycle-stamp hooks used by tools/.  The production library is built WITHOUT it.
 # Objects live in _obj/<key>/ where <key> hashes the compiler version and the flag line, so objects of another compiler or
-# another flag set are never reused; inside a key a source is rebuilt when it or a shared header is newer than its object.
+# another flag set are never reused; inside a key a source is rebuilt when it or any header is newer than its object.
 set -euo pipefail
 cd "$(dirname "$0")"
 OUT=../libsceneego_hip.so
@@ -15,13 +15,14 @@ KEY=$( (hipcc --version 2>/dev/null; echo "$FLAGS") | sha256sum | cut -c1-12)
 OBJ=_obj/$KEY
 mkdir -p "$OBJ"
 pids=()
-newer() {  # source $1, a shared header or (development builds) a devtools/ include newer than object $2
-  [ ! -f "$2" ] || [ "$1" -nt "$2" ] || [ common.h -nt "$2" ] || [ row_reduce.h -nt "$2" ] || [ conv_common.h -nt "$2" ] || [ conv3d_plan.h -nt "$2" ] || [ bf16_common.h -nt "$2" ] || [ wino67_matrices.h -nt "$2" ] || [ fft24.h -nt "$2" ] || [ ../../include/sceneego_hip.h -nt "$2" ] && return 0
+newer() {  # source $1, a header or (development builds) a devtools/ include newer than object $2
+  [ ! -f "$2" ] || [ "$1" -nt "$2" ] && return 0
+  for i in *.h ../../include/sceneego_hip.h; do [ "$i" -nt "$2" ] && return 0; done
   if [ -n "$DEV" ]; then for i in devtools/*.inc; do [ "$i" -nt "$2" ] && return 0; done; fi
   return 1
 }
 OBJS=()
-for f in voxelize gather softargmax joint_stats joint_modes volume_filter conv2d_1x1 conv2d_3x3 conv3d conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc render render_volume scene_probe scene_constraint; do
+for f in voxelize gather softargmax joint_stats joint_modes volume_filter conv2d_1x1 conv2d_3x3 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc render render_volume scene_probe scene_constraint; do
   [ -f $f.hip ] || { echo "build.sh: source $f.hip is missing" >&2; exit 1; }
   OBJS+=($OBJ/$f.o)
   extra=""
@@ -51,7 +52,7 @@ fi
 # the F(4,7) 7^3 kernel: one object per input layout (each takes minutes to compile: 390 unrolled MFMAs under sched_group_barrier)
 for v in 0 1; do
   OBJS+=($OBJ/conv3d_wino47_$v.o)
-  if newer conv3d_wino47.hip $OBJ/conv3d_wino47_$v.o || [ wino47_matrices.h -nt $OBJ/conv3d_wino47_$v.o ]; then
+  if newer conv3d_wino47.hip $OBJ/conv3d_wino47_$v.o; then
     hipcc $FLAGS -DSE_K7F_PLANAR=$v -c conv3d_wino47.hip -o $OBJ/conv3d_wino47_$v.o &
     pids+=($!)
   fi

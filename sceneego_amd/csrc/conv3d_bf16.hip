@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void pointwise_chain3_bf16_kernel(
 }
 
 // The same chain with pass 1 of the soft-argmax folded in (round 6; the float32 program has had this since round 4:
-// pointwise_chain3_sa_kernel in conv3d.hip, same chunking, same SE_SA_PART records, same fixed-order fold): the workgroup (chunk s,
+// pointwise_chain3_sa_kernel in conv3d_tail.hip, same chunking, same SE_SA_PART records, same fixed-order fold): the workgroup (chunk s,
 // sample b) owns the voxels [s * chunk, (s + 1) * chunk) of its sample, every lane keeps a running (max, sum exp, sum exp * coord) for its
 // 4 joints while the float32 logits are in registers, and softargmax_finish_kernel does pass 2.  Saves the two stand-alone launches of
 // se_softargmax3d_f32's pass 1 and their re-read of the logits (0.35 ms at B = 32).  Reference: utils/op.py:83-96.

@@ -14,10 +14,10 @@ enum SeConvKernel {
     SE_CONV_K7_WINO47_CL,    // 7^3: 1-D Winograd F(4,7), channels-last input
     SE_CONV_TILED_K3,        // LDS-tiled direct 3^3 (conv3d_tiled.hip); form: cout tiles per workgroup (4, 2, 1)
     SE_CONV_TILED_K7,        // LDS-tiled direct 7^3
-    SE_CONV_HALO64,          // small levels (conv3d.hip): 64-voxel tiles through LDS; form: dim (8, 16)
+    SE_CONV_HALO64,          // small levels (conv3d_small.hip): 64-voxel tiles through LDS; form: dim (8, 16)
     SE_CONV_WAVESPLIT,       // small levels: in-workgroup split-K; form: waves per workgroup (4: two cout tile pairs of 2 x 4 waves, 8, 16)
     SE_CONV_SPLITK_GRID,     // small levels: taps split over grid.z into the caller's workspace + reduce; `splits`
-    SE_CONV_DIRECT,          // any shape: activations straight from global memory; form: ksize
+    SE_CONV_DIRECT,          // any shape (conv3d_direct.hip): activations straight from global memory; form: ksize
 #ifdef SE_DEVTOOLS           // retired kernels, reachable only through se_debug_set_variant (devtools/*.inc, conv3d_wino44.hip)
     SE_CONV_DEV_WINO44,            // (63) F(4,3) x F(4,3), lockstep form; form: octet layout bits
     SE_CONV_DEV_WINO23_1D,         // (4) 1-D Winograd F(2,3)
@@ -49,14 +49,10 @@ bool se_conv3d_wino44pp_layout_ok(int cin, int flags);
 bool se_conv3d_wino44pp_fits(int batch, int dim, int cout);
 int se_conv3d_wino44pp_form(const ConvArgs& a);
 int se_conv3d_wino44pp_launch(const ConvArgs& a, int batch, int form, hipStream_t s);
-int se_conv3d_pack_wino44(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin, int cin_pad,
-                          long long elems, hipStream_t s);   // section I
 // conv3d_wino2d.hip
 bool se_conv3d_wino2d_fits(int batch, int dim, int cout);
 int se_conv3d_wino2d_form(const ConvArgs& a);
 int se_conv3d_wino2d_launch(const ConvArgs& a, int batch, int form, int exp, hipStream_t s);
-int se_conv3d_pack_wino2d(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin, int cin_pad,
-                          long long elems, hipStream_t s);   // section G
 // conv3d_wino.hip: the 1-D Winograd kernels; `kernel` is the plan's (SE_CONV_WINO43PP_1D, SE_CONV_K7_*, in development builds their
 // retired forms).  _fits: the unit table of `kernel` holds a launch of `batch` samples
 bool se_conv3d_wino1d_fits(int kernel, int batch, int dim, int cout, int num_cus);
@@ -70,6 +66,10 @@ int se_conv3d_k7_wino47_launch_cl(const ConvArgs& a, int batch, int num_cus, hip
 int se_conv3d_k7_wino47_launch_p3(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
 // conv3d_tiled.hip: SE_CONV_TILED_K3 / _K7 (development builds: the retired persistent direct kernels too)
 int se_conv3d_tiled_launch(const ConvArgs& a, int batch, int kernel, int form, hipStream_t s);
+// conv3d_small.hip: SE_CONV_HALO64 / _WAVESPLIT / _SPLITK_GRID, on the whole batch; reads p.kernel, p.form and p.splits
+int se_conv3d_small_launch(const ConvArgs& a, const SeConvPlan& p, hipStream_t s);
+// conv3d_direct.hip: SE_CONV_DIRECT, on the whole batch
+int se_conv3d_direct_launch(const ConvArgs& a, int ksize, hipStream_t s);
 #ifdef SE_DEVTOOLS
 // conv3d_wino44.hip
 bool se_conv3d_wino44_takes(const ConvArgs& a);

@@ -703,52 +703,6 @@ __global__ __launch_bounds__(512) void conv3d_k3_wino2d_kernel(ConvArgs a, const
 
 }  // namespace
 
-// Section G of the packed 3x3x3 weights (appended by se_conv3d_pack_f32): per (32-cout block cb, 8-channel chunk)
-//   [xi_z 6][q 2][dx 3][ct 2][lane 64][e 2][c 2] = U[xi_z][xi_y = 2q + e][dx] of cout cb*32 + ct*16 + (lane & 15),
-//   cin chunk*8 + 2*(lane >> 4) + c;  U = (G43 (x) G23) g over (dz, dy), times the folded BatchNorm scale.
-__global__ void pack_k3_wino2d_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ var,
-                                      float eps, float* __restrict__ out, int cout, int cin, int cin_pad, long long total) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= total) return;
-    const int e = (int)(t & 1);                 // channel of the k lane's pair
-    const int exi = (int)((t >> 1) & 1);        // xi_y inside the pair
-    const int lane = (int)((t >> 2) & 63);
-    long long r = t >> 8;
-    const int ct = (int)(r % 2); r /= 2;
-    const int dx = (int)(r % 3); r /= 3;
-    const int xy = (int)(r % 2) * 2 + exi; r /= 2;
-    const int xz = (int)(r % 6); r /= 6;
-    const int chunks = cin_pad / 8;
-    const int chunk = (int)(r % chunks);
-    const int cb = (int)(r / chunks);
-    const int co = cb * 32 + ct * 16 + (lane & 15);
-    const int ci = chunk * 8 + 2 * (lane >> 4) + e;
-    float v = 0.f;
-    if (co < cout && ci < cin) {
-        const float sc = gamma ? gamma[co] / sqrtf(var[co] + eps) : 1.f;
-        const float* wp = w + ((size_t)co * cin + ci) * 27 + dx;
-        // G of F(4,3), points {0, 1, -1, 2, -2, inf}; G of F(2,3)
-        const float gz[6][3] = {{0.25f, 0.f, 0.f},          {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
-                                {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0.f, 0.f, 1.f}};
-        const float gy[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
-        double u = 0.0;
-#pragma unroll
-        for (int kz = 0; kz < 3; ++kz)
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) u += (double)gz[xz][kz] * (double)gy[xy][ky] * (double)wp[kz * 9 + ky * 3];
-        v = (float)(u * (double)sc);
-    }
-    out[t] = v;
-}
-
-int se_conv3d_pack_wino2d(const float* w, const float* gamma, const float* var, float eps, float* out, int cout, int cin,
-                          int cin_pad, long long elems, hipStream_t s) {
-    hipLaunchKernelGGL(pack_k3_wino2d_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, w, gamma, var, eps, out, cout,
-                       cin, cin_pad, elems);
-    SE_CHECK_LAUNCH();
-    return 0;
-}
-
 // work units (4 x 8 x 16 tile, 32-cout block) of one launch: the kernel packs a unit index into 30 bits
 static long long wino2d_units(int batch, int dim, int cout) { return (long long)batch * (dim / 16) * (dim / 8) * (dim / 4) * (cout / 32); }
 bool se_conv3d_wino2d_fits(int batch, int dim, int cout) { return wino2d_units(batch, dim, cout) < (1LL << 30); }

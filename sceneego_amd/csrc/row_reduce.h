@@ -19,7 +19,7 @@
 // any reduction tree gives the same pair.  PEAK_NONE (-inf, INT_MAX) is its neutral element; it survives only where nothing was offered.
 // A NaN value is carried in the same pair as PEAK_NAN (+inf, -1), which wins every combine: a row whose folded index is negative
 // held a NaN.  In a record the peak follows the N sums: p at [N], the index's bits at [N + 1].
-// Who writes which records: softargmax.hip and the fused V2V tails (conv3d.hip, conv3d_bf16.hip) write SE_SA_PART records that
+// Who writes which records: softargmax.hip and the fused V2V tails (conv3d_tail.hip, conv3d_bf16.hip) write SE_SA_PART records that
 // softargmax_finish_kernel reads; joint_stats.hip and scene_constraint.hip write and fold their own; volume_filter.hip uses the
 // workgroup fold and the record fold over its G records per row (no peak, no empty record).
 //

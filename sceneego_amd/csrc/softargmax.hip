@@ -4,7 +4,7 @@
 //
 // Two launches, split-row (row_reduce.h states the scheme, the record and why the result is bitwise deterministic):
 //   pass 1: per chunk  m = max v, l = sum exp(v-m), s = sum exp(v-m) * coord      -> one SE_SA_PART record (m, l, sx, sy, sz) in scratch;
-//           the fused V2V tails (pointwise_chain3_sa_kernel in conv3d.hip, its bf16 twin) write the same records
+//           the fused V2V tails (pointwise_chain3_sa_kernel in conv3d_tail.hip, its bf16 twin) write the same records
 //   pass 2: every chunk re-derives the row's (M, L) from the row's records, writes exp(v-M)/L; chunk 0 also writes the joint.
 #include "row_reduce.h"
 

@@ -10,7 +10,7 @@ Two layers:
   published checkpoint loads strictly.  The modules own no arithmetic.
 * ``V2VProgram`` is what runs: built once from the tree (``V2VModel.compile``), it folds every eval-mode
   BatchNorm3d into its convolution, re-orders the weights into MFMA fragment order on the device
-  (``se_conv3d_pack_f32``) and walks the network's fixed structure, one kernel per Conv3d+BN(+ReLU)(+residual) /
+  (``se_conv3d_pack_f32``: csrc/conv3d_pack.hip, once per layer, here and never in a timed step) and walks the network's fixed structure, one kernel per Conv3d+BN(+ReLU)(+residual) /
   ConvTranspose3d+BN+ReLU(+skip) / max-pool.  What each launch looks like - tensor layouts (channels-last, quad- or
   octet-planar), flag words, fused skip / pooled / tail forms - is decided once per (batch, grid, input form, fused
   soft-argmax, fork set) by the pure function ``v2v_route`` and cached; ``run()`` only reads that table and launches.

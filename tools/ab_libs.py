@@ -3,7 +3,8 @@
 usage: python tools/ab_libs.py libA.so libB.so [...] [--shapes 0,3] [--rounds 12] [--batch 8] [--octet 3]
 
 Each library packs its own weights (se_conv3d_pack_f32) and runs the same input; per shape the median / min launch time per
-library and the max |difference| of every library's output to the first one's are printed.
+library, the max |difference| of every library's output to the first one's and whether its packed buffers (weights and bias)
+are byte-equal to the first one's are printed.
 """
 import argparse
 import ctypes
@@ -103,8 +104,9 @@ def main():
             t = sorted(times[i])
             med = t[len(t) // 2]
             diff = float((outs[i] - outs[0]).abs().max())
-            print(f"   {os.path.basename(p):32s} med {med:.4f} ms  min {t[0]:.4f}  ({flop / med / 1e9:.1f} TF/s direct-equivalent)  max|out - out[0]| {diff:.2e}",
-                  flush=True)
+            same = all(a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(packs[i], packs[0]))
+            print(f"   {os.path.basename(p):32s} med {med:.4f} ms  min {t[0]:.4f}  ({flop / med / 1e9:.1f} TF/s direct-equivalent)  max|out - out[0]| {diff:.2e}"
+                  f"  packed {'byte-equal' if same else 'DIFFERS'}", flush=True)
 
 
 if __name__ == "__main__":
