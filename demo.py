@@ -35,7 +35,8 @@ import torch
 
 from sceneego_amd import load_config, synth
 from sceneego_amd.jpeg_device import JpegFile, decode_jpeg_batch
-from sceneego_amd.op import joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy
+from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
+                             skeleton_couple_to_numpy)
 from sceneego_amd.preprocess import (DEPTH_CLAMP, load_depth, load_image_bgr, prepare_depth, preprocess_image,
                                      preprocess_image_device)
 from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
@@ -47,7 +48,8 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 
 class Demo:
     def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False,
-                 render_format="png", render_volumes=False, volume_joints=None, save_volumes=None, constrain=False, modes=0):
+                 render_format="png", render_volumes=False, volume_joints=None, save_volumes=None, constrain=False, modes=0,
+                 bone_lengths=None):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
@@ -65,6 +67,8 @@ class Demo:
         self.scene_check = scene_check
         self.constrain = constrain
         self.modes = int(modes)                # modes kept per joint; 0: off
+        self.bone_lengths = bone_lengths       # 14 or 15 metres: couple the joints over the skeleton (--skeleton_dir); None: off
+        self.skeleton = None
         self.scene = None
         self.items = []
         for img_name in sorted(os.listdir(img_dir)):
@@ -82,6 +86,8 @@ class Demo:
             self.network.load_state_dict(loads["state_dict"])
         self.network = self.network.to(self.device).eval()
         self.network.enable_graphs(True)       # batch 1: replay the captured forward
+        if self.bone_lengths is not None:
+            self.skeleton = self.network.skeleton_prior(self.bone_lengths)
 
     def run(self):
         results = []
@@ -121,6 +127,9 @@ class Demo:
                 if self.modes:
                     # likewise before the next frame
                     results[-1]["modes"] = joint_modes_to_numpy(self.network.joint_modes(volumes, k=self.modes))[0]
+                if self.skeleton is not None:
+                    # likewise before the next frame
+                    results[-1]["skeleton"] = skeleton_couple_to_numpy(self.skeleton.couple(volumes, joints=kp))[0]
                 if self.scene_check:
                     results[-1]["scene"] = scene_check_to_numpy(self.check_scene(depth, kp))[0]
                 if self.save_volumes is not None:
@@ -167,7 +176,7 @@ class Demo:
                  self.renderer.overlay_volumes(frame_u8, kp, volumes, side, depth=depth, joint_mask=self.volume_joints)[0])
 
 
-def parse_args(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="experiments/sceneego/test/sceneego.yaml")
     ap.add_argument("--img_dir", type=str, default="data/demo/imgs")
@@ -198,7 +207,19 @@ def parse_args(argv=None):
                     help="true: also write <img_name>.modes.pkl (the strongest peaks of every joint's volume: coord, peak_coord, "
                          "peak_prob, mass, index, count, total, valid)")
     ap.add_argument("--modes_k", type=int, default=4, help="with --modes true: modes kept per joint, 1..16")
-    args = ap.parse_args(argv)
+    ap.add_argument("--skeleton_dir", type=str, default=None,
+                    help="also write <img_name>.pkl here: the joints coupled over the kinematic tree with the bone lengths of "
+                         "--bone_lengths (float32 [15,3], readable by evaluate.py --pred_dir), and <img_name>.skeleton.pkl (evidence, "
+                         "coupled, bone_error, shift, bone_error_before)")
+    ap.add_argument("--bone_lengths", type=str, default=None,
+                    help="with --skeleton_dir: a .npy of 14 bone lengths in metres (edges 1..14 of the kinematic tree) or 15 (entry 0 ignored)")
+    return ap
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if (args.skeleton_dir is None) != (args.bone_lengths is None):
+        raise SystemExit("--skeleton_dir and --bone_lengths go together: single frames cannot estimate the bone lengths")
     if args.vis.lower() == "true":
         raise SystemExit("--vis true (open3d visualisation) is out of scope of this build")
     if args.stats.lower() not in ("true", "false"):
@@ -231,7 +252,8 @@ def main(argv=None):
     demo = Demo(config, args.img_dir, args.depth_dir, weights=args.weights, stats=args.stats, render_dir=args.render_dir,
                 scene_check=args.scene_check, render_format=args.render_format, render_volumes=args.render_volumes,
                 volume_joints=args.volume_joints, save_volumes=args.output_dir if args.save_volumes else None,
-                constrain=args.constrained_dir is not None, modes=args.modes_k if args.modes else 0)
+                constrain=args.constrained_dir is not None, modes=args.modes_k if args.modes else 0,
+                bone_lengths=np.load(args.bone_lengths) if args.bone_lengths is not None else None)
     os.makedirs(args.output_dir, exist_ok=True)
     if args.constrained_dir is not None:
         os.makedirs(args.constrained_dir, exist_ok=True)
@@ -256,6 +278,14 @@ def main(argv=None):
                 pickle.dump(np.asarray(c.pop("joints"), dtype=np.float32), f)      # [15,3], the format of the prediction
             with open(name + ".constraint.pkl", "wb") as f:
                 pickle.dump(c, f)                         # dict of numpy arrays, the other keys of op.CONSTRAINT_KEYS
+        if args.skeleton_dir is not None:
+            c = dict(r["skeleton"])
+            os.makedirs(args.skeleton_dir, exist_ok=True)
+            name = os.path.join(args.skeleton_dir, os.path.split(r["img_path"])[1])
+            with open(name + ".pkl", "wb") as f:
+                pickle.dump(np.asarray(c.pop("joints"), dtype=np.float32), f)      # [15,3], the format of the prediction
+            with open(name + ".skeleton.pkl", "wb") as f:
+                pickle.dump(c, f)                         # dict of numpy arrays, the other keys of op.SKELETON_KEYS
 
 
 if __name__ == "__main__":

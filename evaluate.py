@@ -28,7 +28,7 @@ def load_predictions(pred_dir):
             raise SystemExit(f"{pred_dir}: expected a list of [15,3] poses, got {poses.shape}")
         return ["%06d.pkl" % t for t in range(poses.shape[0])], poses
     names = sorted(n for n in os.listdir(pred_dir)
-                   if n.endswith(".pkl") and not n.endswith((".stats.pkl", ".scene.pkl", ".constraint.pkl", ".modes.pkl")))
+                   if n.endswith(".pkl") and not n.endswith((".stats.pkl", ".scene.pkl", ".constraint.pkl", ".modes.pkl", ".skeleton.pkl")))
     if not names:
         raise SystemExit(f"no .pkl predictions in {pred_dir}")
     poses = []
@@ -133,11 +133,12 @@ def evaluate(pred, gt, scale=True):
             "per_joint": M.per_joint_error(pred, gt).tolist(), "root_trajectory": M.root_trajectory_error(pred, gt)}
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--pred_dir", required=True, help="directory of <image name>.pkl files written by demo.py, or the one pickle of "
                     "run_sequence.py --output / --track_output")
-    ap.add_argument("--gt", required=True, help="pickle: dict name -> [15,3], or [T,15,3] in sorted file order")
+    ap.add_argument("--gt", default=None, help="pickle: dict name -> [15,3], or [T,15,3] in sorted file order (required unless --bones "
+                    "is all that is asked for)")
     ap.add_argument("--no-scale", action="store_true", help="rigid instead of similarity alignment (align_skeleton(scale=False))")
     ap.add_argument("--unit", default="m", help="label only; the numbers are in the unit of the inputs")
     ap.add_argument("--stats", default=None, help="joint statistics of the same frames: a directory of <image name>.stats.pkl files "
@@ -147,8 +148,28 @@ def main(argv=None):
                     "(demo.py --scene_check true) or the one pickle of run_sequence.py --scene_output; adds the plausibility summary")
     ap.add_argument("--modes", default=None, help="joint modes of the same frames: a directory of <image name>.modes.pkl files "
                     "(demo.py --modes true) or the one pickle of run_sequence.py --modes_output; adds the best-of-K MPJPE")
-    args = ap.parse_args(argv)
+    ap.add_argument("--bones", nargs="?", const="", default=None, metavar="FILE.npy",
+                    help="bone-length summary of the predictions (needs no ground truth): the per-bone standard deviation over the "
+                    "sequence and, with FILE.npy (14 or 15 lengths, as run_sequence.py --bone_lengths takes them), the mean absolute "
+                    "deviation from them")
+    return ap
+
+
+def bones(pred, path, unit="m"):
+    """--bones: metrics.bone_length_summary of the predictions, printed."""
+    from sceneego_amd import metrics as M
+    s = M.bone_length_summary(pred, np.load(path) if path else None)
+    print(M.format_bone_length_summary(s, unit))
+    return s
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     names, pred = load_predictions(args.pred_dir)
+    if args.gt is None:
+        if args.bones is None:
+            raise SystemExit("--gt is required (only --bones works without it)")
+        return {"frames": int(pred.shape[0]), "bones": bones(pred, args.bones, args.unit)}
     with open(args.gt, "rb") as f:
         gt = match_ground_truth(pickle.load(f), names)
     r = evaluate(pred, gt, scale=not args.no_scale)
@@ -169,6 +190,8 @@ def main(argv=None):
         r.update(best_of_k(load_modes(args.modes, names), pred, gt))
         print(f"best-of-K MPJPE {r['best_of_k_mpjpe']:.6f} {args.unit} (the closest valid mode of every joint); the best mode is not "
               f"mode 0 in {r['best_not_first_share']:.1%} of {r['joints_with_modes']} joints")
+    if args.bones is not None:
+        r["bones"] = bones(pred, args.bones, args.unit)
     return r
 
 

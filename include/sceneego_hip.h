@@ -683,6 +683,62 @@ int se_volume_filter_f32(const float* prob, const float* coord, const float* tap
                          int G, int radius, float floor, const int* have_prior, void* stream);
 long long se_volume_filter_scratch_bytes(int rows, int G, int radius);
 
+/* Skeleton-coupled joints: sum-product belief propagation over the kinematic tree of the joint volumes, with a spherical-shell
+ * bone-length factor on every edge (sceneego_amd/skeleton_prior.py: SkeletonPrior; VoxelNetwork_depth.skeleton_prior returns one).  The
+ * reference forces bone lengths onto a finished pose (utils/skeleton.py: kinematic_parents, _skeleton_resize); this couples the whole
+ * distributions inside one frame - the in-frame counterpart of se_volume_filter_f32.  A convention, not a calibrated model: the softmaxed
+ * volume is read as a likelihood, a Gaussian shell of width tau as the bone model and a uniform floor as the chance that the bone prior
+ * is wrong for an edge.  The beliefs have the shape and the meaning of the volumes.  tests/skeleton_prior_model.py restates the
+ * definition in float64.
+ * TREE       J joints, 1..32; parent[j] < j for j >= 1 and parent[0] = 0 (HOST int array, read during the call).  ch(j): the children of j
+ *            in ascending order.  The reference's kinematic_parents {0,0,1,2,0,4,5,1,7,8,9,4,11,12,13} is one; the fifteenth line of its
+ *            Skeleton.lines, hip to hip (7, 11), closes a loop and is not part of the tree.
+ * TAPS       [rows][(2R+1)^3] float32 on the DEVICE, row j the edge parent[j] -> j (row 0 is unused), dense, index
+ *            ((di+R)(2R+1) + dj+R)(2R+1) + dk+R.  The caller computes them in float64 and rounds to float32:
+ *            w(d) = exp(-(|d| h - L_j)^2 / (2 tau^2)), exactly 0 where | |d| h - L_j | > 3 tau, normalised to sum 1; h the voxel edge.
+ *            R in 0..min(24, G - 1) covers every edge: R = ceil((max L + 3 tau) / h).
+ * CORRELATE  corr(a, w)(x) = sum over d with w(d) != 0 and x + d inside the grid of w(d) a(x + d): zero-padded (mass that leaves the grid
+ *            is lost), exact-zero taps are skipped.  The Python layer builds symmetric taps (w(d) = w(-d)), so one operator serves both
+ *            directions; the entry points do not check the symmetry.
+ * UPWARD     j = J-1 .. 1:  A_j = p_j prod_{c in ch(j)} U_c,  s_j = sum A_j,  U_j = (1 - floor) corr(A_j, w_j) / s_j + floor / N
+ * DOWNWARD   j = 0 .. J-1 (D_0 absent):  T_j = p_j D_j prod_c U_c,  Z_j = sum T_j,  b_j = T_j / Z_j,  joints_j = (sum T_j coord) / Z_j;
+ *            then for each child c:  E = p_j D_j prod_{c' != c} U_c',  t_c = sum E,  D_c = (1 - floor) corr(E, w_c) / t_c + floor / N
+ *            Products are taken left to right (p, D, the U in ascending order) in float32; 1 - floor and floor / N are float32.
+ * FALLBACK   a frame falls back when any of its s_j, t_c, Z_j is not a finite number > 0 (a NaN or inf anywhere in the frame's volumes
+ *            gets there through the sums).  Then all J beliefs of that frame are p, copied bit for bit, joints = sum p coord and
+ *            coupled = 0; evidence still holds the Z_j as computed.  Other frames are unaffected.
+ *   prob       [frames][J][voxels] float32 probabilities; voxels = G^3, flat index n = (i G + j) G + k; frames are independent
+ *   coord      [voxels][3] float32 voxel-centre coordinates
+ *   beliefs    NULL or [frames][J][voxels] float32         joints  [frames][J][3] float32
+ *   evidence   [frames][J] float32: Z_j, how well joint j's own volume agrees with what the rest of the skeleton predicts for it
+ *   coupled    [frames] int32: 1, or 0 where the frame fell back
+ *   scratch    se_skeleton_couple_scratch_bytes(frames, J, G, R) bytes, 4-byte aligned; 0 for a shape out of range.  About 3 J G^3
+ *              floats for each of min(frames, 4) frames: longer calls walk their frames in groups of four.
+ * The tree is processed by depth level: per level a product-and-sum pass, a fold of the sums and one correlation launch for all the
+ * level's edges and frames (33 launches and one for the run table with the reference tree, per group of four frames).  No atomics; every sum
+ * is taken in an order fixed by the shape and the taps alone (skeleton_prior.hip states it): a correlation output is a chain of at most
+ * SE_SK_SHELL_CHAIN(R) roundings, a row sum one of at most SE_SK_SUM_CHAIN.  Bitwise identical from run to run and independent of how
+ * frames are batched into calls.  Allocates nothing (legal inside hipGraph capture).
+ * SE_ERR_BAD_ARG, with nothing launched: a null pointer other than beliefs, a pointer that is not 4-byte aligned, J outside 1..32,
+ * parent[0] != 0 or a parent[j] outside 0..j-1, G outside 2..128, voxels != G^3, R outside 0..min(24, G - 1), floor outside [0, 1] or
+ * NaN, frames < 1, scratch_bytes below se_skeleton_couple_scratch_bytes(frames, J, G, R).
+ *
+ * se_shell_correlate_f32 is the hot path on its own:  out[r] = scale_mul * corr(a[r], taps[tap_row[r]]) / s[r] + add  for `rows`
+ * volumes a[r] of G^3 float32 (computed as fmaf(scale_mul, corr / s[r], add)); s [rows] float32 and tap_row [rows] int32 are read from
+ * DEVICE memory; taps [tap_rows][(2R+1)^3].  A tap_row outside 0..tap_rows-1 fills its row with NaN.  scratch:
+ * se_shell_correlate_scratch_bytes(tap_rows, R) bytes for the run table (per column of a block the first and the last run of non-zero
+ * taps), built by a small launch before the correlation.  SE_ERR_BAD_ARG: a null or misaligned pointer, out == a, rows or tap_rows
+ * outside 1..65535, G outside 2..128, R outside 0..min(24, G - 1), a short scratch.                                                  */
+#define SE_SK_SHELL_CHAIN(R) ((2 * (R) + 1) * (2 * (R) + 1) + 2 * (R))
+#define SE_SK_SUM_CHAIN 142
+int se_shell_correlate_f32(const float* a, const float* taps, const int* tap_row, const float* s, float* out, void* scratch,
+                           long long scratch_bytes, int rows, int tap_rows, int G, int R, float scale_mul, float add, void* stream);
+long long se_shell_correlate_scratch_bytes(int tap_rows, int R);
+int se_skeleton_couple_f32(const float* prob, const float* coord, const float* taps, const int* parent, float* beliefs, float* joints,
+                           float* evidence, int* coupled, void* scratch, long long scratch_bytes, int frames, int J, int voxels, int G,
+                           int R, float floor, void* stream);
+long long se_skeleton_couple_scratch_bytes(int frames, int J, int G, int R);
+
 /* Baseline JPEG encoder (no counterpart in the reference; sceneego_amd/jpeg_encode.py writes the file headers around it).
  *   frames    uint8 [batch][height][width][3] on the device, R, G, B (bgr = 0) or B, G, R (bgr = 1); any height, width in 1..65535
  *   quant_luma, quant_chroma   HOST pointers: unsigned short [64], natural order, every value in 1..255 (baseline tables)

@@ -11,6 +11,8 @@
                            [--modes_output out/no_body_diogo1.modes.pkl [--modes_k 4] [--track_output out/tracked.pkl [--track_sigma 0.1]]]
                            [--filter_output out/filtered.pkl [--filter_info_output out/filter.pkl] [--filter_sigma 0.1]
                             [--filter_radius R] [--filter_floor 1e-3]] [--render_volumes filtered]
+                           [--skeleton_output out/skeleton.pkl [--skeleton_info_output out/skeleton_info.pkl] [--bone_lengths FILE.npy]
+                            [--bone_frames 64] [--skeleton_tau 0.03] [--skeleton_floor 1e-3]] [--render_volumes coupled]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -45,6 +47,14 @@ blurred by a Gaussian step of ``--filter_sigma`` metres truncated at ``--filter_
 across the pipelined streams; ``--filter_info_output`` adds the per-frame dicts (joints, evidence, restarted, shift) and
 ``--render_volumes filtered`` draws the beliefs instead of the raw volumes.  It prints its MPJPE beside the soft-argmax's: the volume
 as likelihood, the Gaussian step and the floor are a convention, not calibrated.
+``--skeleton_output`` writes a pickle in the format of ``--output`` whose joints are coupled over the kinematic tree inside every frame
+(``VoxelNetwork_depth.skeleton_prior``, ``sceneego_amd/skeleton_prior.py``: belief propagation over the fifteen volumes with a
+bone-length shell of ``--skeleton_tau`` metres on every edge and a uniform floor ``--skeleton_floor``), per batch on the stream the
+batch ran on.  The bone lengths come from ``--bone_lengths`` (a .npy of 14 or 15 metres) or, without it, from a first forward pass over
+at most ``--bone_frames`` evenly spaced frames (``estimate_bone_lengths``: the per-bone median of the soft-argmax joints' distances).
+``--skeleton_info_output`` adds the per-frame dicts (joints, evidence, coupled, bone_error, shift, bone_error_before) and
+``--render_volumes coupled`` draws the coupled beliefs.  With ``--filter_output`` as well the order is couple, then filter: the filter
+runs on the coupled beliefs.  The volume as likelihood, the shell and the floor are a convention, not calibrated.
 """
 import argparse
 import json
@@ -225,7 +235,7 @@ class SequenceRunner:
     @torch.no_grad()
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
-            volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False):
+            volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -236,18 +246,40 @@ class SequenceRunner:
         dicts (``VoxelNetwork_depth.joint_modes(k=modes)``) are appended after those.  ``filter``: a dict of ``sigma`` / ``radius`` /
         ``floor`` for ``VoxelNetwork_depth.volume_filter``: the whole sequence is one track, filtered batch by batch in frame order on
         the stream each batch ran on, and the per-frame filter dicts are appended last; ``render_filtered`` (with ``render_volumes``)
-        draws its beliefs instead of the raw volumes."""
+        draws its beliefs instead of the raw volumes.  ``skeleton``: a dict of ``bone_lengths`` / ``tau`` / ``floor`` for
+        ``VoxelNetwork_depth.skeleton_prior``: every batch's joints are coupled over the kinematic tree on the stream the batch ran on
+        and the per-frame skeleton dicts are appended after the filter's; ``render_coupled`` (with ``render_volumes``) draws the
+        coupled beliefs.  With ``filter`` as well the order is couple, then filter: the filter runs on the coupled beliefs (its
+        ``shift`` is still measured from the soft-argmax joints)."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
-                                     volume_filter_to_numpy)
+                                     skeleton_couple_to_numpy, volume_filter_to_numpy)
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
         preds, frame_stats, frame_scene, pending = [], [], [], []
-        frame_constraint, frame_scene_constrained, frame_modes, frame_filter = [], [], [], []
+        frame_constraint, frame_scene_constrained, frame_modes, frame_filter, frame_skeleton = [], [], [], [], []
         if render_filtered and (filter is None or not render_volumes):
             raise ValueError("render_filtered needs filter and render_volumes")
         vf = self.net.volume_filter(**filter) if filter is not None else None
+        if render_coupled and (skeleton is None or not render_volumes or render_filtered):
+            raise ValueError("render_coupled needs skeleton and render_volumes, and excludes render_filtered")
+        sp = self.net.skeleton_prior(**skeleton) if skeleton is not None else None
+
+        def couple_and_filter(vol, kp, job, stream=None):
+            """The skeleton coupling and the filter of one batch, in that order: (filter dict, skeleton dict, job)."""
+            fr = sk = None
+            if sp is not None:
+                sk = sp.couple(vol, joints=kp, return_beliefs=vf is not None or (render_coupled and job is not None), stream=stream)
+                if vf is not None:
+                    vol = sk["beliefs"]
+                if render_coupled and job is not None:
+                    job = job[:-1] + (sk["beliefs"],)
+            if vf is not None:
+                fr = vf.step(vol, joints=kp, return_beliefs=render_filtered and job is not None, stream=stream)
+                if "beliefs" in fr:
+                    job = job[:-1] + (fr["beliefs"],)
+            return fr, sk, job
 
         rendering = render_dir is not None or render_video is not None
         if rendering:
@@ -263,7 +295,7 @@ class SequenceRunner:
 
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done, job, sc, con, md, fr = pending.pop(0)
+                kp, st, done, job, sc, con, md, fr, sk = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 kp_host = kp.cpu().numpy()
@@ -280,6 +312,8 @@ class SequenceRunner:
                     frame_modes.extend(joint_modes_to_numpy(md))
                 if fr is not None:
                     frame_filter.extend(volume_filter_to_numpy(fr))
+                if sk is not None:
+                    frame_skeleton.extend(skeleton_couple_to_numpy(sk))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -304,20 +338,16 @@ class SequenceRunner:
                     if constrain:
                         c = self.net.constrain_to_scene(vol, kp, depth)
                         con = (c, self._scene().check(depth, c["joints"]) if scene else None)
-                    fr = None
-                    if vf is not None:                                    # before the next forward overwrites the volumes
-                        fr = vf.step(vol, joints=kp, return_beliefs=render_filtered and job is not None)
-                        if "beliefs" in fr:
-                            job = job[:-1] + (fr["beliefs"],)
+                    fr, sk, job = couple_and_filter(vol, kp, job)         # before the next forward overwrites the volumes
                     pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
                                     self._scene().check(depth, kp) if scene else None, con,
-                                    self.net.joint_modes(vol, k=modes) if modes else None, fr))
+                                    self.net.joint_modes(vol, k=modes) if modes else None, fr, sk))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
-                    st = sc = con = md = fr = None
-                    if stats or scene or constrain or modes or vf is not None:
+                    st = sc = con = md = fr = sk = None
+                    if stats or scene or constrain or modes or vf is not None or sp is not None:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
@@ -330,14 +360,12 @@ class SequenceRunner:
                                 con = (c, self._scene(stream.cuda_stream).check(depth, c["joints"]) if scene else None)
                             if modes:
                                 md = net.joint_modes(vol, k=modes)
-                            if vf is not None:
-                                # one filter for all slots: its own event chain makes this stream wait for the step of the batch before
-                                fr = vf.step(vol, joints=kp, return_beliefs=render_filtered and job is not None, stream=stream)
-                                if "beliefs" in fr:
-                                    job = job[:-1] + (fr["beliefs"],)
+                            # one filter for all slots: its own event chain makes this stream wait for the step of the batch before;
+                            # one skeleton prior too: it carries no state and keeps one workspace per stream
+                            fr, sk, job = couple_and_filter(vol, kp, job, stream)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done, job, sc, con, md, fr))
+                    pending.append((kp, st, done, job, sc, con, md, fr, sk))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             try:
                 drain(0)
@@ -345,11 +373,12 @@ class SequenceRunner:
                 if self.video is not None:
                     self.video.close()
                     self.video = None
-        if not (stats or scene or constrain or modes or vf is not None):
+        if not (stats or scene or constrain or modes or vf is not None or sp is not None):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
             + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
-            + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ())
+            + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ()) \
+            + ((frame_skeleton,) if sp is not None else ())
 
 
 def _size(text):
@@ -411,6 +440,17 @@ def build_parser():
     ap.add_argument("--filter_radius", type=int, default=None, help="voxels the Gaussian step is truncated at, 0..16 "
                     "(default: min(16, G - 1, ceil(3 sigma / voxel edge)))")
     ap.add_argument("--filter_floor", type=float, default=1e-3, help="the filter's uniform floor in [0, 1]: the chance of a jump")
+    ap.add_argument("--skeleton_output", default=None, help="pickle in the format of --output holding the joints coupled over the "
+                    "kinematic tree inside every frame (sceneego_amd/skeleton_prior.py: a convention, not calibrated)")
+    ap.add_argument("--skeleton_info_output", default=None, help="pickle of the per-frame skeleton dicts (list of dicts of numpy arrays: "
+                    "joints, evidence, coupled, bone_error, shift, bone_error_before)")
+    ap.add_argument("--bone_lengths", default=None, help="a .npy of 14 bone lengths in metres (edges 1..14 of the kinematic tree) or 15 "
+                    "(entry 0 ignored); default: estimated from a first pass over --bone_frames frames")
+    ap.add_argument("--bone_frames", type=int, default=64, help="without --bone_lengths: at most this many evenly spaced frames feed "
+                    "the bone-length estimate")
+    ap.add_argument("--skeleton_tau", type=float, default=0.03, help="the width of the bone-length shell in metres")
+    ap.add_argument("--skeleton_floor", type=float, default=1e-3, help="the skeleton prior's uniform floor in [0, 1]: the chance that "
+                    "the bone prior is wrong for an edge")
     ap.add_argument("--render_format", default="png", choices=("png", "jpg"),
                     help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG files encoded on the device)")
     ap.add_argument("--render_video", default=None, help="write the picked frames as one Motion-JPEG AVI (4:2:0, encoded on the device)")
@@ -422,17 +462,19 @@ def build_parser():
     ap.add_argument("--render_volumes", default="false",
                     help="true (with --render_dir / --render_video): also write <img_name>.volumes.render.* and .volumes.overlay.* (the "
                          "joint probability volumes drawn over the pair); the video shows the volume views.  filtered: the same with the "
-                         "beliefs of the grid Bayes filter (--filter_sigma, --filter_radius, --filter_floor) instead of the raw volumes")
+                         "beliefs of the grid Bayes filter (--filter_sigma, --filter_radius, --filter_floor) instead of the raw volumes; "
+                         "coupled: with the skeleton-coupled beliefs (--skeleton_tau, --skeleton_floor)")
     ap.add_argument("--volume_joints", default=None, help="with --render_volumes true: the joints to draw, e.g. 9,10,13,14 (default: all)")
     return ap
 
 
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
-    if args.render_volumes.lower() not in ("true", "false", "filtered"):
-        raise SystemExit("--render_volumes must be true, false or filtered")
+    if args.render_volumes.lower() not in ("true", "false", "filtered", "coupled"):
+        raise SystemExit("--render_volumes must be true, false, filtered or coupled")
     args.render_filtered = args.render_volumes.lower() == "filtered"
-    args.render_volumes = args.render_volumes.lower() in ("true", "filtered")
+    args.render_coupled = args.render_volumes.lower() == "coupled"
+    args.render_volumes = args.render_volumes.lower() in ("true", "filtered", "coupled")
     if args.render_volumes and args.render_dir is None and args.render_video is None:
         raise SystemExit("--render_volumes true / filtered needs --render_dir or --render_video")
     if args.volume_joints is not None and not args.render_volumes:
@@ -446,6 +488,13 @@ def parse_args(argv=None):
     args.filter = None
     if args.filter_output is not None or args.filter_info_output is not None or args.render_filtered:
         args.filter = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor}
+    if not (args.skeleton_tau > 0 and args.skeleton_tau != float("inf")):
+        raise SystemExit("--skeleton_tau must be a finite number > 0")
+    if not 0.0 <= args.skeleton_floor <= 1.0:
+        raise SystemExit("--skeleton_floor must lie in [0, 1]")
+    if args.bone_frames < 1:
+        raise SystemExit("--bone_frames must be >= 1")
+    args.skeleton = args.skeleton_output is not None or args.skeleton_info_output is not None or args.render_coupled
     if args.track_output is not None and args.modes_output is None:
         raise SystemExit("--track_output needs --modes_output")
     if not 1 <= args.modes_k <= 16:
@@ -471,6 +520,18 @@ def main(argv=None):
     print(f"dataset length: {len(images)}")
     runner = SequenceRunner(config, weights=args.weights, streams=args.streams, depth_decode=args.depth_decode,
                             workers=args.workers, image_decode=args.image_decode)
+    skeleton = None
+    if args.skeleton:
+        from sceneego_amd.skeleton_prior import estimate_bone_lengths
+        if args.bone_lengths is not None:
+            lengths = np.load(args.bone_lengths)
+        else:
+            # a first pass over at most --bone_frames evenly spaced frames: the per-bone median of the raw joints' distances
+            pick = sorted({int(round(v)) for v in np.linspace(0, len(images) - 1, min(args.bone_frames, len(images)))})
+            raw = runner.run([images[k] for k in pick], [depths[k] for k in pick], config.test.batch_size)
+            lengths = estimate_bone_lengths(np.stack(raw))
+            print(f"bone lengths estimated from {len(pick)} frames: " + " ".join(f"{v:.4f}" for v in lengths[1:]))
+        skeleton = {"bone_lengths": lengths, "tau": args.skeleton_tau, "floor": args.skeleton_floor}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     want_stats = args.stats_output is not None
@@ -483,8 +544,8 @@ def main(argv=None):
                        render_video=args.render_video, render_fps=args.render_fps, render_view=args.render_view,
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
                        volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
-                       filter=args.filter, render_filtered=args.render_filtered)
-    if want_stats or want_scene or want_constraint or want_modes or want_filter:
+                       filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled)
+    if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
         frame_scene = extra.pop(0) if want_scene else None
@@ -492,6 +553,7 @@ def main(argv=None):
         frame_scene_constrained = extra.pop(0) if want_constraint and want_scene else None
         frame_modes = extra.pop(0) if want_modes else None
         frame_filter = extra.pop(0) if want_filter else None
+        frame_skeleton = extra.pop(0) if skeleton is not None else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -554,6 +616,20 @@ def main(argv=None):
         print("filtered volumes (a convention, not calibrated): mpjpe: {}, mean shift {:.4f} m, {} restarts after the first frame".format(
             result["filtered_mpjpe"], float(np.mean([fr["shift"] for fr in frame_filter])),
             int(sum(fr["restarted"].sum() for fr in frame_filter[1:]))))
+    if skeleton is not None:
+        coupled = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_skeleton]
+        for path, obj in ((args.skeleton_output, coupled), (args.skeleton_info_output, frame_skeleton)):
+            if path is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "wb") as f:
+                    pickle.dump(obj, f)
+        result["coupled"], result["skeleton"], result["bone_lengths"] = coupled, frame_skeleton, np.asarray(lengths, dtype=np.float64)
+        result["coupled_mpjpe"] = M.mpjpe(np.stack(coupled).astype(np.float64), gt)
+        print("skeleton-coupled joints (a convention, not calibrated): mpjpe: {}, mean shift {:.4f} m, mean bone error {:.4f} -> {:.4f} m, "
+              "{} frames fell back".format(result["coupled_mpjpe"], float(np.mean([fr["shift"] for fr in frame_skeleton])),
+                                           float(np.mean([fr["bone_error_before"] for fr in frame_skeleton])),
+                                           float(np.mean([fr["bone_error"] for fr in frame_skeleton])),
+                                           int(sum(not fr["coupled"] for fr in frame_skeleton))))
     return result
 
 

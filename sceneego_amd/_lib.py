@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -113,6 +113,10 @@ SIGNATURES = {
     "se_joint_modes_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
     "se_volume_filter_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_volume_filter_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "se_shell_correlate_scratch_bytes": (_ll, [_i, _i]),
+    "se_shell_correlate_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _f, _vp]),
+    "se_skeleton_couple_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_skeleton_couple_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -1019,6 +1023,9 @@ SCENE_PROBE_SLOTS = 8      # nearest_q, nearest point x y z, c.c, sight_dot, sur
 # Skeleton.lines of the reference (utils/skeleton.py:20-21), the table csrc/render.hip holds as c_bones
 SKELETON_LINES = ((0, 1), (0, 4), (1, 2), (2, 3), (4, 5), (5, 6), (1, 7), (4, 11), (7, 8), (8, 9), (9, 10), (11, 12), (12, 13), (13, 14),
                   (7, 11))
+# Skeleton.kinematic_parents of the reference (utils/skeleton.py): the tree csrc/skeleton_prior.hip couples the joints over.  Its
+# fourteen edges are the first fourteen SKELETON_LINES; the fifteenth, hip to hip (7, 11), closes a loop and is not part of the tree.
+KINEMATIC_PARENTS = (0, 0, 1, 2, 0, 4, 5, 1, 7, 8, 9, 4, 11, 12, 13)
 
 
 def scene_probe_scratch_bytes(batch, height, width, probes) -> int:
@@ -1179,6 +1186,98 @@ def volume_filter(prob, coord, taps, state, belief_out, joints, evidence, restar
                                        _ptr(evidence), _ptr(restarted), _ptr(scratch), scratch.numel(), frames, rows, voxels, grid,
                                        radius, floor, _ptr(have_prior), _stream()), "se_volume_filter_f32")
     return joints, evidence, restarted
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Skeleton-coupled joints (csrc/skeleton_prior.hip; sceneego_amd/skeleton_prior.py drives it)
+SKELETON_MAX_JOINTS, SKELETON_MAX_GRID, SKELETON_MAX_RADIUS = 32, 128, 24
+SKELETON_SUM_CHAIN = 142   # sequential float32 additions on the longest path of a row sum s, t, Z (csrc/skeleton_prior.hip: L)
+
+
+def SHELL_CHAIN(radius) -> int:
+    """T(R) = (2R+1)^2 + 2R: the roundings on the longest path of one output of the shell correlation (csrc/skeleton_prior.hip: one
+    chain of fused multiply-adds per di-plane, the planes added in sequence).  Never more than the block's non-zero taps."""
+    radius = int(radius)
+    return (2 * radius + 1) ** 2 + 2 * radius
+
+
+def _skeleton_shape(what, grid, radius):
+    if not 2 <= grid <= SKELETON_MAX_GRID:
+        raise HipExtensionError(f"{what}: grid = {grid} (2..{SKELETON_MAX_GRID}) expected")
+    if not 0 <= radius <= min(SKELETON_MAX_RADIUS, grid - 1):
+        raise HipExtensionError(f"{what}: radius = {radius} (0..{min(SKELETON_MAX_RADIUS, grid - 1)}) expected")
+
+
+def shell_correlate_scratch_bytes(tap_rows, radius) -> int:
+    return int(load().se_shell_correlate_scratch_bytes(int(tap_rows), int(radius)))
+
+
+def shell_correlate(a, taps, tap_row, s, out, rows, grid, radius, scale_mul=1.0, add=0.0, scratch=None):
+    """se_shell_correlate_f32: ``out[r] = scale_mul * corr(a[r], taps[tap_row[r]]) / s[r] + add`` for the ``rows`` volumes ``a``
+    [rows, grid^3]; ``taps`` [tap_rows, (2 radius + 1)^3] float32, ``tap_row`` [rows] int32 and ``s`` [rows] float32 on the device (the
+    header states the correlation).  ``scratch``: an optional uint8 workspace of at least ``shell_correlate_scratch_bytes(tap_rows,
+    radius)`` bytes.  Every argument is checked here and a bad one raises HipExtensionError before anything is launched."""
+    what = "shell_correlate"
+    rows, grid, radius, scale_mul, add = int(rows), int(grid), int(radius), float(scale_mul), float(add)
+    if not 1 <= rows <= 65535:
+        raise HipExtensionError(f"{what}: rows = {rows} (1..65535) expected")
+    _skeleton_shape(what, grid, radius)
+    voxels, block = grid ** 3, (2 * radius + 1) ** 3
+    dev = _check_args(what, (("a", a, torch.float32, rows * voxels), ("taps", taps, torch.float32, (None, block)),
+                             ("tap_row", tap_row, torch.int32, rows), ("s", s, torch.float32, rows),
+                             ("out", out, torch.float32, rows * voxels)), (("scratch", scratch, torch.uint8, None),))
+    tap_rows = int(taps.shape[0])
+    if not 1 <= tap_rows <= 65535:
+        raise HipExtensionError(f"{what}: taps holds {tap_rows} blocks, 1..65535 expected")
+    if out.data_ptr() == a.data_ptr():
+        raise HipExtensionError(f"{what}: out must not alias a")
+    scratch = _scratch(what, scratch, shell_correlate_scratch_bytes(tap_rows, radius), torch.uint8, dev)
+    _check(load().se_shell_correlate_f32(_ptr(a), _ptr(taps), _ptr(tap_row), _ptr(s), _ptr(out), _ptr(scratch), scratch.numel(), rows,
+                                         tap_rows, grid, radius, scale_mul, add, _stream()), "se_shell_correlate_f32")
+    return out
+
+
+def skeleton_couple_scratch_bytes(frames, joints, grid, radius) -> int:
+    return int(load().se_skeleton_couple_scratch_bytes(int(frames), int(joints), int(grid), int(radius)))
+
+
+def skeleton_couple(prob, coord, taps, parents, beliefs, joints, evidence, coupled, frames, voxels, grid, radius, floor, scratch=None):
+    """se_skeleton_couple_f32: belief propagation over the tree ``parents`` (a sequence of J ints, parents[0] = 0, parents[j] < j) on
+    ``prob`` [frames, J, voxels] (voxels = grid^3) with the shell taps ``taps`` [J, (2 radius + 1)^3] on the device (the header states
+    the definition).  ``beliefs`` None or [frames, J, voxels]; ``joints`` [frames, J, 3], ``evidence`` [frames, J] float32 and
+    ``coupled`` [frames] int32 are written.  ``scratch``: an optional uint8 workspace of at least ``skeleton_couple_scratch_bytes(
+    frames, J, grid, radius)`` bytes.  Every argument is checked here and a bad one raises HipExtensionError before anything is
+    launched: the kernels trust the sizes they are given."""
+    what = "skeleton_couple"
+    try:
+        parents = [int(v) for v in parents]
+    except (TypeError, ValueError):
+        raise HipExtensionError(f"{what}: parents must be a sequence of integers") from None
+    J = len(parents)
+    frames, voxels, grid, radius, floor = int(frames), int(voxels), int(grid), int(radius), float(floor)
+    if not 1 <= J <= SKELETON_MAX_JOINTS or parents[0] != 0 or any(not 0 <= parents[j] < j for j in range(1, J)):
+        raise HipExtensionError(f"{what}: parents = {parents}: 1..{SKELETON_MAX_JOINTS} joints with parents[0] = 0 and "
+                                "0 <= parents[j] < j expected")
+    if frames < 1:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1) expected")
+    _skeleton_shape(what, grid, radius)
+    if voxels != grid ** 3:
+        raise HipExtensionError(f"{what}: voxels = {voxels} is not grid^3 = {grid ** 3}")
+    if not 0.0 <= floor <= 1.0:
+        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    dev = _check_args(what, (("prob", prob, torch.float32, frames * J * voxels), ("coord", coord, torch.float32, voxels * 3),
+                             ("taps", taps, torch.float32, J * (2 * radius + 1) ** 3),
+                             ("joints", joints, torch.float32, frames * J * 3), ("evidence", evidence, torch.float32, frames * J),
+                             ("coupled", coupled, torch.int32, frames)),
+                      (("beliefs", beliefs, torch.float32, frames * J * voxels), ("scratch", scratch, torch.uint8, None)))
+    if beliefs is not None and beliefs.data_ptr() == prob.data_ptr():
+        raise HipExtensionError(f"{what}: beliefs must not alias prob")
+    scratch = _scratch(what, scratch, skeleton_couple_scratch_bytes(frames, J, grid, radius), torch.uint8, dev)
+    par = (ctypes.c_int * J)(*parents)
+    _check(load().se_skeleton_couple_f32(_ptr(prob), _ptr(coord), _ptr(taps), ctypes.cast(par, ctypes.c_void_p), _ptr(beliefs),
+                                         _ptr(joints), _ptr(evidence), _ptr(coupled), _ptr(scratch), scratch.numel(), frames, J,
+                                         voxels, grid, radius, floor, _stream()), "se_skeleton_couple_f32")
+    return joints, evidence, coupled
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

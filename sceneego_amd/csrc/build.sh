@@ -22,7 +22,7 @@ newer() {  # source $1, a header or (development builds) a devtools/ include new
   return 1
 }
 OBJS=()
-for f in voxelize gather softargmax joint_stats joint_modes volume_filter conv2d_1x1 conv2d_3x3 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc render render_volume scene_probe scene_constraint; do
+for f in voxelize gather softargmax joint_stats joint_modes volume_filter skeleton_prior conv2d_1x1 conv2d_3x3 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc render render_volume scene_probe scene_constraint; do
   [ -f $f.hip ] || { echo "build.sh: source $f.hip is missing" >&2; exit 1; }
   OBJS+=($OBJ/$f.o)
   extra=""

@@ -1,0 +1,444 @@
+// Skeleton-coupled joints: sum-product belief propagation over the kinematic tree of the joint volumes, with a spherical-shell
+// bone-length factor on every edge (sceneego_amd/skeleton_prior.py: SkeletonPrior; VoxelNetwork_depth.skeleton_prior returns one).
+// The reference forces bone lengths onto a finished pose (utils/skeleton.py: _skeleton_resize); this runs on the whole distributions.
+// include/sceneego_hip.h states the definition; tests/skeleton_prior_model.py restates it in float64.
+//
+// THE CORRELATION (se_shell_correlate_f32; 2 (J - 1) of them per frame inside se_skeleton_couple_f32)
+//     out(x) = scale_mul * (sum over d with w(d) != 0 and x + d inside the grid of w(d) a(x + d)) / s + add
+// with w a dense (2R+1)^3 block that is mostly zero: a shell.
+//   sk_runs_kernel      grid (2R+1, tap rows), block 64: for one di-plane of one block, lane dk finds in the column w(di, ., dk) the first
+//                       and the last maximal run of non-zero taps along dj and whether anything non-zero lies between them (for a
+//                       shell: two runs, or one, and nothing between); entry 2R+1 of the plane says whether the plane has a tap at all.
+//                       (2R+1) x (2R+2) records of 4 ints per block, built once per call.
+//   sk_correlate_kernel grid (G x ceil(G/16) x ceil(G/64), rows), block 256: a workgroup owns the outputs (i, 16 rows j, 64 columns k)
+//                       of one volume; lane = k, a wave owns SK_JR = 4 consecutive j.  For every di whose plane has a tap and lies inside
+//                       the grid, the source plane i + di is staged in LDS with a zero halo of R rows and R columns ((16 + 2R) x (64 + 2R)
+//                       floats: 20.8 KB at R = 18), so the loops below carry no bounds test.  Then for dk ascending and dj ascending over
+//                       the column's runs the taps - wave-uniform, read through scalar loads - are taken four at a time: 4 LDS reads
+//                       (consecutive lanes, consecutive addresses: no bank conflict) feed 16 fused multiply-adds, the window of 7 rows
+//                       a lane holds slides down by 4 with 3 values carried in registers.  A run's last 1..3 taps and the taps between
+//                       the two runs go one at a time (4 reads, 4 FMAs; between the runs each tap is tested and a zero is skipped).
+//                       LDS reads per FMA: 1/4 in the groups of four, 1 in the tails.
+// SUMMATION ORDER of one output: inside a plane one chain of fused multiply-adds, dk ascending, then dj ascending, started from 0; the
+// planes' sums are added in ascending di.  The longest chain is therefore
+//     T(R) = (2R+1)^2 + 2R            (SE_SK_SHELL_CHAIN(R); never more than the non-zero taps: every plane that is added holds one)
+// roundings, 1405 at R = 18 against about 15,000 taps.  It depends on the taps alone.
+//
+// THE TREE (se_skeleton_couple_f32).  Joints are processed by depth level: a call is a chain of launches bounded by the tree, not the batch.
+//   upward, depth d = deepest .. 1:   sk_product_kernel  A_j = p_j prod_c U_c for every j of the level, with the chunk sums of A_j
+//                                     sk_fold_kernel     s_j
+//                                     sk_correlate_kernel U_j = (1 - floor) corr(A_j, w_j) / s_j + floor / N
+//   downward, depth d = 0 .. deepest: sk_product_kernel  T_j = p_j D_j prod_c U_c (with the chunk sums Z, sum T c, sum p c) for every j
+//                                                        of the level and E_c = p_j D_j prod_{c' != c} U_c' (chunk sum t_c) for every
+//                                                        child c of such a j, in one launch
+//                                     sk_fold_kernel     Z_j, the joint sums, t_c
+//                                     sk_correlate_kernel D_c = (1 - floor) corr(E_c, w_c) / t_c + floor / N
+//   sk_finish_kernel    b_j = T_j / Z_j, joints, evidence, coupled - or, when one of the frame's s, t, Z is not a finite number > 0, the
+//                       copy of p and sum p c.
+// The reference tree (depths 0..5) takes 15 + 17 + 1 = 33 launches and the run table's one.  Products are taken left to right: p, then D, then
+// the children's U in ascending order.  Scratch per frame: A / E, U (T_j overwrites U_j, which nobody reads once level depth(j) of the
+// downward pass begins) and D: 3 J N floats, the chunk records and the folded sums; frames are walked in groups of SK_GROUP inside
+// the call, so the scratch does not grow with the batch.
+// SUMS.  No atomics.  A row of N values is cut into CH = min(64, ceil(N / 256)) chunks of ceil(N / CH) values, one workgroup each: thread
+// t adds the values t, t + 256, ... of its chunk in sequence (<= 128 terms at 128^3), the workgroup folds them by row_reduce.h
+// (butterfly 6, four waves 2), sk_fold_kernel gives lane l record l (CH <= 64: one each) and folds the lanes by a butterfly (6):
+// L = 128 + 6 + 2 + 6 = 142 (SE_SK_SUM_CHAIN).  The chunk rule depends on N alone - not on the rows of a launch, as se_sa_splits does - so a
+// frame's results are bitwise identical from run to run and do not depend on how frames are batched into calls or groups.
+#include <float.h>
+
+#include <initializer_list>
+
+#include "row_reduce.h"
+
+#define SK_THREADS 256
+#define SK_MAX_J 32
+#define SK_MAX_G 128
+#define SK_MAX_R 24
+#define SK_TJ 16                 // output rows j per workgroup
+#define SK_JR 4                  // ... per wave
+#define SK_KC 64                 // output columns k per workgroup: one per lane
+#define SK_PART 8                // one chunk record: sum, sum v c (x y z), sum p c (x y z), pad
+#define SK_MAX_CH 64
+#define SK_GROUP 4               // frames in flight inside se_skeleton_couple_f32
+#define SK_MAX_ITEMS (2 * SK_MAX_J)
+
+namespace {
+
+struct SkTree {
+    int J;
+    signed char parent[SK_MAX_J];
+};
+// one product of sk_product_kernel: kind 0 = A_j (into A[j]; sum s_j), 1 = T_j (into U[j]; Z_j and the joint sums), 2 = E_c for child
+// c = excl of j (into A[c]; sum t_c)
+struct SkItems {
+    int n;
+    unsigned char j[SK_MAX_ITEMS];
+    signed char excl[SK_MAX_ITEMS];
+    unsigned char kind[SK_MAX_ITEMS];
+};
+// rows of a correlation launch inside the tree: row r = (frame r / n, joint slot[r % n])
+struct SkRows {
+    int n;
+    unsigned char slot[SK_MAX_J];
+};
+
+__host__ __device__ inline int sk_chunks(int voxels) { return min(SK_MAX_CH, (voxels + 255) / 256); }
+__host__ __device__ inline int sk_chunk(int voxels) { const int ch = sk_chunks(voxels); return (voxels + ch - 1) / ch; }
+inline long long sk_runs_ints(int tap_rows, int R) { return (long long)tap_rows * (2 * R + 1) * (2 * R + 2) * 4; }
+
+// grid (2R+1, tap_rows), block 64
+__global__ __launch_bounds__(64) void sk_runs_kernel(const float* __restrict__ taps, int* __restrict__ runs, int R) {
+    const int W = 2 * R + 1, t = threadIdx.x, dI = blockIdx.x, row = blockIdx.y;
+    const float* w = taps + (size_t)row * W * W * W + (size_t)dI * W * W;
+    int lo1 = 1, hi1 = 0, lo2 = 1, hi2 = 0, mid = 0;                     // dj + R; lo > hi: empty
+    if (t < W) {
+        int a = 0;
+        while (a < W && w[a * W + t] == 0.f) ++a;
+        if (a < W) {
+            int b = a;
+            while (b + 1 < W && w[(b + 1) * W + t] != 0.f) ++b;
+            lo1 = a; hi1 = b;
+            int d = W - 1;
+            while (w[d * W + t] == 0.f) --d;                             // stops at b at the latest
+            if (d > b) {
+                int c = d;
+                while (w[(c - 1) * W + t] != 0.f) --c;                   // stops above b: w[b + 1] is zero
+                lo2 = c; hi2 = d;
+                for (int e = b + 1; e < c; ++e) mid |= w[e * W + t] != 0.f;
+            }
+        }
+    }
+    const int any = __syncthreads_or(lo1 <= hi1);
+    int* o = runs + (((size_t)row * W + dI) * (W + 1)) * 4;
+    if (t < W) { o[t * 4 + 0] = lo1; o[t * 4 + 1] = hi1; o[t * 4 + 2] = lo2; o[t * 4 + 3] = hi2 | (mid << 8); }
+    if (t == 0) { o[W * 4 + 0] = any; o[W * 4 + 1] = 0; o[W * 4 + 2] = 0; o[W * 4 + 3] = 0; }
+}
+
+// the taps lo..hi (dj + R) of one column, all non-zero: four at a time, then one at a time.  wp: the column's taps at dj + R = 0, stride W;
+// lp: the lane's LDS value under output row 0 and dj + R = 0, stride LW.
+__device__ __forceinline__ void sk_run(const float* __restrict__ wp, int W, const float* lp, int LW, int lo, int hi, float (&acc)[SK_JR]) {
+    int d = lo;
+    if (d + 3 <= hi) {
+        float v0 = lp[(d + 0) * LW], v1 = lp[(d + 1) * LW], v2 = lp[(d + 2) * LW];
+        for (; d + 3 <= hi; d += 4) {
+            const float w0 = wp[(d + 0) * W], w1 = wp[(d + 1) * W], w2 = wp[(d + 2) * W], w3 = wp[(d + 3) * W];
+            const float v3 = lp[(d + 3) * LW], v4 = lp[(d + 4) * LW], v5 = lp[(d + 5) * LW], v6 = lp[(d + 6) * LW];
+            acc[0] = fmaf(w0, v0, acc[0]); acc[1] = fmaf(w0, v1, acc[1]); acc[2] = fmaf(w0, v2, acc[2]); acc[3] = fmaf(w0, v3, acc[3]);
+            acc[0] = fmaf(w1, v1, acc[0]); acc[1] = fmaf(w1, v2, acc[1]); acc[2] = fmaf(w1, v3, acc[2]); acc[3] = fmaf(w1, v4, acc[3]);
+            acc[0] = fmaf(w2, v2, acc[0]); acc[1] = fmaf(w2, v3, acc[1]); acc[2] = fmaf(w2, v4, acc[2]); acc[3] = fmaf(w2, v5, acc[3]);
+            acc[0] = fmaf(w3, v3, acc[0]); acc[1] = fmaf(w3, v4, acc[1]); acc[2] = fmaf(w3, v5, acc[2]); acc[3] = fmaf(w3, v6, acc[3]);
+            v0 = v4; v1 = v5; v2 = v6;
+        }
+    }
+    for (; d <= hi; ++d) {
+        const float w = wp[d * W];
+#pragma unroll
+        for (int x = 0; x < SK_JR; ++x) acc[x] = fmaf(w, lp[(d + x) * LW], acc[x]);
+    }
+}
+static_assert(SK_JR == 4, "sk_run is written out for four rows per lane");
+
+// grid (G * ceil(G / SK_TJ) * ceil(G / SK_KC), rows), block 256, dynamic LDS (SK_TJ + 2R)(SK_KC + 2R) floats.
+// tap_row != NULL (se_shell_correlate_f32): row r reads a + r N, taps[tap_row[r]], s[r] and writes out + r N; a tap_row outside
+// 0..tap_rows-1 fills the row with NaN.  tap_row == NULL (inside the tree): row r is joint map.slot[r % map.n] of frame r / map.n in
+// [frame][J][N] buffers, its taps are the joint's and its s is s[(frame J + joint) s_stride].
+__global__ __launch_bounds__(SK_THREADS) void sk_correlate_kernel(const float* __restrict__ a, const float* __restrict__ taps,
+                                                                  const int* __restrict__ tap_row, const float* __restrict__ s,
+                                                                  int s_stride, float* __restrict__ out, const int* __restrict__ runs,
+                                                                  SkRows map, int J, int tap_rows, int G, int R, float scale_mul,
+                                                                  float add) {
+    extern __shared__ __align__(16) float lds[];
+    const int t = threadIdx.x, kl = t & 63, wv = t >> 6;
+    const int W = 2 * R + 1, LW = SK_KC + 2 * R, LH = SK_TJ + 2 * R;
+    const int jt_n = (G + SK_TJ - 1) / SK_TJ, kc_n = (G + SK_KC - 1) / SK_KC;
+    int bx = blockIdx.x;
+    const int kc = bx % kc_n; bx /= kc_n;
+    const int jt = bx % jt_n;
+    const int i = bx / jt_n;
+    const size_t N = (size_t)G * G * G;
+    size_t row;
+    int tr;
+    float sval;
+    if (tap_row) {
+        row = blockIdx.y;
+        tr = tap_row[row];
+        sval = s[row];
+    } else {
+        const int f = blockIdx.y / map.n;
+        tr = map.slot[blockIdx.y % map.n];
+        row = (size_t)f * J + tr;
+        sval = s[row * s_stride];
+    }
+    const float* in = a + row * N;
+    float* o = out + row * N;
+    const int k = kc * SK_KC + kl, j0 = jt * SK_TJ + wv * SK_JR;
+    if (tr < 0 || tr >= tap_rows) {                                      // uniform
+        if (k < G)
+            for (int x = 0; x < SK_JR; ++x)
+                if (j0 + x < G) o[((size_t)i * G + j0 + x) * G + k] = __int_as_float(0x7fc00000);
+        return;
+    }
+    const float* wt = taps + (size_t)tr * W * W * W;
+    const int* rn = runs + (size_t)tr * W * (W + 1) * 4;
+    float total[SK_JR] = {0.f, 0.f, 0.f, 0.f};
+    const int dlo = max(-R, -i), dhi = min(R, G - 1 - i);
+    for (int di = dlo; di <= dhi; ++di) {
+        const int* rp = rn + (size_t)(di + R) * (W + 1) * 4;
+        if (!rp[W * 4]) continue;                                        // uniform: the plane has no tap
+        __syncthreads();                                                 // everyone is done with the plane before
+        const float* src = in + (size_t)(i + di) * G * G;
+        for (int r = wv; r < LH; r += 4) {
+            const int jj = jt * SK_TJ + r - R;
+            for (int c = kl; c < LW; c += 64) {
+                const int kk = kc * SK_KC + c - R;
+                float v = 0.f;
+                if (jj >= 0 && jj < G && kk >= 0 && kk < G) v = src[jj * G + kk];
+                lds[r * LW + c] = v;
+            }
+        }
+        __syncthreads();
+        float acc[SK_JR] = {0.f, 0.f, 0.f, 0.f};
+        for (int dk = 0; dk < W; ++dk) {                                 // dk + R
+            const int lo1 = rp[dk * 4 + 0], hi1 = rp[dk * 4 + 1], lo2 = rp[dk * 4 + 2], h2 = rp[dk * 4 + 3];
+            if (lo1 > hi1) continue;
+            const float* wp = wt + (size_t)(di + R) * W * W + dk;
+            const float* lp = lds + (wv * SK_JR) * LW + kl + dk;         // row (wv JR + x) + (dj + R), column kl + (dk + R)
+            sk_run(wp, W, lp, LW, lo1, hi1, acc);
+            const int hi2 = h2 & 0xff;
+            if (lo2 <= hi2) {
+                if (h2 >> 8) {
+                    for (int d = hi1 + 1; d < lo2; ++d) {
+                        const float w = wp[d * W];
+                        if (w != 0.f) {
+#pragma unroll
+                            for (int x = 0; x < SK_JR; ++x) acc[x] = fmaf(w, lp[(d + x) * LW], acc[x]);
+                        }
+                    }
+                }
+                sk_run(wp, W, lp, LW, lo2, hi2, acc);
+            }
+        }
+#pragma unroll
+        for (int x = 0; x < SK_JR; ++x) total[x] += acc[x];
+    }
+    if (k < G) {
+#pragma unroll
+        for (int x = 0; x < SK_JR; ++x)
+            if (j0 + x < G) o[((size_t)i * G + j0 + x) * G + k] = fmaf(scale_mul, total[x] / sval, add);
+    }
+}
+
+// grid (CH, items * frames), block 256.  All buffers [frames][J][N]; part [frames][items][CH][SK_PART].
+__global__ __launch_bounds__(SK_THREADS) void sk_product_kernel(const float* __restrict__ prob, const float* __restrict__ coord,
+                                                                const float* __restrict__ U, const float* __restrict__ D,
+                                                                float* __restrict__ A, float* __restrict__ Tout, float* __restrict__ part,
+                                                                SkTree tree, SkItems items, int voxels) {
+    __shared__ float sm[4][SK_PART];
+    const int t = threadIdx.x, it = blockIdx.y % items.n, f = blockIdx.y / items.n;
+    const int J = tree.J, j = items.j[it], excl = items.excl[it], kind = items.kind[it];
+    const size_t fb = (size_t)f * J * voxels;
+    const float* p = prob + fb + (size_t)j * voxels;
+    const float* d = (kind != 0 && j > 0) ? D + fb + (size_t)j * voxels : nullptr;
+    float* o = kind == 1 ? Tout + fb + (size_t)j * voxels : A + fb + (size_t)(kind == 2 ? excl : j) * voxels;
+    const int chunk = sk_chunk(voxels), c0 = blockIdx.x * chunk, c1 = min(c0 + chunk, voxels);
+    float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int n = c0 + t; n < c1; n += SK_THREADS) {
+        const float pv = p[n];
+        float v = pv;
+        if (d) v *= d[n];
+        for (int c = j + 1; c < J; ++c)                                  // the children in ascending order (uniform)
+            if (tree.parent[c] == j && c != excl) v *= U[fb + (size_t)c * voxels + n];
+        o[n] = v;
+        acc[0] += v;
+        if (kind == 1) {
+            const float cx = coord[(size_t)n * 3 + 0], cy = coord[(size_t)n * 3 + 1], cz = coord[(size_t)n * 3 + 2];
+            acc[1] += v * cx; acc[2] += v * cy; acc[3] += v * cz;
+            acc[4] += pv * cx; acc[5] += pv * cy; acc[6] += pv * cz;
+        }
+    }
+    block_fold_stage<7, SK_PART>(acc, sm);
+    if (t < 7) part[(((size_t)f * items.n + it) * gridDim.x + blockIdx.x) * SK_PART + t] = block_fold_sum<SK_PART>(sm, t);
+}
+
+// grid (items, frames), block 64.  sums [frames][J][3][SK_PART]: plane 0 = s_j, 1 = t_c, 2 = Z_j and the joint sums
+__global__ __launch_bounds__(64) void sk_fold_kernel(const float* __restrict__ part, float* __restrict__ sums, SkItems items, int J, int CH) {
+    const int it = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+    float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    wave_fold_records<7, SK_PART>(part, ((size_t)f * items.n + it) * CH, CH, t, acc);
+    const int kind = items.kind[it], slot = kind == 2 ? items.excl[it] : items.j[it];
+    const int plane = kind == 0 ? 0 : kind == 2 ? 1 : 2;
+    float* o = sums + (((size_t)f * J + slot) * 3 + plane) * SK_PART;
+    if (t == 0) {
+#pragma unroll
+        for (int x = 0; x < 7; ++x) o[x] = acc[x];
+    }
+}
+
+// grid (chunks, J, frames), block 256.  T [frames][J][N] (the U buffer); outputs at the call's frame f0 + frame.
+__global__ __launch_bounds__(SK_THREADS) void sk_finish_kernel(const float* __restrict__ prob, const float* __restrict__ T,
+                                                               const float* __restrict__ sums, float* __restrict__ beliefs,
+                                                               float* __restrict__ joints, float* __restrict__ evidence,
+                                                               int* __restrict__ coupled, int J, int voxels) {
+    const int t = threadIdx.x, j = blockIdx.y, f = blockIdx.z;
+    const float* sf = sums + (size_t)f * 3 * J * SK_PART;
+    int bad = 0;
+    for (int e = t; e < 3 * J; e += SK_THREADS) {
+        const int plane = e / J, jj = e % J;
+        if (plane < 2 && jj == 0) continue;                              // the root sends no message and receives none
+        const float v = sf[((size_t)jj * 3 + plane) * SK_PART];
+        bad |= !(v > 0.f && v <= FLT_MAX);                               // a NaN fails both comparisons
+    }
+    const bool fallback = __syncthreads_or(bad) != 0;
+    const float* fin = sf + ((size_t)j * 3 + 2) * SK_PART;
+    const float Z = fin[0];
+    const size_t row = (size_t)f * J + j;
+    if (blockIdx.x == 0 && t == 0) {
+        float* o = joints + row * 3;
+        if (fallback) { o[0] = fin[4]; o[1] = fin[5]; o[2] = fin[6]; }
+        else { o[0] = fin[1] / Z; o[1] = fin[2] / Z; o[2] = fin[3] / Z; }
+        evidence[row] = Z;
+        if (j == 0) coupled[f] = fallback ? 0 : 1;
+    }
+    if (!beliefs) return;
+    const float* src = (fallback ? prob : T) + row * voxels;             // the copy of p is bit for bit
+    float* dst = beliefs + row * voxels;
+    for (int n = blockIdx.x * SK_THREADS + t; n < voxels; n += gridDim.x * SK_THREADS) {
+        float x = src[n];
+        if (!fallback) x = x / Z;
+        dst[n] = x;
+    }
+}
+
+inline bool sk_shape_ok(int G, int R) { return G >= 2 && G <= SK_MAX_G && R >= 0 && R <= SK_MAX_R && R <= G - 1; }
+inline int sk_lds_bytes(int R) { return (SK_TJ + 2 * R) * (SK_KC + 2 * R) * 4; }
+inline dim3 sk_corr_grid(int G, int rows) {
+    return dim3(G * ((G + SK_TJ - 1) / SK_TJ) * ((G + SK_KC - 1) / SK_KC), rows);
+}
+inline bool sk_aligned4(std::initializer_list<const void*> ps) {
+    uintptr_t all = 0;
+    for (const void* p : ps) all |= reinterpret_cast<uintptr_t>(p);
+    return (all & 3) == 0;
+}
+inline long long sk_frame_floats(int J, int G) {
+    const long long N = (long long)G * G * G;
+    return 3 * J * N + (long long)SK_MAX_ITEMS * sk_chunks((int)N) * SK_PART + 3LL * J * SK_PART;
+}
+
+}  // namespace
+
+extern "C" long long se_shell_correlate_scratch_bytes(int tap_rows, int R) {
+    if (tap_rows < 1 || tap_rows > 65535 || R < 0 || R > SK_MAX_R) return 0;
+    return sk_runs_ints(tap_rows, R) * 4;
+}
+
+extern "C" int se_shell_correlate_f32(const float* a, const float* taps, const int* tap_row, const float* s, float* out, void* scratch,
+                                      long long scratch_bytes, int rows, int tap_rows, int G, int R, float scale_mul, float add,
+                                      void* stream) {
+    if (!a || !taps || !tap_row || !s || !out || !scratch) return SE_ERR_BAD_ARG;
+    if (rows < 1 || rows > 65535 || tap_rows < 1 || tap_rows > 65535 || !sk_shape_ok(G, R)) return SE_ERR_BAD_ARG;
+    if (!sk_aligned4({a, taps, tap_row, s, out, scratch}) || a == out) return SE_ERR_BAD_ARG;
+    if (scratch_bytes < se_shell_correlate_scratch_bytes(tap_rows, R)) return SE_ERR_BAD_ARG;
+    hipStream_t st = se_stream(stream);
+    int* runs = reinterpret_cast<int*>(scratch);
+    hipLaunchKernelGGL(sk_runs_kernel, dim3(2 * R + 1, tap_rows), dim3(64), 0, st, taps, runs, R);
+    SE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sk_correlate_kernel, sk_corr_grid(G, rows), dim3(SK_THREADS), sk_lds_bytes(R), st, a, taps, tap_row, s, 1, out, runs,
+                       SkRows{}, 0, tap_rows, G, R, scale_mul, add);
+    SE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" long long se_skeleton_couple_scratch_bytes(int frames, int J, int G, int R) {
+    if (frames < 1 || J < 1 || J > SK_MAX_J || !sk_shape_ok(G, R)) return 0;
+    return ((long long)min(frames, SK_GROUP) * sk_frame_floats(J, G) + sk_runs_ints(J, R)) * 4;
+}
+
+extern "C" int se_skeleton_couple_f32(const float* prob, const float* coord, const float* taps, const int* parent, float* beliefs,
+                                      float* joints, float* evidence, int* coupled, void* scratch, long long scratch_bytes, int frames,
+                                      int J, int voxels, int G, int R, float floor, void* stream) {
+    if (!prob || !coord || !taps || !parent || !joints || !evidence || !coupled || !scratch) return SE_ERR_BAD_ARG;
+    if (frames < 1 || J < 1 || J > SK_MAX_J || !sk_shape_ok(G, R)) return SE_ERR_BAD_ARG;
+    if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
+    if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
+    if (parent[0] != 0) return SE_ERR_BAD_ARG;
+    for (int j = 1; j < J; ++j)
+        if (parent[j] < 0 || parent[j] >= j) return SE_ERR_BAD_ARG;
+    if (!sk_aligned4({prob, coord, taps, beliefs, joints, evidence, coupled, scratch})) return SE_ERR_BAD_ARG;
+    if (scratch_bytes < se_skeleton_couple_scratch_bytes(frames, J, G, R)) return SE_ERR_BAD_ARG;
+    hipStream_t st = se_stream(stream);
+
+    SkTree tree{};
+    tree.J = J;
+    int depth[SK_MAX_J], deepest = 0;
+    depth[0] = 0;
+    for (int j = 0; j < J; ++j) {
+        tree.parent[j] = (signed char)parent[j];
+        if (j) depth[j] = depth[parent[j]] + 1;
+        deepest = max(deepest, depth[j]);
+    }
+    const size_t N = (size_t)voxels;
+    const int group = min(frames, SK_GROUP), CH = sk_chunks(voxels);
+    float* A = reinterpret_cast<float*>(scratch);
+    float* U = A + (size_t)group * J * N;
+    float* D = U + (size_t)group * J * N;
+    float* part = D + (size_t)group * J * N;
+    float* sums = part + (size_t)group * SK_MAX_ITEMS * CH * SK_PART;
+    int* runs = reinterpret_cast<int*>(sums + (size_t)group * 3 * J * SK_PART);
+    const float keep = 1.0f - floor, uniform = floor / (float)voxels;
+    const int lds = sk_lds_bytes(R);
+    const int fin_chunks = min(64, (voxels + SK_THREADS * 4 - 1) / (SK_THREADS * 4));
+
+    if (J > 1) {
+        hipLaunchKernelGGL(sk_runs_kernel, dim3(2 * R + 1, J), dim3(64), 0, st, taps, runs, R);
+        SE_CHECK_LAUNCH();
+    }
+    for (int f0 = 0; f0 < frames; f0 += group) {
+        const int nf = min(group, frames - f0);
+        const float* p = prob + (size_t)f0 * J * N;
+        // one level: the products, their sums, then the messages of `rows`
+        auto level = [&](const SkItems& items, const SkRows& rows, int plane, float* msg) -> int {
+            if (items.n) {
+                hipLaunchKernelGGL(sk_product_kernel, dim3(CH, items.n * nf), dim3(SK_THREADS), 0, st, p, coord, U, D, A, U, part, tree,
+                                   items, voxels);
+                SE_CHECK_LAUNCH();
+                hipLaunchKernelGGL(sk_fold_kernel, dim3(items.n, nf), dim3(64), 0, st, part, sums, items, J, CH);
+                SE_CHECK_LAUNCH();
+            }
+            if (rows.n) {
+                hipLaunchKernelGGL(sk_correlate_kernel, sk_corr_grid(G, rows.n * nf), dim3(SK_THREADS), lds, st, A, taps, nullptr,
+                                   sums + (size_t)plane * SK_PART, 3 * SK_PART, msg, runs, rows, J, J, G, R, keep, uniform);
+                SE_CHECK_LAUNCH();
+            }
+            return 0;
+        };
+        for (int d = deepest; d >= 1; --d) {
+            SkItems items{};
+            SkRows rows{};
+            for (int j = 1; j < J; ++j)
+                if (depth[j] == d) {
+                    items.j[items.n] = (unsigned char)j; items.excl[items.n] = -1; items.kind[items.n] = 0; ++items.n;
+                    rows.slot[rows.n++] = (unsigned char)j;
+                }
+            const int rc = level(items, rows, 0, U);
+            if (rc) return rc;
+        }
+        for (int d = 0; d <= deepest; ++d) {
+            SkItems items{};
+            SkRows rows{};
+            for (int j = 0; j < J; ++j)
+                if (depth[j] == d) { items.j[items.n] = (unsigned char)j; items.excl[items.n] = -1; items.kind[items.n] = 1; ++items.n; }
+            for (int c = 1; c < J; ++c)
+                if (depth[c] == d + 1) {
+                    items.j[items.n] = (unsigned char)parent[c]; items.excl[items.n] = (signed char)c; items.kind[items.n] = 2; ++items.n;
+                    rows.slot[rows.n++] = (unsigned char)c;
+                }
+            const int rc = level(items, rows, 1, D);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(sk_finish_kernel, dim3(fin_chunks, J, nf), dim3(SK_THREADS), 0, st, p, U, sums,
+                           beliefs ? beliefs + (size_t)f0 * J * N : nullptr, joints + (size_t)f0 * J * 3, evidence + (size_t)f0 * J,
+                           coupled + f0, J, voxels);
+        SE_CHECK_LAUNCH();
+    }
+    return 0;
+}

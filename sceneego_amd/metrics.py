@@ -166,3 +166,43 @@ def format_scene_summary(s, unit="m") -> str:
     """The one line demo / sequence / evaluation tools print for ``scene_summary``."""
     return (f"scene check: {s['frames']} frames  non-penetration rate {s['non_penetration_rate']:.4f}  mean penetration depth "
             f"{s['mean_penetration_depth']:.6f} {unit}  foot contact rate {s['foot_contact_rate']:.4f}")
+
+
+# Skeleton.kinematic_parents of the reference (utils/skeleton.py); sceneego_amd/_lib.py holds the same table beside SKELETON_LINES
+KINEMATIC_PARENTS = (0, 0, 1, 2, 0, 4, 5, 1, 7, 8, 9, 4, 11, 12, 13)
+
+
+def bone_length_summary(poses, bone_lengths=None, parents=KINEMATIC_PARENTS):
+    """How constant the bones of a sequence of predictions ``poses`` [T,J,3] are, and, with ``bone_lengths`` (J - 1 values for the
+    edges 1..J-1, or J with entry 0 ignored), how far they are from those lengths.  A frame in which either end of a bone is not
+    finite is skipped for that bone.  Returns a dict: ``frames``, ``mean`` and ``std`` [J-1] (per bone over the sequence),
+    ``mean_std`` (their mean) and, with ``bone_lengths``, ``deviation`` [J-1] (per bone the mean of | length - target |) and
+    ``mean_deviation``.  It needs no ground truth, so it shows what ``SkeletonPrior`` does to any prediction directory."""
+    x = np.asarray(poses, dtype=np.float64)
+    par = [int(v) for v in parents]
+    J = len(par)
+    if x.ndim != 3 or x.shape[1:] != (J, 3):
+        raise ValueError(f"poses {x.shape}, expected [T, {J}, 3]")
+    d = np.linalg.norm(x[:, 1:] - x[:, par[1:]], axis=2)                   # [T, J-1]
+    out = {"frames": int(x.shape[0]), "mean": np.nanmean(d, axis=0) if d.size else np.zeros(J - 1),
+           "std": np.nanstd(d, axis=0) if d.size else np.zeros(J - 1)}
+    out["mean_std"] = float(np.mean(out["std"])) if J > 1 else 0.0
+    if bone_lengths is not None:
+        L = np.asarray(bone_lengths, dtype=np.float64).reshape(-1)
+        if L.size == J:
+            L = L[1:]
+        elif L.size != J - 1:
+            raise ValueError(f"bone_lengths holds {L.size} values, {J - 1} or {J} expected")
+        dev = np.abs(d - L[None])
+        out["deviation"] = np.nanmean(dev, axis=0)
+        out["mean_deviation"] = float(np.nanmean(dev))
+    return out
+
+
+def format_bone_length_summary(s, unit="m") -> str:
+    text = f"bone lengths over {s['frames']} frames: mean per-bone std {s['mean_std']:.6f} {unit}; per bone: " \
+        + " ".join(f"{v:.4f}" for v in s["std"])
+    if "deviation" in s:
+        text += f"\nmean |length - given| {s['mean_deviation']:.6f} {unit}; per bone: " + " ".join(f"{v:.4f}" for v in s["deviation"])
+    return text
+

@@ -416,3 +416,17 @@ def volume_filter_to_numpy(result):
     """The dict of ``VolumeFilter.step`` as a list of per-frame dicts of numpy arrays (the keys without the batch dimension and
     without the ``beliefs``; ``shift`` when the step was given joints): what run_sequence.py --filter_info_output writes."""
     return _per_frame(result, FILTER_KEYS + (("shift",) if "shift" in result else ()), "evidence")
+
+
+# ----------------------------------------------------------------------------------------------
+# skeleton-coupled joints (csrc/skeleton_prior.hip; sceneego_amd/skeleton_prior.py; the reference has only Skeleton._skeleton_resize)
+# ----------------------------------------------------------------------------------------------
+SKELETON_KEYS = ("joints", "evidence", "coupled", "bone_error")
+
+
+def skeleton_couple_to_numpy(result):
+    """The dict of ``SkeletonPrior.couple`` as a list of per-frame dicts of numpy arrays (the keys without the batch dimension and
+    without the ``beliefs``; ``shift`` and ``bone_error_before`` when the call was given joints): what run_sequence.py
+    --skeleton_info_output writes."""
+    extra = tuple(k for k in ("shift", "bone_error_before") if k in result)
+    return _per_frame(result, SKELETON_KEYS + extra, "evidence")

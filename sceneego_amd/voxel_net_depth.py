@@ -482,6 +482,26 @@ class VoxelNetwork_depth(nn.Module):
         from .volume_filter import VolumeFilter
         return VolumeFilter(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor)
 
+    def skeleton_prior(self, bone_lengths, tau=0.03, floor=1e-3):
+        """A ``sceneego_amd.skeleton_prior.SkeletonPrior`` bound to the module's own ``coord_volumes``, grid and cuboid side: belief
+        propagation over the kinematic tree with a bone-length shell on every edge.  ``s = net.skeleton_prior(lengths);
+        s.couple(volumes)`` with the volumes ``forward()`` returned gives joints that use what the other fourteen joints say about
+        each one, the evidence of every joint and, when asked for, the coupled beliefs: tensors of the shape and meaning of the
+        volumes, which ``joint_statistics``, ``joint_modes``, ``constrain_to_scene``, ``VolumeFilter.step`` and the volume renderer take
+        unchanged.  ``bone_lengths``: 14 values (edges 1..14 of ``_lib.KINEMATIC_PARENTS``) or 15 (entry 0 ignored), metres;
+        ``skeleton_prior.estimate_bone_lengths`` makes them from raw joints.  ``tau`` (the width of the shell) and ``floor`` (the chance
+        that the bone prior is wrong for an edge) are a convention, not calibrated.  ``forward()`` itself is unchanged.
+
+        Under ``enable_graphs(True)`` the volumes are the graph's STATIC buffer, overwritten by the next replay: call ``couple`` before
+        the next ``forward()`` (the call is queued on the current stream, so stream order is enough).
+
+        Raises ValueError when ``config.model.volume_softmax`` is false (the ReLU volumes are not a distribution) or a parameter is
+        out of range; nothing touches the device before the first ``couple``."""
+        if not self.volume_softmax:
+            raise ValueError("skeleton_prior needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        from .skeleton_prior import SkeletonPrior
+        return SkeletonPrior(self.coord_volumes[0], self.volume_size, self.cuboid_side, bone_lengths, tau=tau, floor=floor)
+
     def _voxelise(self, x, planar3, fast_occ, prog, scene_volumes, depth_map_batch, B, G, N, C, dev, planar1=False):
         """Occupancy into the V2V input buffer ``x`` (reference ``:246-262``)."""
         if planar1 and self.with_scene is not True:
