@@ -683,6 +683,48 @@ int se_volume_filter_f32(const float* prob, const float* coord, const float* tap
                          int G, int radius, float floor, const int* have_prior, void* stream);
 long long se_volume_filter_scratch_bytes(int rows, int G, int radius);
 
+/* Forward-backward smoother over the joint volumes of a sequence: the backward pass that goes with se_volume_filter_f32
+ * (sceneego_amd/volume_smoother.py: VolumeSmoother; VoxelNetwork_depth.volume_smoother returns one).  It adds no convention: motion
+ * model, floor and restart rule are the filter's; only the frames a belief conditions on change (all of the track's, not 0..t).
+ * tests/volume_smoother_model.py restates the definition in float64.
+ *   prob       [frames][rows][voxels] float32: the volumes p_t the filter was given
+ *   belief     [frames][rows][voxels] float32: the filter's belief_out b_t for the same frames
+ *   restarted  [frames][rows] int32: the filter's output for the same frames
+ *   coord, taps, G, radius, floor, rows, frames: as for se_volume_filter_f32.  blur3T below is blur3 with the taps REVERSED (w'[d] =
+ *              w[-d]: the adjoint of blur3; the same for symmetric taps).  The call reverses them itself: pass the filter's taps.
+ *   state      [rows][voxels] float32: the backward belief r.  In: r of the frame behind the call's last frame, read only for rows
+ *              that have_link marks.  Out: r of the call's first frame.
+ *   have_link  NULL (no row: the call ends the track) or int32 [rows] on the device: non-zero where the call's last frame is linked
+ *              to the frame behind it, that is where that frame exists and its `restarted` is 0.
+ * The frames of a call are processed from LAST to FIRST; a sequence is smoothed by calls over consecutive chunks in reverse order,
+ * `state` carried from call to call.
+ * LINK       frame t is linked to t + 1 unless t is the last frame of the track or restarted[t + 1][row] is set: a forward restart
+ *            cuts the chain in both directions.
+ * NO LINK    gamma_t = b_t and r_t = p_t, copied bit for bit; smoothed = 0, agreement NaN.
+ * LINKED     u = (1 - floor) blur3T(r_{t+1}) + floor / voxels
+ *            g = b_t u,  S = sum g,  gamma_t = g / S;   where S is not a finite number > 0: gamma_t = b_t (a copy), smoothed = 0
+ *            a = p_t u,  s = sum a,  r_t = a / s;       where s is not a finite number > 0: r_t = p_t (a copy)
+ *   smoothed_out NULL, or [frames][rows][voxels] float32: gamma_t of every frame.  It may be `belief` itself (in place); any other
+ *              overlap with an input is the caller's error.
+ *   joints     [frames][rows][3] float32: sum_n gamma_n coord_n (computed as (sum g c) / S; sum b c where gamma is the copy)
+ *   agreement  [frames][rows] float32: S, how well the future's prediction for the frame agrees with the filtered belief (1 / voxels is
+ *              chance); NaN where the row is not linked
+ *   smoothed   [frames][rows] int32: 1 where gamma_t = g / S
+ *   scratch    se_volume_smooth_scratch_bytes(rows, G, radius) bytes of workspace, 4-byte aligned (16-byte for the fast finish pass); 0
+ *              for a shape out of range.  rows (2 G^3 + 8 G) floats and a few hundred bytes; the second G^3 array holds g and is
+ *              reserved but left untouched by a call without smoothed_out.
+ * One launch per call (the reversed taps) and three per frame on `stream`: the filter's k/j-blur kernel on r, an update kernel that
+ * forms both products from one u, a finish pass.  No atomics; every sum is taken in the filter's fixed order, at most 80 sequential
+ * float32 additions on the longest path: bitwise identical from run to run and independent of how the frames are cut into calls.
+ * Allocates nothing.  SE_ERR_BAD_ARG, with nothing launched: a null pointer other than smoothed_out / have_link, a pointer that is not
+ * 4-byte aligned, frames < 1, rows outside 1..65535, G outside 2..128, voxels != G^3, radius outside 0..min(16, G - 1), floor outside
+ * [0, 1] or NaN, scratch_bytes below se_volume_smooth_scratch_bytes(rows, G, radius).                                               */
+int se_volume_smooth_f32(const float* prob, const float* belief, const int* restarted, const float* coord, const float* taps,
+                         float* state, float* smoothed_out, float* joints, float* agreement, int* smoothed, void* scratch,
+                         long long scratch_bytes, int frames, int rows, int voxels, int G, int radius, float floor,
+                         const int* have_link, void* stream);
+long long se_volume_smooth_scratch_bytes(int rows, int G, int radius);
+
 /* Skeleton-coupled joints: sum-product belief propagation over the kinematic tree of the joint volumes, with a spherical-shell
  * bone-length factor on every edge (sceneego_amd/skeleton_prior.py: SkeletonPrior; VoxelNetwork_depth.skeleton_prior returns one).  The
  * reference forces bone lengths onto a finished pose (utils/skeleton.py: kinematic_parents, _skeleton_resize); this couples the whole

@@ -47,14 +47,21 @@ blurred by a Gaussian step of ``--filter_sigma`` metres truncated at ``--filter_
 across the pipelined streams; ``--filter_info_output`` adds the per-frame dicts (joints, evidence, restarted, shift) and
 ``--render_volumes filtered`` draws the beliefs instead of the raw volumes.  It prints its MPJPE beside the soft-argmax's: the volume
 as likelihood, the Gaussian step and the floor are a convention, not calibrated.
+``--smooth_output`` writes a pickle in the format of ``--output`` whose joints are those of the forward-backward smoother that goes with
+that filter (``VoxelNetwork_depth.volume_smoother``, ``sceneego_amd/volume_smoother.py``): the filter runs as above, the volumes and the
+beliefs of every frame stay on the device (31.4 MB per frame at 15 x 64^3; at most ``--smooth_max_gb``, default half of the free device
+memory) and a backward pass at the end of the sequence conditions every frame on the whole track.  It uses ``--filter_sigma``,
+``--filter_radius`` and ``--filter_floor`` and implies the filter, so ``--filter_output`` may be given as well and gets the same joints
+as without it; ``--smooth_info_output`` adds the per-frame dicts (joints, smoothed, agreement, filtered_joints, shift_filtered, shift).
+Smoothed beliefs are not rendered: frames are rendered per batch, before the future exists.
 ``--skeleton_output`` writes a pickle in the format of ``--output`` whose joints are coupled over the kinematic tree inside every frame
 (``VoxelNetwork_depth.skeleton_prior``, ``sceneego_amd/skeleton_prior.py``: belief propagation over the fifteen volumes with a
 bone-length shell of ``--skeleton_tau`` metres on every edge and a uniform floor ``--skeleton_floor``), per batch on the stream the
 batch ran on.  The bone lengths come from ``--bone_lengths`` (a .npy of 14 or 15 metres) or, without it, from a first forward pass over
 at most ``--bone_frames`` evenly spaced frames (``estimate_bone_lengths``: the per-bone median of the soft-argmax joints' distances).
 ``--skeleton_info_output`` adds the per-frame dicts (joints, evidence, coupled, bone_error, shift, bone_error_before) and
-``--render_volumes coupled`` draws the coupled beliefs.  With ``--filter_output`` as well the order is couple, then filter: the filter
-runs on the coupled beliefs.  The volume as likelihood, the shell and the floor are a convention, not calibrated.
+``--render_volumes coupled`` draws the coupled beliefs.  With ``--filter_output`` as well the order is couple, then filter (with
+``--smooth_output``: couple, filter, smooth): the filter runs on the coupled beliefs.  The volume as likelihood, the shell and the floor are a convention, not calibrated.
 """
 import argparse
 import json
@@ -235,7 +242,8 @@ class SequenceRunner:
     @torch.no_grad()
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
-            volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False):
+            volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False,
+            smooth=None):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -250,10 +258,12 @@ class SequenceRunner:
         ``VoxelNetwork_depth.skeleton_prior``: every batch's joints are coupled over the kinematic tree on the stream the batch ran on
         and the per-frame skeleton dicts are appended after the filter's; ``render_coupled`` (with ``render_volumes``) draws the
         coupled beliefs.  With ``filter`` as well the order is couple, then filter: the filter runs on the coupled beliefs (its
-        ``shift`` is still measured from the soft-argmax joints)."""
+        ``shift`` is still measured from the soft-argmax joints).  ``smooth`` (with ``filter``): a dict with ``max_bytes`` for
+        ``VoxelNetwork_depth.volume_smoother``: the filter is the smoother's own, every batch is pushed instead of stepped, and the
+        per-frame dicts of its ``finish()``, run once behind the last batch, are appended after the skeleton's."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
-                                     skeleton_couple_to_numpy, volume_filter_to_numpy)
+                                     skeleton_couple_to_numpy, volume_filter_to_numpy, volume_smoother_to_numpy)
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
@@ -261,7 +271,10 @@ class SequenceRunner:
         frame_constraint, frame_scene_constrained, frame_modes, frame_filter, frame_skeleton = [], [], [], [], []
         if render_filtered and (filter is None or not render_volumes):
             raise ValueError("render_filtered needs filter and render_volumes")
-        vf = self.net.volume_filter(**filter) if filter is not None else None
+        if smooth is not None and filter is None:
+            raise ValueError("smooth needs filter")
+        vs = self.net.volume_smoother(**filter, **smooth) if smooth is not None else None
+        vf = vs.filter if vs is not None else self.net.volume_filter(**filter) if filter is not None else None
         if render_coupled and (skeleton is None or not render_volumes or render_filtered):
             raise ValueError("render_coupled needs skeleton and render_volumes, and excludes render_filtered")
         sp = self.net.skeleton_prior(**skeleton) if skeleton is not None else None
@@ -276,7 +289,11 @@ class SequenceRunner:
                 if render_coupled and job is not None:
                     job = job[:-1] + (sk["beliefs"],)
             if vf is not None:
-                fr = vf.step(vol, joints=kp, return_beliefs=render_filtered and job is not None, stream=stream)
+                want_beliefs = render_filtered and job is not None
+                if vs is not None:     # the same dict; the smoother keeps copies of its own, so the beliefs are dropped unless drawn
+                    fr = {k: v for k, v in vs.push(vol, joints=kp, stream=stream).items() if k != "beliefs" or want_beliefs}
+                else:
+                    fr = vf.step(vol, joints=kp, return_beliefs=want_beliefs, stream=stream)
                 if "beliefs" in fr:
                     job = job[:-1] + (fr["beliefs"],)
             return fr, sk, job
@@ -373,12 +390,13 @@ class SequenceRunner:
                 if self.video is not None:
                     self.video.close()
                     self.video = None
+        frame_smooth = volume_smoother_to_numpy(vs.finish()) if vs is not None else None
         if not (stats or scene or constrain or modes or vf is not None or sp is not None):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
             + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
             + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ()) \
-            + ((frame_skeleton,) if sp is not None else ())
+            + ((frame_skeleton,) if sp is not None else ()) + ((frame_smooth,) if vs is not None else ())
 
 
 def _size(text):
@@ -440,6 +458,13 @@ def build_parser():
     ap.add_argument("--filter_radius", type=int, default=None, help="voxels the Gaussian step is truncated at, 0..16 "
                     "(default: min(16, G - 1, ceil(3 sigma / voxel edge)))")
     ap.add_argument("--filter_floor", type=float, default=1e-3, help="the filter's uniform floor in [0, 1]: the chance of a jump")
+    ap.add_argument("--smooth_output", default=None, help="pickle in the format of --output holding the joints of the forward-backward "
+                    "smoother over the sequence's volumes (sceneego_amd/volume_smoother.py; --filter_sigma, --filter_radius, "
+                    "--filter_floor: the filter's convention, not calibrated); implies the filter")
+    ap.add_argument("--smooth_info_output", default=None, help="pickle of the per-frame smoother dicts (list of dicts of numpy arrays: "
+                    "joints, smoothed, agreement, filtered_joints, shift_filtered, shift)")
+    ap.add_argument("--smooth_max_gb", type=float, default=None, help="with --smooth_output: the most device memory the stored volumes "
+                    "and beliefs may take, in GiB (default: half of what is free at the first batch)")
     ap.add_argument("--skeleton_output", default=None, help="pickle in the format of --output holding the joints coupled over the "
                     "kinematic tree inside every frame (sceneego_amd/skeleton_prior.py: a convention, not calibrated)")
     ap.add_argument("--skeleton_info_output", default=None, help="pickle of the per-frame skeleton dicts (list of dicts of numpy arrays: "
@@ -488,6 +513,14 @@ def parse_args(argv=None):
     args.filter = None
     if args.filter_output is not None or args.filter_info_output is not None or args.render_filtered:
         args.filter = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor}
+    args.smooth = None
+    if args.smooth_output is not None or args.smooth_info_output is not None:
+        if args.smooth_max_gb is not None and not args.smooth_max_gb >= 0:
+            raise SystemExit("--smooth_max_gb must be >= 0")
+        args.smooth = {"max_bytes": None if args.smooth_max_gb is None else int(args.smooth_max_gb * 2 ** 30)}
+        args.filter = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor}
+    elif args.smooth_max_gb is not None:
+        raise SystemExit("--smooth_max_gb needs --smooth_output")
     if not (args.skeleton_tau > 0 and args.skeleton_tau != float("inf")):
         raise SystemExit("--skeleton_tau must be a finite number > 0")
     if not 0.0 <= args.skeleton_floor <= 1.0:
@@ -544,7 +577,8 @@ def main(argv=None):
                        render_video=args.render_video, render_fps=args.render_fps, render_view=args.render_view,
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
                        volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
-                       filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled)
+                       filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled,
+                       smooth=args.smooth)
     if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
@@ -554,6 +588,7 @@ def main(argv=None):
         frame_modes = extra.pop(0) if want_modes else None
         frame_filter = extra.pop(0) if want_filter else None
         frame_skeleton = extra.pop(0) if skeleton is not None else None
+        frame_smooth = extra.pop(0) if args.smooth is not None else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -616,6 +651,19 @@ def main(argv=None):
         print("filtered volumes (a convention, not calibrated): mpjpe: {}, mean shift {:.4f} m, {} restarts after the first frame".format(
             result["filtered_mpjpe"], float(np.mean([fr["shift"] for fr in frame_filter])),
             int(sum(fr["restarted"].sum() for fr in frame_filter[1:]))))
+    if args.smooth is not None:
+        smoothed = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_smooth]
+        for path, obj in ((args.smooth_output, smoothed), (args.smooth_info_output, frame_smooth)):
+            if path is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "wb") as f:
+                    pickle.dump(obj, f)
+        result["smoothed"], result["smoother"] = smoothed, frame_smooth
+        result["smoothed_mpjpe"] = M.mpjpe(np.stack(smoothed).astype(np.float64), gt)
+        print("smoothed volumes (a convention, not calibrated): mpjpe: {} (soft-argmax {}, filtered {}), mean shift from the filtered "
+              "joints {:.4f} m, {} of {} joint-frames smoothed".format(
+                  result["smoothed_mpjpe"], mpjpe, result["filtered_mpjpe"], float(np.mean([fr["shift_filtered"] for fr in frame_smooth])),
+                  int(sum(fr["smoothed"].sum() for fr in frame_smooth)), int(sum(fr["smoothed"].size for fr in frame_smooth))))
     if skeleton is not None:
         coupled = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_skeleton]
         for path, obj in ((args.skeleton_output, coupled), (args.skeleton_info_output, frame_skeleton)):

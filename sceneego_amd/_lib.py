@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -113,6 +113,8 @@ SIGNATURES = {
     "se_joint_modes_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
     "se_volume_filter_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_volume_filter_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "se_volume_smooth_scratch_bytes": (_ll, [_i, _i, _i]),
+    "se_volume_smooth_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "se_shell_correlate_scratch_bytes": (_ll, [_i, _i]),
     "se_shell_correlate_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _f, _vp]),
     "se_skeleton_couple_scratch_bytes": (_ll, [_i, _i, _i, _i]),
@@ -1186,6 +1188,65 @@ def volume_filter(prob, coord, taps, state, belief_out, joints, evidence, restar
                                        _ptr(evidence), _ptr(restarted), _ptr(scratch), scratch.numel(), frames, rows, voxels, grid,
                                        radius, floor, _ptr(have_prior), _stream()), "se_volume_filter_f32")
     return joints, evidence, restarted
+
+
+# The filter's backward pass (csrc/volume_filter.hip: se_volume_smooth_f32; sceneego_amd/volume_smoother.py drives it)
+SMOOTH_CHAIN = 80          # sequential float32 additions on the longest path of s, S and the joint sums: the filter's fold (L)
+
+
+def volume_smooth_scratch_bytes(rows, grid, radius) -> int:
+    return int(load().se_volume_smooth_scratch_bytes(int(rows), int(grid), int(radius)))
+
+
+def _overlap(a, b) -> bool:
+    """The storage of two contiguous tensors overlaps."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def volume_smooth(prob, belief, restarted, coord, taps, state, smoothed_out, joints, agreement, smoothed, frames, rows, voxels, grid,
+                  radius, floor, have_link=None, scratch=None):
+    """se_volume_smooth_f32: the backward pass over ``frames`` consecutive frames, last to first, on the volumes ``prob`` and the
+    filtered beliefs ``belief`` [frames, rows, voxels] with the filter's ``restarted`` [frames, rows] int32 (the header states the
+    definition).  ``state`` [rows, voxels] carries the backward belief from call to call and is updated in place; ``have_link`` None
+    (the call ends the track) or int32 [rows]: where the last frame is linked to the frame behind it.  ``taps``: the filter's, on the
+    device (the call reverses them).  ``smoothed_out`` None, ``belief`` itself (in place) or a tensor disjoint from it; ``joints``
+    [frames, rows, 3], ``agreement`` [frames, rows] float32 and ``smoothed`` [frames, rows] int32 are written.  ``scratch``: an optional
+    uint8 workspace of at least ``volume_smooth_scratch_bytes(rows, grid, radius)`` bytes.  Every argument is checked here and a bad
+    one raises HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
+    what = "volume_smooth"
+    frames, rows, voxels, grid, radius, floor = int(frames), int(rows), int(voxels), int(grid), int(radius), float(floor)
+    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
+                                f"voxels = {voxels} (grid^3) expected")
+    if not 0 <= radius <= min(FILTER_MAX_RADIUS, grid - 1):
+        raise HipExtensionError(f"{what}: radius = {radius} (0..{min(FILTER_MAX_RADIUS, grid - 1)}) expected")
+    if not 0.0 <= floor <= 1.0:
+        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    total = frames * rows * voxels
+    dev = _check_args(what, (("prob", prob, torch.float32, total), ("belief", belief, torch.float32, total),
+                             ("restarted", restarted, torch.int32, frames * rows), ("coord", coord, torch.float32, voxels * 3),
+                             ("taps", taps, torch.float32, 2 * radius + 1), ("state", state, torch.float32, rows * voxels),
+                             ("joints", joints, torch.float32, frames * rows * 3), ("agreement", agreement, torch.float32, frames * rows),
+                             ("smoothed", smoothed, torch.int32, frames * rows)),
+                      (("smoothed_out", smoothed_out, torch.float32, total), ("have_link", have_link, torch.int32, rows),
+                       ("scratch", scratch, torch.uint8, None)))
+    if _overlap(state, prob) or _overlap(state, belief):
+        raise HipExtensionError(f"{what}: state must not alias prob or belief")
+    if smoothed_out is not None:
+        if smoothed_out.data_ptr() != belief.data_ptr() and _overlap(smoothed_out, belief):
+            raise HipExtensionError(f"{what}: smoothed_out must be belief itself (in place) or disjoint from it")
+        if _overlap(smoothed_out, prob) or _overlap(smoothed_out, state):
+            raise HipExtensionError(f"{what}: smoothed_out must not alias prob or state")
+    need = volume_smooth_scratch_bytes(rows, grid, radius)
+    if need <= 0:
+        raise HipExtensionError(f"{what}: rows = {rows}, grid = {grid}, radius = {radius} is not supported")
+    scratch = _scratch(what, scratch, need, torch.uint8, dev)
+    _check(load().se_volume_smooth_f32(_ptr(prob), _ptr(belief), _ptr(restarted), _ptr(coord), _ptr(taps), _ptr(state),
+                                       _ptr(smoothed_out), _ptr(joints), _ptr(agreement), _ptr(smoothed), _ptr(scratch),
+                                       scratch.numel(), frames, rows, voxels, grid, radius, floor, _ptr(have_link), _stream()),
+           "se_volume_smooth_f32")
+    return joints, agreement, smoothed
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

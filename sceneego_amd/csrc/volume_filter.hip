@@ -30,6 +30,26 @@
 // additions on the longest path of Z and of the joint sums (SE_VF_CHAIN; G = 128).  Every order depends on the shape alone: the
 // results are bitwise identical from run to run, and since a frame sees only `state` and its own p they do not depend on how the
 // frames are cut into calls.
+//
+// THE SMOOTHER (se_volume_smooth_f32; sceneego_amd/volume_smoother.py: VolumeSmoother; tests/volume_smoother_model.py) walks the frames
+// of a call from last to first with a backward belief r in `state`.  Frame t is LINKED to t + 1 unless restarted[t + 1] is set (for the
+// call's last frame: unless have_link says so); with b_t the filtered belief and blur3T the blur with the taps reversed (the adjoint):
+//     u = (1 - floor) blur3T(r_{t+1}) + floor / N
+//     g = b_t u,  S = sum g,  gamma_t = g / S         or, unlinked or with an S that is not a finite number > 0:  gamma_t = b_t (a copy)
+//     a = p_t u,  s = sum a,  r_t = a / s             or, unlinked or with an s that is not a finite number > 0:  r_t = p_t (a copy)
+// Three launches per frame again, after one launch per call (vs_prep_kernel) that writes the reversed taps into the scratch:
+//   vf_blur_kj_kernel   the kernel above on r with the reversed taps; its have_prior is the frame's link flags.
+//   vs_update_kernel    vf_update_kernel with two products from the one u: a overwrites q in place, g goes to a second array (only when
+//                       gamma is asked for); the record holds s, S, sum g c (3) and sum b c (3, the joint of an unlinked row).
+//   vs_finish_kernel    folds the records, decides the two fallbacks apart, writes r_t to `state` and gamma_t to `smoothed_out` (which may
+//                       be `belief` itself: the frame's b was read by the update pass, and a copy onto itself is skipped); chunk 0 also
+//                       writes joints, agreement, smoothed and the link flags of the frame processed next (!restarted[t], two arrays in
+//                       turn so that no workgroup of this launch reads what another writes).
+// BYTE MODEL per frame, row and voxel: blur_kj 8 B (r, q); update reads q, p and b and writes a (16 B), and g (4 B) when gamma is asked for;
+// finish reads a and writes r (8 B), and reads g and writes gamma (8 B) when asked for: 32 B, 44 B with the smoothed beliefs, over a
+// working set of r, q, p, b (and g): 63 MB (79 MB) at 64^3 and 15 rows, 126 MB (173 MB) moved per frame.
+// SUMMATION ORDER: that of the filter, for s, S and the joint sums alike: L = 80 (SE_VS_CHAIN).  A frame sees only `state`, its link
+// flags and its own p and b, so the results do not depend on how the frames are cut into calls.
 #include <float.h>
 
 #include "row_reduce.h"
@@ -40,6 +60,7 @@
 #define SE_VF_PART 8              // Z, sum a c (x y z), sum p c (x y z), pad
 #define SE_VF_MAX_CHUNKS 64
 #define SE_VF_CHAIN 80            // L of the header comment
+#define SE_VS_CHAIN 80            // the smoother's: the same fold over the same records
 
 namespace {
 
@@ -176,6 +197,122 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vf_finish_kernel(const float* _
     }
 }
 
+// one workgroup: the taps reversed (blur3T is blur3 with them), for the blur kernel above and the update kernel below
+__global__ void vs_prep_kernel(const float* __restrict__ taps, float* __restrict__ rev, int R) {
+    const int t = threadIdx.x;
+    if (t <= 2 * R) rev[t] = taps[2 * R - t];
+}
+
+// grid (G, rows), block 256, dynamic LDS G^2 floats.  `taps`: already reversed.  `link`: the frame's link flags (or NULL: none).
+// `g_out`: NULL when gamma is not asked for.
+__global__ __launch_bounds__(SE_VF_THREADS) void vs_update_kernel(const float* __restrict__ prob, const float* __restrict__ belief,
+                                                                  const float* __restrict__ coord, const float* __restrict__ taps,
+                                                                  const int* __restrict__ link, float* __restrict__ q,
+                                                                  float* __restrict__ g_out, float* __restrict__ part, int G, int voxels,
+                                                                  int R, int wshift, float keep, float uniform) {
+    extern __shared__ __align__(16) float lds[];
+    __shared__ float w[2 * SE_VF_MAX_R + 1];
+    __shared__ float sm[4][SE_VF_PART];
+    const int t = threadIdx.x, j = blockIdx.x, row = blockIdx.y;
+    const bool linked = vf_has_prior(link, 0, row);                 // uniform
+    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VF_THREADS >> wshift;
+    const size_t base = (size_t)row * voxels;
+    if (linked) {
+        if (k < G)
+            for (int i = ir; i < G; i += RP) lds[i * G + k] = q[base + ((size_t)i * G + j) * G + k];
+        if (t <= 2 * R) w[t] = taps[t];
+    }
+    __syncthreads();
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};       // s, S, sum g c, sum b c
+    if (k < G) {
+        for (int i = ir; i < G; i += RP) {
+            const size_t n = ((size_t)i * G + j) * G + k;
+            const float b = belief[base + n];
+            const float cx = coord[n * 3 + 0], cy = coord[n * 3 + 1], cz = coord[n * 3 + 2];
+            acc[5] += b * cx; acc[6] += b * cy; acc[7] += b * cz;
+            if (linked) {
+                const float p = prob[base + n];
+                const int lo = max(-R, -i), hi = min(R, G - 1 - i);
+                const float* s = lds + i * G + k;
+                float u = 0.f;
+                for (int d = lo; d <= hi; ++d) u = fmaf(w[d + R], s[d * G], u);
+                u = fmaf(keep, u, uniform);
+                const float a = p * u, g = b * u;
+                q[base + n] = a;                                    // staged by this workgroup, read by no other
+                if (g_out) g_out[base + n] = g;
+                acc[0] += a;
+                acc[1] += g;
+                acc[2] += g * cx; acc[3] += g * cy; acc[4] += g * cz;
+            }
+        }
+    }
+    block_fold_stage<8, SE_VF_PART>(acc, sm);
+    if (t < 8) part[((size_t)row * G + j) * SE_VF_PART + t] = block_fold_sum<SE_VF_PART>(sm, t);
+}
+
+// grid (chunks, rows), block 256.  No __restrict__ on belief / smoothed_out: they may be one array.
+template <bool VEC>
+__global__ __launch_bounds__(SE_VF_THREADS) void vs_finish_kernel(const float* __restrict__ prob, const float* belief,
+                                                                  const float* __restrict__ q, const float* __restrict__ g,
+                                                                  const float* __restrict__ part, const int* __restrict__ link,
+                                                                  const int* __restrict__ restarted, int* __restrict__ link_next,
+                                                                  float* __restrict__ state, float* smoothed_out,
+                                                                  float* __restrict__ joints, float* __restrict__ agreement,
+                                                                  int* __restrict__ smoothed, int G, int voxels) {
+    __shared__ float fin[SE_VF_PART];
+    const int t = threadIdx.x, row = blockIdx.y;
+    if (t < 64) {
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        wave_fold_records<8, SE_VF_PART>(part, (size_t)row * G, G, t, acc);
+        if (t == 0) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) fin[x] = acc[x];
+        }
+    }
+    __syncthreads();
+    const bool linked = vf_has_prior(link, 0, row);
+    const float s = fin[0], S = fin[1];
+    const bool back = linked && s > 0.f && s <= FLT_MAX;            // r_t = a / s; a NaN fails both comparisons
+    const bool smooth = linked && S > 0.f && S <= FLT_MAX;          // gamma_t = g / S
+    if (blockIdx.x == 0 && t == 0) {
+        float* o = joints + (size_t)row * 3;
+        if (smooth) { o[0] = fin[2] / S; o[1] = fin[3] / S; o[2] = fin[4] / S; }
+        else { o[0] = fin[5]; o[1] = fin[6]; o[2] = fin[7]; }
+        agreement[row] = linked ? S : __int_as_float(0x7fc00000);
+        smoothed[row] = smooth ? 1 : 0;
+        link_next[row] = restarted[row] == 0;                       // the frame before this one is linked to it unless it restarted
+    }
+    const size_t base = (size_t)row * voxels;
+    const float* rsrc = (back ? q : prob) + base;                   // the copies are bit for bit
+    float* rdst = state + base;
+    const bool write_gamma = smoothed_out != nullptr && (smooth || smoothed_out != belief);
+    const float* gsrc = write_gamma ? (smooth ? g : belief) + base : nullptr;
+    float* gdst = write_gamma ? smoothed_out + base : nullptr;
+    for (int n = (blockIdx.x * SE_VF_THREADS + t) * 4; n < voxels; n += gridDim.x * SE_VF_THREADS * 4) {
+        if (VEC) {
+            f32x4 x = *reinterpret_cast<const f32x4*>(rsrc + n);
+            if (back) { x.x = x.x / s; x.y = x.y / s; x.z = x.z / s; x.w = x.w / s; }
+            *reinterpret_cast<f32x4*>(rdst + n) = x;
+            if (write_gamma) {
+                f32x4 y = *reinterpret_cast<const f32x4*>(gsrc + n);
+                if (smooth) { y.x = y.x / S; y.y = y.y / S; y.z = y.z / S; y.w = y.w / S; }
+                *reinterpret_cast<f32x4*>(gdst + n) = y;
+            }
+        } else {
+            for (int e = n; e < min(n + 4, voxels); ++e) {
+                float x = rsrc[e];
+                if (back) x = x / s;
+                rdst[e] = x;
+                if (write_gamma) {
+                    float y = gsrc[e];
+                    if (smooth) y = y / S;
+                    gdst[e] = y;
+                }
+            }
+        }
+    }
+}
+
 inline bool vf_shape_ok(int rows, int G, int R) {
     return rows >= 1 && rows <= 65535 && G >= 2 && G <= SE_VF_MAX_G && R >= 0 && R <= SE_VF_MAX_R && R <= G - 1;
 }
@@ -237,6 +374,81 @@ extern "C" int se_volume_filter_f32(const float* prob, const float* coord, const
             hipLaunchKernelGGL(vf_finish_kernel<false>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, q, part, have_prior,
                                prior_all, state, bo, joints + (size_t)f * rows * 3, evidence + (size_t)f * rows,
                                restarted + (size_t)f * rows, G, voxels);
+        SE_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// scratch of the smoother: q and g [rows][voxels], the records [rows][G][8], the reversed taps (40 floats), two arrays of link flags.
+// g is reserved whether or not smoothed_out is given (the size is asked for before the call's arguments are known): a call without
+// smoothed_out leaves it untouched, 15.7 MB of the workspace at 15 x 64^3 and 126 MB at 15 x 128^3.
+inline long long vs_tail_elems(int rows, int G) { return (long long)rows * G * SE_VF_PART + 40 + 2LL * ((rows + 3) & ~3); }
+
+extern "C" long long se_volume_smooth_scratch_bytes(int rows, int G, int radius) {
+    if (!vf_shape_ok(rows, G, radius)) return 0;
+    return (2 * vf_q_elems(rows, G) + vs_tail_elems(rows, G)) * 4;
+}
+
+extern "C" int se_volume_smooth_f32(const float* prob, const float* belief, const int* restarted, const float* coord, const float* taps,
+                                    float* state, float* smoothed_out, float* joints, float* agreement, int* smoothed, void* scratch,
+                                    long long scratch_bytes, int frames, int rows, int voxels, int G, int radius, float floor,
+                                    const int* have_link, void* stream) {
+    if (!prob || !belief || !restarted || !coord || !taps || !state || !joints || !agreement || !smoothed || !scratch)
+        return SE_ERR_BAD_ARG;
+    if (frames < 1 || !vf_shape_ok(rows, G, radius)) return SE_ERR_BAD_ARG;
+    if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
+    if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
+    const uintptr_t all = reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(belief) | reinterpret_cast<uintptr_t>(restarted) |
+                          reinterpret_cast<uintptr_t>(coord) | reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(state) |
+                          reinterpret_cast<uintptr_t>(smoothed_out) | reinterpret_cast<uintptr_t>(joints) |
+                          reinterpret_cast<uintptr_t>(agreement) | reinterpret_cast<uintptr_t>(smoothed) |
+                          reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(have_link);
+    if (all & 3) return SE_ERR_BAD_ARG;
+    if (scratch_bytes < se_volume_smooth_scratch_bytes(rows, G, radius)) return SE_ERR_BAD_ARG;
+    hipStream_t s = se_stream(stream);
+    float* q = reinterpret_cast<float*>(scratch);
+    float* g = q + vf_q_elems(rows, G);
+    float* part = g + vf_q_elems(rows, G);
+    float* rev = part + (long long)rows * G * SE_VF_PART;
+    int* link2 = reinterpret_cast<int*>(rev + 40);
+    const int link_stride = (rows + 3) & ~3;
+    int wshift = 0;
+    while ((1 << wshift) < G) ++wshift;
+    const int plane_bytes = G * G * 4;
+    SE_ENSURE_LDS(vf_blur_kj_kernel, 2 * SE_VF_MAX_G * SE_VF_MAX_G * 4);
+    SE_ENSURE_LDS(vs_update_kernel, SE_VF_MAX_G * SE_VF_MAX_G * 4);
+    const bool vec = (voxels & 3) == 0 && !((reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(belief) |
+                                             reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(smoothed_out) |
+                                             reinterpret_cast<uintptr_t>(scratch)) & 15);
+    const int chunks = min(SE_VF_MAX_CHUNKS, (voxels + SE_VF_THREADS * 4 - 1) / (SE_VF_THREADS * 4));
+    const float keep = 1.0f - floor, uniform = floor / (float)voxels;
+    const size_t frame_elems = (size_t)rows * voxels;
+    hipLaunchKernelGGL(vs_prep_kernel, dim3(1), dim3(64), 0, s, taps, rev, radius);
+    SE_CHECK_LAUNCH();
+    for (int f = frames - 1; f >= 0; --f) {
+        const float* p = prob + f * frame_elems;
+        const float* b = belief + f * frame_elems;
+        // the link flags of frame f: the caller's for the last frame, else what the finish pass of frame f + 1 wrote
+        const int* link = f == frames - 1 ? have_link : link2 + (size_t)(f & 1) * link_stride;
+        int* link_next = link2 + (size_t)((f + 1) & 1) * link_stride;                    // read by frame f - 1
+        if (link) {
+            hipLaunchKernelGGL(vf_blur_kj_kernel, dim3(G, rows), dim3(SE_VF_THREADS), 2 * plane_bytes, s, state, rev, link, 0, q, G,
+                               voxels, radius, wshift);
+            SE_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(vs_update_kernel, dim3(G, rows), dim3(SE_VF_THREADS), plane_bytes, s, p, b, coord, rev, link, q,
+                           smoothed_out ? g : nullptr, part, G, voxels, radius, wshift, keep, uniform);
+        SE_CHECK_LAUNCH();
+        float* so = smoothed_out ? smoothed_out + f * frame_elems : nullptr;
+        const int* rs = restarted + (size_t)f * rows;
+        if (vec)
+            hipLaunchKernelGGL(vs_finish_kernel<true>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, b, q, g, part, link, rs, link_next,
+                               state, so, joints + (size_t)f * rows * 3, agreement + (size_t)f * rows, smoothed + (size_t)f * rows, G,
+                               voxels);
+        else
+            hipLaunchKernelGGL(vs_finish_kernel<false>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, b, q, g, part, link, rs,
+                               link_next, state, so, joints + (size_t)f * rows * 3, agreement + (size_t)f * rows,
+                               smoothed + (size_t)f * rows, G, voxels);
         SE_CHECK_LAUNCH();
     }
     return 0;

@@ -418,6 +418,15 @@ def volume_filter_to_numpy(result):
     return _per_frame(result, FILTER_KEYS + (("shift",) if "shift" in result else ()), "evidence")
 
 
+SMOOTHER_KEYS = ("joints", "smoothed", "agreement", "filtered_joints", "shift_filtered")
+
+
+def volume_smoother_to_numpy(result):
+    """The dict of ``VolumeSmoother.finish`` as a list of per-frame dicts of numpy arrays (the keys without the frame dimension and
+    without the ``beliefs``; ``shift`` when joints were pushed): what run_sequence.py --smooth_info_output writes."""
+    return _per_frame(result, SMOOTHER_KEYS + (("shift",) if "shift" in result else ()), "agreement")
+
+
 # ----------------------------------------------------------------------------------------------
 # skeleton-coupled joints (csrc/skeleton_prior.hip; sceneego_amd/skeleton_prior.py; the reference has only Skeleton._skeleton_resize)
 # ----------------------------------------------------------------------------------------------

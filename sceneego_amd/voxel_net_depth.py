@@ -482,6 +482,24 @@ class VoxelNetwork_depth(nn.Module):
         from .volume_filter import VolumeFilter
         return VolumeFilter(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor)
 
+    def volume_smoother(self, sigma=0.10, radius=None, floor=1e-3, max_bytes=None):
+        """A ``sceneego_amd.volume_smoother.VolumeSmoother`` bound to the module's own ``coord_volumes``, grid and cuboid side: the
+        forward-backward smoother that goes with ``volume_filter``, for ONE recorded track.  ``s = net.volume_smoother();
+        s.push(volumes)`` per batch of consecutive frames returns what ``volume_filter().step(..., return_beliefs=True)`` returns and
+        keeps copies of the volumes and the beliefs on the device (2 x B x J x G^3 x 4 bytes per push, at most ``max_bytes``; default:
+        half of the free device memory at the first push); ``s.finish()`` walks them from last to first and returns the smoothed
+        joints of all frames, each conditioned on the whole track, and with ``return_beliefs`` the smoothed beliefs, which
+        ``joint_statistics``, ``joint_modes``, ``constrain_to_scene`` and the volume renderer take unchanged.  The parameters are the
+        filter's: a convention, not calibrated.  ``forward()`` itself is unchanged.
+
+        Raises ValueError when ``config.model.volume_softmax`` is false or a parameter is out of range; nothing touches the device
+        before the first ``push``."""
+        if not self.volume_softmax:
+            raise ValueError("volume_smoother needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        from .volume_smoother import VolumeSmoother
+        return VolumeSmoother(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor,
+                              max_bytes=max_bytes)
+
     def skeleton_prior(self, bone_lengths, tau=0.03, floor=1e-3):
         """A ``sceneego_amd.skeleton_prior.SkeletonPrior`` bound to the module's own ``coord_volumes``, grid and cuboid side: belief
         propagation over the kinematic tree with a bone-length shell on every edge.  ``s = net.skeleton_prior(lengths);
