@@ -21,7 +21,7 @@ if ROOT not in sys.path:
 
 
 def load_predictions(pred_dir):
-    if os.path.isfile(pred_dir):                             # the one pickle of run_sequence.py --output / --track_output
+    if os.path.isfile(pred_dir):                             # the one pickle of run_sequence.py --output / --track_output / --path_output
         with open(pred_dir, "rb") as f:
             poses = np.asarray(pickle.load(f), dtype=np.float64)
         if poses.ndim != 3 or poses.shape[1:] != (15, 3):
@@ -136,7 +136,7 @@ def evaluate(pred, gt, scale=True):
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--pred_dir", required=True, help="directory of <image name>.pkl files written by demo.py, or the one pickle of "
-                    "run_sequence.py --output / --track_output")
+                    "run_sequence.py --output / --track_output / --path_output")
     ap.add_argument("--gt", default=None, help="pickle: dict name -> [15,3], or [T,15,3] in sorted file order (required unless --bones "
                     "is all that is asked for)")
     ap.add_argument("--no-scale", action="store_true", help="rigid instead of similarity alignment (align_skeleton(scale=False))")

@@ -725,6 +725,71 @@ int se_volume_smooth_f32(const float* prob, const float* belief, const int* rest
                          const int* have_link, void* stream);
 long long se_volume_smooth_scratch_bytes(int rows, int G, int radius);
 
+/* Most probable joint trajectory: the max-product (Viterbi) pass that goes with se_volume_filter_f32 and se_volume_smooth_f32
+ * (sceneego_amd/volume_viterbi.py: VolumeViterbi; VoxelNetwork_depth.volume_path returns one).  The filter and the smoother give per
+ * frame the marginal of each joint; this gives the single most probable trajectory of each joint through the grid.
+ * MODEL NOTE: it is the Viterbi recursion of the model whose transition score is max((1 - floor) W(d), floor / N), W the separable
+ * product of the taps: within a factor of 2 of the filter's (1 - floor) W + floor / N, and separable.  No other convention is added.
+ * tests/volume_viterbi_model.py restates the definition in numpy float32 and every output is compared with it BIT FOR BIT: all
+ * arithmetic is float32, one rounding per operation (no fused multiply-add), in exactly the order below; float32 gradual underflow is
+ * part of the definition (the library is built with denormals kept, hipcc's default for gfx950).
+ *   prob, taps, G, radius, floor, rows, frames, voxels, flat index n = (i G + j) G + k: as for se_volume_filter_f32.
+ *   keep = 1.0f - floor,  uniform = floor / (float)voxels   (floor rounded to float32 first)
+ * STAGE      the maximum along one axis: best = 0.0f, offset 0; for d = -radius..radius ascending, skipping taps that leave the grid:
+ *            cand = v[n + d] * w[d]; if cand > best, take it and d.  A NaN never wins (> is false), equal candidates keep the lowest
+ *            d, all-zero keeps d = 0.
+ * THREE STAGES along k, then j, then i, as in blur3, each on the values of the stage before: e3 = ((s w) w) w.  The winning offsets
+ *            compose into the predecessor voxel y(x), x = (i, j, k):  i' = i + di(x);  j' = j + dj at (i', j, k);  k' = k + dk at
+ *            (i', j', k).
+ * STEP/JUMP  step = keep * e3(x),  jump = uniform * best_prev, best_prev the maximum of the previous frame's scaled scores at voxel
+ *            peak_prev (lowest index among equals).  If jump > step: m = jump, predecessor peak_prev, jump bit set; otherwise m = step
+ *            with predecessor y(x).
+ * UPDATE     a = p(x) * m.  M = max a under the same rule (from 0.0f, strictly greater wins, ascending index: a NaN never wins, equals
+ *            keep the lowest index), peak its index, e = ilogb(M), s = ldexpf(a, -e): an exact scaling but for underflow, best =
+ *            ldexpf(M, -e) in [1, 2).  No division, no drift over long sequences.
+ * RESTART    without a prior, or when M is not a finite number > 0: a = p, M, peak and e come from p, every back-pointer of the frame
+ *            is -1 (segment start), restarted = 1.  If p has no finite positive maximum either: s = p unscaled, peak = -1, best = NaN,
+ *            e = 0 and the next frame restarts.
+ *   state      [rows][voxels] float32: the scaled scores s.  In: those before the call's first frame, read only for rows with a
+ *              prior.  Out: those of the call's last frame.
+ *   peak_state [rows] int32, best_state [rows] float32: peak and best that go with `state`, in / out like it
+ *   have_prior NULL (no row has a prior: the first call of a track) or int32 [rows] on the device; a row has a prior where it is
+ *              non-zero AND peak_state >= 0
+ *   back_out   [frames][rows][voxels] int32: the predecessor's flat index, plus 1 << 30 for a jump, or -1
+ *   peak, exponent, restarted [frames][rows] int32 and best [frames][rows] float32
+ *   scratch    se_volume_viterbi_scratch_bytes(rows, G, radius) bytes, 4-byte aligned; 0 for a shape out of range.  rows (G^3 + 4 G)
+ *              words and 2 rows G^3 bytes (the k and j offsets, int8).
+ * Three launches per frame on `stream` (k and j stage of one i-plane per workgroup in LDS; i stage of one j-slab fused with the offset
+ * composition, step or jump and the product; a fold of one (max, lowest index) record per workgroup) and one per call that scales the
+ * state.  No atomics and no sums: every result is a product, a comparison or a selection under a total order, so the results are
+ * bitwise identical from run to run and independent of how the frames are cut into calls.  Allocates nothing.
+ * SE_ERR_BAD_ARG, with nothing launched: a null pointer other than have_prior, a pointer that is not 4-byte aligned, frames < 1, rows
+ * outside 1..65535, G outside 2..128, voxels != G^3, radius outside 0..min(16, G - 1), floor outside [0, 1] or NaN, scratch_bytes below
+ * se_volume_viterbi_scratch_bytes(rows, G, radius).
+ *
+ * se_volume_viterbi_path_i32: the back-walk over one stored chunk of `frames` frames, from its last frame to its first; a track is walked
+ * by calls over its chunks LAST CHUNK FIRST.  x of the track's last frame is its peak; x_{t-1} = back_t[x_t] & (2^30 - 1); where frame
+ * t starts a segment (restarted, back-pointer -1) x_{t-1} = peak_{t-1}.  A frame without a peak has index -1.
+ *   cursor     [rows] int32, in / out: what the chunk's first frame points back to (< 0: the frame before it takes its own peak).  Read
+ *              only with have_next = 1 (a later chunk was walked before); have_next = 0: the chunk's last frame ends the track.
+ *   index      [frames][rows] int32: x_t          jumped  [frames][rows] int32: 1 where the path reached x_t by a jump
+ * An index outside 0..voxels-1 found in `back` or `cursor` is never followed: the frame takes its own peak.  SE_ERR_BAD_ARG: a null or
+ * misaligned pointer, frames < 1, rows outside 1..65535, voxels outside 1..128^3, have_next other than 0 / 1.
+ *
+ * se_volume_viterbi_refine_f32: joints [frames][rows][3] float32 from index [frames][rows]: the centroid of prob over the window
+ * |delta| <= refine around x_t, clipped to the grid: float64 sums of p and p c in ascending flat index (as se_joint_modes_f32 does its
+ * windows), NaN cells passed over, the quotient rounded once to float32.  Where the window sum is not a finite number > 0, or refine =
+ * 0 (prob may then be NULL), the joint is the voxel centre; index -1 gives NaN.  refine in 0..3.  SE_ERR_BAD_ARG: a null or misaligned
+ * pointer, frames < 1, rows outside 1..65535, G outside 2..128, voxels != G^3, refine outside 0..3.                                   */
+int se_volume_viterbi_f32(const float* prob, const float* taps, float* state, int* peak_state, float* best_state, int* back_out,
+                          int* peak, float* best, int* exponent, int* restarted, void* scratch, long long scratch_bytes, int frames,
+                          int rows, int voxels, int G, int radius, float floor, const int* have_prior, void* stream);
+long long se_volume_viterbi_scratch_bytes(int rows, int G, int radius);
+int se_volume_viterbi_path_i32(const int* back, const int* peak, const int* restarted, int* cursor, int* index, int* jumped,
+                               int frames, int rows, int voxels, int have_next, void* stream);
+int se_volume_viterbi_refine_f32(const float* prob, const float* coord, const int* index, float* joints, int frames, int rows,
+                                 int voxels, int G, int refine, void* stream);
+
 /* Skeleton-coupled joints: sum-product belief propagation over the kinematic tree of the joint volumes, with a spherical-shell
  * bone-length factor on every edge (sceneego_amd/skeleton_prior.py: SkeletonPrior; VoxelNetwork_depth.skeleton_prior returns one).  The
  * reference forces bone lengths onto a finished pose (utils/skeleton.py: kinematic_parents, _skeleton_resize); this couples the whole

@@ -62,6 +62,13 @@ at most ``--bone_frames`` evenly spaced frames (``estimate_bone_lengths``: the p
 ``--skeleton_info_output`` adds the per-frame dicts (joints, evidence, coupled, bone_error, shift, bone_error_before) and
 ``--render_volumes coupled`` draws the coupled beliefs.  With ``--filter_output`` as well the order is couple, then filter (with
 ``--smooth_output``: couple, filter, smooth): the filter runs on the coupled beliefs.  The volume as likelihood, the shell and the floor are a convention, not calibrated.
+``--path_output`` writes a pickle in the format of ``--output`` whose joints lie on the most probable trajectory of every joint through
+the sequence's volumes (``VoxelNetwork_depth.volume_path``, ``sceneego_amd/volume_viterbi.py``: the max-product pass on the filter's
+motion model, ``--filter_sigma``, ``--filter_radius`` and ``--filter_floor``): every batch is pushed on the stream it ran on, the
+back-pointers and, with ``--path_refine`` > 0 (default 1), the volumes stay on the device (31.4 MB per frame at 15 x 64^3; at most
+``--path_max_gb``) and a walk back at the end of the sequence picks the path.  ``--path_info_output`` adds the per-frame dicts (joints,
+index, coord, jumped, segment_start, log_score, moved, shift).  With ``--skeleton_output`` it runs on the coupled beliefs.  It prints
+its MPJPE beside the others; ``evaluate.py --pred_dir path.pkl`` reads the file like ``--output``.
 """
 import argparse
 import json
@@ -243,7 +250,7 @@ class SequenceRunner:
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
             volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False,
-            smooth=None):
+            smooth=None, path=None):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -260,10 +267,14 @@ class SequenceRunner:
         coupled beliefs.  With ``filter`` as well the order is couple, then filter: the filter runs on the coupled beliefs (its
         ``shift`` is still measured from the soft-argmax joints).  ``smooth`` (with ``filter``): a dict with ``max_bytes`` for
         ``VoxelNetwork_depth.volume_smoother``: the filter is the smoother's own, every batch is pushed instead of stepped, and the
-        per-frame dicts of its ``finish()``, run once behind the last batch, are appended after the skeleton's."""
+        per-frame dicts of its ``finish()``, run once behind the last batch, are appended after the skeleton's.  ``path``: a dict of
+        ``sigma`` / ``radius`` / ``floor`` / ``refine`` / ``max_bytes`` for ``VoxelNetwork_depth.volume_path``: every batch's volumes
+        (with ``skeleton`` the coupled beliefs) are pushed on the stream the batch ran on, and the per-frame dicts of its ``finish()``
+        are appended last."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
-                                     skeleton_couple_to_numpy, volume_filter_to_numpy, volume_smoother_to_numpy)
+                                     skeleton_couple_to_numpy, volume_filter_to_numpy, volume_path_to_numpy,
+                                     volume_smoother_to_numpy)
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
@@ -278,13 +289,15 @@ class SequenceRunner:
         if render_coupled and (skeleton is None or not render_volumes or render_filtered):
             raise ValueError("render_coupled needs skeleton and render_volumes, and excludes render_filtered")
         sp = self.net.skeleton_prior(**skeleton) if skeleton is not None else None
+        vp = self.net.volume_path(**path) if path is not None else None
 
         def couple_and_filter(vol, kp, job, stream=None):
             """The skeleton coupling and the filter of one batch, in that order: (filter dict, skeleton dict, job)."""
             fr = sk = None
             if sp is not None:
-                sk = sp.couple(vol, joints=kp, return_beliefs=vf is not None or (render_coupled and job is not None), stream=stream)
-                if vf is not None:
+                sk = sp.couple(vol, joints=kp, return_beliefs=vf is not None or vp is not None or (render_coupled and job is not None),
+                               stream=stream)
+                if vf is not None or vp is not None:
                     vol = sk["beliefs"]
                 if render_coupled and job is not None:
                     job = job[:-1] + (sk["beliefs"],)
@@ -296,6 +309,8 @@ class SequenceRunner:
                     fr = vf.step(vol, joints=kp, return_beliefs=want_beliefs, stream=stream)
                 if "beliefs" in fr:
                     job = job[:-1] + (fr["beliefs"],)
+            if vp is not None:             # on the raw volumes, or the coupled beliefs: never on the filter's
+                vp.push(vol, joints=kp, stream=stream)
             return fr, sk, job
 
         rendering = render_dir is not None or render_video is not None
@@ -364,7 +379,7 @@ class SequenceRunner:
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
                     st = sc = con = md = fr = sk = None
-                    if stats or scene or constrain or modes or vf is not None or sp is not None:
+                    if stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
@@ -391,12 +406,14 @@ class SequenceRunner:
                     self.video.close()
                     self.video = None
         frame_smooth = volume_smoother_to_numpy(vs.finish()) if vs is not None else None
-        if not (stats or scene or constrain or modes or vf is not None or sp is not None):
+        frame_path = volume_path_to_numpy(vp.finish()) if vp is not None else None
+        if not (stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
             + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
             + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ()) \
-            + ((frame_skeleton,) if sp is not None else ()) + ((frame_smooth,) if vs is not None else ())
+            + ((frame_skeleton,) if sp is not None else ()) + ((frame_smooth,) if vs is not None else ()) \
+            + ((frame_path,) if vp is not None else ())
 
 
 def _size(text):
@@ -465,6 +482,16 @@ def build_parser():
                     "joints, smoothed, agreement, filtered_joints, shift_filtered, shift)")
     ap.add_argument("--smooth_max_gb", type=float, default=None, help="with --smooth_output: the most device memory the stored volumes "
                     "and beliefs may take, in GiB (default: half of what is free at the first batch)")
+    ap.add_argument("--path_output", default=None, help="pickle in the format of --output holding the joints of the most probable "
+                    "trajectory of every joint through the sequence's volumes (sceneego_amd/volume_viterbi.py; --filter_sigma, "
+                    "--filter_radius, --filter_floor: the filter's convention, not calibrated); with --skeleton_output it runs on the "
+                    "coupled beliefs")
+    ap.add_argument("--path_info_output", default=None, help="pickle of the per-frame path dicts (list of dicts of numpy arrays: "
+                    "joints, index, coord, jumped, segment_start, log_score, moved, shift)")
+    ap.add_argument("--path_refine", type=int, default=None, help="with --path_output: the path voxel is refined to the centroid of the "
+                    "volume over this many voxels around it, 0..3 (default 1; 0: the voxel centre, and no volumes are stored)")
+    ap.add_argument("--path_max_gb", type=float, default=None, help="with --path_output: the most device memory the stored "
+                    "back-pointers and volumes may take, in GiB (default: half of what is free at the first batch)")
     ap.add_argument("--skeleton_output", default=None, help="pickle in the format of --output holding the joints coupled over the "
                     "kinematic tree inside every frame (sceneego_amd/skeleton_prior.py: a convention, not calibrated)")
     ap.add_argument("--skeleton_info_output", default=None, help="pickle of the per-frame skeleton dicts (list of dicts of numpy arrays: "
@@ -521,6 +548,17 @@ def parse_args(argv=None):
         args.filter = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor}
     elif args.smooth_max_gb is not None:
         raise SystemExit("--smooth_max_gb needs --smooth_output")
+    args.path = None
+    if args.path_output is not None or args.path_info_output is not None:
+        if args.path_max_gb is not None and not args.path_max_gb >= 0:
+            raise SystemExit("--path_max_gb must be >= 0")
+        if args.path_refine is not None and not 0 <= args.path_refine <= 3:
+            raise SystemExit("--path_refine must be in 0..3")
+        args.path = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor,
+                     "refine": 1 if args.path_refine is None else args.path_refine,
+                     "max_bytes": None if args.path_max_gb is None else int(args.path_max_gb * 2 ** 30)}
+    elif args.path_max_gb is not None or args.path_refine is not None:
+        raise SystemExit("--path_max_gb and --path_refine need --path_output")
     if not (args.skeleton_tau > 0 and args.skeleton_tau != float("inf")):
         raise SystemExit("--skeleton_tau must be a finite number > 0")
     if not 0.0 <= args.skeleton_floor <= 1.0:
@@ -578,8 +616,8 @@ def main(argv=None):
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
                        volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
                        filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled,
-                       smooth=args.smooth)
-    if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None:
+                       smooth=args.smooth, path=args.path)
+    if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None or args.path is not None:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
         frame_scene = extra.pop(0) if want_scene else None
@@ -589,6 +627,7 @@ def main(argv=None):
         frame_filter = extra.pop(0) if want_filter else None
         frame_skeleton = extra.pop(0) if skeleton is not None else None
         frame_smooth = extra.pop(0) if args.smooth is not None else None
+        frame_path = extra.pop(0) if args.path is not None else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -678,6 +717,22 @@ def main(argv=None):
                                            float(np.mean([fr["bone_error_before"] for fr in frame_skeleton])),
                                            float(np.mean([fr["bone_error"] for fr in frame_skeleton])),
                                            int(sum(not fr["coupled"] for fr in frame_skeleton))))
+    if args.path is not None:
+        on_path = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_path]
+        for path, obj in ((args.path_output, on_path), (args.path_info_output, frame_path)):
+            if path is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "wb") as f:
+                    pickle.dump(obj, f)
+        result["path"], result["path_info"] = on_path, frame_path
+        result["path_mpjpe"] = M.mpjpe(np.stack(on_path).astype(np.float64), gt)
+        others = "".join(f", {name} {result[key]}" for name, key in (("filtered", "filtered_mpjpe"), ("smoothed", "smoothed_mpjpe"),
+                                                                      ("coupled", "coupled_mpjpe")) if key in result)
+        print("most probable path (a convention, not calibrated): mpjpe: {} (soft-argmax {}{}), mean shift {:.4f} m, {} jumps and {} "
+              "segment starts after the first frame in {} joint-frames".format(
+                  result["path_mpjpe"], mpjpe, others, float(np.nanmean([fr["shift"] for fr in frame_path])),
+                  int(sum(fr["jumped"].sum() for fr in frame_path)), int(sum(fr["segment_start"].sum() for fr in frame_path[1:])),
+                  int(sum(fr["index"].size for fr in frame_path))))
     return result
 
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -115,6 +115,10 @@ SIGNATURES = {
     "se_volume_filter_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "se_volume_smooth_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_volume_smooth_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "se_volume_viterbi_scratch_bytes": (_ll, [_i, _i, _i]),
+    "se_volume_viterbi_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "se_volume_viterbi_path_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "se_volume_viterbi_refine_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "se_shell_correlate_scratch_bytes": (_ll, [_i, _i]),
     "se_shell_correlate_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _f, _vp]),
     "se_skeleton_couple_scratch_bytes": (_ll, [_i, _i, _i, _i]),
@@ -1247,6 +1251,93 @@ def volume_smooth(prob, belief, restarted, coord, taps, state, smoothed_out, joi
                                        scratch.numel(), frames, rows, voxels, grid, radius, floor, _ptr(have_link), _stream()),
            "se_volume_smooth_f32")
     return joints, agreement, smoothed
+
+
+# The max-product pass on the filter's model (csrc/volume_viterbi.hip; sceneego_amd/volume_viterbi.py drives it)
+VITERBI_JUMP = 1 << 30     # the jump bit of a back-pointer; the predecessor's flat index is the rest
+VITERBI_MAX_REFINE = 3
+
+
+def volume_viterbi_scratch_bytes(rows, grid, radius) -> int:
+    return int(load().se_volume_viterbi_scratch_bytes(int(rows), int(grid), int(radius)))
+
+
+def volume_viterbi(prob, taps, state, peak_state, best_state, back_out, peak, best, exponent, restarted, frames, rows, voxels, grid,
+                   radius, floor, have_prior=None, scratch=None):
+    """se_volume_viterbi_f32: ``frames`` consecutive steps of the max-product recursion on ``prob`` [frames, rows, voxels] (voxels =
+    grid^3) from the scaled scores in ``state`` [rows, voxels] with their ``peak_state`` [rows] int32 and ``best_state`` [rows]
+    float32, all three updated in place (the header states the definition).  ``taps`` [2 radius + 1] float32 on the device;
+    ``have_prior`` None (no row has a prior) or int32 [rows].  ``back_out`` [frames, rows, voxels] int32, ``peak``, ``exponent``,
+    ``restarted`` [frames, rows] int32 and ``best`` [frames, rows] float32 are written.  ``scratch``: an optional uint8 workspace of at
+    least ``volume_viterbi_scratch_bytes(rows, grid, radius)`` bytes.  Every argument is checked here and a bad one raises
+    HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
+    what = "volume_viterbi"
+    frames, rows, voxels, grid, radius, floor = int(frames), int(rows), int(voxels), int(grid), int(radius), float(floor)
+    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
+                                f"voxels = {voxels} (grid^3) expected")
+    if not 0 <= radius <= min(FILTER_MAX_RADIUS, grid - 1):
+        raise HipExtensionError(f"{what}: radius = {radius} (0..{min(FILTER_MAX_RADIUS, grid - 1)}) expected")
+    if not 0.0 <= floor <= 1.0:
+        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    total = frames * rows * voxels
+    dev = _check_args(what, (("prob", prob, torch.float32, total), ("taps", taps, torch.float32, 2 * radius + 1),
+                             ("state", state, torch.float32, rows * voxels), ("peak_state", peak_state, torch.int32, rows),
+                             ("best_state", best_state, torch.float32, rows), ("back_out", back_out, torch.int32, total),
+                             ("peak", peak, torch.int32, frames * rows), ("best", best, torch.float32, frames * rows),
+                             ("exponent", exponent, torch.int32, frames * rows), ("restarted", restarted, torch.int32, frames * rows)),
+                      (("have_prior", have_prior, torch.int32, rows), ("scratch", scratch, torch.uint8, None)))
+    if _overlap(state, prob) or _overlap(back_out, prob) or _overlap(back_out, state):
+        raise HipExtensionError(f"{what}: prob, state and back_out must not alias one another")
+    need = volume_viterbi_scratch_bytes(rows, grid, radius)
+    if need <= 0:
+        raise HipExtensionError(f"{what}: rows = {rows}, grid = {grid}, radius = {radius} is not supported")
+    scratch = _scratch(what, scratch, need, torch.uint8, dev)
+    _check(load().se_volume_viterbi_f32(_ptr(prob), _ptr(taps), _ptr(state), _ptr(peak_state), _ptr(best_state), _ptr(back_out),
+                                        _ptr(peak), _ptr(best), _ptr(exponent), _ptr(restarted), _ptr(scratch), scratch.numel(),
+                                        frames, rows, voxels, grid, radius, floor, _ptr(have_prior), _stream()),
+           "se_volume_viterbi_f32")
+    return peak, best, exponent, restarted
+
+
+def volume_viterbi_path(back, peak, restarted, cursor, index, jumped, frames, rows, voxels, have_next):
+    """se_volume_viterbi_path_i32: the back-walk over one stored chunk (``back`` [frames, rows, voxels], ``peak`` and ``restarted``
+    [frames, rows], all int32), last frame to first; ``cursor`` [rows] int32 is read when ``have_next`` (a later chunk was walked
+    before) and written; ``index`` and ``jumped`` [frames, rows] int32 are written.  Arguments are checked before anything is launched."""
+    what = "volume_viterbi_path"
+    frames, rows, voxels = int(frames), int(rows), int(voxels)
+    if frames < 1 or rows <= 0 or rows > 65535 or not 1 <= voxels <= FILTER_MAX_GRID ** 3:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), voxels = {voxels} (1..{FILTER_MAX_GRID}^3) "
+                                "expected")
+    if not isinstance(have_next, (bool, int)) or int(have_next) not in (0, 1):
+        raise HipExtensionError(f"{what}: have_next = {have_next!r} must be 0 or 1")
+    _check_args(what, (("back", back, torch.int32, frames * rows * voxels), ("peak", peak, torch.int32, frames * rows),
+                       ("restarted", restarted, torch.int32, frames * rows), ("cursor", cursor, torch.int32, rows),
+                       ("index", index, torch.int32, frames * rows), ("jumped", jumped, torch.int32, frames * rows)))
+    _check(load().se_volume_viterbi_path_i32(_ptr(back), _ptr(peak), _ptr(restarted), _ptr(cursor), _ptr(index), _ptr(jumped), frames,
+                                             rows, voxels, int(have_next), _stream()), "se_volume_viterbi_path_i32")
+    return index, jumped
+
+
+def volume_viterbi_refine(prob, coord, index, joints, frames, rows, voxels, grid, refine):
+    """se_volume_viterbi_refine_f32: ``joints`` [frames, rows, 3] float32 from the path ``index`` [frames, rows] int32: the centroid of
+    ``prob`` [frames, rows, voxels] over the window of ``refine`` voxels (0..3) around each path voxel, or the voxel centre
+    (``refine`` = 0: ``prob`` may be None).  Arguments are checked before anything is launched."""
+    what = "volume_viterbi_refine"
+    frames, rows, voxels, grid = int(frames), int(rows), int(voxels), int(grid)
+    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
+                                f"voxels = {voxels} (grid^3) expected")
+    if isinstance(refine, bool) or int(refine) != refine or not 0 <= int(refine) <= VITERBI_MAX_REFINE:
+        raise HipExtensionError(f"{what}: refine = {refine!r} (an integer in 0..{VITERBI_MAX_REFINE}) expected")
+    refine = int(refine)
+    named = (("coord", coord, torch.float32, voxels * 3), ("index", index, torch.int32, frames * rows),
+             ("joints", joints, torch.float32, frames * rows * 3))
+    prob_entry = ("prob", prob, torch.float32, frames * rows * voxels)
+    _check_args(what, named + ((prob_entry,) if refine > 0 else ()), () if refine > 0 else (prob_entry,))
+    _check(load().se_volume_viterbi_refine_f32(_ptr(prob), _ptr(coord), _ptr(index), _ptr(joints), frames, rows, voxels, grid, refine,
+                                               _stream()), "se_volume_viterbi_refine_f32")
+    return joints
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

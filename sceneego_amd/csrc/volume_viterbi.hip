@@ -1,0 +1,453 @@
+// Most probable joint trajectory: the max-product (Viterbi) pass over the softmaxed joint volumes of a sequence
+// (sceneego_amd/volume_viterbi.py: VolumeViterbi; VoxelNetwork_depth.volume_path returns one).  No counterpart in the reference.
+// include/sceneego_hip.h states the definition operation by operation; tests/volume_viterbi_model.py restates it in numpy float32 and
+// every value written here is compared with it bit for bit.  This file is built with -ffp-contract=off: one rounding per operation.
+//
+// Per frame and row (one joint of one track), with the scaled scores s of the frame before in `state`:
+//     e1 = stage(s) along k, e2 = stage(e1) along j, e3 = stage(e2) along i         stage: max over d of v[n + d] w[d], with its argmax
+//     step = keep e3(x),  jump = uniform best_prev;  m = jump > step ? jump : step;  a = p m
+//     M = max a, peak = its lowest index, e = ilogb(M), s' = ldexp(a, -e)            or, without a prior or with an M that is not a
+//                                                                                   finite number > 0:  a = p (restart), back = -1
+// Three launches per frame, mirroring the filter's (volume_filter.hip), and one more per call:
+//   vv_stage_kj_kernel  grid (G, rows), block 256: one i-plane [G j][G k] of s staged in LDS (scaled by the exponent of the frame before
+//                       on the way in), the k stage into a second LDS plane, the j stage from there; e2 (float32) and the two winning
+//                       offsets (int8 each) go to scratch.  (2 G + 2 R) G floats of LDS: 38 KB at 64^3 and R = 10, 144 KB at 128^3 and R = 16.
+//   vv_update_kernel    grid (G, rows), block 256: the slab [G i][G k] of e2 and of the j offsets at one j staged in LDS (26 KB; 96 KB),
+//                       the i stage, the composition of the three offsets into the predecessor voxel (the k offset is one gathered
+//                       byte), step or jump, the product with p.  The raw a goes to `state`, the back-pointer to `back_out`, the
+//                       workgroup's (max a, lowest index) and (max p, lowest index) to one record of 4 words.
+//   vv_fold_kernel      grid (chunks, rows), block 256: every workgroup folds the row's G records, decides the restart and, for a row
+//                       that restarts WITH a prior (the others were written as copies by the update pass), writes its share of the
+//                       copy of p and of the -1 back-pointers; chunk 0 writes peak, best, exponent and restarted of the frame.
+//   vv_scale_kernel     once per call: `state` holds the raw a of the last frame and is scaled by that frame's exponent, so the state a
+//                       call returns is the scaled one; chunk 0 hands peak and best on in peak_state / best_state.
+// Inside a call the scaling is applied when the next frame stages the state: ldexp of the same value by the same exponent, so the bits do
+// not depend on how the frames are cut into calls.
+// A thread owns column k of the staged plane and every (256 / W)-th row of it, W the power of two >= G: any G in 2..128.  It takes
+// SE_VV_ROWS = 4 of its rows through the tap loop together: a tap is a product, a comparison and two selects that wait for the `best`
+// of the tap before, and four rows are four independent chains.  For that the planes the j and the i stage read carry R rows of zeros
+// on either side, so that every row runs the same 2 R + 1 taps: a tap that leaves the grid reads 0, its candidate 0 w is never > best
+// (best starts at 0 and only grows; 0 inf = NaN fails too), which is the definition's "skipping taps that leave the grid" bit for bit.
+//
+// BYTE MODEL per frame, row and voxel: the k/j stage reads s and writes e2 and two offset bytes (10 B); the update pass reads e2, the
+// two offset bytes and p and writes a and the back-pointer (18 B): 28 B, the filter's figure (its third pass is the division; here the
+// fold touches voxels only on a restart).  The scale pass adds 8 B per row and voxel per CALL.  The offset gather (one byte at
+// (i', j', k)) stays inside the row's plane set that the k/j stage just wrote.
+//
+// ORDER.  No atomics, no sums: every result is a product, a comparison or a selection under the total order "greater value, then lower
+// index" (row_reduce.h: peak_combine, associative and commutative), so any reduction tree gives the same bits.  Back-pointers and scores
+// are written with plain vector stores.
+//
+// THE WALK (vv_path_kernel, one lane per row, sequential over the frames of a stored chunk, last chunk first, the cursor carried in
+// device memory) and THE REFINEMENT (vv_refine_kernel, one lane per (frame, row): float64 sums over the window in ascending flat index,
+// as joint_modes.hip does its windows) follow the header's definition.
+#include <float.h>
+
+#include "row_reduce.h"
+
+#pragma clang fp contract(off)
+
+#define SE_VV_THREADS 256
+#define SE_VV_MAX_G 128
+#define SE_VV_MAX_R 16
+#define SE_VV_REC 4               // max a, its index, max p, its index
+#define SE_VV_MAX_CHUNKS 64
+#define SE_VV_MAX_REFINE 3
+#define SE_VV_JUMP (1 << 30)
+#define SE_VV_ROWS 4              // rows of its column a thread takes through the tap loop together: independent compare-select chains
+
+namespace {
+
+// The row has a prior at this frame.  Frames behind the call's first: the frame before left a peak (peak_prev = its `peak` output).
+// The call's first frame: the caller says so and the state it hands over has a peak.  Nothing read here is written by a launch of the
+// same frame, so the three passes agree.
+__device__ __forceinline__ bool vv_prior(const int* __restrict__ have_prior, const int* __restrict__ peak_state,
+                                         const int* __restrict__ peak_prev, int row) {
+    if (peak_prev != nullptr) return peak_prev[row] >= 0;
+    return have_prior != nullptr && have_prior[row] != 0 && peak_state[row] >= 0;
+}
+
+// grid (G, rows), block 256, dynamic LDS (2 G + 2 R) G floats
+__global__ __launch_bounds__(SE_VV_THREADS) void vv_stage_kj_kernel(const float* __restrict__ state, const float* __restrict__ taps,
+                                                                    const int* __restrict__ have_prior,
+                                                                    const int* __restrict__ peak_state,
+                                                                    const int* __restrict__ peak_prev, const int* __restrict__ exp_prev,
+                                                                    float* __restrict__ e2, signed char* __restrict__ off_k,
+                                                                    signed char* __restrict__ off_j, int G, int voxels, int R,
+                                                                    int wshift) {
+    extern __shared__ __align__(16) float lds[];
+    __shared__ float w[2 * SE_VV_MAX_R + 1];
+    const int t = threadIdx.x, i = blockIdx.x, row = blockIdx.y;
+    if (!vv_prior(have_prior, peak_state, peak_prev, row)) return;  // uniform: the row restarts, nothing of this pass is read
+    const int GG = G * G;
+    float* A = lds;                                                 // [G j][G k]
+    float* Bk = lds + GG;                                           // [R + G + R j][G k]: R rows of zeros on either side (vv_update_kernel)
+    const size_t base = (size_t)row * voxels + (size_t)i * GG;
+    const int down = exp_prev != nullptr ? -exp_prev[row] : 0;      // the state of the call's first frame arrives scaled
+    for (int e = t; e < GG; e += SE_VV_THREADS) A[e] = ldexpf(state[base + e], down);
+    for (int e = t; e < R * G; e += SE_VV_THREADS) { Bk[e] = 0.f; Bk[(R + G) * G + e] = 0.f; }
+    if (t <= 2 * R) w[t] = taps[t];
+    __syncthreads();
+    const int k = t & ((1 << wshift) - 1), jr = t >> wshift, RP = SE_VV_THREADS >> wshift;
+    if (k < G) {
+        const int lo = max(-R, -k), hi = min(R, G - 1 - k);         // the taps that stay inside the row
+        for (int j0 = jr; j0 < G; j0 += SE_VV_ROWS * RP) {
+            float best[SE_VV_ROWS];
+            int off[SE_VV_ROWS], at[SE_VV_ROWS];
+#pragma unroll
+            for (int u = 0; u < SE_VV_ROWS; ++u) { at[u] = min(j0 + u * RP, G - 1) * G + k; best[u] = 0.f; off[u] = 0; }
+            for (int d = lo; d <= hi; ++d) {
+                const float wd = w[d + R];
+#pragma unroll
+                for (int u = 0; u < SE_VV_ROWS; ++u) {
+                    const float cand = A[at[u] + d] * wd;
+                    if (cand > best[u]) { best[u] = cand; off[u] = d; }      // a NaN never wins; equal candidates keep the lowest d
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < SE_VV_ROWS; ++u) {
+                const int j = j0 + u * RP;
+                if (j < G) { Bk[(R + j) * G + k] = best[u]; off_k[base + j * G + k] = (signed char)off[u]; }
+            }
+        }
+    }
+    __syncthreads();
+    if (k < G) {
+        for (int j0 = jr; j0 < G; j0 += SE_VV_ROWS * RP) {
+            float best[SE_VV_ROWS];
+            int off[SE_VV_ROWS], at[SE_VV_ROWS];
+#pragma unroll
+            for (int u = 0; u < SE_VV_ROWS; ++u) { at[u] = (R + min(j0 + u * RP, G - 1)) * G + k; best[u] = 0.f; off[u] = 0; }
+            for (int d = -R; d <= R; ++d) {                         // a tap that leaves the grid reads a zero of the padding: it never wins
+                const float wd = w[d + R];
+#pragma unroll
+                for (int u = 0; u < SE_VV_ROWS; ++u) {
+                    const float cand = Bk[at[u] + d * G] * wd;
+                    if (cand > best[u]) { best[u] = cand; off[u] = d; }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < SE_VV_ROWS; ++u) {
+                const int j = j0 + u * RP;
+                if (j < G) { e2[base + j * G + k] = best[u]; off_j[base + j * G + k] = (signed char)off[u]; }
+            }
+        }
+    }
+}
+
+// grid (G, rows), block 256, dynamic LDS (G + 2 R) G floats and G^2 bytes
+__global__ __launch_bounds__(SE_VV_THREADS) void vv_update_kernel(const float* __restrict__ prob, const float* __restrict__ taps,
+                                                                  const int* __restrict__ have_prior, const int* __restrict__ peak_state,
+                                                                  const float* __restrict__ best_state,
+                                                                  const int* __restrict__ peak_prev, const float* __restrict__ best_prev,
+                                                                  const float* __restrict__ e2, const signed char* __restrict__ off_k,
+                                                                  const signed char* __restrict__ off_j, float* __restrict__ state,
+                                                                  int* __restrict__ back, int* __restrict__ rec, int G, int voxels,
+                                                                  int R, int wshift, float keep, float uniform) {
+    extern __shared__ __align__(16) float lds[];
+    __shared__ float w[2 * SE_VV_MAX_R + 1];
+    __shared__ float sm_p[4][2];
+    __shared__ int sm_i[4][2];
+    const int t = threadIdx.x, j = blockIdx.x, row = blockIdx.y;
+    const bool prior = vv_prior(have_prior, peak_state, peak_prev, row);    // uniform
+    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VV_THREADS >> wshift;
+    const size_t base = (size_t)row * voxels;
+    float* slab = lds;                                              // [R + G + R i][G k]: R rows of zeros on either side
+    signed char* dj = reinterpret_cast<signed char*>(lds + (G + 2 * R) * G);        // [G i][G k]
+    float jump = 0.f;
+    int jump_to = -1;
+    if (prior) {
+        if (k < G)
+            for (int i = ir; i < G; i += RP) {
+                const size_t n = base + ((size_t)i * G + j) * G + k;
+                slab[(R + i) * G + k] = e2[n];
+                dj[i * G + k] = off_j[n];
+            }
+        for (int e = t; e < R * G; e += SE_VV_THREADS) { slab[e] = 0.f; slab[(R + G) * G + e] = 0.f; }
+        if (t <= 2 * R) w[t] = taps[t];
+        jump = uniform * (peak_prev != nullptr ? best_prev[row] : best_state[row]);
+        jump_to = (peak_prev != nullptr ? peak_prev[row] : peak_state[row]) | SE_VV_JUMP;
+    }
+    __syncthreads();
+    Peak pa = {0.f, INT_MAX}, pp = {0.f, INT_MAX};                  // a value must be > 0 to be a maximum
+    if (k < G) {
+        for (int i0 = ir; i0 < G; i0 += SE_VV_ROWS * RP) {
+            float best[SE_VV_ROWS], p[SE_VV_ROWS];
+            int off[SE_VV_ROWS], at[SE_VV_ROWS];
+#pragma unroll
+            for (int u = 0; u < SE_VV_ROWS; ++u) {
+                const int i = min(i0 + u * RP, G - 1);
+                p[u] = prob[base + (i * G + j) * G + k];
+                at[u] = (R + i) * G + k;
+                best[u] = 0.f;
+                off[u] = 0;
+            }
+            if (prior) {
+                for (int d = -R; d <= R; ++d) {                     // a tap that leaves the grid reads a zero of the padding: it never wins
+                    const float wd = w[d + R];
+#pragma unroll
+                    for (int u = 0; u < SE_VV_ROWS; ++u) {
+                        const float cand = slab[at[u] + d * G] * wd;
+                        if (cand > best[u]) { best[u] = cand; off[u] = d; }
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < SE_VV_ROWS; ++u) {
+                const int i = i0 + u * RP;
+                if (i >= G) continue;
+                const int n = (i * G + j) * G + k;
+                float a = p[u];
+                int pred = -1;
+                if (prior) {
+                    // the predecessor voxel: the three winning offsets composed.  An offset is only ever that of a tap inside the
+                    // grid; the clamps only keep a corrupted scratch from steering the gather outside the row.
+                    const int ip = min(max(i + off[u], 0), G - 1);
+                    const int jp = min(max(j + (int)dj[ip * G + k], 0), G - 1);
+                    const int kp = min(max(k + (int)off_k[base + ((size_t)ip * G + jp) * G + k], 0), G - 1);
+                    const float step = keep * best[u];
+                    float m = step;
+                    pred = (ip * G + jp) * G + kp;
+                    if (jump > step) { m = jump; pred = jump_to; }
+                    a = p[u] * m;
+                }
+                state[base + n] = a;
+                back[base + n] = pred;
+                if (a > 0.f) pa = peak_combine(pa, Peak{a, n});
+                if (p[u] > 0.f) pp = peak_combine(pp, Peak{p[u], n});
+            }
+        }
+    }
+    pa = wave_reduce_peak(pa);
+    pp = wave_reduce_peak(pp);
+    if ((t & 63) == 0) {
+        sm_p[t >> 6][0] = pa.p; sm_i[t >> 6][0] = pa.idx;
+        sm_p[t >> 6][1] = pp.p; sm_i[t >> 6][1] = pp.idx;
+    }
+    __syncthreads();
+    if (t < 2) {
+        Peak r = {sm_p[0][t], sm_i[0][t]};
+#pragma unroll
+        for (int x = 1; x < 4; ++x) r = peak_combine(r, Peak{sm_p[x][t], sm_i[x][t]});
+        int* o = rec + ((size_t)row * G + j) * SE_VV_REC + 2 * t;
+        o[0] = __float_as_int(r.p);
+        o[1] = r.idx;
+    }
+}
+
+// grid (chunks, rows), block 256
+__global__ __launch_bounds__(SE_VV_THREADS) void vv_fold_kernel(const float* __restrict__ prob, const int* __restrict__ rec,
+                                                                const int* __restrict__ have_prior, const int* __restrict__ peak_state,
+                                                                const int* __restrict__ peak_prev, float* __restrict__ state,
+                                                                int* __restrict__ back, int* __restrict__ peak, float* __restrict__ best,
+                                                                int* __restrict__ exponent, int* __restrict__ restarted, int G,
+                                                                int voxels) {
+    __shared__ float fin_p[2];
+    __shared__ int fin_i[2];
+    const int t = threadIdx.x, row = blockIdx.y;
+    if (t < 64) {
+        Peak a = {0.f, INT_MAX}, p = {0.f, INT_MAX};
+        for (int x = t; x < G; x += 64) {
+            const int* r = rec + ((size_t)row * G + x) * SE_VV_REC;
+            a = peak_combine(a, Peak{__int_as_float(r[0]), r[1]});
+            p = peak_combine(p, Peak{__int_as_float(r[2]), r[3]});
+        }
+        a = wave_reduce_peak(a);
+        p = wave_reduce_peak(p);
+        if (t == 0) { fin_p[0] = a.p; fin_i[0] = a.idx; fin_p[1] = p.p; fin_i[1] = p.idx; }
+    }
+    __syncthreads();
+    const bool prior = vv_prior(have_prior, peak_state, peak_prev, row);
+    const bool restart = !prior || !(fin_p[0] > 0.f && fin_p[0] <= FLT_MAX);        // a NaN never became a maximum; +inf fails here
+    if (blockIdx.x == 0 && t == 0) {
+        const float M = restart ? fin_p[1] : fin_p[0];
+        const bool alive = M > 0.f && M <= FLT_MAX;                 // no finite positive cell in p either: the next frame restarts
+        const int e = alive ? ilogbf(M) : 0;
+        peak[row] = alive ? (restart ? fin_i[1] : fin_i[0]) : -1;
+        best[row] = alive ? ldexpf(M, -e) : __int_as_float(0x7fc00000);
+        exponent[row] = e;
+        restarted[row] = restart ? 1 : 0;
+    }
+    if (!restart || !prior) return;                                 // a row without a prior was written as the copy already
+    const size_t base = (size_t)row * voxels;
+    for (int n = blockIdx.x * SE_VV_THREADS + t; n < voxels; n += gridDim.x * SE_VV_THREADS) {
+        state[base + n] = prob[base + n];                           // bit for bit
+        back[base + n] = -1;
+    }
+}
+
+// grid (chunks, rows), block 256: the state a call returns is the scaled one
+__global__ __launch_bounds__(SE_VV_THREADS) void vv_scale_kernel(float* __restrict__ state, const int* __restrict__ exponent,
+                                                                 const int* __restrict__ peak, const float* __restrict__ best,
+                                                                 int* __restrict__ peak_state, float* __restrict__ best_state,
+                                                                 int voxels) {
+    const int t = threadIdx.x, row = blockIdx.y;
+    const int down = -exponent[row];
+    const size_t base = (size_t)row * voxels;
+    for (int n = blockIdx.x * SE_VV_THREADS + t; n < voxels; n += gridDim.x * SE_VV_THREADS) state[base + n] = ldexpf(state[base + n], down);
+    if (blockIdx.x == 0 && t == 0) { peak_state[row] = peak[row]; best_state[row] = best[row]; }
+}
+
+// grid (ceil(rows / 64)), block 64: one lane per row, sequential over the frames from last to first
+__global__ __launch_bounds__(64) void vv_path_kernel(const int* __restrict__ back, const int* __restrict__ peak,
+                                                     const int* __restrict__ restarted, int* __restrict__ cursor,
+                                                     int* __restrict__ index, int* __restrict__ jumped, int frames, int rows, int voxels,
+                                                     int have_next) {
+    const int row = blockIdx.x * 64 + threadIdx.x;
+    if (row >= rows) return;
+    // the cursor: the voxel the frame behind this chunk points back to, or < 0: that frame starts a segment (or there is none)
+    int x = have_next ? cursor[row] : -1;
+    for (int f = frames - 1; f >= 0; --f) {
+        const size_t fr = (size_t)f * rows + row;
+        if (x < 0 || x >= voxels) x = peak[fr];                     // the frame's own peak (-1: it has none); never an index outside the row
+        if (x >= voxels) x = -1;
+        const int b = (x >= 0 && restarted[fr] == 0) ? back[fr * voxels + x] : -1;
+        index[fr] = x;
+        jumped[fr] = (b >= 0 && (b & SE_VV_JUMP)) ? 1 : 0;
+        x = b >= 0 ? (b & (SE_VV_JUMP - 1)) : -1;
+    }
+    cursor[row] = x;
+}
+
+// grid (ceil(frames rows / 64)), block 64: one lane per (frame, row)
+__global__ __launch_bounds__(64) void vv_refine_kernel(const float* __restrict__ prob, const float* __restrict__ coord,
+                                                       const int* __restrict__ index, float* __restrict__ joints, int total, int voxels,
+                                                       int G, int refine) {
+    const int fr = blockIdx.x * 64 + threadIdx.x;
+    if (fr >= total) return;
+    float* o = joints + (size_t)fr * 3;
+    const int x = index[fr];
+    if (x < 0 || x >= voxels) {
+        o[0] = o[1] = o[2] = __int_as_float(0x7fc00000);
+        return;
+    }
+    const float* c = coord + (size_t)x * 3;
+    float jx = c[0], jy = c[1], jz = c[2];                          // the voxel centre
+    if (refine > 0) {
+        const int ci = x / (G * G), cj = (x / G) % G, ck = x % G;
+        const int ia = max(ci - refine, 0), ib = min(ci + refine, G - 1);
+        const int ja = max(cj - refine, 0), jb = min(cj + refine, G - 1);
+        const int ka = max(ck - refine, 0), kb = min(ck + refine, G - 1);
+        const float* v = prob + (size_t)fr * voxels;
+        double m = 0.0, mx = 0.0, my = 0.0, mz = 0.0;
+        for (int i = ia; i <= ib; ++i)
+            for (int j = ja; j <= jb; ++j)
+                for (int k = ka; k <= kb; ++k) {                    // ascending flat index
+                    const size_t n = ((size_t)i * G + j) * G + k;
+                    const float pf = v[n];
+                    if (pf != pf) continue;                         // a NaN cell is passed over
+                    const double p = (double)pf;
+                    m += p;
+                    mx += p * (double)coord[n * 3 + 0];             // exact products: 24 x 24 bits
+                    my += p * (double)coord[n * 3 + 1];
+                    mz += p * (double)coord[n * 3 + 2];
+                }
+        if (m > 0.0 && m <= DBL_MAX) {
+            jx = (float)(mx / m);
+            jy = (float)(my / m);
+            jz = (float)(mz / m);
+        }
+    }
+    o[0] = jx; o[1] = jy; o[2] = jz;
+}
+
+inline bool vv_shape_ok(int rows, int G, int R) {
+    return rows >= 1 && rows <= 65535 && G >= 2 && G <= SE_VV_MAX_G && R >= 0 && R <= SE_VV_MAX_R && R <= G - 1;
+}
+inline long long vv_elems(int rows, int G) { return (long long)rows * G * G * G; }
+
+}  // namespace
+
+// e2 [rows][voxels] float32, the records [rows][G][4] words, then the k and the j offsets [rows][voxels] int8 each
+extern "C" long long se_volume_viterbi_scratch_bytes(int rows, int G, int radius) {
+    if (!vv_shape_ok(rows, G, radius)) return 0;
+    const long long bytes = (vv_elems(rows, G) + (long long)rows * G * SE_VV_REC) * 4 + 2 * vv_elems(rows, G);
+    return (bytes + 15) & ~15LL;
+}
+
+extern "C" int se_volume_viterbi_f32(const float* prob, const float* taps, float* state, int* peak_state, float* best_state,
+                                     int* back_out, int* peak, float* best, int* exponent, int* restarted, void* scratch,
+                                     long long scratch_bytes, int frames, int rows, int voxels, int G, int radius, float floor,
+                                     const int* have_prior, void* stream) {
+    if (!prob || !taps || !state || !peak_state || !best_state || !back_out || !peak || !best || !exponent || !restarted || !scratch)
+        return SE_ERR_BAD_ARG;
+    if (frames < 1 || !vv_shape_ok(rows, G, radius)) return SE_ERR_BAD_ARG;
+    if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
+    if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
+    const uintptr_t all = reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(state) |
+                          reinterpret_cast<uintptr_t>(peak_state) | reinterpret_cast<uintptr_t>(best_state) |
+                          reinterpret_cast<uintptr_t>(back_out) | reinterpret_cast<uintptr_t>(peak) | reinterpret_cast<uintptr_t>(best) |
+                          reinterpret_cast<uintptr_t>(exponent) | reinterpret_cast<uintptr_t>(restarted) |
+                          reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(have_prior);
+    if (all & 3) return SE_ERR_BAD_ARG;
+    if (scratch_bytes < se_volume_viterbi_scratch_bytes(rows, G, radius)) return SE_ERR_BAD_ARG;
+    hipStream_t s = se_stream(stream);
+    float* e2 = reinterpret_cast<float*>(scratch);
+    int* rec = reinterpret_cast<int*>(e2 + vv_elems(rows, G));
+    signed char* off_k = reinterpret_cast<signed char*>(rec + (long long)rows * G * SE_VV_REC);
+    signed char* off_j = off_k + vv_elems(rows, G);
+    int wshift = 0;
+    while ((1 << wshift) < G) ++wshift;                                                   // W = 1 << wshift <= 128
+    const int plane = G * G, padded = (G + 2 * radius) * G;                              // floats; the padded plane: R rows of zeros on either side
+    const int stage_lds = (plane + padded) * 4, update_lds = (padded * 4 + plane + 15) & ~15;
+    const int max_padded = (SE_VV_MAX_G + 2 * SE_VV_MAX_R) * SE_VV_MAX_G;
+    SE_ENSURE_LDS(vv_stage_kj_kernel, (SE_VV_MAX_G * SE_VV_MAX_G + max_padded) * 4);        // 144 KB
+    SE_ENSURE_LDS(vv_update_kernel, max_padded * 4 + SE_VV_MAX_G * SE_VV_MAX_G);          // 96 KB
+    const int chunks = min(SE_VV_MAX_CHUNKS, (voxels + SE_VV_THREADS * 4 - 1) / (SE_VV_THREADS * 4));
+    const float keep = 1.0f - floor, uniform = floor / (float)voxels;
+    const size_t frame_elems = (size_t)rows * voxels;
+    for (int f = 0; f < frames; ++f) {
+        const float* p = prob + f * frame_elems;
+        const int* peak_prev = f > 0 ? peak + (size_t)(f - 1) * rows : nullptr;
+        const float* best_prev = f > 0 ? best + (size_t)(f - 1) * rows : nullptr;
+        const int* exp_prev = f > 0 ? exponent + (size_t)(f - 1) * rows : nullptr;
+        if (f > 0 || have_prior) {
+            hipLaunchKernelGGL(vv_stage_kj_kernel, dim3(G, rows), dim3(SE_VV_THREADS), stage_lds, s, state, taps, have_prior,
+                               peak_state, peak_prev, exp_prev, e2, off_k, off_j, G, voxels, radius, wshift);
+            SE_CHECK_LAUNCH();
+        }
+        int* bo = back_out + f * frame_elems;
+        hipLaunchKernelGGL(vv_update_kernel, dim3(G, rows), dim3(SE_VV_THREADS), update_lds, s, p, taps, have_prior, peak_state,
+                           best_state, peak_prev, best_prev, e2, off_k, off_j, state, bo, rec, G, voxels, radius, wshift, keep, uniform);
+        SE_CHECK_LAUNCH();
+        hipLaunchKernelGGL(vv_fold_kernel, dim3(chunks, rows), dim3(SE_VV_THREADS), 0, s, p, rec, have_prior, peak_state, peak_prev, state,
+                           bo, peak + (size_t)f * rows, best + (size_t)f * rows, exponent + (size_t)f * rows,
+                           restarted + (size_t)f * rows, G, voxels);
+        SE_CHECK_LAUNCH();
+    }
+    const size_t last = (size_t)(frames - 1) * rows;
+    hipLaunchKernelGGL(vv_scale_kernel, dim3(chunks, rows), dim3(SE_VV_THREADS), 0, s, state, exponent + last, peak + last, best + last,
+                       peak_state, best_state, voxels);
+    SE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int se_volume_viterbi_path_i32(const int* back, const int* peak, const int* restarted, int* cursor, int* index, int* jumped,
+                                          int frames, int rows, int voxels, int have_next, void* stream) {
+    if (!back || !peak || !restarted || !cursor || !index || !jumped) return SE_ERR_BAD_ARG;
+    if (frames < 1 || rows < 1 || rows > 65535 || voxels < 1 || voxels > SE_VV_MAX_G * SE_VV_MAX_G * SE_VV_MAX_G) return SE_ERR_BAD_ARG;
+    if (have_next != 0 && have_next != 1) return SE_ERR_BAD_ARG;
+    const uintptr_t all = reinterpret_cast<uintptr_t>(back) | reinterpret_cast<uintptr_t>(peak) | reinterpret_cast<uintptr_t>(restarted) |
+                          reinterpret_cast<uintptr_t>(cursor) | reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(jumped);
+    if (all & 3) return SE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(vv_path_kernel, dim3((rows + 63) / 64), dim3(64), 0, se_stream(stream), back, peak, restarted, cursor, index,
+                       jumped, frames, rows, voxels, have_next);
+    SE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int se_volume_viterbi_refine_f32(const float* prob, const float* coord, const int* index, float* joints, int frames,
+                                            int rows, int voxels, int G, int refine, void* stream) {
+    if (!coord || !index || !joints || (!prob && refine > 0)) return SE_ERR_BAD_ARG;
+    if (frames < 1 || rows < 1 || rows > 65535 || G < 2 || G > SE_VV_MAX_G) return SE_ERR_BAD_ARG;
+    if ((long long)G * G * G != (long long)voxels || (long long)frames * rows > INT_MAX) return SE_ERR_BAD_ARG;
+    if (refine < 0 || refine > SE_VV_MAX_REFINE) return SE_ERR_BAD_ARG;
+    const uintptr_t all = reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(coord) | reinterpret_cast<uintptr_t>(index) |
+                          reinterpret_cast<uintptr_t>(joints);
+    if (all & 3) return SE_ERR_BAD_ARG;
+    const int total = frames * rows;
+    hipLaunchKernelGGL(vv_refine_kernel, dim3((total + 63) / 64), dim3(64), 0, se_stream(stream), prob, coord, index, joints, total,
+                       voxels, G, refine);
+    SE_CHECK_LAUNCH();
+    return 0;
+}

@@ -427,6 +427,15 @@ def volume_smoother_to_numpy(result):
     return _per_frame(result, SMOOTHER_KEYS + (("shift",) if "shift" in result else ()), "agreement")
 
 
+PATH_KEYS = ("joints", "index", "coord", "jumped", "segment_start", "log_score", "moved")
+
+
+def volume_path_to_numpy(result):
+    """The dict of ``VolumeViterbi.finish`` as a list of per-frame dicts of numpy arrays (the keys without the frame dimension;
+    ``shift`` when joints were pushed): what run_sequence.py --path_info_output writes."""
+    return _per_frame(result, PATH_KEYS + (("shift",) if "shift" in result else ()), "index")
+
+
 # ----------------------------------------------------------------------------------------------
 # skeleton-coupled joints (csrc/skeleton_prior.hip; sceneego_amd/skeleton_prior.py; the reference has only Skeleton._skeleton_resize)
 # ----------------------------------------------------------------------------------------------

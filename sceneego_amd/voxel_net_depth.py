@@ -500,6 +500,24 @@ class VoxelNetwork_depth(nn.Module):
         return VolumeSmoother(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor,
                               max_bytes=max_bytes)
 
+    def volume_path(self, sigma=0.10, radius=None, floor=1e-3, refine=1, max_bytes=None):
+        """A ``sceneego_amd.volume_viterbi.VolumeViterbi`` bound to the module's own ``coord_volumes``, grid and cuboid side: the
+        most probable trajectory of every joint through the volumes of ONE recorded track, the max-product counterpart of
+        ``volume_filter`` / ``volume_smoother`` on the same motion model.  ``v = net.volume_path(); v.push(volumes)`` per batch of
+        consecutive frames runs the forward pass and keeps the back-pointers and, with ``refine`` > 0, a copy of the volumes on the
+        device (4 + 4 bytes per voxel, at most ``max_bytes``; default: half of the free device memory at the first push);
+        ``v.finish()`` walks back from the last frame and returns the path's joints, voxel indices, jumps and segment scores.  Where
+        the smoothed joint between two lobes is a point without probability, the path stays on one lobe; it is all-or-nothing where
+        the marginals hedge.  The parameters are the filter's: a convention, not calibrated.  ``forward()`` itself is unchanged.
+
+        Raises ValueError when ``config.model.volume_softmax`` is false or a parameter is out of range; nothing touches the device
+        before the first ``push``."""
+        if not self.volume_softmax:
+            raise ValueError("volume_path needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        from .volume_viterbi import VolumeViterbi
+        return VolumeViterbi(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor,
+                             refine=refine, max_bytes=max_bytes)
+
     def skeleton_prior(self, bone_lengths, tau=0.03, floor=1e-3):
         """A ``sceneego_amd.skeleton_prior.SkeletonPrior`` bound to the module's own ``coord_volumes``, grid and cuboid side: belief
         propagation over the kinematic tree with a bone-length shell on every edge.  ``s = net.skeleton_prior(lengths);
