@@ -846,6 +846,62 @@ int se_skeleton_couple_f32(const float* prob, const float* coord, const float* t
                            int R, float floor, void* stream);
 long long se_skeleton_couple_scratch_bytes(int frames, int J, int G, int R);
 
+/* Most probable pose: the max-product pass over the kinematic tree that goes with se_skeleton_couple_f32, as se_volume_viterbi_f32
+ * goes with the filter (sceneego_amd/skeleton_pose.py: SkeletonPose; VoxelNetwork_depth.skeleton_pose returns one).  The coupling gives
+ * per joint a marginal and its expectation; this gives the single most probable configuration of all J joints of a frame under the same
+ * model: the same TREE, the same TAPS (block j of the shells is the edge parent[j] -> j, unchanged) and the same floor.
+ * MODEL NOTE: the score of an edge is max((1 - floor) w_j(d), floor / N), within a factor of 2 of the coupling's (1 - floor) w_j + floor /
+ * N, as the Viterbi pass relates to the filter.  No other convention is added.
+ * tests/skeleton_pose_model.py restates the definition in numpy float32 and every output is compared with it BIT FOR BIT: all arithmetic
+ * is float32, one rounding per operation (no fused multiply-add), float32 gradual underflow is part of the definition.
+ *   prob, taps, parent, G, R, floor, frames, J, voxels, flat index n = (i G + j) G + k: as for se_skeleton_couple_f32.  Domain: values
+ *   >= 0 or NaN.   keep = 1.0f - floor,  uniform = floor / (float)voxels   (floor rounded to float32 first)
+ * Joints are taken by depth level, deepest first.  Per joint j:
+ * PRODUCT    A_j = p_j, then times m_c for each child c in ascending order: one rounding per factor, left to right.
+ * ROW MAX    M_j = max A_j taken from 0.0f: a strictly greater value wins, the lowest index wins among equals, a NaN never wins; peak_j
+ *            is the winning index.
+ * RESCALE    e_j = ilogb(M_j),  s_j = ldexpf(A_j, -e_j): exact but for underflow,  best_j = ldexpf(M_j, -e_j) in [1, 2).  Unscaled, a
+ *            leaf-to-root product at 64^3 underflows float32 many times over.
+ * MESSAGE    to the parent, j > 0:  e3_j(x) = max over d with w_j(d) != 0 and x + d inside the grid of s_j(x + d) * w_j(d), from 0.0f,
+ *            cand > best takes it: a value that does not depend on the order of the taps.  Its argument is the LOWEST TAP INDEX among
+ *            the taps that attain it (taps count di, then dj, then dk ascending: the lowest child voxel), -1 when e3_j(x) = 0.
+ *            step = keep * e3_j(x),  jump = uniform * best_j.  Where jump > step: m_j(x) = jump and the predecessor is peak_j, marked
+ *            as a jump; otherwise m_j(x) = step and the predecessor is x + d*.
+ * BACK-WALK  x_0 = peak_0; for j = 1..J-1 ascending x_j is the predecessor of edge j at x_parent(j).
+ * FALLBACK   a frame in which some M_j is not a finite number > 0 is not solved: solved = 0, every joint takes the peak of its own p_j
+ *            by the ROW MAX rule (index -1 where p_j has none), jumped = 0, exponent = 0, best_root = NaN.  Other frames are unaffected.
+ *            A single NaN cell does NOT cause this: it never wins a maximum and is passed over (se_skeleton_couple_f32 differs: there
+ *            a NaN reaches the sums and the frame falls back).
+ *   index      [frames][J] int32: x_j                jumped  [frames][J] int32: 1 where edge j jumped (the root: 0)
+ *   exponent   [frames][J] int32: e_j                best_root [frames] float32: best_0          solved [frames] int32
+ *              log score of the pose = ln best_0 + ln 2 * sum_j e_j, for the caller to sum in float64
+ *   scratch    se_skeleton_pose_scratch_bytes(frames, J, G, R) bytes, 4-byte aligned; 0 for a shape out of range.  About 2 J G^3 floats
+ *              (A / s and m) for each of min(frames, 4) frames: longer calls walk their frames in groups of four.
+ * Per level a product pass with one (max, lowest index) record per chunk, a fold of the records and one max-correlation launch for all
+ * the level's edges and frames (the rescaling is applied as the source planes are staged); the back-walk recomputes the argument of
+ * each edge at the one voxel it is needed at, by the same single multiplications (18 launches and one for the run table with the
+ * reference tree, per group of four frames).  No atomics and no sums: bitwise identical from run to run and independent of how frames
+ * are batched into calls.  Allocates nothing.
+ * SE_ERR_BAD_ARG, with nothing launched: a null pointer, a pointer that is not 4-byte aligned, J outside 1..32, parent[0] != 0 or a
+ * parent[j] outside 0..j-1, G outside 2..128, voxels != G^3, R outside 0..min(24, G - 1), floor outside [0, 1] or NaN, frames < 1,
+ * scratch_bytes below se_skeleton_pose_scratch_bytes(frames, J, G, R).
+ *
+ * se_shell_maxcorr_f32 is the hot path on its own:  out[r](x) = scale_mul * e3(x)  with s = a[r] unscaled and w = taps[tap_row[r]], for
+ * `rows` volumes of G^3 float32; tap_row [rows] int32 on the DEVICE; a tap_row outside 0..tap_rows-1 fills its row with NaN.  scratch:
+ * se_shell_correlate_scratch_bytes(tap_rows, R) bytes, the same run table.  SE_ERR_BAD_ARG as se_shell_correlate_f32.
+ * se_shell_argmax_i32: per row r and queried voxel query[q] (int32 [queries] on the device) out_tap[r][q] = the lowest attaining tap
+ * index of e3 there, or -1, and out_value[r][q] = e3.  A tap_row or a query out of range gives -1 and NaN.  The back-walk uses the
+ * same device function.  SE_ERR_BAD_ARG: a null or misaligned pointer, rows or tap_rows outside 1..65535, queries < 1, G outside
+ * 2..128, R outside 0..min(24, G - 1).                                                                                                */
+int se_shell_maxcorr_f32(const float* a, const float* taps, const int* tap_row, float* out, void* scratch, long long scratch_bytes,
+                         int rows, int tap_rows, int G, int R, float scale_mul, void* stream);
+int se_shell_argmax_i32(const float* a, const float* taps, const int* tap_row, const int* query, int* out_tap, float* out_value,
+                        int rows, int queries, int tap_rows, int G, int R, void* stream);
+int se_skeleton_pose_f32(const float* prob, const float* taps, const int* parent, int* index, int* jumped, int* exponent,
+                         float* best_root, int* solved, void* scratch, long long scratch_bytes, int frames, int J, int voxels, int G,
+                         int R, float floor, void* stream);
+long long se_skeleton_pose_scratch_bytes(int frames, int J, int G, int R);
+
 /* Baseline JPEG encoder (no counterpart in the reference; sceneego_amd/jpeg_encode.py writes the file headers around it).
  *   frames    uint8 [batch][height][width][3] on the device, R, G, B (bgr = 0) or B, G, R (bgr = 1); any height, width in 1..65535
  *   quant_luma, quant_chroma   HOST pointers: unsigned short [64], natural order, every value in 1..255 (baseline tables)

@@ -13,6 +13,7 @@
                             [--filter_radius R] [--filter_floor 1e-3]] [--render_volumes filtered]
                            [--skeleton_output out/skeleton.pkl [--skeleton_info_output out/skeleton_info.pkl] [--bone_lengths FILE.npy]
                             [--bone_frames 64] [--skeleton_tau 0.03] [--skeleton_floor 1e-3]] [--render_volumes coupled]
+                           [--map_output out/map.pkl [--map_info_output out/map_info.pkl] [--map_refine 1]]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -62,6 +63,13 @@ at most ``--bone_frames`` evenly spaced frames (``estimate_bone_lengths``: the p
 ``--skeleton_info_output`` adds the per-frame dicts (joints, evidence, coupled, bone_error, shift, bone_error_before) and
 ``--render_volumes coupled`` draws the coupled beliefs.  With ``--filter_output`` as well the order is couple, then filter (with
 ``--smooth_output``: couple, filter, smooth): the filter runs on the coupled beliefs.  The volume as likelihood, the shell and the floor are a convention, not calibrated.
+``--map_output`` writes a pickle in the format of ``--output`` whose joints are the single most probable pose of every frame under
+the same bone-length model (``VoxelNetwork_depth.skeleton_pose``, ``sceneego_amd/skeleton_pose.py``: the max-product pass over the
+kinematic tree, where ``--skeleton_output`` gives the expectations of the marginals), taken from the raw volumes per batch on the stream
+the batch ran on; each pose voxel is refined to the centroid of its joint's volume over a window of ``--map_refine`` voxels (0..3,
+default 1).  ``--bone_lengths``, ``--bone_frames``, ``--skeleton_tau`` and ``--skeleton_floor`` are used exactly as ``--skeleton_output``
+uses them.  ``--map_info_output`` adds the per-frame dicts (joints, index, coord, jumped, solved, log_score, bone_error, shift,
+bone_error_before).  ``evaluate.py --pred_dir map.pkl [--bones]`` reads the file.  The pose is all-or-nothing where the marginals hedge.
 ``--path_output`` writes a pickle in the format of ``--output`` whose joints lie on the most probable trajectory of every joint through
 the sequence's volumes (``VoxelNetwork_depth.volume_path``, ``sceneego_amd/volume_viterbi.py``: the max-product pass on the filter's
 motion model, ``--filter_sigma``, ``--filter_radius`` and ``--filter_floor``): every batch is pushed on the stream it ran on, the
@@ -250,7 +258,7 @@ class SequenceRunner:
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
             volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False,
-            smooth=None, path=None):
+            smooth=None, path=None, map_pose=None):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -270,16 +278,18 @@ class SequenceRunner:
         per-frame dicts of its ``finish()``, run once behind the last batch, are appended after the skeleton's.  ``path``: a dict of
         ``sigma`` / ``radius`` / ``floor`` / ``refine`` / ``max_bytes`` for ``VoxelNetwork_depth.volume_path``: every batch's volumes
         (with ``skeleton`` the coupled beliefs) are pushed on the stream the batch ran on, and the per-frame dicts of its ``finish()``
-        are appended last."""
+        are appended after those.  ``map_pose``: a dict of ``bone_lengths`` / ``tau`` / ``floor`` / ``refine`` for
+        ``VoxelNetwork_depth.skeleton_pose``: the most probable pose of every frame is taken from the batch's raw volumes on the stream
+        the batch ran on and the per-frame pose dicts are appended last."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
-                                     skeleton_couple_to_numpy, volume_filter_to_numpy, volume_path_to_numpy,
+                                     skeleton_couple_to_numpy, skeleton_pose_to_numpy, volume_filter_to_numpy, volume_path_to_numpy,
                                      volume_smoother_to_numpy)
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         batches = [(images[i:i + batch_size], depths[i:i + batch_size]) for i in range(0, len(images), batch_size)]
         preds, frame_stats, frame_scene, pending = [], [], [], []
-        frame_constraint, frame_scene_constrained, frame_modes, frame_filter, frame_skeleton = [], [], [], [], []
+        frame_constraint, frame_scene_constrained, frame_modes, frame_filter, frame_skeleton, frame_map = [], [], [], [], [], []
         if render_filtered and (filter is None or not render_volumes):
             raise ValueError("render_filtered needs filter and render_volumes")
         if smooth is not None and filter is None:
@@ -290,10 +300,13 @@ class SequenceRunner:
             raise ValueError("render_coupled needs skeleton and render_volumes, and excludes render_filtered")
         sp = self.net.skeleton_prior(**skeleton) if skeleton is not None else None
         vp = self.net.volume_path(**path) if path is not None else None
+        mpose = self.net.skeleton_pose(**map_pose) if map_pose is not None else None
 
         def couple_and_filter(vol, kp, job, stream=None):
-            """The skeleton coupling and the filter of one batch, in that order: (filter dict, skeleton dict, job)."""
+            """The most probable pose (from the raw volumes), the skeleton coupling and the filter of one batch, in that order:
+            (filter dict, skeleton dict, job, pose dict)."""
             fr = sk = None
+            mp = mpose.solve(vol, joints=kp, stream=stream) if mpose is not None else None
             if sp is not None:
                 sk = sp.couple(vol, joints=kp, return_beliefs=vf is not None or vp is not None or (render_coupled and job is not None),
                                stream=stream)
@@ -311,7 +324,7 @@ class SequenceRunner:
                     job = job[:-1] + (fr["beliefs"],)
             if vp is not None:             # on the raw volumes, or the coupled beliefs: never on the filter's
                 vp.push(vol, joints=kp, stream=stream)
-            return fr, sk, job
+            return fr, sk, job, mp
 
         rendering = render_dir is not None or render_video is not None
         if rendering:
@@ -327,7 +340,7 @@ class SequenceRunner:
 
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done, job, sc, con, md, fr, sk = pending.pop(0)
+                kp, st, done, job, sc, con, md, fr, sk, mp = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 kp_host = kp.cpu().numpy()
@@ -346,6 +359,8 @@ class SequenceRunner:
                     frame_filter.extend(volume_filter_to_numpy(fr))
                 if sk is not None:
                     frame_skeleton.extend(skeleton_couple_to_numpy(sk))
+                if mp is not None:
+                    frame_map.extend(skeleton_pose_to_numpy(mp))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -370,16 +385,16 @@ class SequenceRunner:
                     if constrain:
                         c = self.net.constrain_to_scene(vol, kp, depth)
                         con = (c, self._scene().check(depth, c["joints"]) if scene else None)
-                    fr, sk, job = couple_and_filter(vol, kp, job)         # before the next forward overwrites the volumes
+                    fr, sk, job, mp = couple_and_filter(vol, kp, job)     # before the next forward overwrites the volumes
                     pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
                                     self._scene().check(depth, kp) if scene else None, con,
-                                    self.net.joint_modes(vol, k=modes) if modes else None, fr, sk))
+                                    self.net.joint_modes(vol, k=modes) if modes else None, fr, sk, mp))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
-                    st = sc = con = md = fr = sk = None
-                    if stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None:
+                    st = sc = con = md = fr = sk = mp = None
+                    if stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
@@ -394,10 +409,10 @@ class SequenceRunner:
                                 md = net.joint_modes(vol, k=modes)
                             # one filter for all slots: its own event chain makes this stream wait for the step of the batch before;
                             # one skeleton prior too: it carries no state and keeps one workspace per stream
-                            fr, sk, job = couple_and_filter(vol, kp, job, stream)
+                            fr, sk, job, mp = couple_and_filter(vol, kp, job, stream)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done, job, sc, con, md, fr, sk))
+                    pending.append((kp, st, done, job, sc, con, md, fr, sk, mp))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             try:
                 drain(0)
@@ -407,13 +422,13 @@ class SequenceRunner:
                     self.video = None
         frame_smooth = volume_smoother_to_numpy(vs.finish()) if vs is not None else None
         frame_path = volume_path_to_numpy(vp.finish()) if vp is not None else None
-        if not (stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None):
+        if not (stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
             + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
             + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ()) \
             + ((frame_skeleton,) if sp is not None else ()) + ((frame_smooth,) if vs is not None else ()) \
-            + ((frame_path,) if vp is not None else ())
+            + ((frame_path,) if vp is not None else ()) + ((frame_map,) if mpose is not None else ())
 
 
 def _size(text):
@@ -496,6 +511,14 @@ def build_parser():
                     "kinematic tree inside every frame (sceneego_amd/skeleton_prior.py: a convention, not calibrated)")
     ap.add_argument("--skeleton_info_output", default=None, help="pickle of the per-frame skeleton dicts (list of dicts of numpy arrays: "
                     "joints, evidence, coupled, bone_error, shift, bone_error_before)")
+    ap.add_argument("--map_output", default=None, help="pickle in the format of --output holding the most probable pose of every frame "
+                    "under the bone-length model of --skeleton_output (sceneego_amd/skeleton_pose.py: max-product over the kinematic "
+                    "tree on the raw volumes; --bone_lengths, --bone_frames, --skeleton_tau, --skeleton_floor as there; a convention, not "
+                    "calibrated)")
+    ap.add_argument("--map_info_output", default=None, help="pickle of the per-frame pose dicts (list of dicts of numpy arrays: joints, "
+                    "index, coord, jumped, solved, log_score, bone_error, shift, bone_error_before)")
+    ap.add_argument("--map_refine", type=int, default=None, help="with --map_output: each pose voxel is refined to the centroid of its "
+                    "joint's volume over a window of this many voxels around it (0..3, default 1; 0: the voxel centre)")
     ap.add_argument("--bone_lengths", default=None, help="a .npy of 14 bone lengths in metres (edges 1..14 of the kinematic tree) or 15 "
                     "(entry 0 ignored); default: estimated from a first pass over --bone_frames frames")
     ap.add_argument("--bone_frames", type=int, default=64, help="without --bone_lengths: at most this many evenly spaced frames feed "
@@ -566,6 +589,11 @@ def parse_args(argv=None):
     if args.bone_frames < 1:
         raise SystemExit("--bone_frames must be >= 1")
     args.skeleton = args.skeleton_output is not None or args.skeleton_info_output is not None or args.render_coupled
+    args.map = args.map_output is not None or args.map_info_output is not None
+    if args.map_refine is not None and not args.map:
+        raise SystemExit("--map_refine needs --map_output")
+    if args.map_refine is not None and not 0 <= args.map_refine <= 3:
+        raise SystemExit("--map_refine must be in 0..3")
     if args.track_output is not None and args.modes_output is None:
         raise SystemExit("--track_output needs --modes_output")
     if not 1 <= args.modes_k <= 16:
@@ -591,8 +619,8 @@ def main(argv=None):
     print(f"dataset length: {len(images)}")
     runner = SequenceRunner(config, weights=args.weights, streams=args.streams, depth_decode=args.depth_decode,
                             workers=args.workers, image_decode=args.image_decode)
-    skeleton = None
-    if args.skeleton:
+    skeleton = map_pose = None
+    if args.skeleton or args.map:
         from sceneego_amd.skeleton_prior import estimate_bone_lengths
         if args.bone_lengths is not None:
             lengths = np.load(args.bone_lengths)
@@ -602,7 +630,11 @@ def main(argv=None):
             raw = runner.run([images[k] for k in pick], [depths[k] for k in pick], config.test.batch_size)
             lengths = estimate_bone_lengths(np.stack(raw))
             print(f"bone lengths estimated from {len(pick)} frames: " + " ".join(f"{v:.4f}" for v in lengths[1:]))
-        skeleton = {"bone_lengths": lengths, "tau": args.skeleton_tau, "floor": args.skeleton_floor}
+        if args.skeleton:
+            skeleton = {"bone_lengths": lengths, "tau": args.skeleton_tau, "floor": args.skeleton_floor}
+        if args.map:
+            map_pose = {"bone_lengths": lengths, "tau": args.skeleton_tau, "floor": args.skeleton_floor,
+                        "refine": 1 if args.map_refine is None else args.map_refine}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     want_stats = args.stats_output is not None
@@ -616,8 +648,9 @@ def main(argv=None):
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
                        volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
                        filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled,
-                       smooth=args.smooth, path=args.path)
-    if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None or args.path is not None:
+                       smooth=args.smooth, path=args.path, map_pose=map_pose)
+    if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None or args.path is not None \
+            or map_pose is not None:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
         frame_scene = extra.pop(0) if want_scene else None
@@ -628,6 +661,7 @@ def main(argv=None):
         frame_skeleton = extra.pop(0) if skeleton is not None else None
         frame_smooth = extra.pop(0) if args.smooth is not None else None
         frame_path = extra.pop(0) if args.path is not None else None
+        frame_map = extra.pop(0) if map_pose is not None else None
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -733,6 +767,23 @@ def main(argv=None):
                   result["path_mpjpe"], mpjpe, others, float(np.nanmean([fr["shift"] for fr in frame_path])),
                   int(sum(fr["jumped"].sum() for fr in frame_path)), int(sum(fr["segment_start"].sum() for fr in frame_path[1:])),
                   int(sum(fr["index"].size for fr in frame_path))))
+    if map_pose is not None:
+        posed = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_map]
+        for path, obj in ((args.map_output, posed), (args.map_info_output, frame_map)):
+            if path is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "wb") as f:
+                    pickle.dump(obj, f)
+        result["map"], result["map_info"], result["bone_lengths"] = posed, frame_map, np.asarray(lengths, dtype=np.float64)
+        result["map_mpjpe"] = M.mpjpe(np.stack(posed).astype(np.float64), gt)
+        others = "".join(f", {name} {result[key]}" for name, key in (("coupled", "coupled_mpjpe"), ("path", "path_mpjpe")) if key in result)
+        bones = ", coupled {:.4f} m".format(float(np.mean([fr["bone_error"] for fr in frame_skeleton]))) if skeleton is not None else ""
+        print("most probable pose (a convention, not calibrated): mpjpe: {} (soft-argmax {}{}), mean shift {:.4f} m, mean bone error "
+              "{:.4f} -> {:.4f} m{}, {} jumps in {} joint-frames, {} frames not solved".format(
+                  result["map_mpjpe"], mpjpe, others, float(np.nanmean([fr["shift"] for fr in frame_map])),
+                  float(np.mean([fr["bone_error_before"] for fr in frame_map])), float(np.nanmean([fr["bone_error"] for fr in frame_map])),
+                  bones, int(sum(fr["jumped"].sum() for fr in frame_map)), int(sum(fr["index"].size for fr in frame_map)),
+                  int(sum(not fr["solved"] for fr in frame_map))))
     return result
 
 

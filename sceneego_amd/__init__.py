@@ -11,11 +11,14 @@ The compute kernels are in sceneego_amd/csrc (HIP, gfx950) behind the C ABI of i
 """
 from .config import EasyDict, load_config  # noqa: F401
 
-__all__ = ["EasyDict", "load_config", "VoxelNetwork_depth", "VoxelNetDepth"]
+__all__ = ["EasyDict", "load_config", "VoxelNetwork_depth", "VoxelNetDepth", "SkeletonPose"]
 
 
 def __getattr__(name):
     if name in ("VoxelNetwork_depth", "VoxelNetDepth"):
         from .voxel_net_depth import VoxelNetwork_depth
         return VoxelNetwork_depth
+    if name == "SkeletonPose":
+        from .skeleton_pose import SkeletonPose
+        return SkeletonPose
     raise AttributeError(name)

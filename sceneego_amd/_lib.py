@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -123,6 +123,10 @@ SIGNATURES = {
     "se_shell_correlate_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _f, _vp]),
     "se_skeleton_couple_scratch_bytes": (_ll, [_i, _i, _i, _i]),
     "se_skeleton_couple_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
+    "se_shell_maxcorr_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _vp]),
+    "se_shell_argmax_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "se_skeleton_pose_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_skeleton_pose_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -1430,6 +1434,96 @@ def skeleton_couple(prob, coord, taps, parents, beliefs, joints, evidence, coupl
                                          _ptr(joints), _ptr(evidence), _ptr(coupled), _ptr(scratch), scratch.numel(), frames, J,
                                          voxels, grid, radius, floor, _stream()), "se_skeleton_couple_f32")
     return joints, evidence, coupled
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Most probable pose (csrc/skeleton_pose.hip; sceneego_amd/skeleton_pose.py drives it)
+def _shell_rows(what, rows, grid, radius, taps):
+    if not 1 <= rows <= 65535:
+        raise HipExtensionError(f"{what}: rows = {rows} (1..65535) expected")
+    _skeleton_shape(what, grid, radius)
+    tap_rows = int(taps.shape[0]) if isinstance(taps, torch.Tensor) and taps.dim() == 2 else 0
+    if not 1 <= tap_rows <= 65535:
+        raise HipExtensionError(f"{what}: taps must be a [1..65535, {(2 * radius + 1) ** 3}] tensor")
+    return tap_rows
+
+
+def shell_maxcorr(a, taps, tap_row, out, rows, grid, radius, scale_mul=1.0, scratch=None):
+    """se_shell_maxcorr_f32: ``out[r](x) = scale_mul * max over the non-zero taps d of a[r](x + d) taps[tap_row[r]](d)`` for the ``rows``
+    volumes ``a`` [rows, grid^3] (the header states it); ``taps`` [tap_rows, (2 radius + 1)^3] float32 and ``tap_row`` [rows] int32 on
+    the device.  ``scratch``: an optional uint8 workspace of at least ``shell_correlate_scratch_bytes(tap_rows, radius)`` bytes.  Every
+    argument is checked here and a bad one raises HipExtensionError before anything is launched."""
+    what = "shell_maxcorr"
+    rows, grid, radius, scale_mul = int(rows), int(grid), int(radius), float(scale_mul)
+    tap_rows = _shell_rows(what, rows, grid, radius, taps)
+    voxels, block = grid ** 3, (2 * radius + 1) ** 3
+    dev = _check_args(what, (("a", a, torch.float32, rows * voxels), ("taps", taps, torch.float32, (None, block)),
+                             ("tap_row", tap_row, torch.int32, rows), ("out", out, torch.float32, rows * voxels)),
+                      (("scratch", scratch, torch.uint8, None),))
+    if out.data_ptr() == a.data_ptr():
+        raise HipExtensionError(f"{what}: out must not alias a")
+    scratch = _scratch(what, scratch, shell_correlate_scratch_bytes(tap_rows, radius), torch.uint8, dev)
+    _check(load().se_shell_maxcorr_f32(_ptr(a), _ptr(taps), _ptr(tap_row), _ptr(out), _ptr(scratch), scratch.numel(), rows, tap_rows,
+                                       grid, radius, scale_mul, _stream()), "se_shell_maxcorr_f32")
+    return out
+
+
+def shell_argmax(a, taps, tap_row, query, out_tap, out_value, rows, grid, radius):
+    """se_shell_argmax_i32: per row of ``a`` [rows, grid^3] and per voxel of ``query`` [queries] int32 the lowest tap index that attains
+    the maximum ``shell_maxcorr`` takes there (-1: none) into ``out_tap`` [rows, queries] int32 and that maximum into ``out_value``
+    [rows, queries] float32.  Every argument is checked here and a bad one raises HipExtensionError before anything is launched."""
+    what = "shell_argmax"
+    rows, grid, radius = int(rows), int(grid), int(radius)
+    tap_rows = _shell_rows(what, rows, grid, radius, taps)
+    queries = int(query.numel()) if isinstance(query, torch.Tensor) else 0
+    if queries < 1:
+        raise HipExtensionError(f"{what}: query must hold at least one voxel")
+    voxels, block = grid ** 3, (2 * radius + 1) ** 3
+    _check_args(what, (("a", a, torch.float32, rows * voxels), ("taps", taps, torch.float32, (None, block)),
+                       ("tap_row", tap_row, torch.int32, rows), ("query", query, torch.int32, queries),
+                       ("out_tap", out_tap, torch.int32, rows * queries), ("out_value", out_value, torch.float32, rows * queries)))
+    _check(load().se_shell_argmax_i32(_ptr(a), _ptr(taps), _ptr(tap_row), _ptr(query), _ptr(out_tap), _ptr(out_value), rows, queries,
+                                      tap_rows, grid, radius, _stream()), "se_shell_argmax_i32")
+    return out_tap, out_value
+
+
+def skeleton_pose_scratch_bytes(frames, joints, grid, radius) -> int:
+    return int(load().se_skeleton_pose_scratch_bytes(int(frames), int(joints), int(grid), int(radius)))
+
+
+def skeleton_pose(prob, taps, parents, index, jumped, exponent, best_root, solved, frames, voxels, grid, radius, floor, scratch=None):
+    """se_skeleton_pose_f32: the max-product pass over the tree ``parents`` (as for ``skeleton_couple``) on ``prob`` [frames, J, voxels]
+    with the shell taps ``taps`` [J, (2 radius + 1)^3] on the device (the header states the definition).  ``index``, ``jumped`` and
+    ``exponent`` [frames, J] int32, ``best_root`` [frames] float32 and ``solved`` [frames] int32 are written.  ``scratch``: an optional
+    uint8 workspace of at least ``skeleton_pose_scratch_bytes(frames, J, grid, radius)`` bytes.  Every argument is checked here and a
+    bad one raises HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
+    what = "skeleton_pose"
+    try:
+        parents = [int(v) for v in parents]
+    except (TypeError, ValueError):
+        raise HipExtensionError(f"{what}: parents must be a sequence of integers") from None
+    J = len(parents)
+    frames, voxels, grid, radius, floor = int(frames), int(voxels), int(grid), int(radius), float(floor)
+    if not 1 <= J <= SKELETON_MAX_JOINTS or parents[0] != 0 or any(not 0 <= parents[j] < j for j in range(1, J)):
+        raise HipExtensionError(f"{what}: parents = {parents}: 1..{SKELETON_MAX_JOINTS} joints with parents[0] = 0 and "
+                                "0 <= parents[j] < j expected")
+    if frames < 1:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1) expected")
+    _skeleton_shape(what, grid, radius)
+    if voxels != grid ** 3:
+        raise HipExtensionError(f"{what}: voxels = {voxels} is not grid^3 = {grid ** 3}")
+    if not 0.0 <= floor <= 1.0:
+        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    dev = _check_args(what, (("prob", prob, torch.float32, frames * J * voxels), ("taps", taps, torch.float32, J * (2 * radius + 1) ** 3),
+                             ("index", index, torch.int32, frames * J), ("jumped", jumped, torch.int32, frames * J),
+                             ("exponent", exponent, torch.int32, frames * J), ("best_root", best_root, torch.float32, frames),
+                             ("solved", solved, torch.int32, frames)), (("scratch", scratch, torch.uint8, None),))
+    scratch = _scratch(what, scratch, skeleton_pose_scratch_bytes(frames, J, grid, radius), torch.uint8, dev)
+    par = (ctypes.c_int * J)(*parents)
+    _check(load().se_skeleton_pose_f32(_ptr(prob), _ptr(taps), ctypes.cast(par, ctypes.c_void_p), _ptr(index), _ptr(jumped),
+                                       _ptr(exponent), _ptr(best_root), _ptr(solved), _ptr(scratch), scratch.numel(), frames, J, voxels,
+                                       grid, radius, floor, _stream()), "se_skeleton_pose_f32")
+    return index, jumped, exponent, best_root, solved
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@
 // THE CORRELATION (se_shell_correlate_f32; 2 (J - 1) of them per frame inside se_skeleton_couple_f32)
 //     out(x) = scale_mul * (sum over d with w(d) != 0 and x + d inside the grid of w(d) a(x + d)) / s + add
 // with w a dense (2R+1)^3 block that is mostly zero: a shell.
-//   sk_runs_kernel      grid (2R+1, tap rows), block 64: for one di-plane of one block, lane dk finds in the column w(di, ., dk) the first
+//   sk_runs_kernel      (skeleton_shell.h) grid (2R+1, tap rows), block 64: for one di-plane of one block, lane dk finds in the column w(di, ., dk) the first
 //                       and the last maximal run of non-zero taps along dj and whether anything non-zero lies between them (for a
 //                       shell: two runs, or one, and nothing between); entry 2R+1 of the plane says whether the plane has a tap at all.
 //                       (2R+1) x (2R+2) records of 4 ints per block, built once per call.
@@ -46,28 +46,14 @@
 // frame's results are bitwise identical from run to run and do not depend on how frames are batched into calls or groups.
 #include <float.h>
 
-#include <initializer_list>
-
 #include "row_reduce.h"
+#include "skeleton_shell.h"      // the limits, SkTree / SkRows, the chunk rule, sk_runs_kernel and the launch geometry: shared with skeleton_pose.hip
 
-#define SK_THREADS 256
-#define SK_MAX_J 32
-#define SK_MAX_G 128
-#define SK_MAX_R 24
-#define SK_TJ 16                 // output rows j per workgroup
-#define SK_JR 4                  // ... per wave
-#define SK_KC 64                 // output columns k per workgroup: one per lane
 #define SK_PART 8                // one chunk record: sum, sum v c (x y z), sum p c (x y z), pad
-#define SK_MAX_CH 64
-#define SK_GROUP 4               // frames in flight inside se_skeleton_couple_f32
 #define SK_MAX_ITEMS (2 * SK_MAX_J)
 
 namespace {
 
-struct SkTree {
-    int J;
-    signed char parent[SK_MAX_J];
-};
 // one product of sk_product_kernel: kind 0 = A_j (into A[j]; sum s_j), 1 = T_j (into U[j]; Z_j and the joint sums), 2 = E_c for child
 // c = excl of j (into A[c]; sum t_c)
 struct SkItems {
@@ -76,43 +62,6 @@ struct SkItems {
     signed char excl[SK_MAX_ITEMS];
     unsigned char kind[SK_MAX_ITEMS];
 };
-// rows of a correlation launch inside the tree: row r = (frame r / n, joint slot[r % n])
-struct SkRows {
-    int n;
-    unsigned char slot[SK_MAX_J];
-};
-
-__host__ __device__ inline int sk_chunks(int voxels) { return min(SK_MAX_CH, (voxels + 255) / 256); }
-__host__ __device__ inline int sk_chunk(int voxels) { const int ch = sk_chunks(voxels); return (voxels + ch - 1) / ch; }
-inline long long sk_runs_ints(int tap_rows, int R) { return (long long)tap_rows * (2 * R + 1) * (2 * R + 2) * 4; }
-
-// grid (2R+1, tap_rows), block 64
-__global__ __launch_bounds__(64) void sk_runs_kernel(const float* __restrict__ taps, int* __restrict__ runs, int R) {
-    const int W = 2 * R + 1, t = threadIdx.x, dI = blockIdx.x, row = blockIdx.y;
-    const float* w = taps + (size_t)row * W * W * W + (size_t)dI * W * W;
-    int lo1 = 1, hi1 = 0, lo2 = 1, hi2 = 0, mid = 0;                     // dj + R; lo > hi: empty
-    if (t < W) {
-        int a = 0;
-        while (a < W && w[a * W + t] == 0.f) ++a;
-        if (a < W) {
-            int b = a;
-            while (b + 1 < W && w[(b + 1) * W + t] != 0.f) ++b;
-            lo1 = a; hi1 = b;
-            int d = W - 1;
-            while (w[d * W + t] == 0.f) --d;                             // stops at b at the latest
-            if (d > b) {
-                int c = d;
-                while (w[(c - 1) * W + t] != 0.f) --c;                   // stops above b: w[b + 1] is zero
-                lo2 = c; hi2 = d;
-                for (int e = b + 1; e < c; ++e) mid |= w[e * W + t] != 0.f;
-            }
-        }
-    }
-    const int any = __syncthreads_or(lo1 <= hi1);
-    int* o = runs + (((size_t)row * W + dI) * (W + 1)) * 4;
-    if (t < W) { o[t * 4 + 0] = lo1; o[t * 4 + 1] = hi1; o[t * 4 + 2] = lo2; o[t * 4 + 3] = hi2 | (mid << 8); }
-    if (t == 0) { o[W * 4 + 0] = any; o[W * 4 + 1] = 0; o[W * 4 + 2] = 0; o[W * 4 + 3] = 0; }
-}
 
 // the taps lo..hi (dj + R) of one column, all non-zero: four at a time, then one at a time.  wp: the column's taps at dj + R = 0, stride W;
 // lp: the lane's LDS value under output row 0 and dj + R = 0, stride LW.
@@ -309,16 +258,6 @@ __global__ __launch_bounds__(SK_THREADS) void sk_finish_kernel(const float* __re
     }
 }
 
-inline bool sk_shape_ok(int G, int R) { return G >= 2 && G <= SK_MAX_G && R >= 0 && R <= SK_MAX_R && R <= G - 1; }
-inline int sk_lds_bytes(int R) { return (SK_TJ + 2 * R) * (SK_KC + 2 * R) * 4; }
-inline dim3 sk_corr_grid(int G, int rows) {
-    return dim3(G * ((G + SK_TJ - 1) / SK_TJ) * ((G + SK_KC - 1) / SK_KC), rows);
-}
-inline bool sk_aligned4(std::initializer_list<const void*> ps) {
-    uintptr_t all = 0;
-    for (const void* p : ps) all |= reinterpret_cast<uintptr_t>(p);
-    return (all & 3) == 0;
-}
 inline long long sk_frame_floats(int J, int G) {
     const long long N = (long long)G * G * G;
     return 3 * J * N + (long long)SK_MAX_ITEMS * sk_chunks((int)N) * SK_PART + 3LL * J * SK_PART;

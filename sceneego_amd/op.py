@@ -448,3 +448,13 @@ def skeleton_couple_to_numpy(result):
     --skeleton_info_output writes."""
     extra = tuple(k for k in ("shift", "bone_error_before") if k in result)
     return _per_frame(result, SKELETON_KEYS + extra, "evidence")
+
+
+POSE_KEYS = ("joints", "index", "coord", "jumped", "solved", "log_score", "bone_error")
+
+
+def skeleton_pose_to_numpy(result):
+    """The dict of ``SkeletonPose.solve`` as a list of per-frame dicts of numpy arrays (the keys without the batch dimension; ``shift``
+    and ``bone_error_before`` when the call was given joints): what run_sequence.py --map_info_output writes."""
+    extra = tuple(k for k in ("shift", "bone_error_before") if k in result)
+    return _per_frame(result, POSE_KEYS + extra, "solved")

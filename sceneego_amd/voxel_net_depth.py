@@ -538,6 +538,23 @@ class VoxelNetwork_depth(nn.Module):
         from .skeleton_prior import SkeletonPrior
         return SkeletonPrior(self.coord_volumes[0], self.volume_size, self.cuboid_side, bone_lengths, tau=tau, floor=floor)
 
+    def skeleton_pose(self, bone_lengths, tau=0.03, floor=1e-3, refine=1):
+        """A ``sceneego_amd.skeleton_pose.SkeletonPose`` bound to the module's own ``coord_volumes``, grid and cuboid side: the
+        max-product pass over the kinematic tree that goes with ``skeleton_prior``.  ``s = net.skeleton_pose(lengths);
+        s.solve(volumes)`` with the volumes ``forward()`` returned gives the single most probable pose of every frame under the shells,
+        the floor and the tree of ``skeleton_prior`` - one voxel per joint, refined to the centroid of the joint's volume over a window
+        of ``refine`` voxels (0..3) - where ``couple`` gives fifteen expectations of fifteen marginals.  ``bone_lengths``, ``tau`` and
+        ``floor`` as for ``skeleton_prior``: a convention, not calibrated.  ``forward()`` itself is unchanged.
+
+        Under ``enable_graphs(True)`` the volumes are the graph's STATIC buffer: call ``solve`` before the next ``forward()``.
+
+        Raises ValueError when ``config.model.volume_softmax`` is false or a parameter is out of range; nothing touches the device
+        before the first ``solve``."""
+        if not self.volume_softmax:
+            raise ValueError("skeleton_pose needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        from .skeleton_pose import SkeletonPose
+        return SkeletonPose(self.coord_volumes[0], self.volume_size, self.cuboid_side, bone_lengths, tau=tau, floor=floor, refine=refine)
+
     def _voxelise(self, x, planar3, fast_occ, prog, scene_volumes, depth_map_batch, B, G, N, C, dev, planar1=False):
         """Occupancy into the V2V input buffer ``x`` (reference ``:246-262``)."""
         if planar1 and self.with_scene is not True:
