@@ -252,6 +252,12 @@ def _scratch(what, scratch, need, dtype, device):
     return scratch
 
 
+def _overlap(a, b) -> bool:
+    """The storage of two contiguous tensors overlaps."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
 def voxelize(depth, ray_tab, occ, batch, depth_h, depth_w, up, pad_x, volume_size, cuboid_side):
     require_hip(depth, ray_tab, occ)
     _chk_f32(depth, occ)
@@ -1159,6 +1165,31 @@ FILTER_MAX_GRID, FILTER_MAX_RADIUS = 128, 16
 FILTER_CHAIN = 80          # sequential float32 additions on the longest path of Z and of the joint sums (csrc/volume_filter.hip: L)
 
 
+def _grid_args(what, frames, rows, voxels, grid, radius=None, floor=None):
+    """The arguments every operator over [frames, rows, grid^3] volumes takes, as ints and a float, range-checked against the one set
+    of limits of csrc/volume_grid.h.  ``radius`` None: the operator has neither taps nor a floor (both come back as None)."""
+    frames, rows, voxels, grid = int(frames), int(rows), int(voxels), int(grid)
+    if radius is not None:
+        radius, floor = int(radius), float(floor)
+    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
+                                f"voxels = {voxels} (grid^3) expected")
+    if radius is None:
+        return frames, rows, voxels, grid, None, None
+    if not 0 <= radius <= min(FILTER_MAX_RADIUS, grid - 1):
+        raise HipExtensionError(f"{what}: radius = {radius} (0..{min(FILTER_MAX_RADIUS, grid - 1)}) expected")
+    if not 0.0 <= floor <= 1.0:
+        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    return frames, rows, voxels, grid, radius, floor
+
+
+def _grid_scratch(what, scratch, need, rows, grid, radius, dev):
+    """The workspace of a grid-sequence call: ``need`` is what the library asks for, 0 when it does not take the shape."""
+    if need <= 0:
+        raise HipExtensionError(f"{what}: rows = {rows}, grid = {grid}, radius = {radius} is not supported")
+    return _scratch(what, scratch, need, torch.uint8, dev)
+
+
 def volume_filter_scratch_bytes(rows, grid, radius) -> int:
     return int(load().se_volume_filter_scratch_bytes(int(rows), int(grid), int(radius)))
 
@@ -1172,26 +1203,16 @@ def volume_filter(prob, coord, taps, state, belief_out, joints, evidence, restar
     ``scratch``: an optional uint8 workspace of at least ``volume_filter_scratch_bytes(rows, grid, radius)`` bytes.  Every argument
     is checked here and a bad one raises HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
     what = "volume_filter"
-    frames, rows, voxels, grid, radius, floor = int(frames), int(rows), int(voxels), int(grid), int(radius), float(floor)
-    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
-        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
-                                f"voxels = {voxels} (grid^3) expected")
-    if not 0 <= radius <= min(FILTER_MAX_RADIUS, grid - 1):
-        raise HipExtensionError(f"{what}: radius = {radius} (0..{min(FILTER_MAX_RADIUS, grid - 1)}) expected")
-    if not 0.0 <= floor <= 1.0:
-        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    frames, rows, voxels, grid, radius, floor = _grid_args(what, frames, rows, voxels, grid, radius, floor)
     dev = _check_args(what, (("prob", prob, torch.float32, frames * rows * voxels), ("coord", coord, torch.float32, voxels * 3),
                              ("taps", taps, torch.float32, 2 * radius + 1), ("state", state, torch.float32, rows * voxels),
                              ("joints", joints, torch.float32, frames * rows * 3), ("evidence", evidence, torch.float32, frames * rows),
                              ("restarted", restarted, torch.int32, frames * rows)),
                       (("belief_out", belief_out, torch.float32, frames * rows * voxels), ("have_prior", have_prior, torch.int32, rows),
                        ("scratch", scratch, torch.uint8, None)))
-    if belief_out is not None and belief_out.data_ptr() in (prob.data_ptr(), state.data_ptr()):
+    if belief_out is not None and (_overlap(belief_out, prob) or _overlap(belief_out, state)):
         raise HipExtensionError(f"{what}: belief_out must not alias prob or state")
-    need = volume_filter_scratch_bytes(rows, grid, radius)
-    if need <= 0:
-        raise HipExtensionError(f"{what}: rows = {rows}, grid = {grid}, radius = {radius} is not supported")
-    scratch = _scratch(what, scratch, need, torch.uint8, dev)
+    scratch = _grid_scratch(what, scratch, volume_filter_scratch_bytes(rows, grid, radius), rows, grid, radius, dev)
     _check(load().se_volume_filter_f32(_ptr(prob), _ptr(coord), _ptr(taps), _ptr(state), _ptr(belief_out), _ptr(joints),
                                        _ptr(evidence), _ptr(restarted), _ptr(scratch), scratch.numel(), frames, rows, voxels, grid,
                                        radius, floor, _ptr(have_prior), _stream()), "se_volume_filter_f32")
@@ -1206,12 +1227,6 @@ def volume_smooth_scratch_bytes(rows, grid, radius) -> int:
     return int(load().se_volume_smooth_scratch_bytes(int(rows), int(grid), int(radius)))
 
 
-def _overlap(a, b) -> bool:
-    """The storage of two contiguous tensors overlaps."""
-    a0, b0 = a.data_ptr(), b.data_ptr()
-    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
-
-
 def volume_smooth(prob, belief, restarted, coord, taps, state, smoothed_out, joints, agreement, smoothed, frames, rows, voxels, grid,
                   radius, floor, have_link=None, scratch=None):
     """se_volume_smooth_f32: the backward pass over ``frames`` consecutive frames, last to first, on the volumes ``prob`` and the
@@ -1223,14 +1238,7 @@ def volume_smooth(prob, belief, restarted, coord, taps, state, smoothed_out, joi
     uint8 workspace of at least ``volume_smooth_scratch_bytes(rows, grid, radius)`` bytes.  Every argument is checked here and a bad
     one raises HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
     what = "volume_smooth"
-    frames, rows, voxels, grid, radius, floor = int(frames), int(rows), int(voxels), int(grid), int(radius), float(floor)
-    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
-        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
-                                f"voxels = {voxels} (grid^3) expected")
-    if not 0 <= radius <= min(FILTER_MAX_RADIUS, grid - 1):
-        raise HipExtensionError(f"{what}: radius = {radius} (0..{min(FILTER_MAX_RADIUS, grid - 1)}) expected")
-    if not 0.0 <= floor <= 1.0:
-        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    frames, rows, voxels, grid, radius, floor = _grid_args(what, frames, rows, voxels, grid, radius, floor)
     total = frames * rows * voxels
     dev = _check_args(what, (("prob", prob, torch.float32, total), ("belief", belief, torch.float32, total),
                              ("restarted", restarted, torch.int32, frames * rows), ("coord", coord, torch.float32, voxels * 3),
@@ -1246,10 +1254,7 @@ def volume_smooth(prob, belief, restarted, coord, taps, state, smoothed_out, joi
             raise HipExtensionError(f"{what}: smoothed_out must be belief itself (in place) or disjoint from it")
         if _overlap(smoothed_out, prob) or _overlap(smoothed_out, state):
             raise HipExtensionError(f"{what}: smoothed_out must not alias prob or state")
-    need = volume_smooth_scratch_bytes(rows, grid, radius)
-    if need <= 0:
-        raise HipExtensionError(f"{what}: rows = {rows}, grid = {grid}, radius = {radius} is not supported")
-    scratch = _scratch(what, scratch, need, torch.uint8, dev)
+    scratch = _grid_scratch(what, scratch, volume_smooth_scratch_bytes(rows, grid, radius), rows, grid, radius, dev)
     _check(load().se_volume_smooth_f32(_ptr(prob), _ptr(belief), _ptr(restarted), _ptr(coord), _ptr(taps), _ptr(state),
                                        _ptr(smoothed_out), _ptr(joints), _ptr(agreement), _ptr(smoothed), _ptr(scratch),
                                        scratch.numel(), frames, rows, voxels, grid, radius, floor, _ptr(have_link), _stream()),
@@ -1276,14 +1281,7 @@ def volume_viterbi(prob, taps, state, peak_state, best_state, back_out, peak, be
     least ``volume_viterbi_scratch_bytes(rows, grid, radius)`` bytes.  Every argument is checked here and a bad one raises
     HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
     what = "volume_viterbi"
-    frames, rows, voxels, grid, radius, floor = int(frames), int(rows), int(voxels), int(grid), int(radius), float(floor)
-    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
-        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
-                                f"voxels = {voxels} (grid^3) expected")
-    if not 0 <= radius <= min(FILTER_MAX_RADIUS, grid - 1):
-        raise HipExtensionError(f"{what}: radius = {radius} (0..{min(FILTER_MAX_RADIUS, grid - 1)}) expected")
-    if not 0.0 <= floor <= 1.0:
-        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    frames, rows, voxels, grid, radius, floor = _grid_args(what, frames, rows, voxels, grid, radius, floor)
     total = frames * rows * voxels
     dev = _check_args(what, (("prob", prob, torch.float32, total), ("taps", taps, torch.float32, 2 * radius + 1),
                              ("state", state, torch.float32, rows * voxels), ("peak_state", peak_state, torch.int32, rows),
@@ -1293,10 +1291,7 @@ def volume_viterbi(prob, taps, state, peak_state, best_state, back_out, peak, be
                       (("have_prior", have_prior, torch.int32, rows), ("scratch", scratch, torch.uint8, None)))
     if _overlap(state, prob) or _overlap(back_out, prob) or _overlap(back_out, state):
         raise HipExtensionError(f"{what}: prob, state and back_out must not alias one another")
-    need = volume_viterbi_scratch_bytes(rows, grid, radius)
-    if need <= 0:
-        raise HipExtensionError(f"{what}: rows = {rows}, grid = {grid}, radius = {radius} is not supported")
-    scratch = _scratch(what, scratch, need, torch.uint8, dev)
+    scratch = _grid_scratch(what, scratch, volume_viterbi_scratch_bytes(rows, grid, radius), rows, grid, radius, dev)
     _check(load().se_volume_viterbi_f32(_ptr(prob), _ptr(taps), _ptr(state), _ptr(peak_state), _ptr(best_state), _ptr(back_out),
                                         _ptr(peak), _ptr(best), _ptr(exponent), _ptr(restarted), _ptr(scratch), scratch.numel(),
                                         frames, rows, voxels, grid, radius, floor, _ptr(have_prior), _stream()),
@@ -1328,10 +1323,7 @@ def volume_viterbi_refine(prob, coord, index, joints, frames, rows, voxels, grid
     ``prob`` [frames, rows, voxels] over the window of ``refine`` voxels (0..3) around each path voxel, or the voxel centre
     (``refine`` = 0: ``prob`` may be None).  Arguments are checked before anything is launched."""
     what = "volume_viterbi_refine"
-    frames, rows, voxels, grid = int(frames), int(rows), int(voxels), int(grid)
-    if frames < 1 or rows <= 0 or rows > 65535 or not 2 <= grid <= FILTER_MAX_GRID or voxels != grid ** 3:
-        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), grid = {grid} (2..{FILTER_MAX_GRID}), "
-                                f"voxels = {voxels} (grid^3) expected")
+    frames, rows, voxels, grid = _grid_args(what, frames, rows, voxels, grid)[:4]
     if isinstance(refine, bool) or int(refine) != refine or not 0 <= int(refine) <= VITERBI_MAX_REFINE:
         raise HipExtensionError(f"{what}: refine = {refine!r} (an integer in 0..{VITERBI_MAX_REFINE}) expected")
     refine = int(refine)
@@ -1364,6 +1356,28 @@ def _skeleton_shape(what, grid, radius):
         raise HipExtensionError(f"{what}: radius = {radius} (0..{min(SKELETON_MAX_RADIUS, grid - 1)}) expected")
 
 
+def _tree_args(what, parents, frames, voxels, grid, radius, floor):
+    """The arguments of the two passes over the kinematic tree: ``parents`` as a list of ints that obeys the parent rule, its length J,
+    and the rest as ints and a float, range-checked."""
+    try:
+        parents = [int(v) for v in parents]
+    except (TypeError, ValueError):
+        raise HipExtensionError(f"{what}: parents must be a sequence of integers") from None
+    J = len(parents)
+    frames, voxels, grid, radius, floor = int(frames), int(voxels), int(grid), int(radius), float(floor)
+    if not 1 <= J <= SKELETON_MAX_JOINTS or parents[0] != 0 or any(not 0 <= parents[j] < j for j in range(1, J)):
+        raise HipExtensionError(f"{what}: parents = {parents}: 1..{SKELETON_MAX_JOINTS} joints with parents[0] = 0 and "
+                                "0 <= parents[j] < j expected")
+    if frames < 1:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1) expected")
+    _skeleton_shape(what, grid, radius)
+    if voxels != grid ** 3:
+        raise HipExtensionError(f"{what}: voxels = {voxels} is not grid^3 = {grid ** 3}")
+    if not 0.0 <= floor <= 1.0:
+        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    return parents, J, frames, voxels, grid, radius, floor
+
+
 def shell_correlate_scratch_bytes(tap_rows, radius) -> int:
     return int(load().se_shell_correlate_scratch_bytes(int(tap_rows), int(radius)))
 
@@ -1385,7 +1399,7 @@ def shell_correlate(a, taps, tap_row, s, out, rows, grid, radius, scale_mul=1.0,
     tap_rows = int(taps.shape[0])
     if not 1 <= tap_rows <= 65535:
         raise HipExtensionError(f"{what}: taps holds {tap_rows} blocks, 1..65535 expected")
-    if out.data_ptr() == a.data_ptr():
+    if _overlap(out, a):
         raise HipExtensionError(f"{what}: out must not alias a")
     scratch = _scratch(what, scratch, shell_correlate_scratch_bytes(tap_rows, radius), torch.uint8, dev)
     _check(load().se_shell_correlate_f32(_ptr(a), _ptr(taps), _ptr(tap_row), _ptr(s), _ptr(out), _ptr(scratch), scratch.numel(), rows,
@@ -1405,28 +1419,13 @@ def skeleton_couple(prob, coord, taps, parents, beliefs, joints, evidence, coupl
     frames, J, grid, radius)`` bytes.  Every argument is checked here and a bad one raises HipExtensionError before anything is
     launched: the kernels trust the sizes they are given."""
     what = "skeleton_couple"
-    try:
-        parents = [int(v) for v in parents]
-    except (TypeError, ValueError):
-        raise HipExtensionError(f"{what}: parents must be a sequence of integers") from None
-    J = len(parents)
-    frames, voxels, grid, radius, floor = int(frames), int(voxels), int(grid), int(radius), float(floor)
-    if not 1 <= J <= SKELETON_MAX_JOINTS or parents[0] != 0 or any(not 0 <= parents[j] < j for j in range(1, J)):
-        raise HipExtensionError(f"{what}: parents = {parents}: 1..{SKELETON_MAX_JOINTS} joints with parents[0] = 0 and "
-                                "0 <= parents[j] < j expected")
-    if frames < 1:
-        raise HipExtensionError(f"{what}: frames = {frames} (>= 1) expected")
-    _skeleton_shape(what, grid, radius)
-    if voxels != grid ** 3:
-        raise HipExtensionError(f"{what}: voxels = {voxels} is not grid^3 = {grid ** 3}")
-    if not 0.0 <= floor <= 1.0:
-        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    parents, J, frames, voxels, grid, radius, floor = _tree_args(what, parents, frames, voxels, grid, radius, floor)
     dev = _check_args(what, (("prob", prob, torch.float32, frames * J * voxels), ("coord", coord, torch.float32, voxels * 3),
                              ("taps", taps, torch.float32, J * (2 * radius + 1) ** 3),
                              ("joints", joints, torch.float32, frames * J * 3), ("evidence", evidence, torch.float32, frames * J),
                              ("coupled", coupled, torch.int32, frames)),
                       (("beliefs", beliefs, torch.float32, frames * J * voxels), ("scratch", scratch, torch.uint8, None)))
-    if beliefs is not None and beliefs.data_ptr() == prob.data_ptr():
+    if beliefs is not None and _overlap(beliefs, prob):
         raise HipExtensionError(f"{what}: beliefs must not alias prob")
     scratch = _scratch(what, scratch, skeleton_couple_scratch_bytes(frames, J, grid, radius), torch.uint8, dev)
     par = (ctypes.c_int * J)(*parents)
@@ -1460,7 +1459,7 @@ def shell_maxcorr(a, taps, tap_row, out, rows, grid, radius, scale_mul=1.0, scra
     dev = _check_args(what, (("a", a, torch.float32, rows * voxels), ("taps", taps, torch.float32, (None, block)),
                              ("tap_row", tap_row, torch.int32, rows), ("out", out, torch.float32, rows * voxels)),
                       (("scratch", scratch, torch.uint8, None),))
-    if out.data_ptr() == a.data_ptr():
+    if _overlap(out, a):
         raise HipExtensionError(f"{what}: out must not alias a")
     scratch = _scratch(what, scratch, shell_correlate_scratch_bytes(tap_rows, radius), torch.uint8, dev)
     _check(load().se_shell_maxcorr_f32(_ptr(a), _ptr(taps), _ptr(tap_row), _ptr(out), _ptr(scratch), scratch.numel(), rows, tap_rows,
@@ -1498,22 +1497,7 @@ def skeleton_pose(prob, taps, parents, index, jumped, exponent, best_root, solve
     uint8 workspace of at least ``skeleton_pose_scratch_bytes(frames, J, grid, radius)`` bytes.  Every argument is checked here and a
     bad one raises HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
     what = "skeleton_pose"
-    try:
-        parents = [int(v) for v in parents]
-    except (TypeError, ValueError):
-        raise HipExtensionError(f"{what}: parents must be a sequence of integers") from None
-    J = len(parents)
-    frames, voxels, grid, radius, floor = int(frames), int(voxels), int(grid), int(radius), float(floor)
-    if not 1 <= J <= SKELETON_MAX_JOINTS or parents[0] != 0 or any(not 0 <= parents[j] < j for j in range(1, J)):
-        raise HipExtensionError(f"{what}: parents = {parents}: 1..{SKELETON_MAX_JOINTS} joints with parents[0] = 0 and "
-                                "0 <= parents[j] < j expected")
-    if frames < 1:
-        raise HipExtensionError(f"{what}: frames = {frames} (>= 1) expected")
-    _skeleton_shape(what, grid, radius)
-    if voxels != grid ** 3:
-        raise HipExtensionError(f"{what}: voxels = {voxels} is not grid^3 = {grid ** 3}")
-    if not 0.0 <= floor <= 1.0:
-        raise HipExtensionError(f"{what}: floor = {floor} must lie in [0, 1]")
+    parents, J, frames, voxels, grid, radius, floor = _tree_args(what, parents, frames, voxels, grid, radius, floor)
     dev = _check_args(what, (("prob", prob, torch.float32, frames * J * voxels), ("taps", taps, torch.float32, J * (2 * radius + 1) ** 3),
                              ("index", index, torch.int32, frames * J), ("jumped", jumped, torch.int32, frames * J),
                              ("exponent", exponent, torch.int32, frames * J), ("best_root", best_root, torch.float32, frames),

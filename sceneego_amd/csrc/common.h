@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <initializer_list>
 
 #include "../../include/sceneego_hip.h"
 
@@ -27,6 +28,13 @@ static constexpr int g_variant = 0;
     } while (0)
 
 static inline hipStream_t se_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// every pointer of the list on a boundary of `bytes` (a power of two); a null pointer passes: optional arguments go in as they are
+inline bool se_aligned(std::initializer_list<const void*> ps, uintptr_t bytes) {
+    uintptr_t all = 0;
+    for (const void* p : ps) all |= reinterpret_cast<uintptr_t>(p);
+    return (all & (bytes - 1)) == 0;
+}
 
 // Per-device launch state.  A process may drive several devices from several threads, so nothing device-dependent is
 // cached per process: the CU count and the "dynamic LDS limit raised" flags are kept per device (ids 0..63).

@@ -275,7 +275,7 @@ extern "C" int se_shell_correlate_f32(const float* a, const float* taps, const i
                                       void* stream) {
     if (!a || !taps || !tap_row || !s || !out || !scratch) return SE_ERR_BAD_ARG;
     if (rows < 1 || rows > 65535 || tap_rows < 1 || tap_rows > 65535 || !sk_shape_ok(G, R)) return SE_ERR_BAD_ARG;
-    if (!sk_aligned4({a, taps, tap_row, s, out, scratch}) || a == out) return SE_ERR_BAD_ARG;
+    if (!se_aligned({a, taps, tap_row, s, out, scratch}, 4) || a == out) return SE_ERR_BAD_ARG;
     if (scratch_bytes < se_shell_correlate_scratch_bytes(tap_rows, R)) return SE_ERR_BAD_ARG;
     hipStream_t st = se_stream(stream);
     int* runs = reinterpret_cast<int*>(scratch);
@@ -299,22 +299,13 @@ extern "C" int se_skeleton_couple_f32(const float* prob, const float* coord, con
     if (frames < 1 || J < 1 || J > SK_MAX_J || !sk_shape_ok(G, R)) return SE_ERR_BAD_ARG;
     if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
     if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
-    if (parent[0] != 0) return SE_ERR_BAD_ARG;
-    for (int j = 1; j < J; ++j)
-        if (parent[j] < 0 || parent[j] >= j) return SE_ERR_BAD_ARG;
-    if (!sk_aligned4({prob, coord, taps, beliefs, joints, evidence, coupled, scratch})) return SE_ERR_BAD_ARG;
+    SkTree tree{};
+    int depth[SK_MAX_J], deepest;
+    if (!sk_build_tree(parent, J, tree, depth, deepest)) return SE_ERR_BAD_ARG;
+    if (!se_aligned({prob, coord, taps, beliefs, joints, evidence, coupled, scratch}, 4)) return SE_ERR_BAD_ARG;
     if (scratch_bytes < se_skeleton_couple_scratch_bytes(frames, J, G, R)) return SE_ERR_BAD_ARG;
     hipStream_t st = se_stream(stream);
 
-    SkTree tree{};
-    tree.J = J;
-    int depth[SK_MAX_J], deepest = 0;
-    depth[0] = 0;
-    for (int j = 0; j < J; ++j) {
-        tree.parent[j] = (signed char)parent[j];
-        if (j) depth[j] = depth[parent[j]] + 1;
-        deepest = max(deepest, depth[j]);
-    }
     const size_t N = (size_t)voxels;
     const int group = min(frames, SK_GROUP), CH = sk_chunks(voxels);
     float* A = reinterpret_cast<float*>(scratch);

@@ -1,12 +1,11 @@
 // What the two passes over the kinematic tree share: skeleton_prior.hip (sum-product, se_skeleton_couple_f32) and skeleton_pose.hip
 // (max-product, se_skeleton_pose_f32) walk the same tree over the same dense shell blocks with the same workgroup tiling.  Stated once
-// here: the limits, the tree and row maps handed to the kernels by value, the chunk rule of a row, the run table of a block of taps
-// (sk_runs_kernel) and the launch geometry of a shell pass over G^3 outputs.  skeleton_prior.hip describes the tiling.
+// here: the limits, the tree and row maps handed to the kernels by value, the check of parent[] that builds them (sk_build_tree), the
+// chunk rule of a row, the run table of a block of taps (sk_runs_kernel) and the launch geometry of a shell pass over G^3 outputs.
+// skeleton_prior.hip describes the tiling.
 //
 // No `fp contract` pragma here: nothing below rounds.
 #pragma once
-#include <initializer_list>
-
 #include "common.h"
 
 #define SK_THREADS 256
@@ -68,10 +67,22 @@ inline int sk_lds_bytes(int R) { return (SK_TJ + 2 * R) * (SK_KC + 2 * R) * 4; }
 inline dim3 sk_corr_grid(int G, int rows) {
     return dim3(G * ((G + SK_TJ - 1) / SK_TJ) * ((G + SK_KC - 1) / SK_KC), rows);
 }
-inline bool sk_aligned4(std::initializer_list<const void*> ps) {
-    uintptr_t all = 0;
-    for (const void* p : ps) all |= reinterpret_cast<uintptr_t>(p);
-    return (all & 3) == 0;
+
+// The tree of a call: false unless parent[0] == 0 and 0 <= parent[j] < j behind it (parents come first, so one ascending pass gives
+// every depth).  Fills the tree handed to the kernels, the depth of every joint and the deepest level.
+inline bool sk_build_tree(const int* parent, int J, SkTree& tree, int* depth, int& deepest) {
+    if (parent[0] != 0) return false;
+    tree.J = J;
+    tree.parent[0] = 0;
+    depth[0] = 0;
+    deepest = 0;
+    for (int j = 1; j < J; ++j) {
+        if (parent[j] < 0 || parent[j] >= j) return false;
+        tree.parent[j] = (signed char)parent[j];
+        depth[j] = depth[parent[j]] + 1;
+        deepest = max(deepest, depth[j]);
+    }
+    return true;
 }
 
 }  // namespace

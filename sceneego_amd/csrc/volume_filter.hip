@@ -53,12 +53,9 @@
 #include <float.h>
 
 #include "row_reduce.h"
+#include "volume_grid.h"          // the limits, the shape predicate, the launch parameters and the argument gate: shared with volume_viterbi.hip
 
-#define SE_VF_THREADS 256
-#define SE_VF_MAX_G 128
-#define SE_VF_MAX_R 16
 #define SE_VF_PART 8              // Z, sum a c (x y z), sum p c (x y z), pad
-#define SE_VF_MAX_CHUNKS 64
 #define SE_VF_CHAIN 80            // L of the header comment
 #define SE_VS_CHAIN 80            // the smoother's: the same fold over the same records
 
@@ -68,22 +65,94 @@ __device__ __forceinline__ bool vf_has_prior(const int* __restrict__ have_prior,
     return prior_all || (have_prior != nullptr && have_prior[row] != 0);
 }
 
+// What the update kernels of the filter and of the smoother share.  Thread t owns column k = t & (W - 1) of the slab and the rows
+// ir, ir + RP, ... of it (ir = t >> wshift, RP = 256 >> wshift).
+// The slab [G i][G k] of q at one j and the taps, staged by the whole workgroup; the caller's __syncthreads() follows.
+__device__ __forceinline__ void vf_stage_slab(const float* __restrict__ q, const float* __restrict__ taps, float* __restrict__ slab,
+                                              float* __restrict__ w, size_t base, int j, int G, int R, int t, int k, int ir, int RP) {
+    if (k < G)
+        for (int i = ir; i < G; i += RP) slab[i * G + k] = q[base + ((size_t)i * G + j) * G + k];
+    if (t <= 2 * R) w[t] = taps[t];
+}
+// u of voxel (i, k) of the staged slab: the blur along i over the taps that stay inside the grid, in ascending d, then the floor
+__device__ __forceinline__ float vf_blur_i_floor(const float* __restrict__ slab, const float* __restrict__ w, int i, int k, int G, int R,
+                                                 float keep, float uniform) {
+    const int lo = max(-R, -i), hi = min(R, G - 1 - i);
+    const float* s = slab + i * G + k;
+    float u = 0.f;
+    for (int d = lo; d <= hi; ++d) u = fmaf(w[d + R], s[d * G], u);
+    return fmaf(keep, u, uniform);
+}
+
+// What the finish kernels share.
+// Wave 0 folds the first NV values of the row's G records into fin[]; every thread of the workgroup may read fin[] on return.
+template <int NV>
+__device__ __forceinline__ void vf_fold_records(const float* __restrict__ part, int row, int G, int t, float* __restrict__ fin) {
+    if (t < 64) {
+        float acc[NV];
+#pragma unroll
+        for (int x = 0; x < NV; ++x) acc[x] = 0.f;
+        wave_fold_records<NV, SE_VF_PART>(part, (size_t)row * G, G, t, acc);
+        if (t == 0) {
+#pragma unroll
+            for (int x = 0; x < NV; ++x) fin[x] = acc[x];
+        }
+    }
+    __syncthreads();
+}
+// The row pass of a finish kernel: this workgroup's share of a row of `voxels` floats, for each of NS streams dst = src / Z (scale) or
+// the copy of src, bit for bit; `out` (or NULL) receives the same values; a stream without src is skipped.  16 bytes per lane (VEC)
+// or one float at a time.  The streams take turns inside one loop, so that the loads of the smoother's two are in flight together.
+struct VfStream {
+    const float* src;
+    bool scale;
+    float Z;
+    float* dst;
+    float* out;
+};
+template <bool VEC, int NS>
+__device__ __forceinline__ void vf_scale_or_copy(const VfStream (&st)[NS], int voxels, int t) {
+    for (int n = (blockIdx.x * SE_VG_THREADS + t) * 4; n < voxels; n += gridDim.x * SE_VG_THREADS * 4) {
+        if (VEC) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                if (!st[s].src) continue;
+                f32x4 x = *reinterpret_cast<const f32x4*>(st[s].src + n);
+                if (st[s].scale) { x.x = x.x / st[s].Z; x.y = x.y / st[s].Z; x.z = x.z / st[s].Z; x.w = x.w / st[s].Z; }
+                *reinterpret_cast<f32x4*>(st[s].dst + n) = x;
+                if (st[s].out) *reinterpret_cast<f32x4*>(st[s].out + n) = x;
+            }
+        } else {
+            for (int e = n; e < min(n + 4, voxels); ++e) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    if (!st[s].src) continue;
+                    float x = st[s].src[e];
+                    if (st[s].scale) x = x / st[s].Z;
+                    st[s].dst[e] = x;
+                    if (st[s].out) st[s].out[e] = x;
+                }
+            }
+        }
+    }
+}
+
 // grid (G, rows), block 256, dynamic LDS 2 G^2 floats
-__global__ __launch_bounds__(SE_VF_THREADS) void vf_blur_kj_kernel(const float* __restrict__ state, const float* __restrict__ taps,
+__global__ __launch_bounds__(SE_VG_THREADS) void vf_blur_kj_kernel(const float* __restrict__ state, const float* __restrict__ taps,
                                                                    const int* __restrict__ have_prior, int prior_all,
                                                                    float* __restrict__ q, int G, int voxels, int R, int wshift) {
     extern __shared__ __align__(16) float lds[];
-    __shared__ float w[2 * SE_VF_MAX_R + 1];
+    __shared__ float w[2 * SE_VG_MAX_R + 1];
     const int t = threadIdx.x, i = blockIdx.x, row = blockIdx.y;
     if (!vf_has_prior(have_prior, prior_all, row)) return;          // uniform: the row restarts, q is not read
     const int GG = G * G;
     float* A = lds;
     float* Bk = lds + GG;
     const size_t base = (size_t)row * voxels + (size_t)i * GG;
-    for (int e = t; e < GG; e += SE_VF_THREADS) A[e] = state[base + e];
+    for (int e = t; e < GG; e += SE_VG_THREADS) A[e] = state[base + e];
     if (t <= 2 * R) w[t] = taps[t];
     __syncthreads();
-    const int k = t & ((1 << wshift) - 1), jr = t >> wshift, RP = SE_VF_THREADS >> wshift;
+    const int k = t & ((1 << wshift) - 1), jr = t >> wshift, RP = SE_VG_THREADS >> wshift;
     if (k < G) {
         const int lo = max(-R, -k), hi = min(R, G - 1 - k);         // the taps that stay inside the row
         for (int j = jr; j < G; j += RP) {
@@ -106,22 +175,18 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vf_blur_kj_kernel(const float* 
 }
 
 // grid (G, rows), block 256, dynamic LDS G^2 floats
-__global__ __launch_bounds__(SE_VF_THREADS) void vf_update_kernel(const float* __restrict__ prob, const float* __restrict__ coord,
+__global__ __launch_bounds__(SE_VG_THREADS) void vf_update_kernel(const float* __restrict__ prob, const float* __restrict__ coord,
                                                                   const float* __restrict__ taps, const int* __restrict__ have_prior,
                                                                   int prior_all, float* __restrict__ q, float* __restrict__ part,
                                                                   int G, int voxels, int R, int wshift, float keep, float uniform) {
     extern __shared__ __align__(16) float lds[];
-    __shared__ float w[2 * SE_VF_MAX_R + 1];
+    __shared__ float w[2 * SE_VG_MAX_R + 1];
     __shared__ float sm[4][SE_VF_PART];
     const int t = threadIdx.x, j = blockIdx.x, row = blockIdx.y;
     const bool prior = vf_has_prior(have_prior, prior_all, row);    // uniform
-    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VF_THREADS >> wshift;
+    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VG_THREADS >> wshift;
     const size_t base = (size_t)row * voxels;
-    if (prior) {
-        if (k < G)
-            for (int i = ir; i < G; i += RP) lds[i * G + k] = q[base + ((size_t)i * G + j) * G + k];
-        if (t <= 2 * R) w[t] = taps[t];
-    }
+    if (prior) vf_stage_slab(q, taps, lds, w, base, j, G, R, t, k, ir, RP);
     __syncthreads();
     float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};            // Z, sum a c, sum p c
     if (k < G) {
@@ -131,11 +196,7 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vf_update_kernel(const float* _
             const float cx = coord[n * 3 + 0], cy = coord[n * 3 + 1], cz = coord[n * 3 + 2];
             acc[4] += p * cx; acc[5] += p * cy; acc[6] += p * cz;
             if (prior) {
-                const int lo = max(-R, -i), hi = min(R, G - 1 - i);
-                const float* s = lds + i * G + k;
-                float u = 0.f;
-                for (int d = lo; d <= hi; ++d) u = fmaf(w[d + R], s[d * G], u);
-                u = fmaf(keep, u, uniform);
+                const float u = vf_blur_i_floor(lds, w, i, k, G, R, keep, uniform);
                 const float a = p * u;
                 q[base + n] = a;                                    // staged by this workgroup, read by no other
                 acc[0] += a;
@@ -149,7 +210,7 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vf_update_kernel(const float* _
 
 // grid (chunks, rows), block 256
 template <bool VEC>
-__global__ __launch_bounds__(SE_VF_THREADS) void vf_finish_kernel(const float* __restrict__ prob, const float* __restrict__ q,
+__global__ __launch_bounds__(SE_VG_THREADS) void vf_finish_kernel(const float* __restrict__ prob, const float* __restrict__ q,
                                                                   const float* __restrict__ part, const int* __restrict__ have_prior,
                                                                   int prior_all, float* __restrict__ state,
                                                                   float* __restrict__ belief_out, float* __restrict__ joints,
@@ -157,15 +218,7 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vf_finish_kernel(const float* _
                                                                   int voxels) {
     __shared__ float fin[SE_VF_PART];
     const int t = threadIdx.x, row = blockIdx.y;
-    if (t < 64) {
-        float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        wave_fold_records<7, SE_VF_PART>(part, (size_t)row * G, G, t, acc);
-        if (t == 0) {
-#pragma unroll
-            for (int x = 0; x < 7; ++x) fin[x] = acc[x];
-        }
-    }
-    __syncthreads();
+    vf_fold_records<7>(part, row, G, t, fin);
     const bool prior = vf_has_prior(have_prior, prior_all, row);
     const float Z = fin[0];
     const bool restart = !prior || !(Z > 0.f && Z <= FLT_MAX);      // a NaN fails both comparisons
@@ -177,24 +230,9 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vf_finish_kernel(const float* _
         restarted[row] = restart ? 1 : 0;
     }
     const size_t base = (size_t)row * voxels;
-    const float* src = (restart ? prob : q) + base;                 // the copy of p is bit for bit
-    float* dst = state + base;
-    float* out = belief_out ? belief_out + base : nullptr;
-    for (int n = (blockIdx.x * SE_VF_THREADS + t) * 4; n < voxels; n += gridDim.x * SE_VF_THREADS * 4) {
-        if (VEC) {
-            f32x4 x = *reinterpret_cast<const f32x4*>(src + n);
-            if (!restart) { x.x = x.x / Z; x.y = x.y / Z; x.z = x.z / Z; x.w = x.w / Z; }
-            *reinterpret_cast<f32x4*>(dst + n) = x;
-            if (out) *reinterpret_cast<f32x4*>(out + n) = x;
-        } else {
-            for (int e = n; e < min(n + 4, voxels); ++e) {
-                float x = src[e];
-                if (!restart) x = x / Z;
-                dst[e] = x;
-                if (out) out[e] = x;
-            }
-        }
-    }
+    // b' = a / Z, or the copy of p
+    const VfStream st[1] = {{(restart ? prob : q) + base, !restart, Z, state + base, belief_out ? belief_out + base : nullptr}};
+    vf_scale_or_copy<VEC>(st, voxels, t);
 }
 
 // one workgroup: the taps reversed (blur3T is blur3 with them), for the blur kernel above and the update kernel below
@@ -205,23 +243,19 @@ __global__ void vs_prep_kernel(const float* __restrict__ taps, float* __restrict
 
 // grid (G, rows), block 256, dynamic LDS G^2 floats.  `taps`: already reversed.  `link`: the frame's link flags (or NULL: none).
 // `g_out`: NULL when gamma is not asked for.
-__global__ __launch_bounds__(SE_VF_THREADS) void vs_update_kernel(const float* __restrict__ prob, const float* __restrict__ belief,
+__global__ __launch_bounds__(SE_VG_THREADS) void vs_update_kernel(const float* __restrict__ prob, const float* __restrict__ belief,
                                                                   const float* __restrict__ coord, const float* __restrict__ taps,
                                                                   const int* __restrict__ link, float* __restrict__ q,
                                                                   float* __restrict__ g_out, float* __restrict__ part, int G, int voxels,
                                                                   int R, int wshift, float keep, float uniform) {
     extern __shared__ __align__(16) float lds[];
-    __shared__ float w[2 * SE_VF_MAX_R + 1];
+    __shared__ float w[2 * SE_VG_MAX_R + 1];
     __shared__ float sm[4][SE_VF_PART];
     const int t = threadIdx.x, j = blockIdx.x, row = blockIdx.y;
     const bool linked = vf_has_prior(link, 0, row);                 // uniform
-    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VF_THREADS >> wshift;
+    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VG_THREADS >> wshift;
     const size_t base = (size_t)row * voxels;
-    if (linked) {
-        if (k < G)
-            for (int i = ir; i < G; i += RP) lds[i * G + k] = q[base + ((size_t)i * G + j) * G + k];
-        if (t <= 2 * R) w[t] = taps[t];
-    }
+    if (linked) vf_stage_slab(q, taps, lds, w, base, j, G, R, t, k, ir, RP);
     __syncthreads();
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};       // s, S, sum g c, sum b c
     if (k < G) {
@@ -232,11 +266,7 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vs_update_kernel(const float* _
             acc[5] += b * cx; acc[6] += b * cy; acc[7] += b * cz;
             if (linked) {
                 const float p = prob[base + n];
-                const int lo = max(-R, -i), hi = min(R, G - 1 - i);
-                const float* s = lds + i * G + k;
-                float u = 0.f;
-                for (int d = lo; d <= hi; ++d) u = fmaf(w[d + R], s[d * G], u);
-                u = fmaf(keep, u, uniform);
+                const float u = vf_blur_i_floor(lds, w, i, k, G, R, keep, uniform);
                 const float a = p * u, g = b * u;
                 q[base + n] = a;                                    // staged by this workgroup, read by no other
                 if (g_out) g_out[base + n] = g;
@@ -252,7 +282,7 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vs_update_kernel(const float* _
 
 // grid (chunks, rows), block 256.  No __restrict__ on belief / smoothed_out: they may be one array.
 template <bool VEC>
-__global__ __launch_bounds__(SE_VF_THREADS) void vs_finish_kernel(const float* __restrict__ prob, const float* belief,
+__global__ __launch_bounds__(SE_VG_THREADS) void vs_finish_kernel(const float* __restrict__ prob, const float* belief,
                                                                   const float* __restrict__ q, const float* __restrict__ g,
                                                                   const float* __restrict__ part, const int* __restrict__ link,
                                                                   const int* __restrict__ restarted, int* __restrict__ link_next,
@@ -261,15 +291,7 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vs_finish_kernel(const float* _
                                                                   int* __restrict__ smoothed, int G, int voxels) {
     __shared__ float fin[SE_VF_PART];
     const int t = threadIdx.x, row = blockIdx.y;
-    if (t < 64) {
-        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        wave_fold_records<8, SE_VF_PART>(part, (size_t)row * G, G, t, acc);
-        if (t == 0) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) fin[x] = acc[x];
-        }
-    }
-    __syncthreads();
+    vf_fold_records<8>(part, row, G, t, fin);
     const bool linked = vf_has_prior(link, 0, row);
     const float s = fin[0], S = fin[1];
     const bool back = linked && s > 0.f && s <= FLT_MAX;            // r_t = a / s; a NaN fails both comparisons
@@ -283,46 +305,18 @@ __global__ __launch_bounds__(SE_VF_THREADS) void vs_finish_kernel(const float* _
         link_next[row] = restarted[row] == 0;                       // the frame before this one is linked to it unless it restarted
     }
     const size_t base = (size_t)row * voxels;
-    const float* rsrc = (back ? q : prob) + base;                   // the copies are bit for bit
-    float* rdst = state + base;
+    // r_t = a / s, or the copy of p_t; gamma_t = g / S, or the copy of b_t (skipped onto itself)
     const bool write_gamma = smoothed_out != nullptr && (smooth || smoothed_out != belief);
-    const float* gsrc = write_gamma ? (smooth ? g : belief) + base : nullptr;
-    float* gdst = write_gamma ? smoothed_out + base : nullptr;
-    for (int n = (blockIdx.x * SE_VF_THREADS + t) * 4; n < voxels; n += gridDim.x * SE_VF_THREADS * 4) {
-        if (VEC) {
-            f32x4 x = *reinterpret_cast<const f32x4*>(rsrc + n);
-            if (back) { x.x = x.x / s; x.y = x.y / s; x.z = x.z / s; x.w = x.w / s; }
-            *reinterpret_cast<f32x4*>(rdst + n) = x;
-            if (write_gamma) {
-                f32x4 y = *reinterpret_cast<const f32x4*>(gsrc + n);
-                if (smooth) { y.x = y.x / S; y.y = y.y / S; y.z = y.z / S; y.w = y.w / S; }
-                *reinterpret_cast<f32x4*>(gdst + n) = y;
-            }
-        } else {
-            for (int e = n; e < min(n + 4, voxels); ++e) {
-                float x = rsrc[e];
-                if (back) x = x / s;
-                rdst[e] = x;
-                if (write_gamma) {
-                    float y = gsrc[e];
-                    if (smooth) y = y / S;
-                    gdst[e] = y;
-                }
-            }
-        }
-    }
+    const VfStream st[2] = {{(back ? q : prob) + base, back, s, state + base, nullptr},
+                            {write_gamma ? (smooth ? g : belief) + base : nullptr, smooth, S, write_gamma ? smoothed_out + base : nullptr, nullptr}};
+    vf_scale_or_copy<VEC>(st, voxels, t);
 }
-
-inline bool vf_shape_ok(int rows, int G, int R) {
-    return rows >= 1 && rows <= 65535 && G >= 2 && G <= SE_VF_MAX_G && R >= 0 && R <= SE_VF_MAX_R && R <= G - 1;
-}
-inline long long vf_q_elems(int rows, int G) { return (long long)rows * G * G * G; }
 
 }  // namespace
 
 extern "C" long long se_volume_filter_scratch_bytes(int rows, int G, int radius) {
-    if (!vf_shape_ok(rows, G, radius)) return 0;
-    return (vf_q_elems(rows, G) + (long long)rows * G * SE_VF_PART) * 4;
+    if (!vg_shape_ok(rows, G, radius)) return 0;
+    return (vg_elems(rows, G) + (long long)rows * G * SE_VF_PART) * 4;
 }
 
 extern "C" int se_volume_filter_f32(const float* prob, const float* coord, const float* taps, float* state, float* belief_out,
@@ -330,50 +324,34 @@ extern "C" int se_volume_filter_f32(const float* prob, const float* coord, const
                                     int frames, int rows, int voxels, int G, int radius, float floor, const int* have_prior,
                                     void* stream) {
     if (!prob || !coord || !taps || !state || !joints || !evidence || !restarted || !scratch) return SE_ERR_BAD_ARG;
-    if (frames < 1 || !vf_shape_ok(rows, G, radius)) return SE_ERR_BAD_ARG;
-    if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
-    if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
-    const uintptr_t all = reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(coord) | reinterpret_cast<uintptr_t>(taps) |
-                          reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(belief_out) |
-                          reinterpret_cast<uintptr_t>(joints) | reinterpret_cast<uintptr_t>(evidence) |
-                          reinterpret_cast<uintptr_t>(restarted) | reinterpret_cast<uintptr_t>(scratch) |
-                          reinterpret_cast<uintptr_t>(have_prior);
-    if (all & 3) return SE_ERR_BAD_ARG;
+    if (!vg_args_ok(frames, rows, voxels, G, radius, floor)) return SE_ERR_BAD_ARG;
+    if (!se_aligned({prob, coord, taps, state, belief_out, joints, evidence, restarted, scratch, have_prior}, 4)) return SE_ERR_BAD_ARG;
     if (scratch_bytes < se_volume_filter_scratch_bytes(rows, G, radius)) return SE_ERR_BAD_ARG;
     hipStream_t s = se_stream(stream);
     float* q = reinterpret_cast<float*>(scratch);
-    float* part = q + vf_q_elems(rows, G);
-    int wshift = 0;
-    while ((1 << wshift) < G) ++wshift;                                                   // W = 1 << wshift <= 128
+    float* part = q + vg_elems(rows, G);
+    const auto [wshift, chunks, keep, uniform] = vg_launch(voxels, G, floor);
     const int plane_bytes = G * G * 4;
-    SE_ENSURE_LDS(vf_blur_kj_kernel, 2 * SE_VF_MAX_G * SE_VF_MAX_G * 4);
-    SE_ENSURE_LDS(vf_update_kernel, SE_VF_MAX_G * SE_VF_MAX_G * 4);
+    SE_ENSURE_LDS(vf_blur_kj_kernel, 2 * SE_VG_MAX_G * SE_VG_MAX_G * 4);
+    SE_ENSURE_LDS(vf_update_kernel, SE_VG_MAX_G * SE_VG_MAX_G * 4);
     // 16-byte moves in the finish pass: whole quads per row and every base it touches aligned
-    const bool vec = (voxels & 3) == 0 && !((reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(state) |
-                                             reinterpret_cast<uintptr_t>(belief_out) | reinterpret_cast<uintptr_t>(scratch)) & 15);
-    const int chunks = min(SE_VF_MAX_CHUNKS, (voxels + SE_VF_THREADS * 4 - 1) / (SE_VF_THREADS * 4));
-    const float keep = 1.0f - floor, uniform = floor / (float)voxels;
+    const bool vec = (voxels & 3) == 0 && se_aligned({prob, state, belief_out, scratch}, 16);
+    const auto finish = vec ? vf_finish_kernel<true> : vf_finish_kernel<false>;
     const size_t frame_elems = (size_t)rows * voxels;
     for (int f = 0; f < frames; ++f) {
         const float* p = prob + f * frame_elems;
         const int prior_all = f > 0;
         if (prior_all || have_prior) {
-            hipLaunchKernelGGL(vf_blur_kj_kernel, dim3(G, rows), dim3(SE_VF_THREADS), 2 * plane_bytes, s, state, taps, have_prior,
+            hipLaunchKernelGGL(vf_blur_kj_kernel, dim3(G, rows), dim3(SE_VG_THREADS), 2 * plane_bytes, s, state, taps, have_prior,
                                prior_all, q, G, voxels, radius, wshift);
             SE_CHECK_LAUNCH();
         }
-        hipLaunchKernelGGL(vf_update_kernel, dim3(G, rows), dim3(SE_VF_THREADS), plane_bytes, s, p, coord, taps, have_prior, prior_all,
+        hipLaunchKernelGGL(vf_update_kernel, dim3(G, rows), dim3(SE_VG_THREADS), plane_bytes, s, p, coord, taps, have_prior, prior_all,
                            q, part, G, voxels, radius, wshift, keep, uniform);
         SE_CHECK_LAUNCH();
         float* bo = belief_out ? belief_out + f * frame_elems : nullptr;
-        if (vec)
-            hipLaunchKernelGGL(vf_finish_kernel<true>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, q, part, have_prior, prior_all,
-                               state, bo, joints + (size_t)f * rows * 3, evidence + (size_t)f * rows, restarted + (size_t)f * rows, G,
-                               voxels);
-        else
-            hipLaunchKernelGGL(vf_finish_kernel<false>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, q, part, have_prior,
-                               prior_all, state, bo, joints + (size_t)f * rows * 3, evidence + (size_t)f * rows,
-                               restarted + (size_t)f * rows, G, voxels);
+        hipLaunchKernelGGL(finish, dim3(chunks, rows), dim3(SE_VG_THREADS), 0, s, p, q, part, have_prior, prior_all, state, bo,
+                           joints + (size_t)f * rows * 3, evidence + (size_t)f * rows, restarted + (size_t)f * rows, G, voxels);
         SE_CHECK_LAUNCH();
     }
     return 0;
@@ -385,8 +363,8 @@ extern "C" int se_volume_filter_f32(const float* prob, const float* coord, const
 inline long long vs_tail_elems(int rows, int G) { return (long long)rows * G * SE_VF_PART + 40 + 2LL * ((rows + 3) & ~3); }
 
 extern "C" long long se_volume_smooth_scratch_bytes(int rows, int G, int radius) {
-    if (!vf_shape_ok(rows, G, radius)) return 0;
-    return (2 * vf_q_elems(rows, G) + vs_tail_elems(rows, G)) * 4;
+    if (!vg_shape_ok(rows, G, radius)) return 0;
+    return (2 * vg_elems(rows, G) + vs_tail_elems(rows, G)) * 4;
 }
 
 extern "C" int se_volume_smooth_f32(const float* prob, const float* belief, const int* restarted, const float* coord, const float* taps,
@@ -395,33 +373,23 @@ extern "C" int se_volume_smooth_f32(const float* prob, const float* belief, cons
                                     const int* have_link, void* stream) {
     if (!prob || !belief || !restarted || !coord || !taps || !state || !joints || !agreement || !smoothed || !scratch)
         return SE_ERR_BAD_ARG;
-    if (frames < 1 || !vf_shape_ok(rows, G, radius)) return SE_ERR_BAD_ARG;
-    if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
-    if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
-    const uintptr_t all = reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(belief) | reinterpret_cast<uintptr_t>(restarted) |
-                          reinterpret_cast<uintptr_t>(coord) | reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(state) |
-                          reinterpret_cast<uintptr_t>(smoothed_out) | reinterpret_cast<uintptr_t>(joints) |
-                          reinterpret_cast<uintptr_t>(agreement) | reinterpret_cast<uintptr_t>(smoothed) |
-                          reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(have_link);
-    if (all & 3) return SE_ERR_BAD_ARG;
+    if (!vg_args_ok(frames, rows, voxels, G, radius, floor)) return SE_ERR_BAD_ARG;
+    if (!se_aligned({prob, belief, restarted, coord, taps, state, smoothed_out, joints, agreement, smoothed, scratch, have_link}, 4))
+        return SE_ERR_BAD_ARG;
     if (scratch_bytes < se_volume_smooth_scratch_bytes(rows, G, radius)) return SE_ERR_BAD_ARG;
     hipStream_t s = se_stream(stream);
     float* q = reinterpret_cast<float*>(scratch);
-    float* g = q + vf_q_elems(rows, G);
-    float* part = g + vf_q_elems(rows, G);
+    float* g = q + vg_elems(rows, G);
+    float* part = g + vg_elems(rows, G);
     float* rev = part + (long long)rows * G * SE_VF_PART;
     int* link2 = reinterpret_cast<int*>(rev + 40);
     const int link_stride = (rows + 3) & ~3;
-    int wshift = 0;
-    while ((1 << wshift) < G) ++wshift;
+    const auto [wshift, chunks, keep, uniform] = vg_launch(voxels, G, floor);
     const int plane_bytes = G * G * 4;
-    SE_ENSURE_LDS(vf_blur_kj_kernel, 2 * SE_VF_MAX_G * SE_VF_MAX_G * 4);
-    SE_ENSURE_LDS(vs_update_kernel, SE_VF_MAX_G * SE_VF_MAX_G * 4);
-    const bool vec = (voxels & 3) == 0 && !((reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(belief) |
-                                             reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(smoothed_out) |
-                                             reinterpret_cast<uintptr_t>(scratch)) & 15);
-    const int chunks = min(SE_VF_MAX_CHUNKS, (voxels + SE_VF_THREADS * 4 - 1) / (SE_VF_THREADS * 4));
-    const float keep = 1.0f - floor, uniform = floor / (float)voxels;
+    SE_ENSURE_LDS(vf_blur_kj_kernel, 2 * SE_VG_MAX_G * SE_VG_MAX_G * 4);
+    SE_ENSURE_LDS(vs_update_kernel, SE_VG_MAX_G * SE_VG_MAX_G * 4);
+    const bool vec = (voxels & 3) == 0 && se_aligned({prob, belief, state, smoothed_out, scratch}, 16);
+    const auto finish = vec ? vs_finish_kernel<true> : vs_finish_kernel<false>;
     const size_t frame_elems = (size_t)rows * voxels;
     hipLaunchKernelGGL(vs_prep_kernel, dim3(1), dim3(64), 0, s, taps, rev, radius);
     SE_CHECK_LAUNCH();
@@ -432,23 +400,17 @@ extern "C" int se_volume_smooth_f32(const float* prob, const float* belief, cons
         const int* link = f == frames - 1 ? have_link : link2 + (size_t)(f & 1) * link_stride;
         int* link_next = link2 + (size_t)((f + 1) & 1) * link_stride;                    // read by frame f - 1
         if (link) {
-            hipLaunchKernelGGL(vf_blur_kj_kernel, dim3(G, rows), dim3(SE_VF_THREADS), 2 * plane_bytes, s, state, rev, link, 0, q, G,
+            hipLaunchKernelGGL(vf_blur_kj_kernel, dim3(G, rows), dim3(SE_VG_THREADS), 2 * plane_bytes, s, state, rev, link, 0, q, G,
                                voxels, radius, wshift);
             SE_CHECK_LAUNCH();
         }
-        hipLaunchKernelGGL(vs_update_kernel, dim3(G, rows), dim3(SE_VF_THREADS), plane_bytes, s, p, b, coord, rev, link, q,
+        hipLaunchKernelGGL(vs_update_kernel, dim3(G, rows), dim3(SE_VG_THREADS), plane_bytes, s, p, b, coord, rev, link, q,
                            smoothed_out ? g : nullptr, part, G, voxels, radius, wshift, keep, uniform);
         SE_CHECK_LAUNCH();
         float* so = smoothed_out ? smoothed_out + f * frame_elems : nullptr;
         const int* rs = restarted + (size_t)f * rows;
-        if (vec)
-            hipLaunchKernelGGL(vs_finish_kernel<true>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, b, q, g, part, link, rs, link_next,
-                               state, so, joints + (size_t)f * rows * 3, agreement + (size_t)f * rows, smoothed + (size_t)f * rows, G,
-                               voxels);
-        else
-            hipLaunchKernelGGL(vs_finish_kernel<false>, dim3(chunks, rows), dim3(SE_VF_THREADS), 0, s, p, b, q, g, part, link, rs,
-                               link_next, state, so, joints + (size_t)f * rows * 3, agreement + (size_t)f * rows,
-                               smoothed + (size_t)f * rows, G, voxels);
+        hipLaunchKernelGGL(finish, dim3(chunks, rows), dim3(SE_VG_THREADS), 0, s, p, b, q, g, part, link, rs, link_next, state, so,
+                           joints + (size_t)f * rows * 3, agreement + (size_t)f * rows, smoothed + (size_t)f * rows, G, voxels);
         SE_CHECK_LAUNCH();
     }
     return 0;

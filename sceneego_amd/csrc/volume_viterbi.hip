@@ -44,14 +44,11 @@
 #include <float.h>
 
 #include "row_reduce.h"
+#include "volume_grid.h"          // the limits, the shape predicate, the launch parameters and the argument gate: shared with volume_filter.hip
 
 #pragma clang fp contract(off)
 
-#define SE_VV_THREADS 256
-#define SE_VV_MAX_G 128
-#define SE_VV_MAX_R 16
 #define SE_VV_REC 4               // max a, its index, max p, its index
-#define SE_VV_MAX_CHUNKS 64
 #define SE_VV_MAX_REFINE 3
 #define SE_VV_JUMP (1 << 30)
 #define SE_VV_ROWS 4              // rows of its column a thread takes through the tap loop together: independent compare-select chains
@@ -68,7 +65,7 @@ __device__ __forceinline__ bool vv_prior(const int* __restrict__ have_prior, con
 }
 
 // grid (G, rows), block 256, dynamic LDS (2 G + 2 R) G floats
-__global__ __launch_bounds__(SE_VV_THREADS) void vv_stage_kj_kernel(const float* __restrict__ state, const float* __restrict__ taps,
+__global__ __launch_bounds__(SE_VG_THREADS) void vv_stage_kj_kernel(const float* __restrict__ state, const float* __restrict__ taps,
                                                                     const int* __restrict__ have_prior,
                                                                     const int* __restrict__ peak_state,
                                                                     const int* __restrict__ peak_prev, const int* __restrict__ exp_prev,
@@ -76,7 +73,7 @@ __global__ __launch_bounds__(SE_VV_THREADS) void vv_stage_kj_kernel(const float*
                                                                     signed char* __restrict__ off_j, int G, int voxels, int R,
                                                                     int wshift) {
     extern __shared__ __align__(16) float lds[];
-    __shared__ float w[2 * SE_VV_MAX_R + 1];
+    __shared__ float w[2 * SE_VG_MAX_R + 1];
     const int t = threadIdx.x, i = blockIdx.x, row = blockIdx.y;
     if (!vv_prior(have_prior, peak_state, peak_prev, row)) return;  // uniform: the row restarts, nothing of this pass is read
     const int GG = G * G;
@@ -84,11 +81,11 @@ __global__ __launch_bounds__(SE_VV_THREADS) void vv_stage_kj_kernel(const float*
     float* Bk = lds + GG;                                           // [R + G + R j][G k]: R rows of zeros on either side (vv_update_kernel)
     const size_t base = (size_t)row * voxels + (size_t)i * GG;
     const int down = exp_prev != nullptr ? -exp_prev[row] : 0;      // the state of the call's first frame arrives scaled
-    for (int e = t; e < GG; e += SE_VV_THREADS) A[e] = ldexpf(state[base + e], down);
-    for (int e = t; e < R * G; e += SE_VV_THREADS) { Bk[e] = 0.f; Bk[(R + G) * G + e] = 0.f; }
+    for (int e = t; e < GG; e += SE_VG_THREADS) A[e] = ldexpf(state[base + e], down);
+    for (int e = t; e < R * G; e += SE_VG_THREADS) { Bk[e] = 0.f; Bk[(R + G) * G + e] = 0.f; }
     if (t <= 2 * R) w[t] = taps[t];
     __syncthreads();
-    const int k = t & ((1 << wshift) - 1), jr = t >> wshift, RP = SE_VV_THREADS >> wshift;
+    const int k = t & ((1 << wshift) - 1), jr = t >> wshift, RP = SE_VG_THREADS >> wshift;
     if (k < G) {
         const int lo = max(-R, -k), hi = min(R, G - 1 - k);         // the taps that stay inside the row
         for (int j0 = jr; j0 < G; j0 += SE_VV_ROWS * RP) {
@@ -136,7 +133,7 @@ __global__ __launch_bounds__(SE_VV_THREADS) void vv_stage_kj_kernel(const float*
 }
 
 // grid (G, rows), block 256, dynamic LDS (G + 2 R) G floats and G^2 bytes
-__global__ __launch_bounds__(SE_VV_THREADS) void vv_update_kernel(const float* __restrict__ prob, const float* __restrict__ taps,
+__global__ __launch_bounds__(SE_VG_THREADS) void vv_update_kernel(const float* __restrict__ prob, const float* __restrict__ taps,
                                                                   const int* __restrict__ have_prior, const int* __restrict__ peak_state,
                                                                   const float* __restrict__ best_state,
                                                                   const int* __restrict__ peak_prev, const float* __restrict__ best_prev,
@@ -145,12 +142,12 @@ __global__ __launch_bounds__(SE_VV_THREADS) void vv_update_kernel(const float* _
                                                                   int* __restrict__ back, int* __restrict__ rec, int G, int voxels,
                                                                   int R, int wshift, float keep, float uniform) {
     extern __shared__ __align__(16) float lds[];
-    __shared__ float w[2 * SE_VV_MAX_R + 1];
+    __shared__ float w[2 * SE_VG_MAX_R + 1];
     __shared__ float sm_p[4][2];
     __shared__ int sm_i[4][2];
     const int t = threadIdx.x, j = blockIdx.x, row = blockIdx.y;
     const bool prior = vv_prior(have_prior, peak_state, peak_prev, row);    // uniform
-    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VV_THREADS >> wshift;
+    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VG_THREADS >> wshift;
     const size_t base = (size_t)row * voxels;
     float* slab = lds;                                              // [R + G + R i][G k]: R rows of zeros on either side
     signed char* dj = reinterpret_cast<signed char*>(lds + (G + 2 * R) * G);        // [G i][G k]
@@ -163,7 +160,7 @@ __global__ __launch_bounds__(SE_VV_THREADS) void vv_update_kernel(const float* _
                 slab[(R + i) * G + k] = e2[n];
                 dj[i * G + k] = off_j[n];
             }
-        for (int e = t; e < R * G; e += SE_VV_THREADS) { slab[e] = 0.f; slab[(R + G) * G + e] = 0.f; }
+        for (int e = t; e < R * G; e += SE_VG_THREADS) { slab[e] = 0.f; slab[(R + G) * G + e] = 0.f; }
         if (t <= 2 * R) w[t] = taps[t];
         jump = uniform * (peak_prev != nullptr ? best_prev[row] : best_state[row]);
         jump_to = (peak_prev != nullptr ? peak_prev[row] : peak_state[row]) | SE_VV_JUMP;
@@ -236,7 +233,7 @@ __global__ __launch_bounds__(SE_VV_THREADS) void vv_update_kernel(const float* _
 }
 
 // grid (chunks, rows), block 256
-__global__ __launch_bounds__(SE_VV_THREADS) void vv_fold_kernel(const float* __restrict__ prob, const int* __restrict__ rec,
+__global__ __launch_bounds__(SE_VG_THREADS) void vv_fold_kernel(const float* __restrict__ prob, const int* __restrict__ rec,
                                                                 const int* __restrict__ have_prior, const int* __restrict__ peak_state,
                                                                 const int* __restrict__ peak_prev, float* __restrict__ state,
                                                                 int* __restrict__ back, int* __restrict__ peak, float* __restrict__ best,
@@ -270,21 +267,21 @@ __global__ __launch_bounds__(SE_VV_THREADS) void vv_fold_kernel(const float* __r
     }
     if (!restart || !prior) return;                                 // a row without a prior was written as the copy already
     const size_t base = (size_t)row * voxels;
-    for (int n = blockIdx.x * SE_VV_THREADS + t; n < voxels; n += gridDim.x * SE_VV_THREADS) {
+    for (int n = blockIdx.x * SE_VG_THREADS + t; n < voxels; n += gridDim.x * SE_VG_THREADS) {
         state[base + n] = prob[base + n];                           // bit for bit
         back[base + n] = -1;
     }
 }
 
 // grid (chunks, rows), block 256: the state a call returns is the scaled one
-__global__ __launch_bounds__(SE_VV_THREADS) void vv_scale_kernel(float* __restrict__ state, const int* __restrict__ exponent,
+__global__ __launch_bounds__(SE_VG_THREADS) void vv_scale_kernel(float* __restrict__ state, const int* __restrict__ exponent,
                                                                  const int* __restrict__ peak, const float* __restrict__ best,
                                                                  int* __restrict__ peak_state, float* __restrict__ best_state,
                                                                  int voxels) {
     const int t = threadIdx.x, row = blockIdx.y;
     const int down = -exponent[row];
     const size_t base = (size_t)row * voxels;
-    for (int n = blockIdx.x * SE_VV_THREADS + t; n < voxels; n += gridDim.x * SE_VV_THREADS) state[base + n] = ldexpf(state[base + n], down);
+    for (int n = blockIdx.x * SE_VG_THREADS + t; n < voxels; n += gridDim.x * SE_VG_THREADS) state[base + n] = ldexpf(state[base + n], down);
     if (blockIdx.x == 0 && t == 0) { peak_state[row] = peak[row]; best_state[row] = best[row]; }
 }
 
@@ -351,17 +348,12 @@ __global__ __launch_bounds__(64) void vv_refine_kernel(const float* __restrict__
     o[0] = jx; o[1] = jy; o[2] = jz;
 }
 
-inline bool vv_shape_ok(int rows, int G, int R) {
-    return rows >= 1 && rows <= 65535 && G >= 2 && G <= SE_VV_MAX_G && R >= 0 && R <= SE_VV_MAX_R && R <= G - 1;
-}
-inline long long vv_elems(int rows, int G) { return (long long)rows * G * G * G; }
-
 }  // namespace
 
 // e2 [rows][voxels] float32, the records [rows][G][4] words, then the k and the j offsets [rows][voxels] int8 each
 extern "C" long long se_volume_viterbi_scratch_bytes(int rows, int G, int radius) {
-    if (!vv_shape_ok(rows, G, radius)) return 0;
-    const long long bytes = (vv_elems(rows, G) + (long long)rows * G * SE_VV_REC) * 4 + 2 * vv_elems(rows, G);
+    if (!vg_shape_ok(rows, G, radius)) return 0;
+    const long long bytes = (vg_elems(rows, G) + (long long)rows * G * SE_VV_REC) * 4 + 2 * vg_elems(rows, G);
     return (bytes + 15) & ~15LL;
 }
 
@@ -371,30 +363,21 @@ extern "C" int se_volume_viterbi_f32(const float* prob, const float* taps, float
                                      const int* have_prior, void* stream) {
     if (!prob || !taps || !state || !peak_state || !best_state || !back_out || !peak || !best || !exponent || !restarted || !scratch)
         return SE_ERR_BAD_ARG;
-    if (frames < 1 || !vv_shape_ok(rows, G, radius)) return SE_ERR_BAD_ARG;
-    if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
-    if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
-    const uintptr_t all = reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(state) |
-                          reinterpret_cast<uintptr_t>(peak_state) | reinterpret_cast<uintptr_t>(best_state) |
-                          reinterpret_cast<uintptr_t>(back_out) | reinterpret_cast<uintptr_t>(peak) | reinterpret_cast<uintptr_t>(best) |
-                          reinterpret_cast<uintptr_t>(exponent) | reinterpret_cast<uintptr_t>(restarted) |
-                          reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(have_prior);
-    if (all & 3) return SE_ERR_BAD_ARG;
+    if (!vg_args_ok(frames, rows, voxels, G, radius, floor)) return SE_ERR_BAD_ARG;
+    if (!se_aligned({prob, taps, state, peak_state, best_state, back_out, peak, best, exponent, restarted, scratch, have_prior}, 4))
+        return SE_ERR_BAD_ARG;
     if (scratch_bytes < se_volume_viterbi_scratch_bytes(rows, G, radius)) return SE_ERR_BAD_ARG;
     hipStream_t s = se_stream(stream);
     float* e2 = reinterpret_cast<float*>(scratch);
-    int* rec = reinterpret_cast<int*>(e2 + vv_elems(rows, G));
+    int* rec = reinterpret_cast<int*>(e2 + vg_elems(rows, G));
     signed char* off_k = reinterpret_cast<signed char*>(rec + (long long)rows * G * SE_VV_REC);
-    signed char* off_j = off_k + vv_elems(rows, G);
-    int wshift = 0;
-    while ((1 << wshift) < G) ++wshift;                                                   // W = 1 << wshift <= 128
+    signed char* off_j = off_k + vg_elems(rows, G);
+    const auto [wshift, chunks, keep, uniform] = vg_launch(voxels, G, floor);
     const int plane = G * G, padded = (G + 2 * radius) * G;                              // floats; the padded plane: R rows of zeros on either side
     const int stage_lds = (plane + padded) * 4, update_lds = (padded * 4 + plane + 15) & ~15;
-    const int max_padded = (SE_VV_MAX_G + 2 * SE_VV_MAX_R) * SE_VV_MAX_G;
-    SE_ENSURE_LDS(vv_stage_kj_kernel, (SE_VV_MAX_G * SE_VV_MAX_G + max_padded) * 4);        // 144 KB
-    SE_ENSURE_LDS(vv_update_kernel, max_padded * 4 + SE_VV_MAX_G * SE_VV_MAX_G);          // 96 KB
-    const int chunks = min(SE_VV_MAX_CHUNKS, (voxels + SE_VV_THREADS * 4 - 1) / (SE_VV_THREADS * 4));
-    const float keep = 1.0f - floor, uniform = floor / (float)voxels;
+    const int max_padded = (SE_VG_MAX_G + 2 * SE_VG_MAX_R) * SE_VG_MAX_G;
+    SE_ENSURE_LDS(vv_stage_kj_kernel, (SE_VG_MAX_G * SE_VG_MAX_G + max_padded) * 4);        // 144 KB
+    SE_ENSURE_LDS(vv_update_kernel, max_padded * 4 + SE_VG_MAX_G * SE_VG_MAX_G);          // 96 KB
     const size_t frame_elems = (size_t)rows * voxels;
     for (int f = 0; f < frames; ++f) {
         const float* p = prob + f * frame_elems;
@@ -402,21 +385,21 @@ extern "C" int se_volume_viterbi_f32(const float* prob, const float* taps, float
         const float* best_prev = f > 0 ? best + (size_t)(f - 1) * rows : nullptr;
         const int* exp_prev = f > 0 ? exponent + (size_t)(f - 1) * rows : nullptr;
         if (f > 0 || have_prior) {
-            hipLaunchKernelGGL(vv_stage_kj_kernel, dim3(G, rows), dim3(SE_VV_THREADS), stage_lds, s, state, taps, have_prior,
+            hipLaunchKernelGGL(vv_stage_kj_kernel, dim3(G, rows), dim3(SE_VG_THREADS), stage_lds, s, state, taps, have_prior,
                                peak_state, peak_prev, exp_prev, e2, off_k, off_j, G, voxels, radius, wshift);
             SE_CHECK_LAUNCH();
         }
         int* bo = back_out + f * frame_elems;
-        hipLaunchKernelGGL(vv_update_kernel, dim3(G, rows), dim3(SE_VV_THREADS), update_lds, s, p, taps, have_prior, peak_state,
+        hipLaunchKernelGGL(vv_update_kernel, dim3(G, rows), dim3(SE_VG_THREADS), update_lds, s, p, taps, have_prior, peak_state,
                            best_state, peak_prev, best_prev, e2, off_k, off_j, state, bo, rec, G, voxels, radius, wshift, keep, uniform);
         SE_CHECK_LAUNCH();
-        hipLaunchKernelGGL(vv_fold_kernel, dim3(chunks, rows), dim3(SE_VV_THREADS), 0, s, p, rec, have_prior, peak_state, peak_prev, state,
+        hipLaunchKernelGGL(vv_fold_kernel, dim3(chunks, rows), dim3(SE_VG_THREADS), 0, s, p, rec, have_prior, peak_state, peak_prev, state,
                            bo, peak + (size_t)f * rows, best + (size_t)f * rows, exponent + (size_t)f * rows,
                            restarted + (size_t)f * rows, G, voxels);
         SE_CHECK_LAUNCH();
     }
     const size_t last = (size_t)(frames - 1) * rows;
-    hipLaunchKernelGGL(vv_scale_kernel, dim3(chunks, rows), dim3(SE_VV_THREADS), 0, s, state, exponent + last, peak + last, best + last,
+    hipLaunchKernelGGL(vv_scale_kernel, dim3(chunks, rows), dim3(SE_VG_THREADS), 0, s, state, exponent + last, peak + last, best + last,
                        peak_state, best_state, voxels);
     SE_CHECK_LAUNCH();
     return 0;
@@ -425,11 +408,9 @@ extern "C" int se_volume_viterbi_f32(const float* prob, const float* taps, float
 extern "C" int se_volume_viterbi_path_i32(const int* back, const int* peak, const int* restarted, int* cursor, int* index, int* jumped,
                                           int frames, int rows, int voxels, int have_next, void* stream) {
     if (!back || !peak || !restarted || !cursor || !index || !jumped) return SE_ERR_BAD_ARG;
-    if (frames < 1 || rows < 1 || rows > 65535 || voxels < 1 || voxels > SE_VV_MAX_G * SE_VV_MAX_G * SE_VV_MAX_G) return SE_ERR_BAD_ARG;
+    if (frames < 1 || rows < 1 || rows > 65535 || voxels < 1 || voxels > SE_VG_MAX_G * SE_VG_MAX_G * SE_VG_MAX_G) return SE_ERR_BAD_ARG;
     if (have_next != 0 && have_next != 1) return SE_ERR_BAD_ARG;
-    const uintptr_t all = reinterpret_cast<uintptr_t>(back) | reinterpret_cast<uintptr_t>(peak) | reinterpret_cast<uintptr_t>(restarted) |
-                          reinterpret_cast<uintptr_t>(cursor) | reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(jumped);
-    if (all & 3) return SE_ERR_BAD_ARG;
+    if (!se_aligned({back, peak, restarted, cursor, index, jumped}, 4)) return SE_ERR_BAD_ARG;
     hipLaunchKernelGGL(vv_path_kernel, dim3((rows + 63) / 64), dim3(64), 0, se_stream(stream), back, peak, restarted, cursor, index,
                        jumped, frames, rows, voxels, have_next);
     SE_CHECK_LAUNCH();
@@ -439,12 +420,10 @@ extern "C" int se_volume_viterbi_path_i32(const int* back, const int* peak, cons
 extern "C" int se_volume_viterbi_refine_f32(const float* prob, const float* coord, const int* index, float* joints, int frames,
                                             int rows, int voxels, int G, int refine, void* stream) {
     if (!coord || !index || !joints || (!prob && refine > 0)) return SE_ERR_BAD_ARG;
-    if (frames < 1 || rows < 1 || rows > 65535 || G < 2 || G > SE_VV_MAX_G) return SE_ERR_BAD_ARG;
+    if (frames < 1 || rows < 1 || rows > 65535 || G < 2 || G > SE_VG_MAX_G) return SE_ERR_BAD_ARG;
     if ((long long)G * G * G != (long long)voxels || (long long)frames * rows > INT_MAX) return SE_ERR_BAD_ARG;
     if (refine < 0 || refine > SE_VV_MAX_REFINE) return SE_ERR_BAD_ARG;
-    const uintptr_t all = reinterpret_cast<uintptr_t>(prob) | reinterpret_cast<uintptr_t>(coord) | reinterpret_cast<uintptr_t>(index) |
-                          reinterpret_cast<uintptr_t>(joints);
-    if (all & 3) return SE_ERR_BAD_ARG;
+    if (!se_aligned({prob, coord, index, joints}, 4)) return SE_ERR_BAD_ARG;
     const int total = frames * rows;
     hipLaunchKernelGGL(vv_refine_kernel, dim3((total + 63) / 64), dim3(64), 0, se_stream(stream), prob, coord, index, joints, total,
                        voxels, G, refine);

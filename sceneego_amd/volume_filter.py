@@ -121,7 +121,9 @@ class VolumeFilter:
             raise ValueError("step: joints %s, expected %s" % (tuple(getattr(joints, "shape", ())), (B, J, 3)))
         return B, J
 
-    def _device_state(self, dev, J):
+    def _device_constants(self, dev, J):
+        """``coord``, ``taps`` and a row of ones on ``dev``: what every operator on the filter's model reads.  ``VolumeSmoother`` and
+        ``VolumeViterbi`` take them from here; the belief and its workspace are added by the filter's own first step."""
         key = str(dev)
         if self._dev.get("key") != key:
             if self._dev and self._prior is not None and self._prior.any():
@@ -130,11 +132,16 @@ class VolumeFilter:
                 "key": key,
                 "coord": self._coord_src.to(device=dev, dtype=torch.float32).contiguous(),
                 "taps": torch.from_numpy(self.taps).to(dev),
-                "state": torch.empty((J, self.voxels), device=dev, dtype=torch.float32),
-                "scratch": torch.empty(_lib.volume_filter_scratch_bytes(J, self.grid, self.radius), device=dev, dtype=torch.uint8),
                 "ones": torch.ones(J, device=dev, dtype=torch.int32),
             }
         return self._dev
+
+    def _device_state(self, dev, J):
+        d = self._device_constants(dev, J)
+        if "state" not in d:
+            d["state"] = torch.empty((J, self.voxels), device=dev, dtype=torch.float32)
+            d["scratch"] = torch.empty(_lib.volume_filter_scratch_bytes(J, self.grid, self.radius), device=dev, dtype=torch.uint8)
+        return d
 
     @property
     def state(self):
@@ -188,3 +195,55 @@ class VolumeFilter:
         self._prior[:] = True
         self.frames_seen += B
         return result
+
+
+class StoredTrack:
+    """What ``VolumeSmoother`` and ``VolumeViterbi`` share: both run a forward pass as the frames are pushed, keep what the backward
+    pass needs on the device under a byte budget and release it in ``finish()``.  A stored push is a NamedTuple of the subclass with
+    at least ``restarted`` [B,J], ``given`` (the joints pushed with it, or None) and ``event`` (recorded behind everything the push
+    queued).  The subclass says what a push weighs (``bytes_stored``)."""
+
+    def _init_store(self, max_bytes):
+        if max_bytes is not None and (isinstance(max_bytes, bool) or not float(max_bytes) >= 0):
+            raise ValueError(f"max_bytes = {max_bytes} must be None or a number >= 0")
+        self.max_bytes = None if max_bytes is None else int(max_bytes)
+        # The forward pass's own event chain orders the steps only: what a push stores is queued behind the event its step recorded,
+        # so the next push on another stream is not ordered behind it and finish() waits for the event of every push.
+        self._pushes = []
+        self._done = None                # recorded behind the last finish(): the next one reuses its workspace
+
+    @property
+    def frames_stored(self):
+        return sum(int(p.restarted.shape[0]) for p in self._pushes)
+
+    def _admit(self, B, need, dev):
+        """The budget gate of a push of ``B`` frames that would store ``need`` bytes: ValueError, with nothing allocated, over it."""
+        if self.max_bytes is None:
+            self.max_bytes = int(torch.cuda.mem_get_info(dev)[0]) // 2
+        if self.bytes_stored + need > self.max_bytes:
+            raise ValueError(f"push: {self.frames_stored} frames are stored ({self.bytes_stored} bytes) and {B} more need {need} bytes: "
+                             f"over max_bytes = {self.max_bytes}; finish() the track in pieces or raise max_bytes")
+
+    def _begin_finish(self, stream):
+        """The stored pushes, their device, J and the stream finish() runs on (default: the current one), which is made to wait for
+        every push, whatever stream each ran on, and for the finish() before this one.  ValueError when nothing is stored."""
+        if not self._pushes:
+            raise ValueError("finish: nothing is stored; push() the frames of the track first")
+        first = self._pushes[0].restarted
+        stream = stream if stream is not None else torch.cuda.current_stream(first.device)
+        for p in self._pushes:
+            stream.wait_event(p.event)
+        if self._done is not None:
+            stream.wait_event(self._done)
+        return self._pushes, first.device, int(first.shape[1]), stream
+
+    @staticmethod
+    def _add_shift(result, pushes):
+        """``result["shift"]`` [T,J]: metres between ``result["joints"]`` and the joints given with the pushes, NaN for a push without;
+        no key when no push had any."""
+        if any(p.given is not None for p in pushes):
+            joints = result["joints"]
+            given = torch.cat([p.given if p.given is not None
+                               else torch.full(tuple(p.restarted.shape) + (3,), float("nan"), device=joints.device, dtype=torch.float32)
+                               for p in pushes])
+            result["shift"] = (joints - given).norm(dim=-1)

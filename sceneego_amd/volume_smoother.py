@@ -21,13 +21,26 @@ explanation under any ``floor > 0``, because one jump is then cheaper than the w
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import torch
 
 from . import _lib
-from .volume_filter import VolumeFilter
+from .volume_filter import StoredTrack, VolumeFilter
 
 
-class VolumeSmoother:
+class _Push(NamedTuple):
+    """One stored push: the copies of its volumes and filtered beliefs [B,J,G^3 as G,G,G], the filter's restart flags (int32) and
+    joints, the joints given with it and the event behind the copies."""
+    volumes: torch.Tensor
+    beliefs: torch.Tensor
+    restarted: torch.Tensor
+    given: Optional[torch.Tensor]
+    filtered: torch.Tensor
+    event: torch.cuda.Event
+
+
+class VolumeSmoother(StoredTrack):
     """``s = VolumeSmoother(coord, grid, cuboid_side, sigma=0.10, radius=None, floor=1e-3, max_bytes=None)``; ``s.push(volumes)`` per
     batch in frame order, ``s.finish()`` at the end of the track.  The parameters are ``VolumeFilter``'s and a bad one raises its
     ValueError here, before anything touches the device.  ``max_bytes``: the most the stored volumes and beliefs may take (2 x B x J x
@@ -35,24 +48,13 @@ class VolumeSmoother:
 
     def __init__(self, coord, grid, cuboid_side, sigma=0.10, radius=None, floor=1e-3, max_bytes=None):
         self.filter = VolumeFilter(coord, grid, cuboid_side, sigma=sigma, radius=radius, floor=floor)
-        if max_bytes is not None and (isinstance(max_bytes, bool) or not float(max_bytes) >= 0):
-            raise ValueError(f"max_bytes = {max_bytes} must be None or a number >= 0")
-        self.max_bytes = None if max_bytes is None else int(max_bytes)
-        # per push: (volumes copy, beliefs copy, restarted int32, given joints or None, filtered joints, event behind the copies).
-        # The filter's own event chain orders the steps only: a push's copies are queued behind the event its step recorded, so the
-        # next push on another stream is not ordered behind them and finish() waits for the event of every push.
-        self._pushes = []
-        self._done = None                # recorded behind the last finish(): the next one reuses its workspace
+        self._init_store(max_bytes)
         self._dev = {}
 
     # ------------------------------------------------------------------------------------------------------------------------
     @property
-    def frames_stored(self):
-        return sum(int(p[0].shape[0]) for p in self._pushes)
-
-    @property
     def bytes_stored(self):
-        return sum(2 * p[0].numel() * 4 for p in self._pushes)
+        return sum(2 * p.volumes.numel() * 4 for p in self._pushes)
 
     def reset(self):
         """Forget everything: the stored frames and the filter's prior.  Nothing is queued on the device."""
@@ -68,12 +70,7 @@ class VolumeSmoother:
         f = self.filter
         B, J = f._check_step(volumes, joints)
         _lib.require_hip(volumes, joints)
-        need = 2 * B * J * f.voxels * 4
-        if self.max_bytes is None:
-            self.max_bytes = int(torch.cuda.mem_get_info(volumes.device)[0]) // 2
-        if self.bytes_stored + need > self.max_bytes:
-            raise ValueError(f"push: {self.frames_stored} frames are stored ({self.bytes_stored} bytes) and {B} more need {need} bytes: "
-                             f"over max_bytes = {self.max_bytes}; finish() the track in pieces or raise max_bytes")
+        self._admit(B, 2 * B * J * f.voxels * 4, volumes.device)
         stream = stream if stream is not None else torch.cuda.current_stream(volumes.device)
         result = f.step(volumes, joints=joints, return_beliefs=True, stream=stream)
         with torch.cuda.stream(stream):
@@ -82,7 +79,7 @@ class VolumeSmoother:
                       result["restarted"].to(torch.int32), given, result["joints"].clone())
             event = torch.cuda.Event()
             event.record(stream)
-            self._pushes.append(copies + (event,))
+            self._pushes.append(_Push(*copies, event))
         return result
 
     def _workspace(self, dev, J):
@@ -107,32 +104,23 @@ class VolumeSmoother:
         written.  The storage is released once every launch is queued (an argument error leaves the stored track as it was); the
         filter keeps its state, so frames pushed afterwards continue the track for the filter but are smoothed as a piece of their
         own."""
-        if not self._pushes:
-            raise ValueError("finish: nothing is stored; push() the frames of the track first")
+        pushes, dev, J, stream = self._begin_finish(stream)
         f = self.filter
-        pushes = self._pushes
-        dev = pushes[0][0].device
-        J = int(pushes[0][0].shape[1])
-        stream = stream if stream is not None else torch.cuda.current_stream(dev)
-        for p in pushes:
-            stream.wait_event(p[5])
-        if self._done is not None:
-            stream.wait_event(self._done)
         fd = f._dev
         with torch.cuda.stream(stream):
             ws = self._workspace(dev, J)
-            T = sum(int(p[0].shape[0]) for p in pushes)
+            T = self.frames_stored
             joints = torch.empty((T, J, 3), device=dev, dtype=torch.float32)
             agreement = torch.empty((T, J), device=dev, dtype=torch.float32)
             smoothed = torch.empty((T, J), device=dev, dtype=torch.int32)
             t1 = T
             for i in range(len(pushes) - 1, -1, -1):
-                vol, bel, restarted = pushes[i][:3]
+                vol, bel, restarted = pushes[i].volumes, pushes[i].beliefs, pushes[i].restarted
                 for t in (vol, bel, restarted):
                     t.record_stream(stream)
                 B = int(vol.shape[0])
                 t0 = t1 - B
-                link = None if i == len(pushes) - 1 else (pushes[i + 1][2][0] == 0).to(torch.int32)
+                link = None if i == len(pushes) - 1 else (pushes[i + 1].restarted[0] == 0).to(torch.int32)
                 _lib.volume_smooth(vol, bel, restarted, fd["coord"], fd["taps"], ws["state"], bel if return_beliefs else None,
                                    joints[t0:t1], agreement[t0:t1], smoothed[t0:t1], B, J, f.voxels, f.grid, f.radius, f.floor,
                                    have_link=link, scratch=ws["scratch"])
@@ -140,15 +128,13 @@ class VolumeSmoother:
             self._done = torch.cuda.Event()
             self._done.record(stream)
             self._pushes = []
-            filtered = torch.cat([p[4] for p in pushes])
+            filtered = torch.cat([p.filtered for p in pushes])
             # where gamma_t is the copy of b_t the joint is the filter's own, bit for bit: the kernel's sum b c there is the same
             # expectation summed in another order ((sum a c) / Z in the filter)
             joints = torch.where((smoothed != 0).unsqueeze(-1), joints, filtered)
             result = {"joints": joints, "smoothed": smoothed != 0, "agreement": agreement, "filtered_joints": filtered,
                       "shift_filtered": (joints - filtered).norm(dim=-1)}
-            if any(p[3] is not None for p in pushes):
-                given = torch.cat([p[3] if p[3] is not None else torch.full_like(p[4], float("nan")) for p in pushes])
-                result["shift"] = (joints - given).norm(dim=-1)
+            self._add_shift(result, pushes)
             if return_beliefs:
-                result["beliefs"] = [p[1] for p in pushes]
+                result["beliefs"] = [p.beliefs for p in pushes]
         return result

@@ -23,19 +23,33 @@ slightly stronger than the true one throughout is followed in every frame (READM
 from __future__ import annotations
 
 import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from .volume_filter import VolumeFilter
+from .volume_filter import StoredTrack, VolumeFilter
 
 PATH_KEYS = ("joints", "index", "coord", "jumped", "segment_start", "log_score", "moved")
 PUSH_KEYS = ("peak_index", "best", "exponent", "restarted")
 MAX_REFINE = _lib.VITERBI_MAX_REFINE
 
 
-class VolumeViterbi:
+class _Push(NamedTuple):
+    """One stored push: its back-pointers [B,J,G^3] int32, the copy of its volumes (None with ``refine`` = 0), the forward pass's
+    ``peak``, ``best``, ``exponent`` and ``restarted`` [B,J], the joints given with it and the event behind it all."""
+    back: torch.Tensor
+    volumes: Optional[torch.Tensor]
+    peak: torch.Tensor
+    best: torch.Tensor
+    exponent: torch.Tensor
+    restarted: torch.Tensor
+    given: Optional[torch.Tensor]
+    event: torch.cuda.Event
+
+
+class VolumeViterbi(StoredTrack):
     """``v = VolumeViterbi(coord, grid, cuboid_side, sigma=0.10, radius=None, floor=1e-3, refine=1, max_bytes=None)``; ``v.push(volumes)``
     per batch in frame order, ``v.finish()`` at the end of the track.  ``sigma``, ``radius`` and ``floor`` are ``VolumeFilter``'s and a
     bad one raises its ValueError here, before anything touches the device.  ``refine``: the half-width in voxels (0..3) of the window
@@ -47,27 +61,18 @@ class VolumeViterbi:
         self.filter = VolumeFilter(coord, grid, cuboid_side, sigma=sigma, radius=radius, floor=floor)     # the parameters, checked
         if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= MAX_REFINE:
             raise ValueError(f"refine = {refine!r} (an integer in 0..{MAX_REFINE}) expected")
-        if max_bytes is not None and (isinstance(max_bytes, bool) or not float(max_bytes) >= 0):
-            raise ValueError(f"max_bytes = {max_bytes} must be None or a number >= 0")
+        self._init_store(max_bytes)
         self.refine = int(refine)
-        self.max_bytes = None if max_bytes is None else int(max_bytes)
         self.frames_seen = 0
         self.rows = None                 # the joints per frame, fixed by the first push
         self._has_prior = False
-        # per push: (back-pointers, volumes copy or None, peak, best, exponent, restarted, given joints or None, event behind it all)
-        self._pushes = []
         self._event = None               # recorded behind the last forward pass: the next one waits for it, whatever its stream
-        self._done = None                # recorded behind the last finish(): the next one reuses its cursor
         self._dev = {}
 
     # ------------------------------------------------------------------------------------------------------------------------
     @property
-    def frames_stored(self):
-        return sum(int(p[0].shape[0]) for p in self._pushes)
-
-    @property
     def bytes_stored(self):
-        return sum(p[0].numel() * 4 + (0 if p[1] is None else p[1].numel() * 4) for p in self._pushes)
+        return sum(p.back.numel() * 4 + (0 if p.volumes is None else p.volumes.numel() * 4) for p in self._pushes)
 
     @property
     def state(self):
@@ -83,6 +88,7 @@ class VolumeViterbi:
         self.frames_seen = 0
 
     def _device_state(self, dev, J):
+        """The recursion's own state on ``dev``; ``coord``, ``taps`` and the row of ones are the filter's (``_device_constants``)."""
         f = self.filter
         key = str(dev)
         if self._dev.get("key") != key:
@@ -90,14 +96,11 @@ class VolumeViterbi:
                 raise ValueError(f"push: the state is on {self._dev['key']}, the volumes on {key}")
             self._dev = {
                 "key": key,
-                "coord": f._coord_src.to(device=dev, dtype=torch.float32).contiguous(),
-                "taps": torch.from_numpy(f.taps).to(dev),
                 "state": torch.empty((J, f.voxels), device=dev, dtype=torch.float32),
                 "peak": torch.full((J,), -1, device=dev, dtype=torch.int32),
                 "best": torch.full((J,), float("nan"), device=dev, dtype=torch.float32),
                 "cursor": torch.full((J,), -1, device=dev, dtype=torch.int32),
                 "scratch": torch.empty(_lib.volume_viterbi_scratch_bytes(J, f.grid, f.radius), device=dev, dtype=torch.uint8),
-                "ones": torch.ones(J, device=dev, dtype=torch.int32),
             }
         return self._dev
 
@@ -116,33 +119,29 @@ class VolumeViterbi:
             raise ValueError(f"push: {J} joints per frame, the state holds {self.rows}")
         _lib.require_hip(volumes, joints)
         dev = volumes.device
-        need = (2 if self.refine > 0 else 1) * B * J * f.voxels * 4
-        if self.max_bytes is None:
-            self.max_bytes = int(torch.cuda.mem_get_info(dev)[0]) // 2
-        if self.bytes_stored + need > self.max_bytes:
-            raise ValueError(f"push: {self.frames_stored} frames are stored ({self.bytes_stored} bytes) and {B} more need {need} bytes: "
-                             f"over max_bytes = {self.max_bytes}; finish() the track in pieces or raise max_bytes")
+        self._admit(B, (2 if self.refine > 0 else 1) * B * J * f.voxels * 4, dev)
         self.rows = J
         stream = stream if stream is not None else torch.cuda.current_stream(dev)
         if self._event is not None:
             stream.wait_event(self._event)
         with torch.cuda.stream(stream):
             d = self._device_state(dev, J)
+            c = f._device_constants(dev, J)
             vol = volumes.contiguous()
             back = torch.empty((B, J, f.voxels), device=dev, dtype=torch.int32)
             peak = torch.empty((B, J), device=dev, dtype=torch.int32)
             best = torch.empty((B, J), device=dev, dtype=torch.float32)
             exponent = torch.empty((B, J), device=dev, dtype=torch.int32)
             restarted = torch.empty((B, J), device=dev, dtype=torch.int32)
-            _lib.volume_viterbi(vol, d["taps"], d["state"], d["peak"], d["best"], back, peak, best, exponent, restarted, B, J, f.voxels,
-                                f.grid, f.radius, f.floor, have_prior=d["ones"] if self._has_prior else None, scratch=d["scratch"])
+            _lib.volume_viterbi(vol, c["taps"], d["state"], d["peak"], d["best"], back, peak, best, exponent, restarted, B, J, f.voxels,
+                                f.grid, f.radius, f.floor, have_prior=c["ones"] if self._has_prior else None, scratch=d["scratch"])
             self._event = torch.cuda.Event()
             self._event.record(stream)
             given = None if joints is None else joints.to(device=dev, dtype=torch.float32).clone()
             copy = volumes.clone(memory_format=torch.contiguous_format) if self.refine > 0 else None
             event = torch.cuda.Event()
             event.record(stream)
-            self._pushes.append((back, copy, peak, best, exponent, restarted, given, event))
+            self._pushes.append(_Push(back, copy, peak, best, exponent, restarted, given, event))
         self._has_prior = True
         self.frames_seen += B
         return {"peak_index": peak, "best": best, "exponent": exponent, "restarted": restarted != 0}
@@ -161,26 +160,17 @@ class VolumeViterbi:
         when joints were pushed (metres from those; NaN for a push without).  The host waits for ``stream`` (the log scores are
         summed there).  The storage is released; the scores keep their state, so frames pushed afterwards continue the recursion but
         are walked as a piece of their own."""
-        if not self._pushes:
-            raise ValueError("finish: nothing is stored; push() the frames of the track first")
+        pushes, dev, J, stream = self._begin_finish(stream)
         f = self.filter
-        pushes = self._pushes
-        dev = pushes[0][0].device
-        J = int(pushes[0][0].shape[1])
-        stream = stream if stream is not None else torch.cuda.current_stream(dev)
-        for p in pushes:
-            stream.wait_event(p[7])
-        if self._done is not None:
-            stream.wait_event(self._done)
-        d = self._dev
+        d, coord_dev = self._dev, f._dev["coord"]
         with torch.cuda.stream(stream):
-            T = sum(int(p[0].shape[0]) for p in pushes)
+            T = self.frames_stored
             joints = torch.empty((T, J, 3), device=dev, dtype=torch.float32)
             index = torch.empty((T, J), device=dev, dtype=torch.int32)
             jumped = torch.empty((T, J), device=dev, dtype=torch.int32)
             t1 = T
             for i in range(len(pushes) - 1, -1, -1):
-                back, vol, peak, _, _, restarted = pushes[i][:6]
+                back, vol, peak, restarted = pushes[i].back, pushes[i].volumes, pushes[i].peak, pushes[i].restarted
                 for t in (back, vol, peak, restarted):
                     if t is not None:
                         t.record_stream(stream)
@@ -188,26 +178,23 @@ class VolumeViterbi:
                 t0 = t1 - B
                 _lib.volume_viterbi_path(back, peak, restarted, d["cursor"], index[t0:t1], jumped[t0:t1], B, J, f.voxels,
                                          have_next=int(i != len(pushes) - 1))
-                _lib.volume_viterbi_refine(vol, d["coord"], index[t0:t1], joints[t0:t1], B, J, f.voxels, f.grid, self.refine)
+                _lib.volume_viterbi_refine(vol, coord_dev, index[t0:t1], joints[t0:t1], B, J, f.voxels, f.grid, self.refine)
                 t1 = t0
             self._done = torch.cuda.Event()
             self._done.record(stream)
             self._pushes = []
-            restarted = torch.cat([p[5] for p in pushes]) != 0
+            restarted = torch.cat([p.restarted for p in pushes]) != 0
             nan = torch.full((), float("nan"), device=dev, dtype=torch.float32)
             on_path = (index >= 0).unsqueeze(-1)
-            coord = torch.where(on_path, d["coord"][index.clamp(min=0).long()], nan)
+            coord = torch.where(on_path, coord_dev[index.clamp(min=0).long()], nan)
             moved = torch.full((T, J), float("nan"), device=dev, dtype=torch.float32)
             moved[1:] = (coord[1:] - coord[:-1]).norm(dim=-1)
-            best = torch.cat([p[3] for p in pushes]).cpu().numpy().astype(np.float64)
-            exponent = torch.cat([p[4] for p in pushes]).cpu().numpy().astype(np.float64)
+            best = torch.cat([p.best for p in pushes]).cpu().numpy().astype(np.float64)
+            exponent = torch.cat([p.exponent for p in pushes]).cpu().numpy().astype(np.float64)
             log_score = torch.from_numpy(segment_log_scores(best, exponent, restarted.cpu().numpy())).to(dev)
             result = {"joints": joints, "index": index, "coord": coord, "jumped": jumped != 0, "segment_start": restarted,
                       "log_score": log_score, "moved": moved}
-            if any(p[6] is not None for p in pushes):
-                given = torch.cat([p[6] if p[6] is not None else torch.full((int(p[0].shape[0]), J, 3), float("nan"), device=dev)
-                                   for p in pushes])
-                result["shift"] = (joints - given).norm(dim=-1)
+            self._add_shift(result, pushes)
         return result
 
 

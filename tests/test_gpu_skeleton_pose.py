@@ -276,8 +276,10 @@ def test_bad_arguments_raise_and_do_not_launch():
             call(**kw)
     a = prob[0, :2].contiguous()
     tr, out = torch.ones(2, device=DEV, dtype=torch.int32), torch.full((2, N), -7.0, device=DEV)
+    both = torch.empty((3, N), device=DEV)
     for kw in ({"radius": 25}, {"radius": G}, {"grid": G + 1}, {"rows": 3}, {"rows": 0}, {"out": a}, {"tap_row": tr.float()},
-               {"taps": k["taps_dev"].reshape(-1)}, {"scratch": torch.empty(16, device=DEV, dtype=torch.uint8)}):
+               {"a": both[:2], "out": both[1:]}, {"taps": k["taps_dev"].reshape(-1)},
+               {"scratch": torch.empty(16, device=DEV, dtype=torch.uint8)}):
         b = {"a": a, "taps": k["taps_dev"], "tap_row": tr, "out": out, "rows": 2, "grid": G, "radius": R}
         b.update(kw)
         with pytest.raises(_lib.HipExtensionError):

@@ -350,11 +350,13 @@ def test_bad_arguments_raise_and_do_not_launch():
     call()
     bad_tree = list(TREE)
     bad_tree[5] = 5
+    both = torch.empty((3, J, N), device=DEV)
     for kw in ({"radius": 25}, {"radius": -1}, {"radius": G}, {"floor": -0.1}, {"floor": 1.1}, {"floor": float("nan")}, {"frames": 0},
                {"frames": 3}, {"grid": G + 1}, {"voxels": N + 1}, {"grid": 1, "voxels": 1, "radius": 0}, {"parents": bad_tree},
                {"parents": [1] + list(TREE[1:])}, {"parents": list(TREE) + [3]}, {"parents": [0] * 33}, {"parents": []}, {"parents": None},
                {"prob": prob.cpu()}, {"prob": prob.double()}, {"prob": prob[:, :, ::2]}, {"taps": k["taps_dev"][:-1]},
                {"taps": k["taps"]}, {"beliefs": prob}, {"beliefs": torch.empty((1, J, N), device=DEV)},
+               {"prob": both[:2], "beliefs": both[1:]},
                {"coupled": torch.empty((2,), device=DEV)}, {"joints": torch.empty((2, J, 2), device=DEV)},
                {"evidence": torch.empty((2, J + 1), device=DEV)}, {"scratch": torch.empty(16, device=DEV, dtype=torch.uint8)},
                {"coord": k["coord"][:-1]}):
@@ -364,7 +366,7 @@ def test_bad_arguments_raise_and_do_not_launch():
     tr, s, out = torch.zeros(2, device=DEV, dtype=torch.int32), torch.ones(2, device=DEV), torch.empty((2, N), device=DEV)
     _lib.shell_correlate(a, k["taps_dev"], tr, s, out, 2, G, R)
     for kw in ({"radius": 25}, {"radius": G}, {"grid": G + 1}, {"rows": 3}, {"rows": 0}, {"out": a}, {"tap_row": tr.float()},
-               {"s": s[:1]}, {"taps": k["taps_dev"].reshape(-1)}, {"scratch": torch.empty(16, device=DEV, dtype=torch.uint8)}):
+               {"a": both[0, :2], "out": both[0, 1:3]}, {"s": s[:1]}, {"taps": k["taps_dev"].reshape(-1)}, {"scratch": torch.empty(16, device=DEV, dtype=torch.uint8)}):
         b = {"a": a, "taps": k["taps_dev"], "tap_row": tr, "s": s, "out": out, "rows": 2, "grid": G, "radius": R}
         b.update(kw)
         with pytest.raises(_lib.HipExtensionError):

@@ -281,10 +281,12 @@ def test_bad_arguments_raise_and_do_not_launch():
         return _lib.volume_filter(**a)
 
     call()
+    both = torch.empty((3, rows, N), device=DEV)
     for kw in ({"radius": 17}, {"radius": -1}, {"radius": G}, {"floor": -0.1}, {"floor": 1.1}, {"floor": float("nan")}, {"frames": 0},
                {"frames": 3}, {"rows": 0}, {"grid": G + 1}, {"voxels": N + 1}, {"grid": 1, "voxels": 1, "radius": 0},
                {"prob": prob.cpu()}, {"prob": prob.double()}, {"prob": prob[:, :, ::2]}, {"taps": k["taps_dev"][:-1]},
                {"taps": k["taps"]}, {"state": torch.zeros((rows, N - 1), device=DEV)}, {"belief_out": prob},
+               {"prob": both[:2], "belief_out": both[1:]}, {"state": both[0], "belief_out": both[:2]},
                {"belief_out": torch.empty((1, rows, N), device=DEV)}, {"restarted": torch.empty((2, rows), device=DEV)},
                {"have_prior": torch.ones(rows, device=DEV)}, {"have_prior": torch.ones(rows + 1, device=DEV, dtype=torch.int32)},
                {"scratch": torch.empty(16, device=DEV, dtype=torch.uint8)}, {"coord": k["coord"][:-1]}):
