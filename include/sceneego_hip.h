@@ -725,6 +725,39 @@ int se_volume_smooth_f32(const float* prob, const float* belief, const int* rest
                          const int* have_link, void* stream);
 long long se_volume_smooth_scratch_bytes(int rows, int G, int radius);
 
+/* Transition statistics of the filter's motion model: the E-step sums of a Baum-Welch fit of (sigma, floor) to a sequence
+ * (sceneego_amd/motion_fit.py: MotionModelFit; VoxelNetwork_depth.motion_fit returns one).  The transition (1 - floor) W_sigma +
+ * floor / N is a two-component mixture whose Gaussian part is an exponential family in |d|^2, so the fit needs, per linked pair of
+ * frames, the posterior mass of a step, of a jump and the posterior expected squared step.  This call is se_volume_smooth_f32's backward
+ * walk with those sums in place of gamma; tests/motion_fit_model.py restates the definition in float64.
+ *   prob, belief, restarted, taps, state, have_link, G, radius, floor, rows, frames: as for se_volume_smooth_f32, with the same link rule
+ *   and the same order of the frames (last to first; a sequence by calls over consecutive chunks in reverse order).
+ * With w' the taps reversed, m'[d] = (float)(d d) w'[d] (d = -radius..radius; one float32 rounding) and blur3(x; wk, wj, wi) the
+ * zero-padded separable correlation along k, then j, then i with a tap vector per axis (blur3T(x) = blur3(x; w', w', w')):
+ * LINKED     q0 = blur3(r_{t+1}; w', w', w')
+ *            q2 = blur3(r_{t+1}; m', w', w') + blur3(r_{t+1}; w', m', w') + blur3(r_{t+1}; w', w', m')    the squared step, in voxels^2
+ *            u = (1 - floor) q0 + floor / voxels,  a = p_t u,  s = sum a,  r_t = a / s;  where s is not a finite number > 0: r_t = p_t
+ *            stats = { S = sum b_t u,  s,  A0 = sum b_t q0,  A2 = sum b_t q2,  Bsum = sum b_t,  Rsum = sum r_{t+1} }
+ * NO LINK    r_t = p_t, copied bit for bit; the six stats are NaN.
+ *   stats      [frames][rows][6] float32, in the order above.  With keep = 1 - floor and uniform = floor / voxels (float32, as the
+ *              kernel forms them) the posterior of the pair (t, t + 1) holds step = keep A0 / S, jump = uniform Bsum Rsum / S
+ *              (step + jump = 1 up to rounding) and sq = keep A2 / S, the expected squared step over the step component, in voxels^2.
+ *              Bsum and Rsum are given so that the jump mass can be formed directly: at a small floor S - keep A0 cancels.
+ *   linked     [frames][rows] int32: 1 where the frame was linked
+ *   scratch    se_volume_transition_stats_scratch_bytes(rows, G, radius) bytes of workspace, 4-byte aligned (16-byte for the fast
+ *              finish pass); 0 for a shape out of range.  rows (2 G^3 + 8 G) floats and a few hundred bytes.
+ * q0 and u are formed exactly as se_volume_smooth_f32 forms them: `state` after the call and S equal that call's `state` and
+ * `agreement` on the same inputs, bit for bit.  One launch per call (w' and m') and three per frame on `stream` (one for a frame in
+ * which no row can be linked).  No atomics; every sum is taken in the filter's fixed order, at most 80 sequential float32 additions on
+ * the longest path: bitwise identical from run to run and independent of how the frames are cut into calls.  Allocates nothing.
+ * SE_ERR_BAD_ARG, with nothing launched: a null pointer other than have_link, a pointer that is not 4-byte aligned, frames < 1, rows
+ * outside 1..65535, G outside 2..128, voxels != G^3, radius outside 0..min(16, G - 1), floor outside [0, 1] or NaN, scratch_bytes
+ * below se_volume_transition_stats_scratch_bytes(rows, G, radius).                                                                  */
+int se_volume_transition_stats_f32(const float* prob, const float* belief, const int* restarted, const float* taps, float* state,
+                                   float* stats, int* linked, void* scratch, long long scratch_bytes, int frames, int rows,
+                                   int voxels, int G, int radius, float floor, const int* have_link, void* stream);
+long long se_volume_transition_stats_scratch_bytes(int rows, int G, int radius);
+
 /* Most probable joint trajectory: the max-product (Viterbi) pass that goes with se_volume_filter_f32 and se_volume_smooth_f32
  * (sceneego_amd/volume_viterbi.py: VolumeViterbi; VoxelNetwork_depth.volume_path returns one).  The filter and the smoother give per
  * frame the marginal of each joint; this gives the single most probable trajectory of each joint through the grid.

@@ -14,6 +14,7 @@
                            [--skeleton_output out/skeleton.pkl [--skeleton_info_output out/skeleton_info.pkl] [--bone_lengths FILE.npy]
                             [--bone_frames 64] [--skeleton_tau 0.03] [--skeleton_floor 1e-3]] [--render_volumes coupled]
                            [--map_output out/map.pkl [--map_info_output out/map_info.pkl] [--map_refine 1]]
+                           [--fit_frames 64 [--fit_iterations 8] [--fit_output out/fit.json]]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -77,6 +78,12 @@ back-pointers and, with ``--path_refine`` > 0 (default 1), the volumes stay on t
 ``--path_max_gb``) and a walk back at the end of the sequence picks the path.  ``--path_info_output`` adds the per-frame dicts (joints,
 index, coord, jumped, segment_start, log_score, moved, shift).  With ``--skeleton_output`` it runs on the coupled beliefs.  It prints
 its MPJPE beside the others; ``evaluate.py --pred_dir path.pkl`` reads the file like ``--output``.
+``--fit_frames F`` fits the motion model of those three to the sequence before the main pass (``VoxelNetwork_depth.motion_fit``,
+``sceneego_amd/motion_fit.py``: at most ``--fit_iterations`` EM iterations for sigma and floor over the raw volumes of the first F
+consecutive frames, from ``--filter_sigma`` / ``--filter_floor`` at the fixed ``--filter_radius``), prints the start and end values
+with their log-likelihoods, writes the whole result to ``--fit_output`` (JSON) and runs ``--filter_output``, ``--smooth_output`` and
+``--path_output`` on the fitted values; their per-frame info dicts then carry ``sigma``, ``floor`` and ``radius``.  It is a
+maximum-likelihood fit to the network's own volumes read as likelihoods, on this one sequence: not a validation against ground truth.
 """
 import argparse
 import json
@@ -253,6 +260,24 @@ class SequenceRunner:
             from sceneego_amd.jpeg_encode import JpegEncoder
             self.encoder = JpegEncoder(self.device)
         return self.encoder
+
+    @torch.no_grad()
+    def fit_motion(self, images, depths, batch_size, model, iterations=8, max_bytes=None):
+        """The first pass of ``--fit_frames``: the forward over the consecutive frames ``images`` / ``depths`` in batches, their raw
+        volumes pushed into ``VoxelNetwork_depth.motion_fit(**model)`` (``model``: a dict of ``sigma`` / ``radius`` / ``floor``, the
+        values the fit starts from) and the dict of its ``fit(iterations=iterations)``."""
+        from sceneego_amd.jpeg_device import JpegFile
+        from sceneego_amd.preprocess import load_image_bgr
+        load = JpegFile if self.image_decode == "device" else load_image_bgr
+        fit = self.net.motion_fit(**model, max_bytes=max_bytes)
+        for i in range(0, len(images), batch_size):
+            img = self._images([load(p) for p in images[i:i + batch_size]])
+            depth = self._depths(depths[i:i + batch_size])
+            _, _, vol, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
+            fit.push(vol)                                     # a copy: the next forward overwrites the volumes
+        result = fit.fit(iterations=iterations)
+        fit.reset()
+        return result
 
     @torch.no_grad()
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
@@ -490,6 +515,13 @@ def build_parser():
     ap.add_argument("--filter_radius", type=int, default=None, help="voxels the Gaussian step is truncated at, 0..16 "
                     "(default: min(16, G - 1, ceil(3 sigma / voxel edge)))")
     ap.add_argument("--filter_floor", type=float, default=1e-3, help="the filter's uniform floor in [0, 1]: the chance of a jump")
+    ap.add_argument("--fit_frames", type=int, default=None, help="fit --filter_sigma and --filter_floor to the volumes of the first F "
+                    "consecutive frames before the main pass (sceneego_amd/motion_fit.py: EM at the fixed --filter_radius; a fit to the "
+                    "network's own volumes, not a validation against ground truth); --filter_output, --smooth_output and --path_output "
+                    "then run on the fitted values")
+    ap.add_argument("--fit_iterations", type=int, default=None, help="with --fit_frames: at most this many EM iterations (default 8)")
+    ap.add_argument("--fit_output", default=None, help="with --fit_frames: JSON file of the fit (sigma, floor, radius, log_likelihood, "
+                    "history, mean_sq_step, pairs, converged, saturated, truncation_binding, sigma_per_joint, floor_per_joint)")
     ap.add_argument("--smooth_output", default=None, help="pickle in the format of --output holding the joints of the forward-backward "
                     "smoother over the sequence's volumes (sceneego_amd/volume_smoother.py; --filter_sigma, --filter_radius, "
                     "--filter_floor: the filter's convention, not calibrated); implies the filter")
@@ -582,6 +614,15 @@ def parse_args(argv=None):
                      "max_bytes": None if args.path_max_gb is None else int(args.path_max_gb * 2 ** 30)}
     elif args.path_max_gb is not None or args.path_refine is not None:
         raise SystemExit("--path_max_gb and --path_refine need --path_output")
+    args.fit = None
+    if args.fit_frames is not None:
+        if args.fit_frames < 2:
+            raise SystemExit("--fit_frames must be >= 2: the fit needs a pair of consecutive frames")
+        if args.fit_iterations is not None and args.fit_iterations < 1:
+            raise SystemExit("--fit_iterations must be >= 1")
+        args.fit = {"frames": args.fit_frames, "iterations": 8 if args.fit_iterations is None else args.fit_iterations}
+    elif args.fit_iterations is not None or args.fit_output is not None:
+        raise SystemExit("--fit_iterations and --fit_output need --fit_frames")
     if not (args.skeleton_tau > 0 and args.skeleton_tau != float("inf")):
         raise SystemExit("--skeleton_tau must be a finite number > 0")
     if not 0.0 <= args.skeleton_floor <= 1.0:
@@ -635,6 +676,29 @@ def main(argv=None):
         if args.map:
             map_pose = {"bone_lengths": lengths, "tau": args.skeleton_tau, "floor": args.skeleton_floor,
                         "refine": 1 if args.map_refine is None else args.map_refine}
+    fitted = None
+    if args.fit is not None:
+        # a first pass over the first --fit_frames consecutive frames: EM for sigma and floor at the fixed radius
+        from sceneego_amd.op import motion_fit_to_json
+        n = min(args.fit["frames"], len(images))
+        if n < 2:
+            raise SystemExit("--fit_frames: the sequence has fewer than 2 frames")
+        start = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor}
+        fit = runner.fit_motion(images[:n], depths[:n], config.test.batch_size, start, iterations=args.fit["iterations"])
+        fitted = {"sigma": float(fit["sigma"]), "radius": int(fit["radius"]), "floor": float(fit["floor"])}
+        print("motion model fitted to {} frames ({} pairs, {} iterations; a fit to the volumes, not calibrated against ground truth): "
+              "sigma {:.4f} -> {:.4f} m, floor {:.3g} -> {:.3g}, radius {}, log-likelihood {:.6g} -> {:.6g}{}{}".format(
+                  n, fit["pairs"], len(fit["log_likelihood"]) - 1, args.filter_sigma, fitted["sigma"], args.filter_floor,
+                  fitted["floor"], fitted["radius"], fit["log_likelihood"][0], fit["log_likelihood"][-1],
+                  ", sigma saturated" if fit["saturated"] else "",
+                  ", the radius cuts the step: refit with a larger --filter_radius" if fit["truncation_binding"] else ""))
+        if args.fit_output is not None:
+            os.makedirs(os.path.dirname(os.path.abspath(args.fit_output)), exist_ok=True)
+            with open(args.fit_output, "w") as f:
+                json.dump(motion_fit_to_json(fit, frames=n, start=start), f, indent=1)
+        for model in (args.filter, args.path):
+            if model is not None:
+                model.update(fitted)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     want_stats = args.stats_output is not None
@@ -662,6 +726,10 @@ def main(argv=None):
         frame_smooth = extra.pop(0) if args.smooth is not None else None
         frame_path = extra.pop(0) if args.path is not None else None
         frame_map = extra.pop(0) if map_pose is not None else None
+        if fitted is not None:                                # the info pickles record the fitted values the operators ran on
+            for frames in (frame_filter, frame_smooth, frame_path):
+                for fr in frames or ():
+                    fr.update(fitted)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -675,6 +743,8 @@ def main(argv=None):
         with open(args.output, "wb") as f:
             pickle.dump(preds, f)
     result = {"frames": len(preds), "mpjpe": mpjpe, "pa_mpjpe": pampjpe, "fps": len(preds) / dt, "predictions": preds}
+    if fitted is not None:
+        result["fit"] = fit
     if want_stats:
         os.makedirs(os.path.dirname(os.path.abspath(args.stats_output)), exist_ok=True)
         with open(args.stats_output, "wb") as f:

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -115,6 +115,8 @@ SIGNATURES = {
     "se_volume_filter_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "se_volume_smooth_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_volume_smooth_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "se_volume_transition_stats_scratch_bytes": (_ll, [_i, _i, _i]),
+    "se_volume_transition_stats_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "se_volume_viterbi_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_volume_viterbi_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "se_volume_viterbi_path_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -1260,6 +1262,43 @@ def volume_smooth(prob, belief, restarted, coord, taps, state, smoothed_out, joi
                                        scratch.numel(), frames, rows, voxels, grid, radius, floor, _ptr(have_link), _stream()),
            "se_volume_smooth_f32")
     return joints, agreement, smoothed
+
+
+# The E-step sums of a fit of the filter's motion model (csrc/volume_filter.hip: se_volume_transition_stats_f32;
+# sceneego_amd/motion_fit.py drives it)
+STATS_CHAIN = 80           # sequential float32 additions on the longest path of each of the six sums: the filter's fold (L)
+STATS_SLOTS = 6            # S, s, A0, A2, Bsum, Rsum
+
+
+def volume_transition_stats_scratch_bytes(rows, grid, radius) -> int:
+    return int(load().se_volume_transition_stats_scratch_bytes(int(rows), int(grid), int(radius)))
+
+
+def volume_transition_stats(prob, belief, restarted, taps, state, stats, linked, frames, rows, voxels, grid, radius, floor,
+                            have_link=None, scratch=None):
+    """se_volume_transition_stats_f32: the smoother's backward walk over ``frames`` consecutive frames, last to first, on the volumes
+    ``prob`` and the filtered beliefs ``belief`` [frames, rows, voxels] with the filter's ``restarted`` [frames, rows] int32, writing
+    per frame and row the six sums ``stats`` [frames, rows, 6] float32 (S, s, A0, A2, Bsum, Rsum: the header states the definition;
+    NaN where the frame is not linked) and ``linked`` [frames, rows] int32.  ``state`` [rows, voxels] carries the backward belief from
+    call to call and is updated in place; ``have_link`` None (the call ends the track) or int32 [rows].  ``taps``: the filter's, on
+    the device.  ``scratch``: an optional uint8 workspace of at least ``volume_transition_stats_scratch_bytes(rows, grid, radius)``
+    bytes.  Every argument is checked here and a bad one raises HipExtensionError before anything is launched: the kernels trust
+    the sizes they are given."""
+    what = "volume_transition_stats"
+    frames, rows, voxels, grid, radius, floor = _grid_args(what, frames, rows, voxels, grid, radius, floor)
+    total = frames * rows * voxels
+    dev = _check_args(what, (("prob", prob, torch.float32, total), ("belief", belief, torch.float32, total),
+                             ("restarted", restarted, torch.int32, frames * rows), ("taps", taps, torch.float32, 2 * radius + 1),
+                             ("state", state, torch.float32, rows * voxels), ("stats", stats, torch.float32, frames * rows * STATS_SLOTS),
+                             ("linked", linked, torch.int32, frames * rows)),
+                      (("have_link", have_link, torch.int32, rows), ("scratch", scratch, torch.uint8, None)))
+    if _overlap(state, prob) or _overlap(state, belief):
+        raise HipExtensionError(f"{what}: state must not alias prob or belief")
+    scratch = _grid_scratch(what, scratch, volume_transition_stats_scratch_bytes(rows, grid, radius), rows, grid, radius, dev)
+    _check(load().se_volume_transition_stats_f32(_ptr(prob), _ptr(belief), _ptr(restarted), _ptr(taps), _ptr(state), _ptr(stats),
+                                                 _ptr(linked), _ptr(scratch), scratch.numel(), frames, rows, voxels, grid, radius,
+                                                 floor, _ptr(have_link), _stream()), "se_volume_transition_stats_f32")
+    return stats, linked
 
 
 # The max-product pass on the filter's model (csrc/volume_viterbi.hip; sceneego_amd/volume_viterbi.py drives it)

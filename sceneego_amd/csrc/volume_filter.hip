@@ -50,6 +50,31 @@
 // working set of r, q, p, b (and g): 63 MB (79 MB) at 64^3 and 15 rows, 126 MB (173 MB) moved per frame.
 // SUMMATION ORDER: that of the filter, for s, S and the joint sums alike: L = 80 (SE_VS_CHAIN).  A frame sees only `state`, its link
 // flags and its own p and b, so the results do not depend on how the frames are cut into calls.
+//
+// THE TRANSITION STATISTICS (se_volume_transition_stats_f32; sceneego_amd/motion_fit.py: MotionModelFit; tests/motion_fit_model.py) are
+// the smoother's backward walk with the E-step sums of a Baum-Welch fit of (sigma, floor) in place of gamma.  With w' the reversed taps,
+// m'[d] = (float)(d d) w'[d] and blur3(x; wk, wj, wi) the blur with a tap vector per axis, for a linked frame t:
+//     q0 = blur3(r_{t+1}; w', w', w')
+//     q2 = blur3(r_{t+1}; m', w', w') + blur3(r_{t+1}; w', m', w') + blur3(r_{t+1}; w', w', m')       the squared step, voxels^2
+//     u = (1 - floor) q0 + floor / N,  a = p_t u,  s = sum a,  r_t = a / s       the smoother's, bit for bit
+//     stats = { S = sum b_t u,  s,  A0 = sum b_t q0,  A2 = sum b_t q2,  Bsum = sum b_t,  Rsum = sum r_{t+1} }
+// Three launches per frame, after one per call (ts_prep_kernel: w' and m' into the scratch):
+//   ts_blur_kj_kernel   grid (G, rows), block 256: vf_blur_kj_kernel with two outputs per i-plane, P0 = blur_j(w') blur_k(w') r (the
+//                       smoother's q) and P1 = blur_j(w') blur_k(m') r + blur_j(m') blur_k(w') r.  The staged plane and the two k-blurred
+//                       planes are 3 G^2 floats: 48 KB at 64^3.  Above G = 116 that passes the 160 KB of a CU, and the k-blurred planes
+//                       are formed for one half of the columns at a time ((G + 2 ceil(G / 2)) G floats: 128 KB at 128^3); a column's
+//                       values do not depend on the split.  The plane's sum (Rsum) goes to slot 5 of record i of the row.
+//   ts_update_kernel    grid (G, rows), block 256: the slabs of P0 and P1 at one j staged in LDS (2 G^2 floats), q0 = blur_i(w') P0 and
+//                       q2 = blur_i(m') P0 + blur_i(w') P1, then the floor and the products; a overwrites P0 in place; the record
+//                       holds s, S, A0, A2, Bsum in slots 0..4 (record j of the row; slot 5 is the blur pass's).
+//   ts_finish_kernel    folds the records, decides the fallback, writes r_t to `state`; chunk 0 also writes the six stats (NaN for an
+//                       unlinked row), `linked` and the link flags of the frame processed next.
+// An unlinked row is skipped by the first two launches and copied (r_t = p_t) by the third.
+// BYTE MODEL per frame, row and voxel: blur_kj reads r and writes P0 and P1 (12 B); update reads P0, P1, p and b and writes a (20 B);
+// finish reads a and writes r (8 B): 40 B, the smoother's 32 B plus P1 written and read, over a working set of r, P0, P1, p, b: 79 MB at
+// 64^3 and 15 rows, 157 MB moved per frame.
+// SUMMATION ORDER: that of the filter for all six sums: L = 80 (SE_TS_CHAIN).  s and S are the sums of the same values in the same
+// order as the smoother's, so `state` and S equal the smoother's `state` and `agreement` bit for bit.
 #include <float.h>
 
 #include "row_reduce.h"
@@ -58,6 +83,9 @@
 #define SE_VF_PART 8              // Z, sum a c (x y z), sum p c (x y z), pad
 #define SE_VF_CHAIN 80            // L of the header comment
 #define SE_VS_CHAIN 80            // the smoother's: the same fold over the same records
+#define SE_TS_CHAIN 80            // the transition statistics': likewise
+#define SE_TS_STATS 6             // S, s, A0, A2, Bsum, Rsum
+#define SE_TS_LDS_MAX (160 * 1024 - 1024)   // the most dynamic LDS of a workgroup: a CU's 160 KB less 1 KB for the static arrays (392 B)
 
 namespace {
 
@@ -411,6 +439,231 @@ extern "C" int se_volume_smooth_f32(const float* prob, const float* belief, cons
         const int* rs = restarted + (size_t)f * rows;
         hipLaunchKernelGGL(finish, dim3(chunks, rows), dim3(SE_VG_THREADS), 0, s, p, b, q, g, part, link, rs, link_next, state, so,
                            joints + (size_t)f * rows * 3, agreement + (size_t)f * rows, smoothed + (size_t)f * rows, G, voxels);
+        SE_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+namespace {
+
+// one workgroup: the taps reversed (w') and m'[d] = (float)(d d) w'[d]
+__global__ void ts_prep_kernel(const float* __restrict__ taps, float* __restrict__ rev, float* __restrict__ msq, int R) {
+    const int t = threadIdx.x;
+    if (t <= 2 * R) {
+        const float w = taps[2 * R - t];
+        rev[t] = w;
+        msq[t] = (float)((t - R) * (t - R)) * w;
+    }
+}
+
+// grid (G, rows), block 256, dynamic LDS (G + 2 KW) G floats; KW = G, or ceil(G / 2) where three whole planes do not fit.  `rev`, `msq`:
+// what ts_prep_kernel wrote.  `link`: the frame's link flags.
+__global__ __launch_bounds__(SE_VG_THREADS) void ts_blur_kj_kernel(const float* __restrict__ state, const float* __restrict__ rev,
+                                                                   const float* __restrict__ msq, const int* __restrict__ link,
+                                                                   float* __restrict__ P0, float* __restrict__ P1,
+                                                                   float* __restrict__ part, int G, int voxels, int R, int wshift,
+                                                                   int KW) {
+    extern __shared__ __align__(16) float lds[];
+    __shared__ float w[2 * SE_VG_MAX_R + 1];
+    __shared__ float m[2 * SE_VG_MAX_R + 1];
+    __shared__ float sm[4][SE_VF_PART];
+    const int t = threadIdx.x, i = blockIdx.x, row = blockIdx.y;
+    if (!vf_has_prior(link, 0, row)) return;                        // uniform: the row is copied, nothing of it is read
+    const int GG = G * G;
+    float* A = lds;
+    float* B0 = lds + GG;                                           // blur_k(w') A, [G j][KW k]
+    float* B1 = B0 + G * KW;                                        // blur_k(m') A
+    const size_t base = (size_t)row * voxels + (size_t)i * GG;
+    for (int e = t; e < GG; e += SE_VG_THREADS) A[e] = state[base + e];
+    if (t <= 2 * R) { w[t] = rev[t]; m[t] = msq[t]; }
+    __syncthreads();
+    const int k = t & ((1 << wshift) - 1), jr = t >> wshift, RP = SE_VG_THREADS >> wshift;
+    float rs[1] = {0.f};                                            // Rsum: this plane's share
+    if (k < G)
+        for (int j = jr; j < G; j += RP) rs[0] += A[j * G + k];
+    for (int k0 = 0; k0 < G; k0 += KW) {                            // one pass, or two over halves of the columns
+        const bool mine = k >= k0 && k < min(G, k0 + KW);
+        if (mine) {
+            const int lo = max(-R, -k), hi = min(R, G - 1 - k);     // the taps that stay inside the row
+            for (int j = jr; j < G; j += RP) {
+                const float* a = A + j * G + k;
+                float acc = 0.f, acm = 0.f;
+                for (int d = lo; d <= hi; ++d) {                    // one read of a[d] for both sums; each in ascending d
+                    const float x = a[d];
+                    acc = fmaf(w[d + R], x, acc);
+                    acm = fmaf(m[d + R], x, acm);
+                }
+                B0[j * KW + k - k0] = acc;
+                B1[j * KW + k - k0] = acm;
+            }
+        }
+        __syncthreads();
+        if (mine) {
+            for (int j = jr; j < G; j += RP) {
+                const int lo = max(-R, -j), hi = min(R, G - 1 - j);
+                const float* b0 = B0 + j * KW + k - k0;
+                const float* b1 = B1 + j * KW + k - k0;
+                float acc = 0.f, ac1 = 0.f, acm = 0.f;
+                for (int d = lo; d <= hi; ++d) {
+                    const float x0 = b0[d * KW], x1 = b1[d * KW], wd = w[d + R];
+                    acc = fmaf(wd, x0, acc);
+                    ac1 = fmaf(wd, x1, ac1);
+                    acm = fmaf(m[d + R], x0, acm);
+                }
+                P0[base + j * G + k] = acc;
+                P1[base + j * G + k] = ac1 + acm;
+            }
+        }
+        __syncthreads();                                            // the next pass writes B0 and B1 again
+    }
+    block_fold_stage<1, SE_VF_PART>(rs, sm);
+    if (t == 0) part[((size_t)row * G + i) * SE_VF_PART + 5] = block_fold_sum<SE_VF_PART>(sm, 0);
+}
+
+// A product rounded on its own, never fused into the sum that follows it.  vs_update_kernel's a is stored and its g is used four times,
+// and the compiler keeps both as products there; here g has one use and would be contracted into S.
+__device__ __forceinline__ float ts_mul(float x, float y) {
+#pragma clang fp contract(off)
+    return x * y;
+}
+
+// grid (G, rows), block 256, dynamic LDS 2 G^2 floats.  q0 and u are formed as vs_update_kernel forms them (vf_blur_i_floor, with q0
+// kept) and a and g are rounded products: s and S are the smoother's, bit for bit.
+__global__ __launch_bounds__(SE_VG_THREADS) void ts_update_kernel(const float* __restrict__ prob, const float* __restrict__ belief,
+                                                                  const float* __restrict__ rev, const float* __restrict__ msq,
+                                                                  const int* __restrict__ link, float* __restrict__ P0,
+                                                                  const float* __restrict__ P1, float* __restrict__ part, int G,
+                                                                  int voxels, int R, int wshift, float keep, float uniform) {
+    extern __shared__ __align__(16) float lds[];
+    __shared__ float w[2 * SE_VG_MAX_R + 1];
+    __shared__ float m[2 * SE_VG_MAX_R + 1];
+    __shared__ float sm[4][SE_VF_PART];
+    const int t = threadIdx.x, j = blockIdx.x, row = blockIdx.y;
+    if (!vf_has_prior(link, 0, row)) return;                        // uniform
+    const int k = t & ((1 << wshift) - 1), ir = t >> wshift, RP = SE_VG_THREADS >> wshift;
+    const size_t base = (size_t)row * voxels;
+    float* slab0 = lds;
+    float* slab1 = lds + G * G;
+    vf_stage_slab(P0, rev, slab0, w, base, j, G, R, t, k, ir, RP);
+    vf_stage_slab(P1, msq, slab1, m, base, j, G, R, t, k, ir, RP);
+    __syncthreads();
+    float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};                      // s, S, A0, A2, Bsum
+    if (k < G) {
+        for (int i = ir; i < G; i += RP) {
+            const size_t n = ((size_t)i * G + j) * G + k;
+            const float b = belief[base + n];
+            const float p = prob[base + n];
+            const int lo = max(-R, -i), hi = min(R, G - 1 - i);
+            const float* s0 = slab0 + i * G + k;
+            const float* s1 = slab1 + i * G + k;
+            float q0 = 0.f, q2 = 0.f, qm = 0.f;
+            for (int d = lo; d <= hi; ++d) {                        // q0 in vf_blur_i_floor's order
+                const float x0 = s0[d * G], x1 = s1[d * G], wd = w[d + R];
+                q0 = fmaf(wd, x0, q0);
+                q2 = fmaf(wd, x1, q2);
+                qm = fmaf(m[d + R], x0, qm);
+            }
+            q2 += qm;
+            const float u = fmaf(keep, q0, uniform);
+            const float a = ts_mul(p, u), g = ts_mul(b, u);
+            P0[base + n] = a;                                       // staged by this workgroup, read by no other
+            acc[0] += a;
+            acc[1] += g;
+            acc[2] += b * q0;
+            acc[3] += b * q2;
+            acc[4] += b;
+        }
+    }
+    block_fold_stage<5, SE_VF_PART>(acc, sm);
+    if (t < 5) part[((size_t)row * G + j) * SE_VF_PART + t] = block_fold_sum<SE_VF_PART>(sm, t);
+}
+
+// grid (chunks, rows), block 256
+template <bool VEC>
+__global__ __launch_bounds__(SE_VG_THREADS) void ts_finish_kernel(const float* __restrict__ prob, const float* __restrict__ q,
+                                                                  const float* __restrict__ part, const int* __restrict__ link,
+                                                                  const int* __restrict__ restarted, int* __restrict__ link_next,
+                                                                  float* __restrict__ state, float* __restrict__ stats,
+                                                                  int* __restrict__ linked_out, int G, int voxels) {
+    __shared__ float fin[SE_VF_PART];
+    const int t = threadIdx.x, row = blockIdx.y;
+    const bool linked = vf_has_prior(link, 0, row);
+    if (linked) vf_fold_records<SE_TS_STATS>(part, row, G, t, fin);  // uniform; an unlinked row has no records
+    const float s = linked ? fin[0] : 0.f;
+    const bool back = linked && s > 0.f && s <= FLT_MAX;            // r_t = a / s; a NaN fails both comparisons
+    if (blockIdx.x == 0 && t == 0) {
+        float* o = stats + (size_t)row * SE_TS_STATS;
+        const float nan = __int_as_float(0x7fc00000);
+        o[0] = linked ? fin[1] : nan;                               // S
+        o[1] = linked ? s : nan;
+        o[2] = linked ? fin[2] : nan;                               // A0
+        o[3] = linked ? fin[3] : nan;                               // A2
+        o[4] = linked ? fin[4] : nan;                               // Bsum
+        o[5] = linked ? fin[5] : nan;                               // Rsum
+        linked_out[row] = linked ? 1 : 0;
+        link_next[row] = restarted[row] == 0;                       // the frame before this one is linked to it unless it restarted
+    }
+    const size_t base = (size_t)row * voxels;
+    const VfStream st[1] = {{(back ? q : prob) + base, back, s, state + base, nullptr}};
+    vf_scale_or_copy<VEC>(st, voxels, t);
+}
+
+// the dynamic LDS of ts_blur_kj_kernel: whole planes where three fit, else the k-blurred planes by halves of the columns
+inline int ts_kw(int G) { return 3 * G * G * 4 <= SE_TS_LDS_MAX ? G : (G + 1) / 2; }
+
+// scratch of the transition statistics: P0 and P1 [rows][voxels], the records [rows][G][8], w' and m' (40 floats each), two arrays of
+// link flags
+inline long long ts_tail_elems(int rows, int G) { return (long long)rows * G * SE_VF_PART + 80 + 2LL * ((rows + 3) & ~3); }
+
+}  // namespace
+
+extern "C" long long se_volume_transition_stats_scratch_bytes(int rows, int G, int radius) {
+    if (!vg_shape_ok(rows, G, radius)) return 0;
+    return (2 * vg_elems(rows, G) + ts_tail_elems(rows, G)) * 4;
+}
+
+extern "C" int se_volume_transition_stats_f32(const float* prob, const float* belief, const int* restarted, const float* taps,
+                                              float* state, float* stats, int* linked, void* scratch, long long scratch_bytes,
+                                              int frames, int rows, int voxels, int G, int radius, float floor, const int* have_link,
+                                              void* stream) {
+    if (!prob || !belief || !restarted || !taps || !state || !stats || !linked || !scratch) return SE_ERR_BAD_ARG;
+    if (!vg_args_ok(frames, rows, voxels, G, radius, floor)) return SE_ERR_BAD_ARG;
+    if (!se_aligned({prob, belief, restarted, taps, state, stats, linked, scratch, have_link}, 4)) return SE_ERR_BAD_ARG;
+    if (scratch_bytes < se_volume_transition_stats_scratch_bytes(rows, G, radius)) return SE_ERR_BAD_ARG;
+    hipStream_t s = se_stream(stream);
+    float* P0 = reinterpret_cast<float*>(scratch);
+    float* P1 = P0 + vg_elems(rows, G);
+    float* part = P1 + vg_elems(rows, G);
+    float* rev = part + (long long)rows * G * SE_VF_PART;
+    float* msq = rev + 40;
+    int* link2 = reinterpret_cast<int*>(msq + 40);
+    const int link_stride = (rows + 3) & ~3;
+    const auto [wshift, chunks, keep, uniform] = vg_launch(voxels, G, floor);
+    const int KW = ts_kw(G);
+    const int kj_bytes = (G + 2 * KW) * G * 4;
+    SE_ENSURE_LDS(ts_blur_kj_kernel, SE_TS_LDS_MAX);                // three planes at G = 116 are the most: 161,472 B
+    SE_ENSURE_LDS(ts_update_kernel, 2 * SE_VG_MAX_G * SE_VG_MAX_G * 4);
+    const bool vec = (voxels & 3) == 0 && se_aligned({prob, state, scratch}, 16);
+    const auto finish = vec ? ts_finish_kernel<true> : ts_finish_kernel<false>;
+    const size_t frame_elems = (size_t)rows * voxels;
+    hipLaunchKernelGGL(ts_prep_kernel, dim3(1), dim3(64), 0, s, taps, rev, msq, radius);
+    SE_CHECK_LAUNCH();
+    for (int f = frames - 1; f >= 0; --f) {
+        const float* p = prob + f * frame_elems;
+        const float* b = belief + f * frame_elems;
+        // the link flags of frame f: the caller's for the last frame, else what the finish pass of frame f + 1 wrote
+        const int* link = f == frames - 1 ? have_link : link2 + (size_t)(f & 1) * link_stride;
+        int* link_next = link2 + (size_t)((f + 1) & 1) * link_stride;                    // read by frame f - 1
+        if (link) {
+            hipLaunchKernelGGL(ts_blur_kj_kernel, dim3(G, rows), dim3(SE_VG_THREADS), kj_bytes, s, state, rev, msq, link, P0, P1, part,
+                               G, voxels, radius, wshift, KW);
+            SE_CHECK_LAUNCH();
+            hipLaunchKernelGGL(ts_update_kernel, dim3(G, rows), dim3(SE_VG_THREADS), 2 * G * G * 4, s, p, b, rev, msq, link, P0, P1,
+                               part, G, voxels, radius, wshift, keep, uniform);
+            SE_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(finish, dim3(chunks, rows), dim3(SE_VG_THREADS), 0, s, p, P0, part, link, restarted + (size_t)f * rows,
+                           link_next, state, stats + (size_t)f * rows * SE_TS_STATS, linked + (size_t)f * rows, G, voxels);
         SE_CHECK_LAUNCH();
     }
     return 0;

@@ -436,6 +436,31 @@ def volume_path_to_numpy(result):
     return _per_frame(result, PATH_KEYS + (("shift",) if "shift" in result else ()), "index")
 
 
+def motion_fit_to_json(result, **extra):
+    """The dict of ``MotionModelFit.fit`` as plain Python values that ``json.dump`` takes (NaN as null, the per-joint arrays as lists;
+    the keys of ``motion_fit.FIT_KEYS``), with ``extra`` added: what run_sequence.py --fit_output writes."""
+    from .motion_fit import FIT_KEYS
+
+    def plain(v):
+        if isinstance(v, dict):
+            return {k: plain(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [plain(x) for x in v]
+        if isinstance(v, np.ndarray):
+            return plain(v.tolist())
+        if isinstance(v, (bool, np.bool_)):
+            return bool(v)
+        if isinstance(v, (int, np.integer)):
+            return int(v)
+        if isinstance(v, (float, np.floating)):
+            return float(v) if np.isfinite(v) else None
+        return v
+
+    out = {k: plain(result[k]) for k in FIT_KEYS}
+    out.update({k: plain(v) for k, v in extra.items()})
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # skeleton-coupled joints (csrc/skeleton_prior.hip; sceneego_amd/skeleton_prior.py; the reference has only Skeleton._skeleton_resize)
 # ----------------------------------------------------------------------------------------------

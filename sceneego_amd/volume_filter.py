@@ -199,9 +199,12 @@ class VolumeFilter:
 
 class StoredTrack:
     """What ``VolumeSmoother`` and ``VolumeViterbi`` share: both run a forward pass as the frames are pushed, keep what the backward
-    pass needs on the device under a byte budget and release it in ``finish()``.  A stored push is a NamedTuple of the subclass with
+    pass needs on the device under a byte budget and release it in ``finish()``.  (``MotionModelFit`` stores under the same budget
+    and waits for its pushes the same way; it keeps the frames until ``reset()``.)  A stored push is a NamedTuple of the subclass with
     at least ``restarted`` [B,J], ``given`` (the joints pushed with it, or None) and ``event`` (recorded behind everything the push
     queued).  The subclass says what a push weighs (``bytes_stored``)."""
+
+    _budget_advice = "finish() the track in pieces or raise max_bytes"      # what a subclass without finish() says instead
 
     def _init_store(self, max_bytes):
         if max_bytes is not None and (isinstance(max_bytes, bool) or not float(max_bytes) >= 0):
@@ -222,7 +225,7 @@ class StoredTrack:
             self.max_bytes = int(torch.cuda.mem_get_info(dev)[0]) // 2
         if self.bytes_stored + need > self.max_bytes:
             raise ValueError(f"push: {self.frames_stored} frames are stored ({self.bytes_stored} bytes) and {B} more need {need} bytes: "
-                             f"over max_bytes = {self.max_bytes}; finish() the track in pieces or raise max_bytes")
+                             f"over max_bytes = {self.max_bytes}; {self._budget_advice}")
 
     def _begin_finish(self, stream):
         """The stored pushes, their device, J and the stream finish() runs on (default: the current one), which is made to wait for

@@ -518,6 +518,23 @@ class VoxelNetwork_depth(nn.Module):
         return VolumeViterbi(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor,
                              refine=refine, max_bytes=max_bytes)
 
+    def motion_fit(self, sigma=0.10, radius=None, floor=1e-3, max_bytes=None):
+        """A ``sceneego_amd.motion_fit.MotionModelFit`` bound to the module's own ``coord_volumes``, grid and cuboid side: the fit of
+        the motion model that ``volume_filter``, ``volume_smoother`` and ``volume_path`` run on to the volumes of ONE recorded
+        sequence.  ``m = net.motion_fit(); m.push(volumes)`` per batch of consecutive frames keeps a copy of the volumes and a belief
+        buffer on the device (2 x B x J x G^3 x 4 bytes per push, at most ``max_bytes``; default: half of the free device memory at the
+        first push); ``m.fit()`` runs EM for ``sigma`` and ``floor`` from the values given here, at the fixed ``radius``, and returns
+        them with the log-likelihood of every iteration.  It is a maximum-likelihood fit to the network's own volumes read as
+        likelihoods, on one sequence: not a validation against ground truth.  ``forward()`` itself is unchanged.
+
+        Raises ValueError when ``config.model.volume_softmax`` is false or a parameter is out of range; nothing touches the device
+        before the first ``push``."""
+        if not self.volume_softmax:
+            raise ValueError("motion_fit needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        from .motion_fit import MotionModelFit
+        return MotionModelFit(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor,
+                              max_bytes=max_bytes)
+
     def skeleton_prior(self, bone_lengths, tau=0.03, floor=1e-3):
         """A ``sceneego_amd.skeleton_prior.SkeletonPrior`` bound to the module's own ``coord_volumes``, grid and cuboid side: belief
         propagation over the kinematic tree with a bone-length shell on every edge.  ``s = net.skeleton_prior(lengths);
