@@ -879,6 +879,51 @@ int se_skeleton_couple_f32(const float* prob, const float* coord, const float* t
                            int R, float floor, void* stream);
 long long se_skeleton_couple_scratch_bytes(int frames, int J, int G, int R);
 
+/* Edge statistics of the skeleton model: the E-step sums of an EM fit of the bone lengths, tau and floor to a sequence
+ * (sceneego_amd/skeleton_fit.py: SkeletonModelFit; VoxelNetwork_depth.skeleton_fit returns one).  The edge factor (1 - floor) w_L,tau(d)
+ * + floor / N is a two-component mixture whose shell part is an exponential family in (|d|, |d|^2) on a fixed set of taps.  Everything
+ * not stated here is se_skeleton_couple_f32's: the TREE, the TAPS layout, the zero-padded CORRELATE, the floor, the product order and
+ * the FALLBACK rule.  tests/skeleton_fit_model.py restates the definition in float64.
+ *   taps       block c is w_c.  taps_r, taps_r2: the same layout, w1_c = float32(w64_c r) and w2_c = float32(w64_c r^2), r(d) = |d| h in
+ *              metres and w64_c the float64 block before rounding, computed by the caller.  A tap with w_c(d) == 0 is skipped in all three
+ *              blocks: the run table is built from w_c alone.
+ * Per frame and edge c = 1..J-1, with A_c, s_c (upward), E_c = p_j D_j prod_{c' != c} U_c', t_c (downward, j = parent[c]) and Z_j as in
+ * se_skeleton_couple_f32:
+ *   S0 = sum_x E_c(x) corr(A_c, w_c)(x),  S1 = sum_x E_c(x) corr(A_c, w1_c)(x),  S2 = sum_x E_c(x) corr(A_c, w2_c)(x),
+ *   SJ = ((floor / N) t_c) s_c   in float32, floor / N as the coupling forms it.
+ * The posterior mass of a shell step on the edge is m = (1 - floor) S0 / ((1 - floor) S0 + SJ), of a jump 1 - m; the expected bone
+ * length given a step is S1 / S0 and its square S2 / S0.  (1 - floor) S0 + SJ = s_c Z_parent(c), and the frame's likelihood is
+ * ln Z_0 + sum_{c >= 1} ln s_c: the quotients are left to the caller, in float64.
+ *   stats      [frames][J][4] float32: S0, S1, S2, SJ; row 0 is zero
+ *   norms      [frames][J][3] float32: s_j, t_j, Z_j; s_0 and t_0 are NaN (the root sends no message and receives none)
+ *   valid      [frames] int32: 0 where se_skeleton_couple_f32 would fall back.  The statistics of such a frame are written as computed.
+ *   scratch    se_skeleton_edge_stats_scratch_bytes(frames, J, G, R) bytes, 4-byte aligned; 0 for a shape out of range.  About 4 J G^3
+ *              floats for each of min(frames, 4) frames (E_c can no longer overwrite A_c) and 16 J (2R+1)^3 bytes for the three tap
+ *              blocks interleaved.
+ * It is se_skeleton_couple_f32's two passes by depth level on the same product, fold and correlation kernels, so Z equals that call's
+ * `evidence` and valid its `coupled`, bit for bit; one moments launch follows each downward level, no belief is formed and no volume is
+ * written for the statistics.  No atomics.  Each of the three correlation values behind S0, S1, S2 is a chain of at most
+ * SE_SK_SHELL_CHAIN(R) roundings; behind it a lane folds its four outputs with e(x) by fused multiply-adds (4), the workgroup folds its
+ * lanes (6 + 2), and one wave folds the row's G ceil(G / 16) ceil(G / 64) workgroup records: lane l takes records l, l + 64, ... in
+ * sequence, then a butterfly (6): SE_SK_MOMENT_CHAIN(G) roundings on the longest path, 22 at 64^3.  The order depends on (G, R) and
+ * the taps alone: bitwise identical from run to run and independent of how frames are batched into calls.  Allocates nothing.
+ * SE_ERR_BAD_ARG, with nothing launched: as se_skeleton_couple_f32, for its own pointers (none may be null) and scratch size.
+ *
+ * se_shell_moments_f32 is the hot path on its own: out[r] = (S0, S1, S2) of the `rows` pairs (e[r], a[r]) of G^3 float32 with the blocks
+ * tap_row[r] (int32 [rows] on the DEVICE) of taps, taps_r, taps_r2 [tap_rows][(2R+1)^3]; out [rows][3] float32.  A tap_row outside
+ * 0..tap_rows-1 gives NaN for its row.  scratch: se_shell_moments_scratch_bytes(rows, tap_rows, G, R) bytes (the run table, the
+ * workgroup records and the interleaved taps).  SE_ERR_BAD_ARG: a null or misaligned pointer, rows or tap_rows outside 1..65535, G
+ * outside 2..128, R outside 0..min(24, G - 1), a short scratch.                                                                      */
+#define SE_SK_MOMENT_CHAIN(G) (18 + ((G) * (((G) + 15) / 16) * (((G) + 63) / 64) + 63) / 64)
+int se_shell_moments_f32(const float* e, const float* a, const float* taps, const float* taps_r, const float* taps_r2,
+                         const int* tap_row, float* out, void* scratch, long long scratch_bytes, int rows, int tap_rows, int G, int R,
+                         void* stream);
+long long se_shell_moments_scratch_bytes(int rows, int tap_rows, int G, int R);
+int se_skeleton_edge_stats_f32(const float* prob, const float* taps, const float* taps_r, const float* taps_r2, const int* parent,
+                               float* stats, float* norms, int* valid, void* scratch, long long scratch_bytes, int frames, int J,
+                               int voxels, int G, int R, float floor, void* stream);
+long long se_skeleton_edge_stats_scratch_bytes(int frames, int J, int G, int R);
+
 /* Most probable pose: the max-product pass over the kinematic tree that goes with se_skeleton_couple_f32, as se_volume_viterbi_f32
  * goes with the filter (sceneego_amd/skeleton_pose.py: SkeletonPose; VoxelNetwork_depth.skeleton_pose returns one).  The coupling gives
  * per joint a marginal and its expectation; this gives the single most probable configuration of all J joints of a frame under the same

@@ -15,6 +15,7 @@
                             [--bone_frames 64] [--skeleton_tau 0.03] [--skeleton_floor 1e-3]] [--render_volumes coupled]
                            [--map_output out/map.pkl [--map_info_output out/map_info.pkl] [--map_refine 1]]
                            [--fit_frames 64 [--fit_iterations 8] [--fit_output out/fit.json]]
+                           [--skeleton_fit_frames 64 [--skeleton_fit_iterations 8] [--skeleton_fit_output out/skeleton_fit.json]]
 
 Frame list (``TestDataset.get_gt_data``): ``<root>/<seq>/syn.json`` (``ego``, ``ext`` start frames) and ``local_pose_gt.pkl`` (items
 with ``ext_id`` and ``ego_pose_gt``); items whose pose is None or whose image ``imgs/img_%06d.jpg`` is missing are skipped; the depth
@@ -84,6 +85,13 @@ consecutive frames, from ``--filter_sigma`` / ``--filter_floor`` at the fixed ``
 with their log-likelihoods, writes the whole result to ``--fit_output`` (JSON) and runs ``--filter_output``, ``--smooth_output`` and
 ``--path_output`` on the fitted values; their per-frame info dicts then carry ``sigma``, ``floor`` and ``radius``.  It is a
 maximum-likelihood fit to the network's own volumes read as likelihoods, on this one sequence: not a validation against ground truth.
+``--skeleton_fit_frames F`` fits the skeleton model the same way (``VoxelNetwork_depth.skeleton_fit``, ``sceneego_amd/skeleton_fit.py``:
+at most ``--skeleton_fit_iterations`` EM iterations for the bone lengths, tau and floor over the raw volumes of F evenly spaced frames,
+chosen as ``--bone_frames`` chooses its frames, from ``--bone_lengths`` or the median estimate, ``--skeleton_tau`` and
+``--skeleton_floor``), prints the start and fitted values with their log-likelihoods, writes the whole result to
+``--skeleton_fit_output`` (JSON) and runs ``--skeleton_output`` and ``--map_output`` on the fitted values; their per-frame info dicts
+then carry ``bone_lengths``, ``tau`` and ``floor``.  If the fitted shells need more than min(24, G - 1) voxels it exits with
+``SkeletonPrior``'s message.  The same caveat holds: a fit to the volumes, not a validation.
 """
 import argparse
 import json
@@ -270,6 +278,24 @@ class SequenceRunner:
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
         fit = self.net.motion_fit(**model, max_bytes=max_bytes)
+        for i in range(0, len(images), batch_size):
+            img = self._images([load(p) for p in images[i:i + batch_size]])
+            depth = self._depths(depths[i:i + batch_size])
+            _, _, vol, _ = self.net(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
+            fit.push(vol)                                     # a copy: the next forward overwrites the volumes
+        result = fit.fit(iterations=iterations)
+        fit.reset()
+        return result
+
+    @torch.no_grad()
+    def fit_skeleton(self, images, depths, batch_size, model, iterations=8, max_bytes=None):
+        """The first pass of ``--skeleton_fit_frames``: the forward over the frames ``images`` / ``depths`` in batches, their raw
+        volumes pushed into ``VoxelNetwork_depth.skeleton_fit(**model)`` (``model``: a dict of ``bone_lengths`` / ``tau`` / ``floor``,
+        the values the fit starts from) and the dict of its ``fit(iterations=iterations)``."""
+        from sceneego_amd.jpeg_device import JpegFile
+        from sceneego_amd.preprocess import load_image_bgr
+        load = JpegFile if self.image_decode == "device" else load_image_bgr
+        fit = self.net.skeleton_fit(**model, max_bytes=max_bytes)
         for i in range(0, len(images), batch_size):
             img = self._images([load(p) for p in images[i:i + batch_size]])
             depth = self._depths(depths[i:i + batch_size])
@@ -555,6 +581,14 @@ def build_parser():
                     "(entry 0 ignored); default: estimated from a first pass over --bone_frames frames")
     ap.add_argument("--bone_frames", type=int, default=64, help="without --bone_lengths: at most this many evenly spaced frames feed "
                     "the bone-length estimate")
+    ap.add_argument("--skeleton_fit_frames", type=int, default=None, help="fit the bone lengths, --skeleton_tau and --skeleton_floor to "
+                    "the volumes of F evenly spaced frames before the main pass (sceneego_amd/skeleton_fit.py: EM from --bone_lengths or "
+                    "the median estimate; a fit to the volumes, not calibrated against ground truth); --skeleton_output and --map_output "
+                    "then run on the fitted values")
+    ap.add_argument("--skeleton_fit_iterations", type=int, default=None, help="with --skeleton_fit_frames: at most this many EM "
+                    "iterations (default 8)")
+    ap.add_argument("--skeleton_fit_output", default=None, help="with --skeleton_fit_frames: JSON file of the fit (bone_lengths, tau, "
+                    "floor, radius, log_likelihood, history, ...)")
     ap.add_argument("--skeleton_tau", type=float, default=0.03, help="the width of the bone-length shell in metres")
     ap.add_argument("--skeleton_floor", type=float, default=1e-3, help="the skeleton prior's uniform floor in [0, 1]: the chance that "
                     "the bone prior is wrong for an edge")
@@ -623,6 +657,16 @@ def parse_args(argv=None):
         args.fit = {"frames": args.fit_frames, "iterations": 8 if args.fit_iterations is None else args.fit_iterations}
     elif args.fit_iterations is not None or args.fit_output is not None:
         raise SystemExit("--fit_iterations and --fit_output need --fit_frames")
+    args.skeleton_fit = None
+    if args.skeleton_fit_frames is not None:
+        if args.skeleton_fit_frames < 1:
+            raise SystemExit("--skeleton_fit_frames must be >= 1")
+        if args.skeleton_fit_iterations is not None and args.skeleton_fit_iterations < 1:
+            raise SystemExit("--skeleton_fit_iterations must be >= 1")
+        args.skeleton_fit = {"frames": args.skeleton_fit_frames,
+                             "iterations": 8 if args.skeleton_fit_iterations is None else args.skeleton_fit_iterations}
+    elif args.skeleton_fit_iterations is not None or args.skeleton_fit_output is not None:
+        raise SystemExit("--skeleton_fit_iterations and --skeleton_fit_output need --skeleton_fit_frames")
     if not (args.skeleton_tau > 0 and args.skeleton_tau != float("inf")):
         raise SystemExit("--skeleton_tau must be a finite number > 0")
     if not 0.0 <= args.skeleton_floor <= 1.0:
@@ -660,8 +704,8 @@ def main(argv=None):
     print(f"dataset length: {len(images)}")
     runner = SequenceRunner(config, weights=args.weights, streams=args.streams, depth_decode=args.depth_decode,
                             workers=args.workers, image_decode=args.image_decode)
-    skeleton = map_pose = None
-    if args.skeleton or args.map:
+    skeleton = map_pose = skeleton_fitted = None
+    if args.skeleton or args.map or args.skeleton_fit is not None:
         from sceneego_amd.skeleton_prior import estimate_bone_lengths
         if args.bone_lengths is not None:
             lengths = np.load(args.bone_lengths)
@@ -671,11 +715,41 @@ def main(argv=None):
             raw = runner.run([images[k] for k in pick], [depths[k] for k in pick], config.test.batch_size)
             lengths = estimate_bone_lengths(np.stack(raw))
             print(f"bone lengths estimated from {len(pick)} frames: " + " ".join(f"{v:.4f}" for v in lengths[1:]))
+        tau, floor = args.skeleton_tau, args.skeleton_floor
+        if args.skeleton_fit is not None:
+            # a first pass over --skeleton_fit_frames evenly spaced frames: EM for the bone lengths, tau and floor on a fixed support
+            from sceneego_amd.op import skeleton_fit_to_json
+            from sceneego_amd.skeleton_prior import MAX_RADIUS, default_radius
+            pick = sorted({int(round(v)) for v in np.linspace(0, len(images) - 1, min(args.skeleton_fit["frames"], len(images)))})
+            start = {"bone_lengths": np.asarray(lengths, dtype=np.float64), "tau": tau, "floor": floor}
+            try:
+                sfit = runner.fit_skeleton([images[k] for k in pick], [depths[k] for k in pick], config.test.batch_size, start,
+                                           iterations=args.skeleton_fit["iterations"])
+            except ValueError as e:
+                raise SystemExit(str(e))
+            lengths, tau, floor = sfit["bone_lengths"], float(sfit["tau"]), float(sfit["floor"])
+            skeleton_fitted = {"bone_lengths": np.asarray(lengths[1:], dtype=np.float64), "tau": tau, "floor": floor}
+            began = np.asarray(start["bone_lengths"], dtype=np.float64).reshape(-1)[-(len(lengths) - 1):]
+            print("skeleton model fitted to {} frames ({} valid, {} iterations; a fit to the volumes, not calibrated against ground truth): "
+                  "tau {:.4f} -> {:.4f} m, floor {:.3g} -> {:.3g}, log-likelihood {:.6g} -> {:.6g}{}{}".format(
+                      len(pick), sfit["frames_used"], len(sfit["log_likelihood"]) - 1, args.skeleton_tau, tau, args.skeleton_floor, floor,
+                      sfit["log_likelihood"][0], sfit["log_likelihood"][-1], ", a bound is active" if sfit["saturated"] else "",
+                      ", the support cuts a fitted shell: fit again from the fitted values" if sfit["truncation_binding"].any() else ""))
+            print("bone lengths at the start:  " + " ".join(f"{v:.4f}" for v in began))
+            print("bone lengths fitted:        " + " ".join(f"{v:.4f}" for v in lengths[1:]))
+            if args.skeleton_fit_output is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(args.skeleton_fit_output)), exist_ok=True)
+                with open(args.skeleton_fit_output, "w") as f:
+                    json.dump(skeleton_fit_to_json(sfit, frames=len(pick), start={"bone_lengths": began, "tau": args.skeleton_tau,
+                                                                                   "floor": args.skeleton_floor}), f, indent=1)
+            h = runner.net.cuboid_side / runner.net.volume_size
+            reach, most = default_radius(lengths[1:], tau, h), min(MAX_RADIUS, runner.net.volume_size - 1)
+            if reach > most:
+                raise SystemExit(f"the shells reach {reach} voxels of {h:.5f} m; at most min({MAX_RADIUS}, grid - 1) = {most} are supported")
         if args.skeleton:
-            skeleton = {"bone_lengths": lengths, "tau": args.skeleton_tau, "floor": args.skeleton_floor}
+            skeleton = {"bone_lengths": lengths, "tau": tau, "floor": floor}
         if args.map:
-            map_pose = {"bone_lengths": lengths, "tau": args.skeleton_tau, "floor": args.skeleton_floor,
-                        "refine": 1 if args.map_refine is None else args.map_refine}
+            map_pose = {"bone_lengths": lengths, "tau": tau, "floor": floor, "refine": 1 if args.map_refine is None else args.map_refine}
     fitted = None
     if args.fit is not None:
         # a first pass over the first --fit_frames consecutive frames: EM for sigma and floor at the fixed radius
@@ -730,6 +804,10 @@ def main(argv=None):
             for frames in (frame_filter, frame_smooth, frame_path):
                 for fr in frames or ():
                     fr.update(fitted)
+        if skeleton_fitted is not None:
+            for frames in (frame_skeleton, frame_map):
+                for fr in frames or ():
+                    fr.update(skeleton_fitted)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = np.stack(preds).astype(np.float64)
@@ -745,6 +823,8 @@ def main(argv=None):
     result = {"frames": len(preds), "mpjpe": mpjpe, "pa_mpjpe": pampjpe, "fps": len(preds) / dt, "predictions": preds}
     if fitted is not None:
         result["fit"] = fit
+    if skeleton_fitted is not None:
+        result["skeleton_fit"] = sfit
     if want_stats:
         os.makedirs(os.path.dirname(os.path.abspath(args.stats_output)), exist_ok=True)
         with open(args.stats_output, "wb") as f:

@@ -11,7 +11,7 @@ The compute kernels are in sceneego_amd/csrc (HIP, gfx950) behind the C ABI of i
 """
 from .config import EasyDict, load_config  # noqa: F401
 
-__all__ = ["EasyDict", "load_config", "VoxelNetwork_depth", "VoxelNetDepth", "SkeletonPose"]
+__all__ = ["EasyDict", "load_config", "VoxelNetwork_depth", "VoxelNetDepth", "SkeletonPose", "SkeletonModelFit"]
 
 
 def __getattr__(name):
@@ -21,4 +21,7 @@ def __getattr__(name):
     if name == "SkeletonPose":
         from .skeleton_pose import SkeletonPose
         return SkeletonPose
+    if name == "SkeletonModelFit":
+        from .skeleton_fit import SkeletonModelFit
+        return SkeletonModelFit
     raise AttributeError(name)

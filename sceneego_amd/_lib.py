@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -125,6 +125,10 @@ SIGNATURES = {
     "se_shell_correlate_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _f, _vp]),
     "se_skeleton_couple_scratch_bytes": (_ll, [_i, _i, _i, _i]),
     "se_skeleton_couple_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
+    "se_shell_moments_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_shell_moments_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _vp]),
+    "se_skeleton_edge_stats_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_skeleton_edge_stats_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
     "se_shell_maxcorr_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _vp]),
     "se_shell_argmax_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "se_skeleton_pose_scratch_bytes": (_ll, [_i, _i, _i, _i]),
@@ -1472,6 +1476,74 @@ def skeleton_couple(prob, coord, taps, parents, beliefs, joints, evidence, coupl
                                          _ptr(joints), _ptr(evidence), _ptr(coupled), _ptr(scratch), scratch.numel(), frames, J,
                                          voxels, grid, radius, floor, _stream()), "se_skeleton_couple_f32")
     return joints, evidence, coupled
+
+
+# The E-step sums of a fit of the skeleton model (csrc/skeleton_prior.hip: se_skeleton_edge_stats_f32, se_shell_moments_f32;
+# sceneego_amd/skeleton_fit.py drives them)
+EDGE_STATS_SLOTS = 4       # S0, S1, S2, SJ
+
+
+def MOMENT_CHAIN(grid) -> int:
+    """SE_SK_MOMENT_CHAIN(G): the roundings on the longest path of the reduction behind the correlation values of one moment (4 for
+    the lane's four outputs, 6 + 2 for the workgroup, ceil(records / 64) + 6 for the fold of the row's G ceil(G/16) ceil(G/64) records)."""
+    grid = int(grid)
+    return 18 + (grid * ((grid + 15) // 16) * ((grid + 63) // 64) + 63) // 64
+
+
+def shell_moments_scratch_bytes(rows, tap_rows, grid, radius) -> int:
+    return int(load().se_shell_moments_scratch_bytes(int(rows), int(tap_rows), int(grid), int(radius)))
+
+
+def shell_moments(e, a, taps, taps_r, taps_r2, tap_row, out, rows, grid, radius, scratch=None):
+    """se_shell_moments_f32: ``out[r] = (S0, S1, S2)``, S_m = sum_x e[r](x) corr(a[r], w_m[tap_row[r]])(x), for the ``rows`` pairs of
+    volumes ``e``, ``a`` [rows, grid^3]; the three tap blocks [tap_rows, (2 radius + 1)^3] float32 and ``tap_row`` [rows] int32 on the
+    device; ``out`` [rows, 3] float32 (the header states the sums).  ``scratch``: an optional uint8 workspace of at least
+    ``shell_moments_scratch_bytes(rows, tap_rows, grid, radius)`` bytes.  Every argument is checked here and a bad one raises
+    HipExtensionError before anything is launched."""
+    what = "shell_moments"
+    rows, grid, radius = int(rows), int(grid), int(radius)
+    if not 1 <= rows <= 65535:
+        raise HipExtensionError(f"{what}: rows = {rows} (1..65535) expected")
+    _skeleton_shape(what, grid, radius)
+    voxels, block = grid ** 3, (2 * radius + 1) ** 3
+    dev = _check_args(what, (("e", e, torch.float32, rows * voxels), ("a", a, torch.float32, rows * voxels),
+                             ("taps", taps, torch.float32, (None, block)), ("tap_row", tap_row, torch.int32, rows),
+                             ("out", out, torch.float32, rows * 3)), (("scratch", scratch, torch.uint8, None),))
+    tap_rows = int(taps.shape[0])
+    if not 1 <= tap_rows <= 65535:
+        raise HipExtensionError(f"{what}: taps holds {tap_rows} blocks, 1..65535 expected")
+    _check_args(what, (("taps_r", taps_r, torch.float32, tap_rows * block), ("taps_r2", taps_r2, torch.float32, tap_rows * block)),
+                device=dev)
+    scratch = _scratch(what, scratch, shell_moments_scratch_bytes(rows, tap_rows, grid, radius), torch.uint8, dev)
+    _check(load().se_shell_moments_f32(_ptr(e), _ptr(a), _ptr(taps), _ptr(taps_r), _ptr(taps_r2), _ptr(tap_row), _ptr(out),
+                                       _ptr(scratch), scratch.numel(), rows, tap_rows, grid, radius, _stream()), "se_shell_moments_f32")
+    return out
+
+
+def skeleton_edge_stats_scratch_bytes(frames, joints, grid, radius) -> int:
+    return int(load().se_skeleton_edge_stats_scratch_bytes(int(frames), int(joints), int(grid), int(radius)))
+
+
+def skeleton_edge_stats(prob, taps, taps_r, taps_r2, parents, stats, norms, valid, frames, voxels, grid, radius, floor, scratch=None):
+    """se_skeleton_edge_stats_f32: ``skeleton_couple``'s two passes over the tree ``parents`` on ``prob`` [frames, J, voxels] with the
+    three tap blocks [J, (2 radius + 1)^3] on the device, for the edge statistics in place of the beliefs (the header states them):
+    ``stats`` [frames, J, 4] (S0, S1, S2, SJ), ``norms`` [frames, J, 3] (s, t, Z) float32 and ``valid`` [frames] int32 are written.
+    ``scratch``: an optional uint8 workspace of at least ``skeleton_edge_stats_scratch_bytes(frames, J, grid, radius)`` bytes.  Every
+    argument is checked here and a bad one raises HipExtensionError before anything is launched."""
+    what = "skeleton_edge_stats"
+    parents, J, frames, voxels, grid, radius, floor = _tree_args(what, parents, frames, voxels, grid, radius, floor)
+    block = (2 * radius + 1) ** 3
+    dev = _check_args(what, (("prob", prob, torch.float32, frames * J * voxels), ("taps", taps, torch.float32, J * block),
+                             ("taps_r", taps_r, torch.float32, J * block), ("taps_r2", taps_r2, torch.float32, J * block),
+                             ("stats", stats, torch.float32, frames * J * EDGE_STATS_SLOTS),
+                             ("norms", norms, torch.float32, frames * J * 3), ("valid", valid, torch.int32, frames)),
+                      (("scratch", scratch, torch.uint8, None),))
+    scratch = _scratch(what, scratch, skeleton_edge_stats_scratch_bytes(frames, J, grid, radius), torch.uint8, dev)
+    par = (ctypes.c_int * J)(*parents)
+    _check(load().se_skeleton_edge_stats_f32(_ptr(prob), _ptr(taps), _ptr(taps_r), _ptr(taps_r2), ctypes.cast(par, ctypes.c_void_p),
+                                             _ptr(stats), _ptr(norms), _ptr(valid), _ptr(scratch), scratch.numel(), frames, J, voxels,
+                                             grid, radius, floor, _stream()), "se_skeleton_edge_stats_f32")
+    return stats, norms, valid
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -436,11 +436,8 @@ def volume_path_to_numpy(result):
     return _per_frame(result, PATH_KEYS + (("shift",) if "shift" in result else ()), "index")
 
 
-def motion_fit_to_json(result, **extra):
-    """The dict of ``MotionModelFit.fit`` as plain Python values that ``json.dump`` takes (NaN as null, the per-joint arrays as lists;
-    the keys of ``motion_fit.FIT_KEYS``), with ``extra`` added: what run_sequence.py --fit_output writes."""
-    from .motion_fit import FIT_KEYS
-
+def _fit_to_json(result, keys, extra):
+    """``result[k]`` for k in ``keys`` as plain Python values that ``json.dump`` takes (NaN as null, arrays as lists), with ``extra``."""
     def plain(v):
         if isinstance(v, dict):
             return {k: plain(x) for k, x in v.items()}
@@ -456,9 +453,23 @@ def motion_fit_to_json(result, **extra):
             return float(v) if np.isfinite(v) else None
         return v
 
-    out = {k: plain(result[k]) for k in FIT_KEYS}
+    out = {k: plain(result[k]) for k in keys}
     out.update({k: plain(v) for k, v in extra.items()})
     return out
+
+
+def motion_fit_to_json(result, **extra):
+    """The dict of ``MotionModelFit.fit`` as plain Python values that ``json.dump`` takes (NaN as null, the per-joint arrays as lists;
+    the keys of ``motion_fit.FIT_KEYS``), with ``extra`` added: what run_sequence.py --fit_output writes."""
+    from .motion_fit import FIT_KEYS
+    return _fit_to_json(result, FIT_KEYS, extra)
+
+
+def skeleton_fit_to_json(result, **extra):
+    """The dict of ``SkeletonModelFit.fit`` in the same plain form (the keys of ``skeleton_fit.FIT_KEYS``), with ``extra`` added: what
+    run_sequence.py --skeleton_fit_output writes."""
+    from .skeleton_fit import FIT_KEYS
+    return _fit_to_json(result, FIT_KEYS, extra)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -535,6 +535,22 @@ class VoxelNetwork_depth(nn.Module):
         return MotionModelFit(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor,
                               max_bytes=max_bytes)
 
+    def skeleton_fit(self, bone_lengths, tau=0.03, floor=1e-3, max_bytes=None):
+        """A ``sceneego_amd.skeleton_fit.SkeletonModelFit`` bound to the module's own grid and cuboid side: the fit of the model that
+        ``skeleton_prior`` and ``skeleton_pose`` run on - the bone lengths, ``tau`` and ``floor`` - to the volumes of ONE recorded
+        sequence.  ``m = net.skeleton_fit(lengths); m.push(volumes)`` per batch keeps a copy of the volumes on the device (B x J x G^3
+        x 4 bytes per push, at most ``max_bytes``; default: half of the free device memory at the first push; the frames need not be
+        consecutive); ``m.fit()`` runs EM from the values given here and returns the fitted ones with the log-likelihood of every
+        iteration.  It is a maximum-likelihood fit to the network's own volumes read as likelihoods, on one sequence: not a
+        validation against ground truth.  ``forward()`` itself is unchanged.
+
+        Raises ValueError when ``config.model.volume_softmax`` is false or a parameter is out of range; nothing touches the device
+        before the first ``push``."""
+        if not self.volume_softmax:
+            raise ValueError("skeleton_fit needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
+        from .skeleton_fit import SkeletonModelFit
+        return SkeletonModelFit(self.volume_size, self.cuboid_side, bone_lengths, tau=tau, floor=floor, max_bytes=max_bytes)
+
     def skeleton_prior(self, bone_lengths, tau=0.03, floor=1e-3):
         """A ``sceneego_amd.skeleton_prior.SkeletonPrior`` bound to the module's own ``coord_volumes``, grid and cuboid side: belief
         propagation over the kinematic tree with a bone-length shell on every edge.  ``s = net.skeleton_prior(lengths);
