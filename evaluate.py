@@ -112,6 +112,40 @@ def best_of_k(frames, pred, gt):
             "joints_with_modes": have}
 
 
+def load_alternatives(path, count):
+    """The per-frame dicts of run_sequence.py --map_alternatives_output, for the ``count`` frames of --map_output."""
+    with open(path, "rb") as f:
+        frames = pickle.load(f)
+    if len(frames) != count:
+        raise SystemExit(f"{path}: alternatives of {len(frames)} frames for {count} predictions")
+    return frames
+
+
+def best_of_two(frames, pred, gt):
+    """Does the runner-up margin say where the most probable pose is wrong?  Per frame the smaller of the mean joint error of the pose
+    and of its runner-up pose (``runner_up_joints``; the pose alone where there is none), averaged over the frames; the share of the
+    frames in which the runner-up is the closer one; and the rank correlation of the pose's error and ``runner_up_margin`` over the
+    frames with a finite margin (average ranks for ties; NaN when there are fewer than two or either is constant).  No alignment."""
+    from sceneego_amd.metrics import _average_ranks
+    err = np.sqrt(((pred - gt) ** 2).sum(axis=2)).mean(axis=1)
+    best, margins = err.copy(), np.full(len(frames), np.nan)
+    for t, fr in enumerate(frames):
+        margins[t] = float(fr["runner_up_margin"])
+        if int(fr["runner_up"]) >= 0 and np.isfinite(fr["runner_up_joints"]).all():
+            other = np.sqrt(((np.asarray(fr["runner_up_joints"], dtype=np.float64) - gt[t]) ** 2).sum(axis=1)).mean()
+            best[t] = min(best[t], other)
+    ok = np.isfinite(margins)
+    rho = float("nan")
+    if ok.sum() >= 2:
+        re, rm = _average_ranks(err[ok]), _average_ranks(margins[ok])
+        re, rm = re - re.mean(), rm - rm.mean()
+        den = np.sqrt((re * re).sum() * (rm * rm).sum())
+        rho = float((re * rm).sum() / den) if den > 0.0 else rho
+    return {"best_of_two_mpjpe": float(best.mean()), "runner_up_closer_share": float((best < err).mean()),
+            "spearman_error_margin": rho, "frames_with_margin": int(ok.sum()),
+            "mean_runner_up_margin": float(margins[ok].mean()) if ok.any() else float("nan")}
+
+
 def match_ground_truth(gt, names):
     if isinstance(gt, dict):
         def find(n):
@@ -148,6 +182,9 @@ def build_parser():
                     "(demo.py --scene_check true) or the one pickle of run_sequence.py --scene_output; adds the plausibility summary")
     ap.add_argument("--modes", default=None, help="joint modes of the same frames: a directory of <image name>.modes.pkl files "
                     "(demo.py --modes true) or the one pickle of run_sequence.py --modes_output; adds the best-of-K MPJPE")
+    ap.add_argument("--alternatives", default=None, help="with --pred_dir map.pkl: the pickle of run_sequence.py "
+                    "--map_alternatives_output for the same frames; adds the best-of-two MPJPE (pose or runner-up) and "
+                    "spearman(error, runner-up margin); without --gt only the margins are summarised")
     ap.add_argument("--bones", nargs="?", const="", default=None, metavar="FILE.npy",
                     help="bone-length summary of the predictions (needs no ground truth): the per-bone standard deviation over the "
                     "sequence and, with FILE.npy (14 or 15 lengths, as run_sequence.py --bone_lengths takes them), the mean absolute "
@@ -167,9 +204,19 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     names, pred = load_predictions(args.pred_dir)
     if args.gt is None:
-        if args.bones is None:
-            raise SystemExit("--gt is required (only --bones works without it)")
-        return {"frames": int(pred.shape[0]), "bones": bones(pred, args.bones, args.unit)}
+        if args.bones is None and args.alternatives is None:
+            raise SystemExit("--gt is required (only --bones and --alternatives work without it)")
+        r = {"frames": int(pred.shape[0])}
+        if args.alternatives is not None:
+            margins = np.array([float(fr["runner_up_margin"]) for fr in load_alternatives(args.alternatives, len(names))])
+            ok = np.isfinite(margins)
+            r["alternatives"] = {"mean_runner_up_margin": float(margins[ok].mean()) if ok.any() else float("nan"),
+                                 "below_ln2_share": float((margins < np.log(2.0)).mean()), "frames_with_margin": int(ok.sum())}
+            print("runner-up margin: mean {mean_runner_up_margin:.4f} over {frames_with_margin} frames, {below_ln2_share:.1%} below "
+                  "ln 2".format(**r["alternatives"]))
+        if args.bones is not None:
+            r["bones"] = bones(pred, args.bones, args.unit)
+        return r
     with open(args.gt, "rb") as f:
         gt = match_ground_truth(pickle.load(f), names)
     r = evaluate(pred, gt, scale=not args.no_scale)
@@ -190,6 +237,11 @@ def main(argv=None):
         r.update(best_of_k(load_modes(args.modes, names), pred, gt))
         print(f"best-of-K MPJPE {r['best_of_k_mpjpe']:.6f} {args.unit} (the closest valid mode of every joint); the best mode is not "
               f"mode 0 in {r['best_not_first_share']:.1%} of {r['joints_with_modes']} joints")
+    if args.alternatives is not None:
+        a = r["alternatives"] = best_of_two(load_alternatives(args.alternatives, len(names)), pred, gt)
+        print(f"best-of-two MPJPE {a['best_of_two_mpjpe']:.6f} {args.unit} (the pose or its runner-up, whichever is closer; the runner-up "
+              f"in {a['runner_up_closer_share']:.1%} of the frames); spearman(error, runner-up margin): {a['spearman_error_margin']:.4f} "
+              f"over {a['frames_with_margin']} frames")
     if args.bones is not None:
         r["bones"] = bones(pred, args.bones, args.unit)
     return r

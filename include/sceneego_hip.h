@@ -980,6 +980,55 @@ int se_skeleton_pose_f32(const float* prob, const float* taps, const int* parent
                          int R, float floor, void* stream);
 long long se_skeleton_pose_scratch_bytes(int frames, int J, int G, int R);
 
+/* Runner-up poses: the downward max-product pass that goes with se_skeleton_pose_f32, as the downward sum-product pass goes with the
+ * upward one in se_skeleton_couple_f32 (sceneego_amd/skeleton_pose.py: SkeletonPose.alternatives).  It gives for every joint and voxel
+ * the MAX-MARGINAL, the score of the best whole pose that puts that joint there, and from it per joint (the ANCHOR) the best pose that
+ * places the anchor outside a window around its voxel in the most probable pose.  Model, arguments, arithmetic and the ROW MAX rule are
+ * se_skeleton_pose_f32's; tests/skeleton_alternatives_model.py restates the definition in numpy float32 and every output is compared
+ * with it BIT FOR BIT.   separation = S >= 0: the half-width of the window, in voxels.
+ * UPWARD     se_skeleton_pose_f32's pass, unchanged: A_j, M_j at peak_j, e_j, s_j = ldexpf(A_j, -e_j), m_j, the pose x*_j, solved.
+ * DOWNWARD   joints by depth level, shallowest first; d_0 is absent.
+ *            mu_0 = s_0;  mu_j = s_j * d_j for j > 0, one rounding: the max-marginal of j, scaled.
+ *            Per child c of j:  E_c = p_j, then times d_j if j > 0, then times m_c' for every OTHER child c' of j in ascending order:
+ *            one rounding per factor, left to right.   G_c = max E_c at epeak_c (ROW MAX),  q_c = ilogb(G_c),
+ *            t_c = ldexpf(E_c, -q_c),  tbest_c = ldexpf(G_c, -q_c).   e3(y) = max over d with w_c(d) != 0 and y + d inside the grid of
+ *            t_c(y + d) * w_c(d), with the lowest attaining tap d* (MESSAGE above: the same operator on the same block of taps, which
+ *            is the transposed edge for taps with w_c(d) = w_c(-d), as sceneego_amd.skeleton_prior.shell_taps builds them; not checked).
+ *            step = keep * e3(y),  jump = uniform * tbest_c,  d_c(y) = jump > step ? jump : step.  The parent voxel behind d_c(y) is
+ *            epeak_c for a jump, otherwise y + d* (epeak_c where step = jump = 0: not reached from a value > 0).
+ * EXPONENTS  returned as integers for the caller to sum:  Esub_j = e_j + sum over the children c of Esub_c;  F_0 = 0,
+ *            F_c = F_parent(c) + q_c + sum over the siblings c' != c of Esub_c'.  The natural logarithm of the max-marginal of j at x is
+ *            ln mu_j(x) + ln 2 * (Esub_j + F_j); in exact arithmetic its maximum over x is the log score of the pose, for every j.
+ * RECORDS    mm_best_a at mm_peak_a: the ROW MAX of mu_a;  pose_value_a = mu_a(x*_a);  alt_value_a at alt_index_a: the ROW MAX of mu_a
+ *            over the voxels whose Chebyshev distance in voxel indices from x*_a is > S (alt_index -1, alt_value 0: none is > 0).
+ * WALK       anchor a with alt_index_a >= 0:  x_a = alt_index_a; up to the root, the parent of u takes the parent voxel behind d_u at
+ *            x_u; then for j = 1..J-1 ascending and not yet set x_j is the predecessor of upward edge j at x_parent(j) (BACK-WALK
+ *            above).  alt_jumped[a][j] = 1 where the edge parent[j] -> j was taken as a jump, in either direction.  In exact arithmetic
+ *            this is the best pose with joint a outside the window and its score is alt_value_a with its exponent.  An anchor with
+ *            alt_index -1 has an alt_pose row of -1.
+ * FALLBACK   a frame that is not solved keeps se_skeleton_pose_f32's fallback outputs.  Such a frame, or one in which some G_c is not a
+ *            finite number > 0, is not complete: complete = 0, alt_index, mm_peak and alt_pose -1, alt_value, mm_best and pose_value
+ *            NaN, down_exponent and alt_jumped 0, its max_marginals rows p copied bit for bit.  Other frames are unaffected.  A single
+ *            NaN cell does not cause this.
+ *   index, jumped, exponent, best_root, solved: as se_skeleton_pose_f32 writes them, identical bits
+ *   down_exponent [frames][J] int32: q_j (q_0 = 0)      mm_best, pose_value, alt_value [frames][J] float32
+ *   mm_peak, alt_index [frames][J] int32                alt_pose, alt_jumped [frames][J][J] int32 (anchor, joint)
+ *   complete   [frames] int32                           max_marginals [frames][J][voxels] float32 or NULL: mu_j as computed
+ *   scratch    se_skeleton_alternatives_scratch_bytes(frames, J, G, R) bytes, 4-byte aligned; 0 for a shape out of range.  About
+ *              4 J G^3 floats (A, m, E, d) for each of min(frames, 4) frames.
+ * After the upward launches: per level below the root one product pass over all its (parent, child) pairs and frames, a fold of its
+ * records and one max-correlation launch (the kernel and the instantiation of the upward pass: 2 (J - 1) max-correlations per frame in
+ * all); then one record pass over mu, its fold, and the walks of all anchors side by side (grid anchors x frames).  No atomics and no
+ * sums: bitwise identical from run to run and independent of how frames are batched into calls.  Allocates nothing.
+ * SE_ERR_BAD_ARG, with nothing launched: as se_skeleton_pose_f32 (max_marginals may be NULL), separation < 0, max_marginals == prob,
+ * scratch_bytes below se_skeleton_alternatives_scratch_bytes(frames, J, G, R).                                                       */
+int se_skeleton_alternatives_f32(const float* prob, const float* taps, const int* parent, int separation, int* index, int* jumped,
+                                 int* exponent, float* best_root, int* solved, int* down_exponent, float* mm_best, float* pose_value,
+                                 float* alt_value, int* mm_peak, int* alt_index, int* alt_pose, int* alt_jumped, int* complete,
+                                 float* max_marginals, void* scratch, long long scratch_bytes, int frames, int J, int voxels, int G,
+                                 int R, float floor, void* stream);
+long long se_skeleton_alternatives_scratch_bytes(int frames, int J, int G, int R);
+
 /* Baseline JPEG encoder (no counterpart in the reference; sceneego_amd/jpeg_encode.py writes the file headers around it).
  *   frames    uint8 [batch][height][width][3] on the device, R, G, B (bgr = 0) or B, G, R (bgr = 1); any height, width in 1..65535
  *   quant_luma, quant_chroma   HOST pointers: unsigned short [64], natural order, every value in 1..255 (baseline tables)

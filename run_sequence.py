@@ -14,6 +14,7 @@
                            [--skeleton_output out/skeleton.pkl [--skeleton_info_output out/skeleton_info.pkl] [--bone_lengths FILE.npy]
                             [--bone_frames 64] [--skeleton_tau 0.03] [--skeleton_floor 1e-3]] [--render_volumes coupled]
                            [--map_output out/map.pkl [--map_info_output out/map_info.pkl] [--map_refine 1]]
+                           [--map_alternatives_output out/alt.pkl [--map_separation 2]]
                            [--fit_frames 64 [--fit_iterations 8] [--fit_output out/fit.json]]
                            [--skeleton_fit_frames 64 [--skeleton_fit_iterations 8] [--skeleton_fit_output out/skeleton_fit.json]]
 
@@ -72,6 +73,11 @@ the batch ran on; each pose voxel is refined to the centroid of its joint's volu
 default 1).  ``--bone_lengths``, ``--bone_frames``, ``--skeleton_tau`` and ``--skeleton_floor`` are used exactly as ``--skeleton_output``
 uses them.  ``--map_info_output`` adds the per-frame dicts (joints, index, coord, jumped, solved, log_score, bone_error, shift,
 bone_error_before).  ``evaluate.py --pred_dir map.pkl [--bones]`` reads the file.  The pose is all-or-nothing where the marginals hedge.
+``--map_alternatives_output`` says how close the second-best pose was (``SkeletonPose.alternatives``: the downward max-product pass;
+it implies the ``--map_*`` model options and runs in place of ``solve``, with the same pose bit for bit): a pickle of per-frame dicts
+with the pose's entries and, per joint, the log margin to the best pose that places it more than ``--map_separation`` voxels (default
+2) away, that pose, and the runner-up pose of the frame; prints the mean runner-up margin and the share of frames below ln 2.
+``evaluate.py --pred_dir map.pkl --alternatives alt.pkl [--gt gt.pkl]`` reads it.  A convention of its own: a window on one joint.
 ``--path_output`` writes a pickle in the format of ``--output`` whose joints lie on the most probable trajectory of every joint through
 the sequence's volumes (``VoxelNetwork_depth.volume_path``, ``sceneego_amd/volume_viterbi.py``: the max-product pass on the filter's
 motion model, ``--filter_sigma``, ``--filter_radius`` and ``--filter_floor``): every batch is pushed on the stream it ran on, the
@@ -330,11 +336,13 @@ class SequenceRunner:
         ``sigma`` / ``radius`` / ``floor`` / ``refine`` / ``max_bytes`` for ``VoxelNetwork_depth.volume_path``: every batch's volumes
         (with ``skeleton`` the coupled beliefs) are pushed on the stream the batch ran on, and the per-frame dicts of its ``finish()``
         are appended after those.  ``map_pose``: a dict of ``bone_lengths`` / ``tau`` / ``floor`` / ``refine`` for
-        ``VoxelNetwork_depth.skeleton_pose``: the most probable pose of every frame is taken from the batch's raw volumes on the stream
+        ``VoxelNetwork_depth.skeleton_pose``, and optionally ``separation`` (then ``SkeletonPose.alternatives`` runs in place of
+        ``solve`` and the dicts carry its entries too): the most probable pose of every frame is taken from the batch's raw volumes on the stream
         the batch ran on and the per-frame pose dicts are appended last."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
-                                     skeleton_couple_to_numpy, skeleton_pose_to_numpy, volume_filter_to_numpy, volume_path_to_numpy,
+                                     skeleton_alternatives_to_numpy, skeleton_couple_to_numpy, skeleton_pose_to_numpy,
+                                     volume_filter_to_numpy, volume_path_to_numpy,
                                      volume_smoother_to_numpy)
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
@@ -351,13 +359,17 @@ class SequenceRunner:
             raise ValueError("render_coupled needs skeleton and render_volumes, and excludes render_filtered")
         sp = self.net.skeleton_prior(**skeleton) if skeleton is not None else None
         vp = self.net.volume_path(**path) if path is not None else None
-        mpose = self.net.skeleton_pose(**map_pose) if map_pose is not None else None
+        separation = map_pose.get("separation") if map_pose is not None else None
+        mpose = self.net.skeleton_pose(**{k: v for k, v in map_pose.items() if k != "separation"}) if map_pose is not None else None
 
         def couple_and_filter(vol, kp, job, stream=None):
             """The most probable pose (from the raw volumes), the skeleton coupling and the filter of one batch, in that order:
             (filter dict, skeleton dict, job, pose dict)."""
             fr = sk = None
-            mp = mpose.solve(vol, joints=kp, stream=stream) if mpose is not None else None
+            mp = None
+            if mpose is not None:                                        # alternatives: the pose with the same bits, and the runner-up
+                mp = mpose.solve(vol, joints=kp, stream=stream) if separation is None else \
+                    mpose.alternatives(vol, separation=separation, joints=kp, stream=stream)
             if sp is not None:
                 sk = sp.couple(vol, joints=kp, return_beliefs=vf is not None or vp is not None or (render_coupled and job is not None),
                                stream=stream)
@@ -411,7 +423,7 @@ class SequenceRunner:
                 if sk is not None:
                     frame_skeleton.extend(skeleton_couple_to_numpy(sk))
                 if mp is not None:
-                    frame_map.extend(skeleton_pose_to_numpy(mp))
+                    frame_map.extend(skeleton_pose_to_numpy(mp) if separation is None else skeleton_alternatives_to_numpy(mp))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -575,6 +587,12 @@ def build_parser():
                     "calibrated)")
     ap.add_argument("--map_info_output", default=None, help="pickle of the per-frame pose dicts (list of dicts of numpy arrays: joints, "
                     "index, coord, jumped, solved, log_score, bone_error, shift, bone_error_before)")
+    ap.add_argument("--map_alternatives_output", default=None, help="pickle of the per-frame dicts of SkeletonPose.alternatives (the pose "
+                    "dicts of --map_info_output and margin, alt_log_score, alt_index, alt_coord, alt_pose_index, alt_pose_jumped, "
+                    "alt_pose_joints, max_marginal_peak_index, pose_is_peak, runner_up, runner_up_joints, runner_up_margin, "
+                    "runner_up_bone_error): how close the second-best pose was; implies the --map_* model options")
+    ap.add_argument("--map_separation", type=int, default=None, help="with --map_alternatives_output: an alternative places its anchor "
+                    "joint more than this many voxels (Chebyshev, default 2) from the joint's voxel in the most probable pose")
     ap.add_argument("--map_refine", type=int, default=None, help="with --map_output: each pose voxel is refined to the centroid of its "
                     "joint's volume over a window of this many voxels around it (0..3, default 1; 0: the voxel centre)")
     ap.add_argument("--bone_lengths", default=None, help="a .npy of 14 bone lengths in metres (edges 1..14 of the kinematic tree) or 15 "
@@ -674,9 +692,13 @@ def parse_args(argv=None):
     if args.bone_frames < 1:
         raise SystemExit("--bone_frames must be >= 1")
     args.skeleton = args.skeleton_output is not None or args.skeleton_info_output is not None or args.render_coupled
-    args.map = args.map_output is not None or args.map_info_output is not None
+    args.map = args.map_output is not None or args.map_info_output is not None or args.map_alternatives_output is not None
     if args.map_refine is not None and not args.map:
         raise SystemExit("--map_refine needs --map_output")
+    if args.map_separation is not None and args.map_alternatives_output is None:
+        raise SystemExit("--map_separation needs --map_alternatives_output")
+    if args.map_separation is not None and args.map_separation < 0:
+        raise SystemExit("--map_separation must be >= 0")
     if args.map_refine is not None and not 0 <= args.map_refine <= 3:
         raise SystemExit("--map_refine must be in 0..3")
     if args.track_output is not None and args.modes_output is None:
@@ -750,6 +772,8 @@ def main(argv=None):
             skeleton = {"bone_lengths": lengths, "tau": tau, "floor": floor}
         if args.map:
             map_pose = {"bone_lengths": lengths, "tau": tau, "floor": floor, "refine": 1 if args.map_refine is None else args.map_refine}
+            if args.map_alternatives_output is not None:
+                map_pose["separation"] = 2 if args.map_separation is None else args.map_separation
     fitted = None
     if args.fit is not None:
         # a first pass over the first --fit_frames consecutive frames: EM for sigma and floor at the fixed radius
@@ -919,7 +943,11 @@ def main(argv=None):
                   int(sum(fr["index"].size for fr in frame_path))))
     if map_pose is not None:
         posed = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_map]
-        for path, obj in ((args.map_output, posed), (args.map_info_output, frame_map)):
+        frame_alternatives = frame_map if "separation" in map_pose else None
+        if frame_alternatives is not None:                               # the pose dicts are the leading entries
+            from sceneego_amd.op import POSE_KEYS
+            frame_map = [{k: fr[k] for k in POSE_KEYS + ("shift", "bone_error_before")} for fr in frame_alternatives]
+        for path, obj in ((args.map_output, posed), (args.map_info_output, frame_map), (args.map_alternatives_output, frame_alternatives)):
             if path is not None:
                 os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
                 with open(path, "wb") as f:
@@ -934,6 +962,15 @@ def main(argv=None):
                   float(np.mean([fr["bone_error_before"] for fr in frame_map])), float(np.nanmean([fr["bone_error"] for fr in frame_map])),
                   bones, int(sum(fr["jumped"].sum() for fr in frame_map)), int(sum(fr["index"].size for fr in frame_map)),
                   int(sum(not fr["solved"] for fr in frame_map))))
+        if frame_alternatives is not None:
+            margins = np.array([fr["runner_up_margin"] for fr in frame_alternatives], dtype=np.float64)
+            result["map_alternatives"] = frame_alternatives
+            result["map_runner_up_margin"] = float(np.mean(margins[np.isfinite(margins)])) if np.isfinite(margins).any() else float("nan")
+            result["map_runner_up_close"] = float(np.mean(margins < np.log(2.0)))
+            print("runner-up pose (separation {} voxels; a convention, not calibrated): mean runner-up margin {:.4f}, {:.1%} of {} frames "
+                  "below ln 2, {} frames not complete".format(map_pose["separation"], result["map_runner_up_margin"],
+                                                              result["map_runner_up_close"], len(margins),
+                                                              int(sum(not fr["complete"] for fr in frame_alternatives))))
     return result
 
 

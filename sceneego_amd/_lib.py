@@ -7,6 +7,7 @@ is not on a HIP device, the call raises.
 from __future__ import annotations
 
 import ctypes
+import numbers
 import os
 
 import torch
@@ -133,6 +134,8 @@ SIGNATURES = {
     "se_shell_argmax_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "se_skeleton_pose_scratch_bytes": (_ll, [_i, _i, _i, _i]),
     "se_skeleton_pose_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
+    "se_skeleton_alternatives_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_skeleton_alternatives_f32": (_i, [_vp, _vp, _vp, _i] + [_vp] * 16 + [_ll, _i, _i, _i, _i, _i, _f, _vp]),
 }
 # present only in development builds (csrc/build.sh --devtools): A/B kernel selection and cycle-stamp diagnostics (tools/)
 DEVTOOLS_SIGNATURES = {
@@ -1618,6 +1621,50 @@ def skeleton_pose(prob, taps, parents, index, jumped, exponent, best_root, solve
     _check(load().se_skeleton_pose_f32(_ptr(prob), _ptr(taps), ctypes.cast(par, ctypes.c_void_p), _ptr(index), _ptr(jumped),
                                        _ptr(exponent), _ptr(best_root), _ptr(solved), _ptr(scratch), scratch.numel(), frames, J, voxels,
                                        grid, radius, floor, _stream()), "se_skeleton_pose_f32")
+    return index, jumped, exponent, best_root, solved
+
+
+ALTERNATIVES_OUTPUTS = ("index", "jumped", "exponent", "best_root", "solved", "down_exponent", "mm_best", "pose_value", "alt_value",
+                        "mm_peak", "alt_index", "alt_pose", "alt_jumped", "complete")
+
+
+def skeleton_alternatives_scratch_bytes(frames, joints, grid, radius) -> int:
+    return int(load().se_skeleton_alternatives_scratch_bytes(int(frames), int(joints), int(grid), int(radius)))
+
+
+def skeleton_alternatives(prob, taps, parents, separation, index, jumped, exponent, best_root, solved, down_exponent, mm_best, pose_value,
+                          alt_value, mm_peak, alt_index, alt_pose, alt_jumped, complete, frames, voxels, grid, radius, floor,
+                          max_marginals=None, scratch=None):
+    """se_skeleton_alternatives_f32: the upward pass of ``skeleton_pose`` and the downward max-product pass behind it (the header
+    states the definition), with the window half-width ``separation`` (an int >= 0).  Written: ``index``, ``jumped``, ``exponent``
+    [frames, J] int32, ``best_root`` [frames] float32 and ``solved`` [frames] int32 as by ``skeleton_pose``; ``down_exponent``,
+    ``mm_peak``, ``alt_index`` [frames, J] int32; ``mm_best``, ``pose_value``, ``alt_value`` [frames, J] float32; ``alt_pose``,
+    ``alt_jumped`` [frames, J, J] int32; ``complete`` [frames] int32; ``max_marginals`` None or [frames, J, voxels] float32.
+    ``scratch``: an optional uint8 workspace of at least ``skeleton_alternatives_scratch_bytes(frames, J, grid, radius)`` bytes.  Every
+    argument is checked here and a bad one raises HipExtensionError before anything is launched."""
+    what = "skeleton_alternatives"
+    parents, J, frames, voxels, grid, radius, floor = _tree_args(what, parents, frames, voxels, grid, radius, floor)
+    if isinstance(separation, bool) or not isinstance(separation, numbers.Integral) or separation < 0:
+        raise HipExtensionError(f"{what}: separation = {separation!r} (an integer >= 0) expected")
+    i32, f32, FJ = torch.int32, torch.float32, frames * J
+    dev = _check_args(what, (("prob", prob, f32, FJ * voxels), ("taps", taps, f32, J * (2 * radius + 1) ** 3),
+                             ("index", index, i32, FJ), ("jumped", jumped, i32, FJ), ("exponent", exponent, i32, FJ),
+                             ("best_root", best_root, f32, frames), ("solved", solved, i32, frames),
+                             ("down_exponent", down_exponent, i32, FJ), ("mm_best", mm_best, f32, FJ), ("pose_value", pose_value, f32, FJ),
+                             ("alt_value", alt_value, f32, FJ), ("mm_peak", mm_peak, i32, FJ), ("alt_index", alt_index, i32, FJ),
+                             ("alt_pose", alt_pose, i32, FJ * J), ("alt_jumped", alt_jumped, i32, FJ * J),
+                             ("complete", complete, i32, frames)),
+                      (("max_marginals", max_marginals, f32, FJ * voxels), ("scratch", scratch, torch.uint8, None)))
+    if max_marginals is not None and _overlap(max_marginals, prob):
+        raise HipExtensionError(f"{what}: max_marginals must not alias prob")
+    scratch = _scratch(what, scratch, skeleton_alternatives_scratch_bytes(frames, J, grid, radius), torch.uint8, dev)
+    par = (ctypes.c_int * J)(*parents)
+    _check(load().se_skeleton_alternatives_f32(_ptr(prob), _ptr(taps), ctypes.cast(par, ctypes.c_void_p), int(separation), _ptr(index),
+                                               _ptr(jumped), _ptr(exponent), _ptr(best_root), _ptr(solved), _ptr(down_exponent),
+                                               _ptr(mm_best), _ptr(pose_value), _ptr(alt_value), _ptr(mm_peak), _ptr(alt_index),
+                                               _ptr(alt_pose), _ptr(alt_jumped), _ptr(complete), _ptr(max_marginals), _ptr(scratch),
+                                               scratch.numel(), frames, J, voxels, grid, radius, floor, _stream()),
+           "se_skeleton_alternatives_f32")
     return index, jumped, exponent, best_root, solved
 
 

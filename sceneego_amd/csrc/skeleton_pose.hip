@@ -27,6 +27,8 @@
 //                       multiplications, so the same bits, under the order "greater value, then lower tap index".  One voxel per
 //                       edge and frame: no J N back-pointer volume, no compare and selects in the hot loop.
 // se_shell_maxcorr_f32 and se_shell_argmax_i32 run sp_maxcorr_kernel and sp_argmax on stand-alone rows.
+// se_skeleton_alternatives_f32 adds the downward pass on the same kernels (below, at sa_down_kernel): the max-marginals, per joint the
+// best pose that moves it out of a window, with E and d beside A and m in the scratch (tests/skeleton_alternatives_model.py).
 // ORDER.  No atomics, no sums: every result is a product, a comparison or a selection under a total order (row_reduce.h: peak_combine),
 // so the results are bitwise identical from run to run and do not depend on how frames are batched into calls or groups.
 // Scratch per frame in flight: A and m, 2 J N floats, the chunk records and the folded records; frames are walked in groups of SK_GROUP.
@@ -228,12 +230,31 @@ __global__ __launch_bounds__(SP_AT) void sp_argmax_kernel(const float* __restric
     if (threadIdx.x == 0) { out_tap[o] = pk.idx == INT_MAX ? -1 : pk.idx; out_value[o] = pk.p; }
 }
 
+// The calling workgroup (SK_THREADS threads, all of them): the two running maxima of its chunk folded into one record at w.
+__device__ __forceinline__ void sp_chunk_record(Peak pa, Peak pp, int* __restrict__ w) {
+    __shared__ float sm_p[4][2];
+    __shared__ int sm_i[4][2];
+    const int t = threadIdx.x;
+    pa = wave_reduce_peak(pa);
+    pp = wave_reduce_peak(pp);
+    if ((t & 63) == 0) {
+        sm_p[t >> 6][0] = pa.p; sm_i[t >> 6][0] = pa.idx;
+        sm_p[t >> 6][1] = pp.p; sm_i[t >> 6][1] = pp.idx;
+    }
+    __syncthreads();
+    if (t < 2) {
+        Peak r = {sm_p[0][t], sm_i[0][t]};
+#pragma unroll
+        for (int x = 1; x < 4; ++x) r = peak_combine(r, Peak{sm_p[x][t], sm_i[x][t]});
+        w[2 * t + 0] = __float_as_int(r.p);
+        w[2 * t + 1] = r.idx;
+    }
+}
+
 // grid (CH, rows.n * frames), block 256.  prob, A, m [frames][J][N]; part [frames][J][CH][SP_REC]
 __global__ __launch_bounds__(SK_THREADS) void sp_product_kernel(const float* __restrict__ prob, const float* __restrict__ m,
                                                                 float* __restrict__ A, int* __restrict__ part, SkTree tree, SkRows rows,
                                                                 int voxels) {
-    __shared__ float sm_p[4][2];
-    __shared__ int sm_i[4][2];
     const int t = threadIdx.x, f = blockIdx.y / rows.n, J = tree.J, j = rows.slot[blockIdx.y % rows.n];
     const size_t fb = (size_t)f * J * voxels;
     const float* p = prob + fb + (size_t)j * voxels;
@@ -249,21 +270,7 @@ __global__ __launch_bounds__(SK_THREADS) void sp_product_kernel(const float* __r
         if (v > 0.f) pa = peak_combine(pa, Peak{v, n});
         if (pv > 0.f) pp = peak_combine(pp, Peak{pv, n});
     }
-    pa = wave_reduce_peak(pa);
-    pp = wave_reduce_peak(pp);
-    if ((t & 63) == 0) {
-        sm_p[t >> 6][0] = pa.p; sm_i[t >> 6][0] = pa.idx;
-        sm_p[t >> 6][1] = pp.p; sm_i[t >> 6][1] = pp.idx;
-    }
-    __syncthreads();
-    if (t < 2) {
-        Peak r = {sm_p[0][t], sm_i[0][t]};
-#pragma unroll
-        for (int x = 1; x < 4; ++x) r = peak_combine(r, Peak{sm_p[x][t], sm_i[x][t]});
-        int* w = part + (((size_t)f * J + j) * gridDim.x + blockIdx.x) * SP_REC + 2 * t;
-        w[0] = __float_as_int(r.p);
-        w[1] = r.idx;
-    }
+    sp_chunk_record(pa, pp, part + (((size_t)f * J + j) * gridDim.x + blockIdx.x) * SP_REC);
 }
 
 // grid (rows.n, frames), block 64.  rec [frames][J][SP_REC]
@@ -282,6 +289,18 @@ __global__ __launch_bounds__(64) void sp_fold_kernel(const int* __restrict__ par
         int* o = rec + row * SP_REC;
         o[0] = __float_as_int(a.p); o[1] = a.idx; o[2] = __float_as_int(p.p); o[3] = p.idx;
     }
+}
+
+// The voxel behind the message of a row at voxel x: pk = sp_argmax there, sc the scale of the row's maximum, peak its voxel.
+__device__ __forceinline__ int sp_behind(Peak pk, SpScale sc, int peak, int x, int G, int R, float keep, float uniform, int& jumped) {
+    const int W = 2 * R + 1;
+    const float step = keep * pk.p, jump = uniform * sc.best;
+    jumped = 1;
+    if (jump > step) return peak;
+    jumped = 0;
+    if (pk.idx == INT_MAX) return peak;                                  // step = jump = 0: not reached from a value > 0
+    const int d = pk.idx;                                                // the lowest attaining tap: the lowest voxel
+    return ((x / (G * G) + d / (W * W) - R) * G + (x / G % G + d / W % W - R)) * G + (x % G + d % W - R);
 }
 
 // grid (frames), block SP_AT.  Outputs at the call's frame f0 + frame.
@@ -321,15 +340,8 @@ __global__ __launch_bounds__(SP_AT) void sp_walk_kernel(const float* __restrict_
         const SpScale sc = sp_scale(__int_as_float(rf[j * SP_REC]));
         const Peak pk = sp_argmax(A + ((size_t)f * J + j) * N, taps + (size_t)j * W * W * W, G, R, xp, -sc.e, sm_p, sm_i);
         if (t == 0) {
-            const float step = keep * pk.p, jump = uniform * sc.best;
-            int x = rf[j * SP_REC + 1], jmp = 1;                         // peak_j
-            if (!(jump > step)) {
-                jmp = 0;
-                if (pk.idx != INT_MAX) {                                 // the lowest attaining tap: the lowest child voxel
-                    const int d = pk.idx;
-                    x = ((xp / (G * G) + d / (W * W) - R) * G + (xp / G % G + d / W % W - R)) * G + (xp % G + d % W - R);
-                }                                                        // else step = jump = 0: not reached in a solved frame; peak_j
-            }
+            int jmp;
+            const int x = sp_behind(pk, sc, rf[j * SP_REC + 1], xp, G, R, keep, uniform, jmp);
             pose[j] = x; oi[j] = x; oj[j] = jmp; oe[j] = sc.e;
         }
     }
@@ -338,6 +350,170 @@ __global__ __launch_bounds__(SP_AT) void sp_walk_kernel(const float* __restrict_
 inline long long sp_frame_words(int J, int G) {
     const long long N = (long long)G * G * G;
     return 2 * J * N + (long long)J * sk_chunks((int)N) * SP_REC + (long long)J * SP_REC;
+}
+
+// The upward pass of nf frames, shared by se_skeleton_pose_f32 and se_skeleton_alternatives_f32: A, m and the folded records, then the
+// back-walk into the outputs (already at the group's first frame).
+inline int sp_upward(hipStream_t st, const float* p, const float* taps, float* A, float* m, int* part, int* rec, const int* runs,
+                     const SkTree& tree, const int* depth, int deepest, int nf, int voxels, int G, int R, float keep, float uniform,
+                     int* index, int* jumped, int* exponent, float* best_root, int* solved) {
+    const int J = tree.J, CH = sk_chunks(voxels), lds = sk_lds_bytes(R);
+    for (int d = deepest; d >= 0; --d) {
+        SkRows level{};
+        for (int j = 0; j < J; ++j)
+            if (depth[j] == d) level.slot[level.n++] = (unsigned char)j;
+        hipLaunchKernelGGL(sp_product_kernel, dim3(CH, level.n * nf), dim3(SK_THREADS), 0, st, p, m, A, part, tree, level, voxels);
+        SE_CHECK_LAUNCH();
+        hipLaunchKernelGGL(sp_fold_kernel, dim3(level.n, nf), dim3(64), 0, st, part, rec, level, J, CH);
+        SE_CHECK_LAUNCH();
+        if (d > 0) {                                                     // every joint of a level below the root sends a message
+            hipLaunchKernelGGL(sp_maxcorr_kernel, sk_corr_grid(G, level.n * nf), dim3(SK_THREADS), lds, st, A, taps, nullptr, rec, m,
+                               runs, level, J, J, G, R, keep, uniform);
+            SE_CHECK_LAUNCH();
+        }
+    }
+    hipLaunchKernelGGL(sp_walk_kernel, dim3(nf), dim3(SP_AT), 0, st, A, taps, rec, index, jumped, exponent, best_root, solved, tree, G, R,
+                       keep, uniform);
+    SE_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Runner-up poses (se_skeleton_alternatives_f32): the downward max-product pass.  After the upward pass, joints by depth level,
+// shallowest first:
+//   sa_down_kernel      grid (CH, children of the level x frames): E_c = p_j [d_j] prod m_c', the siblings ascending, one rounding per
+//                       factor; per chunk one record (max E, lowest index, -, -).  sp_fold_kernel folds them: G_c at epeak_c.
+//   sp_maxcorr_kernel   the upward launch with E for A and the G_c records for the M_j records: d_c.  The same instantiation.
+// then, once per group of frames:
+//   sa_mu_kernel        grid (CH, J x frames): mu_j = s_j d_j (mu_0 = s_0), written out if asked for; per chunk one record (max mu,
+//                       lowest index, max mu outside the window around x*_j, lowest index).  sp_fold_kernel folds them.
+//   sa_walk_kernel      grid (anchors, frames), block SP_AT: the outputs of one anchor and its alternative pose, up along the
+//                       downward edges and down along the upward ones, every step recomputed by sp_argmax as in sp_walk_kernel.
+// A frame is complete when every M_j and every G_c is a finite number > 0 (sa_complete, uniform per workgroup).
+__device__ __forceinline__ bool sa_complete(const int* __restrict__ rf, const int* __restrict__ ef, int J) {
+    bool ok = sp_scale(__int_as_float(rf[0])).alive;
+    for (int c = 1; c < J; ++c) ok = ok && sp_scale(__int_as_float(rf[c * SP_REC])).alive && sp_scale(__int_as_float(ef[c * SP_REC])).alive;
+    return ok;
+}
+
+// grid (CH, rows.n * frames), block 256; rows: the children c of a level.  prob, m, d, E [frames][J][N]
+__global__ __launch_bounds__(SK_THREADS) void sa_down_kernel(const float* __restrict__ prob, const float* __restrict__ m,
+                                                             const float* __restrict__ d, float* __restrict__ E, int* __restrict__ part,
+                                                             SkTree tree, SkRows rows, int voxels) {
+    const int t = threadIdx.x, f = blockIdx.y / rows.n, J = tree.J, c = rows.slot[blockIdx.y % rows.n], j = tree.parent[c];
+    const size_t fb = (size_t)f * J * voxels;
+    const float* p = prob + fb + (size_t)j * voxels;
+    const float* dj = d + fb + (size_t)j * voxels;
+    float* o = E + fb + (size_t)c * voxels;
+    const int chunk = sk_chunk(voxels), c0 = blockIdx.x * chunk, c1 = min(c0 + chunk, voxels);
+    Peak pa = {0.f, INT_MAX};
+    for (int n = c0 + t; n < c1; n += SK_THREADS) {
+        float v = p[n];
+        if (j > 0) v *= dj[n];
+        for (int s = j + 1; s < J; ++s)                                  // the other children in ascending order (uniform)
+            if (tree.parent[s] == j && s != c) v *= m[fb + (size_t)s * voxels + n];
+        o[n] = v;
+        if (v > 0.f) pa = peak_combine(pa, Peak{v, n});
+    }
+    sp_chunk_record(pa, Peak{0.f, INT_MAX}, part + (((size_t)f * J + c) * gridDim.x + blockIdx.x) * SP_REC);
+}
+
+// grid (CH, J * frames), block 256.  index and mm (NULL: not asked for) at the group's first frame.
+__global__ __launch_bounds__(SK_THREADS) void sa_mu_kernel(const float* __restrict__ prob, const float* __restrict__ A,
+                                                           const float* __restrict__ d, const int* __restrict__ rec,
+                                                           const int* __restrict__ erec, const int* __restrict__ index,
+                                                           float* __restrict__ mm, int* __restrict__ part, int J, int voxels, int G,
+                                                           int separation) {
+    const int t = threadIdx.x, f = blockIdx.y / J, j = blockIdx.y % J;
+    const size_t row = (size_t)f * J + j, rb = row * voxels;
+    const int chunk = sk_chunk(voxels), c0 = blockIdx.x * chunk, c1 = min(c0 + chunk, voxels);
+    if (!sa_complete(rec + (size_t)f * J * SP_REC, erec + (size_t)f * J * SP_REC, J)) {      // uniform: the row is p, bit for bit
+        if (mm)
+            for (int n = c0 + t; n < c1; n += SK_THREADS) mm[rb + n] = prob[rb + n];
+        return;
+    }
+    const int down = -sp_scale(__int_as_float(rec[row * SP_REC])).e;
+    const int xs = min(max(index[row], 0), voxels - 1);                  // x*_j: a voxel in a solved frame
+    const int xi = xs / (G * G), xj = xs / G % G, xk = xs % G;
+    Peak pa = {0.f, INT_MAX}, pw = {0.f, INT_MAX};
+    for (int n = c0 + t; n < c1; n += SK_THREADS) {
+        float v = ldexpf(A[rb + n], down);
+        if (j > 0) v *= d[rb + n];
+        if (mm) mm[rb + n] = v;
+        if (v > 0.f) {
+            pa = peak_combine(pa, Peak{v, n});
+            const int far = max(max(abs(n / (G * G) - xi), abs(n / G % G - xj)), abs(n % G - xk));
+            if (far > separation) pw = peak_combine(pw, Peak{v, n});
+        }
+    }
+    sp_chunk_record(pa, pw, part + (row * gridDim.x + blockIdx.x) * SP_REC);
+}
+
+// grid (J, frames), block SP_AT.  index and every output at the group's first frame.
+__global__ __launch_bounds__(SP_AT) void sa_walk_kernel(const float* __restrict__ A, const float* __restrict__ E,
+                                                        const float* __restrict__ d, const float* __restrict__ taps,
+                                                        const int* __restrict__ rec, const int* __restrict__ erec,
+                                                        const int* __restrict__ murec, const int* __restrict__ index,
+                                                        int* __restrict__ down_exponent, float* __restrict__ mm_best,
+                                                        float* __restrict__ pose_value, float* __restrict__ alt_value,
+                                                        int* __restrict__ mm_peak, int* __restrict__ alt_index, int* __restrict__ alt_pose,
+                                                        int* __restrict__ alt_jumped, int* __restrict__ complete, SkTree tree, int G, int R,
+                                                        float keep, float uniform) {
+    __shared__ float sm_p[SP_AT / 64];
+    __shared__ int sm_i[SP_AT / 64];
+    __shared__ int pose[SK_MAX_J], jmp[SK_MAX_J];
+    const int t = threadIdx.x, a = blockIdx.x, f = blockIdx.y, J = tree.J, W = 2 * R + 1, N = G * G * G;
+    const int* rf = rec + (size_t)f * J * SP_REC;
+    const int* ef = erec + (size_t)f * J * SP_REC;
+    const size_t row = (size_t)f * J + a;
+    const bool ok = sa_complete(rf, ef, J);                              // uniform
+    if (a == 0 && t == 0) complete[f] = ok ? 1 : 0;
+    const int* mr = murec + row * SP_REC;
+    const int at = ok && mr[3] != INT_MAX ? mr[3] : -1;                  // the anchor's voxel outside the window; uniform
+    if (t == 0) {
+        const float nan = __int_as_float(0x7fc00000);
+        down_exponent[row] = ok && a > 0 ? sp_scale(__int_as_float(ef[a * SP_REC])).e : 0;
+        mm_best[row] = ok ? __int_as_float(mr[0]) : nan;
+        mm_peak[row] = ok && mr[1] != INT_MAX ? mr[1] : -1;
+        alt_value[row] = ok ? __int_as_float(mr[2]) : nan;
+        alt_index[row] = at;
+        float pv = nan;
+        if (ok) {                                                        // mu_a at x*_a: the operations of sa_mu_kernel
+            const int xs = min(max(index[row], 0), N - 1);
+            pv = ldexpf(A[row * N + xs], -sp_scale(__int_as_float(rf[a * SP_REC])).e);
+            if (a > 0) pv *= d[row * N + xs];
+        }
+        pose_value[row] = pv;
+    }
+    int* op = alt_pose + row * J;
+    int* oj = alt_jumped + row * J;
+    if (at < 0) {                                                        // uniform: no alternative, or the frame is not complete
+        for (int j = t; j < J; j += SP_AT) { op[j] = -1; oj[j] = 0; }
+        return;
+    }
+    for (int j = t; j < J; j += SP_AT) { pose[j] = j == a ? at : -1; jmp[j] = 0; }
+    for (int u = a; u > 0; u = tree.parent[u]) {                         // up: the parent voxel behind d_u at x_u
+        __syncthreads();                                                 // pose[u] is written
+        const int y = min(max(pose[u], 0), N - 1);
+        const SpScale sc = sp_scale(__int_as_float(ef[u * SP_REC]));
+        const Peak pk = sp_argmax(E + ((size_t)f * J + u) * N, taps + (size_t)u * W * W * W, G, R, y, -sc.e, sm_p, sm_i);
+        if (t == 0) pose[tree.parent[u]] = sp_behind(pk, sc, ef[u * SP_REC + 1], y, G, R, keep, uniform, jmp[u]);
+    }
+    for (int j = 1; j < J; ++j) {                                        // down: the predecessor of upward edge j, as in sp_walk_kernel
+        __syncthreads();                                                 // pose[parent] is written
+        if (pose[j] >= 0) continue;                                      // uniform: on the way up
+        const int xp = min(max(pose[tree.parent[j]], 0), N - 1);
+        const SpScale sc = sp_scale(__int_as_float(rf[j * SP_REC]));
+        const Peak pk = sp_argmax(A + ((size_t)f * J + j) * N, taps + (size_t)j * W * W * W, G, R, xp, -sc.e, sm_p, sm_i);
+        if (t == 0) pose[j] = sp_behind(pk, sc, rf[j * SP_REC + 1], xp, G, R, keep, uniform, jmp[j]);
+    }
+    __syncthreads();
+    for (int j = t; j < J; j += SP_AT) { op[j] = pose[j]; oj[j] = jmp[j]; }
+}
+
+inline long long sa_frame_words(int J, int G) {
+    const long long N = (long long)G * G * G;
+    return 4 * J * N + (long long)J * sk_chunks((int)N) * SP_REC + 3LL * J * SP_REC;
 }
 
 }  // namespace
@@ -396,7 +572,6 @@ extern "C" int se_skeleton_pose_f32(const float* prob, const float* taps, const 
     int* rec = part + (size_t)group * J * CH * SP_REC;
     int* runs = rec + (size_t)group * J * SP_REC;
     const float keep = 1.0f - floor, uniform = floor / (float)voxels;
-    const int lds = sk_lds_bytes(R);
 
     if (J > 1) {
         hipLaunchKernelGGL(sk_runs_kernel, dim3(2 * R + 1, J), dim3(64), 0, st, taps, runs, R);
@@ -404,23 +579,88 @@ extern "C" int se_skeleton_pose_f32(const float* prob, const float* taps, const 
     }
     for (int f0 = 0; f0 < frames; f0 += group) {
         const int nf = min(group, frames - f0);
-        const float* p = prob + (size_t)f0 * J * N;
-        for (int d = deepest; d >= 0; --d) {
+        const int rc = sp_upward(st, prob + (size_t)f0 * J * N, taps, A, m, part, rec, runs, tree, depth, deepest, nf, voxels, G, R, keep,
+                                 uniform, index + (size_t)f0 * J, jumped + (size_t)f0 * J, exponent + (size_t)f0 * J, best_root + f0,
+                                 solved + f0);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" long long se_skeleton_alternatives_scratch_bytes(int frames, int J, int G, int R) {
+    if (frames < 1 || J < 1 || J > SK_MAX_J || !sk_shape_ok(G, R)) return 0;
+    return ((long long)min(frames, SK_GROUP) * sa_frame_words(J, G) + sk_runs_ints(J, R)) * 4;
+}
+
+extern "C" int se_skeleton_alternatives_f32(const float* prob, const float* taps, const int* parent, int separation, int* index,
+                                            int* jumped, int* exponent, float* best_root, int* solved, int* down_exponent,
+                                            float* mm_best, float* pose_value, float* alt_value, int* mm_peak, int* alt_index,
+                                            int* alt_pose, int* alt_jumped, int* complete, float* max_marginals, void* scratch,
+                                            long long scratch_bytes, int frames, int J, int voxels, int G, int R, float floor,
+                                            void* stream) {
+    if (!prob || !taps || !parent || !index || !jumped || !exponent || !best_root || !solved || !scratch) return SE_ERR_BAD_ARG;
+    if (!down_exponent || !mm_best || !pose_value || !alt_value || !mm_peak || !alt_index || !alt_pose || !alt_jumped || !complete)
+        return SE_ERR_BAD_ARG;
+    if (frames < 1 || J < 1 || J > SK_MAX_J || !sk_shape_ok(G, R) || separation < 0) return SE_ERR_BAD_ARG;
+    if ((long long)G * G * G != (long long)voxels) return SE_ERR_BAD_ARG;
+    if (!(floor >= 0.f && floor <= 1.f)) return SE_ERR_BAD_ARG;                           // a NaN fails
+    SkTree tree{};
+    int depth[SK_MAX_J], deepest;
+    if (!sk_build_tree(parent, J, tree, depth, deepest)) return SE_ERR_BAD_ARG;
+    if (!se_aligned({prob, taps, index, jumped, exponent, best_root, solved, down_exponent, mm_best, pose_value, alt_value, mm_peak,
+                     alt_index, alt_pose, alt_jumped, complete, max_marginals, scratch}, 4))
+        return SE_ERR_BAD_ARG;
+    if (max_marginals == prob) return SE_ERR_BAD_ARG;
+    if (scratch_bytes < se_skeleton_alternatives_scratch_bytes(frames, J, G, R)) return SE_ERR_BAD_ARG;
+    hipStream_t st = se_stream(stream);
+
+    const size_t N = (size_t)voxels;
+    const int group = min(frames, SK_GROUP), CH = sk_chunks(voxels);
+    float* A = reinterpret_cast<float*>(scratch);
+    float* m = A + (size_t)group * J * N;
+    float* E = m + (size_t)group * J * N;
+    float* dn = E + (size_t)group * J * N;
+    int* part = reinterpret_cast<int*>(dn + (size_t)group * J * N);
+    int* rec = part + (size_t)group * J * CH * SP_REC;
+    int* erec = rec + (size_t)group * J * SP_REC;
+    int* murec = erec + (size_t)group * J * SP_REC;
+    int* runs = murec + (size_t)group * J * SP_REC;
+    const float keep = 1.0f - floor, uniform = floor / (float)voxels;
+    const int lds = sk_lds_bytes(R);
+    SkRows all{};
+    for (int j = 0; j < J; ++j) all.slot[all.n++] = (unsigned char)j;
+
+    if (J > 1) {
+        hipLaunchKernelGGL(sk_runs_kernel, dim3(2 * R + 1, J), dim3(64), 0, st, taps, runs, R);
+        SE_CHECK_LAUNCH();
+    }
+    for (int f0 = 0; f0 < frames; f0 += group) {
+        const int nf = min(group, frames - f0);
+        const size_t fj = (size_t)f0 * J;
+        const float* p = prob + fj * N;
+        const int rc = sp_upward(st, p, taps, A, m, part, rec, runs, tree, depth, deepest, nf, voxels, G, R, keep, uniform, index + fj,
+                                 jumped + fj, exponent + fj, best_root + f0, solved + f0);
+        if (rc) return rc;
+        for (int d = 1; d <= deepest; ++d) {                             // the children of the level above
             SkRows level{};
             for (int j = 0; j < J; ++j)
                 if (depth[j] == d) level.slot[level.n++] = (unsigned char)j;
-            hipLaunchKernelGGL(sp_product_kernel, dim3(CH, level.n * nf), dim3(SK_THREADS), 0, st, p, m, A, part, tree, level, voxels);
+            hipLaunchKernelGGL(sa_down_kernel, dim3(CH, level.n * nf), dim3(SK_THREADS), 0, st, p, m, dn, E, part, tree, level, voxels);
             SE_CHECK_LAUNCH();
-            hipLaunchKernelGGL(sp_fold_kernel, dim3(level.n, nf), dim3(64), 0, st, part, rec, level, J, CH);
+            hipLaunchKernelGGL(sp_fold_kernel, dim3(level.n, nf), dim3(64), 0, st, part, erec, level, J, CH);
             SE_CHECK_LAUNCH();
-            if (d > 0) {                                                 // every joint of a level below the root sends a message
-                hipLaunchKernelGGL(sp_maxcorr_kernel, sk_corr_grid(G, level.n * nf), dim3(SK_THREADS), lds, st, A, taps, nullptr, rec, m,
-                                   runs, level, J, J, G, R, keep, uniform);
-                SE_CHECK_LAUNCH();
-            }
+            hipLaunchKernelGGL(sp_maxcorr_kernel, sk_corr_grid(G, level.n * nf), dim3(SK_THREADS), lds, st, E, taps, nullptr, erec, dn,
+                               runs, level, J, J, G, R, keep, uniform);
+            SE_CHECK_LAUNCH();
         }
-        hipLaunchKernelGGL(sp_walk_kernel, dim3(nf), dim3(SP_AT), 0, st, A, taps, rec, index + (size_t)f0 * J,
-                           jumped + (size_t)f0 * J, exponent + (size_t)f0 * J, best_root + f0, solved + f0, tree, G, R, keep, uniform);
+        hipLaunchKernelGGL(sa_mu_kernel, dim3(CH, J * nf), dim3(SK_THREADS), 0, st, p, A, dn, rec, erec, index + fj,
+                           max_marginals ? max_marginals + fj * N : nullptr, part, J, voxels, G, separation);
+        SE_CHECK_LAUNCH();
+        hipLaunchKernelGGL(sp_fold_kernel, dim3(J, nf), dim3(64), 0, st, part, murec, all, J, CH);
+        SE_CHECK_LAUNCH();
+        hipLaunchKernelGGL(sa_walk_kernel, dim3(J, nf), dim3(SP_AT), 0, st, A, E, dn, taps, rec, erec, murec, index + fj,
+                           down_exponent + fj, mm_best + fj, pose_value + fj, alt_value + fj, mm_peak + fj, alt_index + fj,
+                           alt_pose + fj * J, alt_jumped + fj * J, complete + f0, tree, G, R, keep, uniform);
         SE_CHECK_LAUNCH();
     }
     return 0;

@@ -494,3 +494,15 @@ def skeleton_pose_to_numpy(result):
     and ``bone_error_before`` when the call was given joints): what run_sequence.py --map_info_output writes."""
     extra = tuple(k for k in ("shift", "bone_error_before") if k in result)
     return _per_frame(result, POSE_KEYS + extra, "solved")
+
+
+ALTERNATIVES_KEYS = ("complete", "margin", "alt_log_score", "alt_index", "alt_coord", "alt_pose_index", "alt_pose_jumped", "alt_pose_joints",
+                     "max_marginal_peak_index", "pose_is_peak", "runner_up", "runner_up_joints", "runner_up_margin", "runner_up_bone_error")
+
+
+def skeleton_alternatives_to_numpy(result):
+    """The dict of ``SkeletonPose.alternatives`` as a list of per-frame dicts of numpy arrays (the keys of ``skeleton_pose_to_numpy``,
+    then ``ALTERNATIVES_KEYS``, then ``max_marginals`` when the call returned them): what run_sequence.py --map_alternatives_output
+    writes."""
+    extra = tuple(k for k in ("shift", "bone_error_before") if k in result)
+    return _per_frame(result, POSE_KEYS + extra + ALTERNATIVES_KEYS + tuple(k for k in ("max_marginals",) if k in result), "solved")
