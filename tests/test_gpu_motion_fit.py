@@ -46,7 +46,7 @@ CASES = [
     (1, 8, 2, 1e-3, 5),
     (15, 8, 3, 0.0, 5),
     (3, 6, 5, 1e-3, 4),          # R = G - 1: every window clipped on both sides
-    (4, 10, 3, 1e-3, 5),         # G % 4 = 2: the scalar finish pass
+    (4, 10, 3, 1e-3, 5),         # G % 4 = 2, yet 1000 voxels are whole quads: the vector finish pass (scalar: test_gpu_sequence_domain.py)
     (15, 16, 5, 0.0, 5),
     (30, 16, 5, 1e-3, 3),
     (2, 24, 8, 1e-3, 4),
@@ -115,7 +115,9 @@ def test_against_the_model_and_the_smoother(rows, G, R, floor, T):
     check_case(filtered(rows, G, R, floor, T), rows, G, R, floor, T)
 
 
-def check_case(k, rows, G, R, floor, T):
+def check_case(k, rows, G, R, floor, T, stats_pass=stats_pass, smooth=smooth):
+    """``stats_pass``, ``smooth``: the launchers, with the signatures and the results of ``stats_pass`` above and of the smoother test's
+    ``smooth`` (the defaults)."""
     N = G ** 3
     want = transition_stats_model(k["p"], k["b"], k["rs"], k["taps"], G, floor)
     lk = want["linked"]

@@ -45,7 +45,7 @@ CASES = [
     (1, 8, 2, 1e-3, 5),
     (15, 8, 3, 0.0, 5),
     (3, 6, 5, 1e-3, 4),          # R = G - 1: every window clipped on both sides
-    (4, 10, 3, 1e-3, 5),         # G % 4 = 2: the scalar finish pass
+    (4, 10, 3, 1e-3, 5),         # G % 4 = 2, yet 1000 voxels are whole quads: the vector finish pass (scalar: test_gpu_sequence_domain.py)
     (15, 16, 5, 0.0, 5),
     (30, 16, 5, 1e-3, 3),
     (2, 24, 8, 1e-3, 4),
@@ -115,7 +115,8 @@ def steps_behind(linked):
     return k
 
 
-def check_against_model(k, G, R, floor, taps, taps_dev, label):
+def check_against_model(k, G, R, floor, taps, taps_dev, label, smooth=smooth):
+    """``smooth``: the launcher, with the signature and the result of ``smooth`` above (the default)."""
     T, rows, N = k["p"].shape
     belief, restarted = (k["belief"], k["restarted"]) if taps is k["taps"] else forward(k["prob"], k["coord"], taps_dev, G, R, floor)
     b, rs = belief.cpu().numpy(), restarted.cpu().numpy()
