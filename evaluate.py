@@ -146,6 +146,29 @@ def best_of_two(frames, pred, gt):
             "mean_runner_up_margin": float(margins[ok].mean()) if ok.any() else float("nan")}
 
 
+def best_of_two_path(frames, pred, gt):
+    """``best_of_two`` per joint, for the per-frame dicts of run_sequence.py --path_alternatives_output: every joint has a trajectory
+    and a runner-up of its own.  Per joint and frame the smaller of the error of the path's joint and of ``runner_up_joints`` (the
+    path's alone where the runner-up has none), averaged; the share of the joint-frames in which the runner-up is the closer one;
+    and the rank correlation of the path's error and the per-frame ``margin`` over the joint-frames with a finite margin."""
+    from sceneego_amd.metrics import _average_ranks
+    err = np.sqrt(((pred - gt) ** 2).sum(axis=2))                                               # [T,15]
+    other = np.sqrt(((np.stack([np.asarray(fr["runner_up_joints"], dtype=np.float64) for fr in frames]) - gt) ** 2).sum(axis=2))
+    best = np.where(np.isfinite(other), np.minimum(err, other), err)
+    margins = np.stack([np.asarray(fr["margin"], dtype=np.float64) for fr in frames])
+    ok = np.isfinite(margins)
+    rho = float("nan")
+    if ok.sum() >= 2:
+        re, rm = _average_ranks(err[ok]), _average_ranks(margins[ok])
+        re, rm = re - re.mean(), rm - rm.mean()
+        den = np.sqrt((re * re).sum() * (rm * rm).sum())
+        rho = float((re * rm).sum() / den) if den > 0.0 else rho
+    return {"best_of_two_mpjpe": float(best.mean()), "runner_up_closer_share": float((best < err).mean()),
+            "spearman_error_margin": rho, "joint_frames_with_margin": int(ok.sum()),
+            "mean_margin": float(margins[ok].mean()) if ok.any() else float("nan"),
+            "below_ln2_share": float((margins < np.log(2.0)).mean())}
+
+
 def match_ground_truth(gt, names):
     if isinstance(gt, dict):
         def find(n):
@@ -185,6 +208,9 @@ def build_parser():
     ap.add_argument("--alternatives", default=None, help="with --pred_dir map.pkl: the pickle of run_sequence.py "
                     "--map_alternatives_output for the same frames; adds the best-of-two MPJPE (pose or runner-up) and "
                     "spearman(error, runner-up margin); without --gt only the margins are summarised")
+    ap.add_argument("--path_alternatives", default=None, help="with --pred_dir path.pkl: the pickle of run_sequence.py "
+                    "--path_alternatives_output for the same frames; adds the best-of-two MPJPE per joint (the path or its runner-up "
+                    "trajectory) and spearman(error, margin); without --gt only the margins are summarised")
     ap.add_argument("--bones", nargs="?", const="", default=None, metavar="FILE.npy",
                     help="bone-length summary of the predictions (needs no ground truth): the per-bone standard deviation over the "
                     "sequence and, with FILE.npy (14 or 15 lengths, as run_sequence.py --bone_lengths takes them), the mean absolute "
@@ -204,9 +230,17 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     names, pred = load_predictions(args.pred_dir)
     if args.gt is None:
-        if args.bones is None and args.alternatives is None:
-            raise SystemExit("--gt is required (only --bones and --alternatives work without it)")
+        if args.bones is None and args.alternatives is None and args.path_alternatives is None:
+            raise SystemExit("--gt is required (only --bones, --alternatives and --path_alternatives work without it)")
         r = {"frames": int(pred.shape[0])}
+        if args.path_alternatives is not None:
+            margins = np.stack([np.asarray(fr["margin"], dtype=np.float64)
+                                for fr in load_alternatives(args.path_alternatives, len(names))])
+            ok = np.isfinite(margins)
+            r["path_alternatives"] = {"mean_margin": float(margins[ok].mean()) if ok.any() else float("nan"),
+                                      "below_ln2_share": float((margins < np.log(2.0)).mean()), "joint_frames_with_margin": int(ok.sum())}
+            print("path margin: mean {mean_margin:.4f} over {joint_frames_with_margin} joint-frames, {below_ln2_share:.1%} below "
+                  "ln 2".format(**r["path_alternatives"]))
         if args.alternatives is not None:
             margins = np.array([float(fr["runner_up_margin"]) for fr in load_alternatives(args.alternatives, len(names))])
             ok = np.isfinite(margins)
@@ -242,6 +276,11 @@ def main(argv=None):
         print(f"best-of-two MPJPE {a['best_of_two_mpjpe']:.6f} {args.unit} (the pose or its runner-up, whichever is closer; the runner-up "
               f"in {a['runner_up_closer_share']:.1%} of the frames); spearman(error, runner-up margin): {a['spearman_error_margin']:.4f} "
               f"over {a['frames_with_margin']} frames")
+    if args.path_alternatives is not None:
+        a = r["path_alternatives"] = best_of_two_path(load_alternatives(args.path_alternatives, len(names)), pred, gt)
+        print(f"best-of-two MPJPE {a['best_of_two_mpjpe']:.6f} {args.unit} (every joint on its path or on its runner-up trajectory, "
+              f"whichever is closer; the runner-up in {a['runner_up_closer_share']:.1%} of the joint-frames); spearman(error, margin): "
+              f"{a['spearman_error_margin']:.4f} over {a['joint_frames_with_margin']} joint-frames")
     if args.bones is not None:
         r["bones"] = bones(pred, args.bones, args.unit)
     return r

@@ -823,6 +823,79 @@ int se_volume_viterbi_path_i32(const int* back, const int* peak, const int* rest
 int se_volume_viterbi_refine_f32(const float* prob, const float* coord, const int* index, float* joints, int frames, int rows,
                                  int voxels, int G, int refine, void* stream);
 
+/* Runner-up trajectories: the backward max-product pass over the sequence (VolumeViterbi(alternatives=True).alternatives()).  The
+ * MAX-MARGINAL mm_t(x) is the score of the best whole trajectory that is at voxel x in frame t: mm_t = alpha_t beta_t with alpha the
+ * forward scores above and beta_t(x) = max over z of tr(x -> z) p_{t+1}(z) beta_{t+1}(z).  From it follow, exactly and
+ * deterministically, the margin by which each frame of the path was decided, the best trajectory that is somewhere else in a frame,
+ * and the runner-up trajectory of a segment.  tests/volume_viterbi_alternatives_model.py restates what follows in numpy float32 and
+ * every output is compared with it BIT FOR BIT; arithmetic, rounding and underflow as for se_volume_viterbi_f32.
+ *
+ * se_volume_viterbi_keep_f32: se_volume_viterbi_f32 with one more output, scores_out [frames][rows][voxels] float32: the frame's
+ * scores as `state` holds them after the frame's fold pass, the raw a, or the copy of p on a restart; ldexpf(scores, -exponent) is
+ * the scaled s of the frame.  Every other output has the bits se_volume_viterbi_f32 gives; scratch as there; scores_out NULL or
+ * misaligned: SE_ERR_BAD_ARG.
+ *
+ * se_volume_viterbi_back_f32: the backward pass over one stored chunk of `frames` frames, from its last frame to its first; a track is
+ * walked by calls over its chunks LAST CHUNK FIRST, the backward state carried in device memory between them.  Per frame t and row:
+ * LINK       t is linked to t + 1 when t + 1 exists in the track (a later frame of the chunk, or have_next = 1), the forward pass
+ *            did not restart at t + 1 and r_{t+1} has a finite positive maximum.  A forward restart cuts the chain in both directions.
+ * UNLINKED   r_t = p_t and mm_t = s_t bit for bit (s_t = ldexpf(scores, -exponent_t)), every successor pointer -1, complete = 1.
+ * LINKED     e3 = the THREE STAGES above (k, then j, then i) on the scaled r_{t+1} with the REVERSED taps w_rev[d] = w[-d]: the step
+ *            from x to x + d has the score the forward pass gives the predecessor offset -d.  The winning offsets compose into the
+ *            successor voxel z(x) as they compose into the predecessor there.  step = keep * e3(x), jump = uniform * best_r(t + 1).
+ *            If jump > step: m = jump, successor peak_r(t + 1), jump bit set; otherwise m = step with successor z(x).
+ *            r_t = p_t * m,  mm_t = s_t * m,  complete_t = complete_{t+1}.
+ * RESCALING  of r as of a: M = max r (from 0.0f, strictly greater wins, lowest index among equals, a NaN never), e = ilogb(M),
+ *            r <- ldexpf(r, -e), best_r = ldexpf(M, -e), peak_r its index.
+ * DEATH      linked, but M is not a finite number > 0: the backward chain restarts here with r_t = p_t (M, e, peak from p), every
+ *            successor pointer -1, the raw max-marginals NaN, and complete = 0 for this frame and, through the links, for every
+ *            earlier frame of the segment.  The frame reports no max-marginal: the five outputs below are -1 / NaN.
+ *   prob, taps, G, radius, floor: as for the forward pass.  scores: scores_out of se_volume_viterbi_keep_f32 for these frames;
+ *   exponent, restarted: the forward pass's.  index [frames][rows]: the path x*_t of these frames (se_volume_viterbi_path_i32: the
+ *   path call for a chunk precedes the backward call for it); a frame whose index is not in 0..voxels-1 has no path voxel: -1 / NaN.
+ *   r_state [rows][voxels] float32, link_state [rows] int32 (peak_r of the chunk's first frame where the frame before it is linked
+ *   to it, -1 otherwise), best_state [rows] float32, complete_state [rows] int32: in (read only with have_next = 1) / out.
+ *   Outputs [frames][rows], all maxima under the one total order (greater value, then lower index; only values > 0 count):
+ *   mm_best, mm_peak   the maximum of mm_t over the row and its voxel
+ *   path_value         mm_t(x*_t)
+ *   alt_value, alt_index  the maximum of mm_t over the voxels at Chebyshev distance in voxel indices > separation from x*_t: the
+ *                      best trajectory that is somewhere else in this frame; -1 / NaN where the window leaves nothing > 0
+ *   complete           1: the max-marginals of this frame span the whole segment behind it
+ *   r_best, r_exponent best_r and e of the frame
+ *   succ               NULL or [frames][rows][voxels] int32: the successor's flat index, plus 1 << 30 for a jump, or -1.  It MAY BE
+ *                      THE MEMORY OF `scores`: a thread reads a voxel's score before it writes that voxel's pointer.
+ *   max_marginals      NULL or [frames][rows][voxels] float32: the raw mm_t
+ *   scratch            se_volume_viterbi_back_scratch_bytes(rows, G, radius) bytes, 4-byte aligned; 0 for a shape out of range
+ * Three launches per frame (the k / j stage kernel of the forward pass, unchanged, on r with the reversed taps; the i stage fused with
+ * the composition, step or jump, the two products, the window test and four (max, lowest index) records per workgroup; the fold) and
+ * two per call.  No atomics and no sums: bitwise reproducible and independent of how the frames are cut into chunks.  BYTE MODEL per
+ * frame, row and voxel: the forward pass's 28 B, the scores read (4 B) and the pointers written (4 B): 36 B; 4 B more with
+ * max_marginals.  SE_ERR_BAD_ARG, with nothing launched: a null pointer other than succ and max_marginals, a pointer that is not
+ * 4-byte aligned, the shape limits of the forward pass, separation < 0, have_next other than 0 / 1, a short scratch.
+ *
+ * se_volume_viterbi_branch_i32: one lane per row over one stored chunk: from the anchors (anchor [frames][rows] int32: a voxel at the
+ * anchor frame of a segment, -1 elsewhere) back through `back` to the segment's start and on through `succ` to its end.
+ *   direction -1   chunks LAST FIRST: x = the anchor, or what the frame behind points back to; index = x (-1: no branch passes),
+ *                  jumped from the back-pointer at x; a restarted frame ends the walk.  Writes every frame.  cursor [rows]: x carried.
+ *   direction +1   afterwards, chunks FIRST TO LAST: from the anchor, x_{t+1} = succ_t[x_t] & (2^30 - 1), jumped_{t+1} its jump bit;
+ *                  writes the frames it reaches and leaves the anchors' own.  cursor [rows]: the successor pointer carried.
+ *   have_carry     0: the first call of a direction; 1: cursor is read.
+ * An index outside 0..voxels-1 found in anchor, back, succ or cursor is never followed.  SE_ERR_BAD_ARG: a null or misaligned pointer,
+ * frames < 1, rows outside 1..65535, voxels outside 1..128^3, direction other than -1 / +1, have_carry other than 0 / 1.            */
+int se_volume_viterbi_keep_f32(const float* prob, const float* taps, float* state, int* peak_state, float* best_state, int* back_out,
+                               int* peak, float* best, int* exponent, int* restarted, float* scores_out, void* scratch,
+                               long long scratch_bytes, int frames, int rows, int voxels, int G, int radius, float floor,
+                               const int* have_prior, void* stream);
+int se_volume_viterbi_back_f32(const float* prob, const float* scores, const int* exponent, const int* restarted,
+                               const int* index, const float* taps, float* r_state, int* link_state, float* best_state,
+                               int* complete_state, float* mm_best, int* mm_peak, float* path_value, float* alt_value, int* alt_index,
+                               int* complete, float* r_best, int* r_exponent, int* succ, float* max_marginals, void* scratch,
+                               long long scratch_bytes, int frames, int rows, int voxels, int G, int radius, float floor,
+                               int separation, int have_next, void* stream);
+long long se_volume_viterbi_back_scratch_bytes(int rows, int G, int radius);
+int se_volume_viterbi_branch_i32(const int* back, const int* succ, const int* restarted, const int* anchor, int* cursor, int* index,
+                                 int* jumped, int frames, int rows, int voxels, int direction, int have_carry, void* stream);
+
 /* Skeleton-coupled joints: sum-product belief propagation over the kinematic tree of the joint volumes, with a spherical-shell
  * bone-length factor on every edge (sceneego_amd/skeleton_prior.py: SkeletonPrior; VoxelNetwork_depth.skeleton_prior returns one).  The
  * reference forces bone lengths onto a finished pose (utils/skeleton.py: kinematic_parents, _skeleton_resize); this couples the whole

@@ -85,6 +85,11 @@ back-pointers and, with ``--path_refine`` > 0 (default 1), the volumes stay on t
 ``--path_max_gb``) and a walk back at the end of the sequence picks the path.  ``--path_info_output`` adds the per-frame dicts (joints,
 index, coord, jumped, segment_start, log_score, moved, shift).  With ``--skeleton_output`` it runs on the coupled beliefs.  It prints
 its MPJPE beside the others; ``evaluate.py --pred_dir path.pkl`` reads the file like ``--output``.
+``--path_alternatives_output`` implies those options, keeps every frame's scores as well (47.2 MB per frame in all) and runs the
+backward max-product pass at the end of the sequence (``VolumeViterbi.alternatives``): the per-frame dicts also carry the margin by
+which every frame of the path was decided, the best trajectory that lies further than ``--path_separation`` voxels (default 2) from
+the path in that frame, and the runner-up trajectory of every segment.  It prints the mean runner-up margin and the share of the
+joint-frames whose margin is below ln 2; ``evaluate.py --pred_dir path.pkl --path_alternatives alt.pkl [--gt gt.pkl]`` reads it.
 ``--fit_frames F`` fits the motion model of those three to the sequence before the main pass (``VoxelNetwork_depth.motion_fit``,
 ``sceneego_amd/motion_fit.py``: at most ``--fit_iterations`` EM iterations for sigma and floor over the raw volumes of the first F
 consecutive frames, from ``--filter_sigma`` / ``--filter_floor`` at the fixed ``--filter_radius``), prints the start and end values
@@ -358,7 +363,11 @@ class SequenceRunner:
         if render_coupled and (skeleton is None or not render_volumes or render_filtered):
             raise ValueError("render_coupled needs skeleton and render_volumes, and excludes render_filtered")
         sp = self.net.skeleton_prior(**skeleton) if skeleton is not None else None
-        vp = self.net.volume_path(**path) if path is not None else None
+        path_separation = None
+        if path is not None:                # "separation": the backward pass too (--path_alternatives_output)
+            path = dict(path)
+            path_separation = path.pop("separation", None)
+        vp = self.net.volume_path(alternatives=path_separation is not None, **path) if path is not None else None
         separation = map_pose.get("separation") if map_pose is not None else None
         mpose = self.net.skeleton_pose(**{k: v for k, v in map_pose.items() if k != "separation"}) if map_pose is not None else None
 
@@ -484,7 +493,11 @@ class SequenceRunner:
                     self.video.close()
                     self.video = None
         frame_smooth = volume_smoother_to_numpy(vs.finish()) if vs is not None else None
-        frame_path = volume_path_to_numpy(vp.finish()) if vp is not None else None
+        if vp is not None and path_separation is not None:
+            from sceneego_amd.op import volume_path_alternatives_to_numpy
+            frame_path = volume_path_alternatives_to_numpy(vp.alternatives(separation=path_separation))
+        else:
+            frame_path = volume_path_to_numpy(vp.finish()) if vp is not None else None
         if not (stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
@@ -573,6 +586,12 @@ def build_parser():
                     "coupled beliefs")
     ap.add_argument("--path_info_output", default=None, help="pickle of the per-frame path dicts (list of dicts of numpy arrays: "
                     "joints, index, coord, jumped, segment_start, log_score, moved, shift)")
+    ap.add_argument("--path_alternatives_output", default=None, help="pickle of the per-frame path dicts with the runner-up: the keys "
+                    "of --path_info_output, then the margin by which every frame of the path was decided, the best trajectory that "
+                    "is somewhere else in that frame and the runner-up trajectory of each segment (VolumeViterbi.alternatives: the "
+                    "backward max-product pass; 47.2 MB per frame at 15 x 64^3 stay on the device); implies the --path_* options")
+    ap.add_argument("--path_separation", type=int, default=None, help="with --path_alternatives_output: an alternative lies further than "
+                    "this many voxels (Chebyshev) from the path voxel in its frame (default 2)")
     ap.add_argument("--path_refine", type=int, default=None, help="with --path_output: the path voxel is refined to the centroid of the "
                     "volume over this many voxels around it, 0..3 (default 1; 0: the voxel centre, and no volumes are stored)")
     ap.add_argument("--path_max_gb", type=float, default=None, help="with --path_output: the most device memory the stored "
@@ -656,7 +675,7 @@ def parse_args(argv=None):
     elif args.smooth_max_gb is not None:
         raise SystemExit("--smooth_max_gb needs --smooth_output")
     args.path = None
-    if args.path_output is not None or args.path_info_output is not None:
+    if args.path_output is not None or args.path_info_output is not None or args.path_alternatives_output is not None:
         if args.path_max_gb is not None and not args.path_max_gb >= 0:
             raise SystemExit("--path_max_gb must be >= 0")
         if args.path_refine is not None and not 0 <= args.path_refine <= 3:
@@ -664,8 +683,14 @@ def parse_args(argv=None):
         args.path = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor,
                      "refine": 1 if args.path_refine is None else args.path_refine,
                      "max_bytes": None if args.path_max_gb is None else int(args.path_max_gb * 2 ** 30)}
-    elif args.path_max_gb is not None or args.path_refine is not None:
-        raise SystemExit("--path_max_gb and --path_refine need --path_output")
+        if args.path_alternatives_output is not None:
+            if args.path_separation is not None and args.path_separation < 0:
+                raise SystemExit("--path_separation must be >= 0")
+            args.path["separation"] = 2 if args.path_separation is None else args.path_separation
+        elif args.path_separation is not None:
+            raise SystemExit("--path_separation needs --path_alternatives_output")
+    elif args.path_max_gb is not None or args.path_refine is not None or args.path_separation is not None:
+        raise SystemExit("--path_max_gb, --path_refine and --path_separation need --path_output")
     args.fit = None
     if args.fit_frames is not None:
         if args.fit_frames < 2:
@@ -927,7 +952,12 @@ def main(argv=None):
                                            int(sum(not fr["coupled"] for fr in frame_skeleton))))
     if args.path is not None:
         on_path = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_path]
-        for path, obj in ((args.path_output, on_path), (args.path_info_output, frame_path)):
+        path_alternatives = frame_path if "separation" in args.path else None
+        if path_alternatives is not None:                                # the path dicts are the leading entries
+            from sceneego_amd.op import PATH_ALTERNATIVE_KEYS
+            frame_path = [{k: v for k, v in fr.items() if k not in PATH_ALTERNATIVE_KEYS} for fr in path_alternatives]
+        for path, obj in ((args.path_output, on_path), (args.path_info_output, frame_path),
+                          (args.path_alternatives_output, path_alternatives)):
             if path is not None:
                 os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
                 with open(path, "wb") as f:
@@ -941,6 +971,16 @@ def main(argv=None):
                   result["path_mpjpe"], mpjpe, others, float(np.nanmean([fr["shift"] for fr in frame_path])),
                   int(sum(fr["jumped"].sum() for fr in frame_path)), int(sum(fr["segment_start"].sum() for fr in frame_path[1:])),
                   int(sum(fr["index"].size for fr in frame_path))))
+        if path_alternatives is not None:
+            margins = np.array([fr["runner_up_margin"] for fr in path_alternatives], dtype=np.float64)
+            per_frame = np.array([fr["margin"] for fr in path_alternatives], dtype=np.float64)
+            result["path_alternatives"] = path_alternatives
+            result["path_runner_up_margin"] = float(np.mean(margins[np.isfinite(margins)])) if np.isfinite(margins).any() else float("nan")
+            result["path_runner_up_close"] = float(np.mean(per_frame < np.log(2.0)))
+            print("runner-up trajectories (log score ratios under the motion model's conventions, not probabilities): mean runner-up "
+                  "margin {:.3f}, {:.1%} of the joint-frames decided by less than ln 2, {} not complete".format(
+                      result["path_runner_up_margin"], result["path_runner_up_close"],
+                      int(sum((~fr["complete"]).sum() for fr in path_alternatives))))
     if map_pose is not None:
         posed = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_map]
         frame_alternatives = frame_map if "separation" in map_pose else None

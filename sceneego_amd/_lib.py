@@ -122,6 +122,10 @@ SIGNATURES = {
     "se_volume_viterbi_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "se_volume_viterbi_path_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "se_volume_viterbi_refine_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "se_volume_viterbi_keep_f32": (_i, [_vp] * 12 + [_ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "se_volume_viterbi_back_scratch_bytes": (_ll, [_i, _i, _i]),
+    "se_volume_viterbi_back_f32": (_i, [_vp] * 21 + [_ll, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    "se_volume_viterbi_branch_i32": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _vp]),
     "se_shell_correlate_scratch_bytes": (_ll, [_i, _i]),
     "se_shell_correlate_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _f, _vp]),
     "se_skeleton_couple_scratch_bytes": (_ll, [_i, _i, _i, _i]),
@@ -1343,6 +1347,108 @@ def volume_viterbi(prob, taps, state, peak_state, best_state, back_out, peak, be
                                         frames, rows, voxels, grid, radius, floor, _ptr(have_prior), _stream()),
            "se_volume_viterbi_f32")
     return peak, best, exponent, restarted
+
+
+def volume_viterbi_keep(prob, taps, state, peak_state, best_state, back_out, peak, best, exponent, restarted, scores_out, frames, rows,
+                        voxels, grid, radius, floor, have_prior=None, scratch=None):
+    """se_volume_viterbi_keep_f32: ``volume_viterbi`` with one more output, ``scores_out`` [frames, rows, voxels] float32 (every frame's
+    scores as ``state`` holds them after its fold pass); every other output has the bits ``volume_viterbi`` gives.  Arguments are
+    checked before anything is launched."""
+    what = "volume_viterbi_keep"
+    frames, rows, voxels, grid, radius, floor = _grid_args(what, frames, rows, voxels, grid, radius, floor)
+    total = frames * rows * voxels
+    dev = _check_args(what, (("prob", prob, torch.float32, total), ("taps", taps, torch.float32, 2 * radius + 1),
+                             ("state", state, torch.float32, rows * voxels), ("peak_state", peak_state, torch.int32, rows),
+                             ("best_state", best_state, torch.float32, rows), ("back_out", back_out, torch.int32, total),
+                             ("peak", peak, torch.int32, frames * rows), ("best", best, torch.float32, frames * rows),
+                             ("exponent", exponent, torch.int32, frames * rows), ("restarted", restarted, torch.int32, frames * rows),
+                             ("scores_out", scores_out, torch.float32, total)),
+                      (("have_prior", have_prior, torch.int32, rows), ("scratch", scratch, torch.uint8, None)))
+    big = (("prob", prob), ("state", state), ("back_out", back_out), ("scores_out", scores_out))
+    if any(_overlap(a, b) for i, (_, a) in enumerate(big) for _, b in big[i + 1:]):
+        raise HipExtensionError(f"{what}: prob, state, back_out and scores_out must not alias one another")
+    scratch = _grid_scratch(what, scratch, volume_viterbi_scratch_bytes(rows, grid, radius), rows, grid, radius, dev)
+    _check(load().se_volume_viterbi_keep_f32(_ptr(prob), _ptr(taps), _ptr(state), _ptr(peak_state), _ptr(best_state), _ptr(back_out),
+                                             _ptr(peak), _ptr(best), _ptr(exponent), _ptr(restarted), _ptr(scores_out), _ptr(scratch),
+                                             scratch.numel(), frames, rows, voxels, grid, radius, floor, _ptr(have_prior), _stream()),
+           "se_volume_viterbi_keep_f32")
+    return peak, best, exponent, restarted
+
+
+def volume_viterbi_back_scratch_bytes(rows, grid, radius) -> int:
+    return int(load().se_volume_viterbi_back_scratch_bytes(int(rows), int(grid), int(radius)))
+
+
+BACK_OUTPUTS = (("mm_best", torch.float32), ("mm_peak", torch.int32), ("path_value", torch.float32), ("alt_value", torch.float32),
+                ("alt_index", torch.int32), ("complete", torch.int32), ("r_best", torch.float32), ("r_exponent", torch.int32))
+
+
+def volume_viterbi_back(prob, scores, exponent, restarted, index, taps, carry, out, frames, rows, voxels, grid, radius, floor,
+                        separation, have_next, succ=None, max_marginals=None, scratch=None):
+    """se_volume_viterbi_back_f32: the backward max-product pass over one stored chunk, last frame to first (the header states the
+    definition).  ``prob``, ``scores`` [frames, rows, voxels] float32; ``exponent``, ``restarted``, ``index`` [frames, rows] int32;
+    ``carry``: a dict of the backward state carried from chunk to chunk on the device, ``r`` [rows, voxels] float32, ``link`` [rows]
+    int32, ``best`` [rows] float32, ``complete`` [rows] int32 (read only with ``have_next`` = 1, always written); ``out``: a dict of
+    the [frames, rows] outputs named in ``BACK_OUTPUTS``.  ``succ`` None or [frames, rows, voxels] int32: it may be the memory of
+    ``scores`` (``scores.view(torch.int32)``); ``max_marginals`` None or [frames, rows, voxels] float32.  Every argument is checked
+    here and a bad one raises HipExtensionError before anything is launched."""
+    what = "volume_viterbi_back"
+    frames, rows, voxels, grid, radius, floor = _grid_args(what, frames, rows, voxels, grid, radius, floor)
+    if isinstance(separation, bool) or not isinstance(separation, numbers.Integral) or separation < 0:
+        raise HipExtensionError(f"{what}: separation = {separation!r} (an integer >= 0) expected")
+    if not isinstance(have_next, (bool, int)) or int(have_next) not in (0, 1):
+        raise HipExtensionError(f"{what}: have_next = {have_next!r} must be 0 or 1")
+    if not isinstance(carry, dict) or tuple(sorted(carry)) != ("best", "complete", "link", "r"):
+        raise HipExtensionError(f"{what}: carry must be a dict with the keys r, link, best, complete")
+    if not isinstance(out, dict) or any(name not in out for name, _ in BACK_OUTPUTS):
+        raise HipExtensionError(f"{what}: out must be a dict with the keys " + ", ".join(name for name, _ in BACK_OUTPUTS))
+    total = frames * rows * voxels
+    named = (("prob", prob, torch.float32, total), ("scores", scores, torch.float32, total),
+             ("exponent", exponent, torch.int32, frames * rows), ("restarted", restarted, torch.int32, frames * rows),
+             ("index", index, torch.int32, frames * rows), ("taps", taps, torch.float32, 2 * radius + 1),
+             ("carry r", carry["r"], torch.float32, rows * voxels), ("carry link", carry["link"], torch.int32, rows),
+             ("carry best", carry["best"], torch.float32, rows), ("carry complete", carry["complete"], torch.int32, rows))
+    named += tuple((name, out[name], dtype, frames * rows) for name, dtype in BACK_OUTPUTS)
+    dev = _check_args(what, named, (("succ", succ, torch.int32, total), ("max_marginals", max_marginals, torch.float32, total),
+                                    ("scratch", scratch, torch.uint8, None)))
+    if _overlap(carry["r"], prob) or _overlap(carry["r"], scores) or _overlap(prob, scores):
+        raise HipExtensionError(f"{what}: prob, scores and the carried r must not alias one another")
+    if succ is not None and (_overlap(succ, prob) or _overlap(succ, carry["r"])
+                             or (_overlap(succ, scores) and succ.data_ptr() != scores.data_ptr())):
+        raise HipExtensionError(f"{what}: succ may be the memory of scores, voxel for voxel, and must not overlap anything else")
+    if max_marginals is not None and any(_overlap(max_marginals, t) for t in (prob, scores, carry["r"]) + (() if succ is None else (succ,))):
+        raise HipExtensionError(f"{what}: max_marginals must not alias prob, scores, succ or the carried r")
+    scratch = _grid_scratch(what, scratch, volume_viterbi_back_scratch_bytes(rows, grid, radius), rows, grid, radius, dev)
+    _check(load().se_volume_viterbi_back_f32(
+        _ptr(prob), _ptr(scores), _ptr(exponent), _ptr(restarted), _ptr(index), _ptr(taps), _ptr(carry["r"]), _ptr(carry["link"]),
+        _ptr(carry["best"]), _ptr(carry["complete"]), *(_ptr(out[name]) for name, _ in BACK_OUTPUTS), _ptr(succ), _ptr(max_marginals),
+        _ptr(scratch), scratch.numel(), frames, rows, voxels, grid, radius, floor, int(separation), int(have_next), _stream()),
+        "se_volume_viterbi_back_f32")
+    return out
+
+
+def volume_viterbi_branch(back, succ, restarted, anchor, cursor, index, jumped, frames, rows, voxels, direction, have_carry):
+    """se_volume_viterbi_branch_i32: the branch walk over one stored chunk from the anchors ``anchor`` [frames, rows] int32 (a voxel at
+    a segment's anchor frame, -1 elsewhere): ``direction`` -1 back through ``back`` (chunks last first; writes every frame of
+    ``index`` and ``jumped``), then +1 on through ``succ`` (chunks first to last; writes the frames it reaches).  ``cursor`` [rows]
+    int32 is read with ``have_carry`` = 1 and written.  Arguments are checked before anything is launched."""
+    what = "volume_viterbi_branch"
+    frames, rows, voxels = int(frames), int(rows), int(voxels)
+    if frames < 1 or rows <= 0 or rows > 65535 or not 1 <= voxels <= FILTER_MAX_GRID ** 3:
+        raise HipExtensionError(f"{what}: frames = {frames} (>= 1), rows = {rows} (1..65535), voxels = {voxels} (1..{FILTER_MAX_GRID}^3) "
+                                "expected")
+    if isinstance(direction, bool) or direction not in (-1, 1):
+        raise HipExtensionError(f"{what}: direction = {direction!r} must be -1 or 1")
+    if not isinstance(have_carry, (bool, int)) or int(have_carry) not in (0, 1):
+        raise HipExtensionError(f"{what}: have_carry = {have_carry!r} must be 0 or 1")
+    _check_args(what, (("back", back, torch.int32, frames * rows * voxels), ("succ", succ, torch.int32, frames * rows * voxels),
+                       ("restarted", restarted, torch.int32, frames * rows), ("anchor", anchor, torch.int32, frames * rows),
+                       ("cursor", cursor, torch.int32, rows), ("index", index, torch.int32, frames * rows),
+                       ("jumped", jumped, torch.int32, frames * rows)))
+    _check(load().se_volume_viterbi_branch_i32(_ptr(back), _ptr(succ), _ptr(restarted), _ptr(anchor), _ptr(cursor), _ptr(index),
+                                               _ptr(jumped), frames, rows, voxels, int(direction), int(have_carry), _stream()),
+           "se_volume_viterbi_branch_i32")
+    return index, jumped
 
 
 def volume_viterbi_path(back, peak, restarted, cursor, index, jumped, frames, rows, voxels, have_next):

@@ -436,6 +436,18 @@ def volume_path_to_numpy(result):
     return _per_frame(result, PATH_KEYS + (("shift",) if "shift" in result else ()), "index")
 
 
+PATH_ALTERNATIVE_KEYS = ("complete", "margin", "alt_index", "alt_coord", "alt_log_score", "max_marginal_peak_index", "path_is_peak",
+                         "runner_up_index", "runner_up_coord", "runner_up_joints", "runner_up_jumped", "runner_up_anchor",
+                         "runner_up_margin")
+
+
+def volume_path_alternatives_to_numpy(result):
+    """The dict of ``VolumeViterbi.alternatives`` as a list of per-frame dicts of numpy arrays: the keys of ``volume_path_to_numpy``,
+    then the margins, the alternative voxels and the runner-up trajectory (``max_marginals`` is left out: volumes stay on the
+    device).  What run_sequence.py --path_alternatives_output writes."""
+    return _per_frame(result, PATH_KEYS + (("shift",) if "shift" in result else ()) + PATH_ALTERNATIVE_KEYS, "index")
+
+
 def _fit_to_json(result, keys, extra):
     """``result[k]`` for k in ``keys`` as plain Python values that ``json.dump`` takes (NaN as null, arrays as lists), with ``extra``."""
     def plain(v):

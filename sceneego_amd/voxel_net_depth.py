@@ -500,7 +500,7 @@ class VoxelNetwork_depth(nn.Module):
         return VolumeSmoother(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor,
                               max_bytes=max_bytes)
 
-    def volume_path(self, sigma=0.10, radius=None, floor=1e-3, refine=1, max_bytes=None):
+    def volume_path(self, sigma=0.10, radius=None, floor=1e-3, refine=1, max_bytes=None, alternatives=False):
         """A ``sceneego_amd.volume_viterbi.VolumeViterbi`` bound to the module's own ``coord_volumes``, grid and cuboid side: the
         most probable trajectory of every joint through the volumes of ONE recorded track, the max-product counterpart of
         ``volume_filter`` / ``volume_smoother`` on the same motion model.  ``v = net.volume_path(); v.push(volumes)`` per batch of
@@ -509,6 +509,8 @@ class VoxelNetwork_depth(nn.Module):
         ``v.finish()`` walks back from the last frame and returns the path's joints, voxel indices, jumps and segment scores.  Where
         the smoothed joint between two lobes is a point without probability, the path stays on one lobe; it is all-or-nothing where
         the marginals hedge.  The parameters are the filter's: a convention, not calibrated.  ``forward()`` itself is unchanged.
+        ``alternatives`` = True also keeps every frame's scores (12 bytes per voxel in all) so that ``v.alternatives()`` can say how
+        close the second-best trajectory was: per-frame margins and the runner-up trajectory of each segment.
 
         Raises ValueError when ``config.model.volume_softmax`` is false or a parameter is out of range; nothing touches the device
         before the first ``push``."""
@@ -516,7 +518,7 @@ class VoxelNetwork_depth(nn.Module):
             raise ValueError("volume_path needs config.model.volume_softmax: the ReLU volumes are not a probability distribution")
         from .volume_viterbi import VolumeViterbi
         return VolumeViterbi(self.coord_volumes[0], self.volume_size, self.cuboid_side, sigma=sigma, radius=radius, floor=floor,
-                             refine=refine, max_bytes=max_bytes)
+                             refine=refine, max_bytes=max_bytes, alternatives=alternatives)
 
     def motion_fit(self, sigma=0.10, radius=None, floor=1e-3, max_bytes=None):
         """A ``sceneego_amd.motion_fit.MotionModelFit`` bound to the module's own ``coord_volumes``, grid and cuboid side: the fit of
