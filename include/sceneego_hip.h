@@ -360,6 +360,29 @@ int se_conv3d_split3_pack(const float* w, se_bf16* wsplit, int cout, int cin, in
 int se_conv3d_k3_split3_f32(const float* in, const se_bf16* wsplit, const float* bpack, const float* residual, float* out,
                             int batch, int dim, int cin_pad, int cout, int flags, void* stream);
 
+/* Six-product split forms of the float32 program (csrc/split6.h): float32 tensors in and out, every float32 product x * w taken as
+ * six bf16 products of a 3-way split of both operands (x = a + b + c, w = p + q + r, round to nearest even; ap, aq, bp, ar, cp, bq)
+ * on v_mfma_f32_16x16x32_bf16 with float32 accumulation: the dropped products total <= 2^-23 |x| |w|.  Part of the float32 parity
+ * surface: the plan of se_conv3d_w6_f32 chooses such a form where one exists and measured faster than its float32 form.
+ * se_conv3d_split6_pack: wpack = the layer's packed float32 buffer (se_conv3d_pack_f32, same cout / cin_pad / ksize / transposed;
+ *   section A is read) -> wsplit, se_conv3d_split6_packed_elems bf16 elements (-1: no split planes for the shape; they exist
+ *   for cin_pad % 32 == 0): the three planes of every folded weight in A-fragment order (csrc/conv3d_pack.h).  Biases stay float32.
+ * se_conv3d_w6_f32: se_conv3d_f32 with the layer's split planes (NULL: exactly se_conv3d_f32).
+ * se_conv3d_f32_split6: 1 when se_conv3d_w6_f32 with split planes runs such a call (cin_pad == cin) on a split form, else 0.
+ * se_conv3d_k3_split6_f32: the split form of the 3^3 kernel of the 8^3-sized levels on its whole domain (dim 8 or 16,
+ *   cin % 32 == 0, cin_pad % 32 == 0, cout % 32 == 0, batch * dim^3 <= 8192; flags SE_EPI_RELU, SE_EPI_RES_PRE_RELU / _POST_RELU),
+ *   whatever se_conv3d_w6_f32 would choose; SE_ERR_BAD_ARG otherwise (nothing launched).
+ * se_split6_planes_f32 (test entry point): the device split of n (even) float32 values -> planes [3][n].                       */
+long long se_conv3d_split6_packed_elems(int cout, int cin_pad, int ksize, int transposed);
+int se_conv3d_split6_pack(const float* wpack, se_bf16* wsplit, int cout, int cin_pad, int ksize, int transposed, void* stream);
+int se_conv3d_w6_f32(const float* in, const float* wpack, const se_bf16* wsplit6, const float* bpack, const float* residual,
+                     float* out, int batch, int dim, int cin, int cin_pad, int cout, int ksize, int flags,
+                     float* workspace, long long workspace_elems, void* stream);
+int se_conv3d_f32_split6(int batch, int dim, int cin, int cout, int ksize, int flags);
+int se_conv3d_k3_split6_f32(const float* in, const se_bf16* wsplit6, const float* bpack, const float* residual, float* out,
+                            int batch, int dim, int cin, int cin_pad, int cout, int flags, void* stream);
+int se_split6_planes_f32(const float* x, se_bf16* planes, long long n, void* stream);
+
 /* Conv3d k = 1, 3 or 7 + folded BN + epilogue (flags as se_conv3d_f32; SE_EPI_OUT_PLANAR is not supported: the
  * float32 planar logits come from se_pointwise_chain3_bf16).  in [B][D]^3[cin_pad] -> out [B][D]^3[cout].
  * k = 7 (the front layer) reads its input OCTET-PLANAR: in [B][cin_pad/8][D]^3[8] — the layer walks the input one

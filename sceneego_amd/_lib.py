@@ -89,6 +89,12 @@ SIGNATURES = {
     "se_conv3d_split3_packed_elems": (_ll, [_i, _i]),
     "se_conv3d_split3_pack": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "se_conv3d_k3_split3_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "se_conv3d_split6_packed_elems": (_ll, [_i, _i, _i, _i]),
+    "se_conv3d_split6_pack": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "se_conv3d_w6_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp]),
+    "se_conv3d_f32_split6": (_i, [_i, _i, _i, _i, _i, _i]),
+    "se_conv3d_k3_split6_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "se_split6_planes_f32": (_i, [_vp, _vp, _ll, _vp]),
     "se_exr_piz_scratch_bytes": (_ll, [_vp, _i, _vp, _i]),
     "se_exr_piz_decode_f32": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _i, _i, _f, _vp, _ll, _vp, _vp]),
     "se_exr_zip_scratch_bytes": (_ll, [_vp, _i, _vp, _i]),
@@ -740,6 +746,11 @@ def conv3d(inp, wpack, bpack, residual, out, batch, dim, cin, cin_pad, cout, ksi
             _check(load().se_conv3d_pool_f32(_ptr(inp), _ptr(wpack), _ptr(bpack), _ptr(residual), _ptr(out), _ptr(pool_out), batch,
                                              dim, cin, cin_pad, cout, ksize, flags, _ptr(workspace),
                                              0 if workspace is None else workspace.numel(), _stream()), "se_conv3d_pool_f32")
+        elif getattr(wpack, "split6", None) is not None:
+            # the layer has split planes (conv3d_split6_pack hangs them on its packed float32 tensor): the plan may choose a split form
+            _check(load().se_conv3d_w6_f32(_ptr(inp), _ptr(wpack), _ptr(wpack.split6), _ptr(bpack), _ptr(residual), _ptr(out), batch, dim,
+                                           cin, cin_pad, cout, ksize, flags, _ptr(workspace),
+                                           0 if workspace is None else workspace.numel(), _stream()), "se_conv3d_w6_f32")
         else:
             _check(load().se_conv3d_f32(_ptr(inp), _ptr(wpack), _ptr(bpack), _ptr(residual), _ptr(out), batch, dim, cin,
                                         cin_pad, cout, ksize, flags, _ptr(workspace),
@@ -800,6 +811,48 @@ def conv3d_k3_split3(inp, wsplit, bpack, residual, out, batch, dim, cin_pad, cou
     with _timed(("conv3d_split3", 3, cin_pad, cout, dim)):
         _check(load().se_conv3d_k3_split3_f32(_ptr(inp), _ptr(wsplit), _ptr(bpack), _ptr(residual), _ptr(out), batch, dim, cin_pad, cout,
                                               flags, _stream()), "se_conv3d_k3_split3_f32")
+
+
+def conv3d_split6_pack(wpack, cout, cin_pad, ksize, transposed=False):
+    """The split planes of a layer (csrc/split6.h: every folded float32 weight as three bf16 parts, A-fragment order) from its packed
+    float32 buffer ``wpack``, or None for a shape that has none (cin_pad % 32 != 0).  The planes are also hung on ``wpack`` as
+    ``wpack.split6``: conv3d() then lets the library's plan choose a six-product form for the launches of that layer."""
+    require_hip(wpack)
+    _chk_f32(wpack)
+    n = int(load().se_conv3d_split6_packed_elems(cout, cin_pad, ksize, 1 if transposed else 0))
+    if n <= 0:
+        return None
+    out = torch.empty(n, device=wpack.device, dtype=torch.bfloat16)
+    _check(load().se_conv3d_split6_pack(_ptr(wpack), _ptr(out), cout, cin_pad, ksize, 1 if transposed else 0, _stream()),
+           "se_conv3d_split6_pack")
+    wpack.split6 = out
+    return out
+
+
+def conv3d_split6(batch, dim, cin, cout, ksize, flags=0) -> bool:
+    """True when conv3d() runs this float32 launch (cin_pad == cin) of a layer with split planes on a six-product bf16 form."""
+    return bool(load().se_conv3d_f32_split6(batch, dim, cin, cout, ksize, flags))
+
+
+def conv3d_k3_split6(inp, wsplit6, bpack, residual, out, batch, dim, cin, cin_pad, cout, flags):
+    """The split form of the 3x3x3 kernel of the 8^3-sized levels on its whole domain (se_conv3d_k3_split6_f32), channels-last."""
+    require_hip(inp, out, wsplit6, bpack)
+    _chk_f32(inp, out, bpack, residual)
+    assert wsplit6.dtype == torch.bfloat16 and inp.numel() == batch * dim ** 3 * cin_pad and out.numel() == batch * dim ** 3 * cout
+    assert wsplit6.numel() == int(load().se_conv3d_split6_packed_elems(cout, cin_pad, 3, 0))
+    assert residual is None or residual.numel() == out.numel()
+    with _timed(("conv3d_split6", 3, cin_pad, cout, dim), flags):
+        _check(load().se_conv3d_k3_split6_f32(_ptr(inp), _ptr(wsplit6), _ptr(bpack), _ptr(residual), _ptr(out), batch, dim, cin, cin_pad,
+                                              cout, flags, _stream()), "se_conv3d_k3_split6_f32")
+
+
+def split6_planes(x):
+    """Test entry point: the device's 3-way bf16 split of a float32 tensor (even element count) -> planes [3, n] bfloat16."""
+    require_hip(x)
+    _chk_f32(x)
+    planes = torch.empty((3, x.numel()), device=x.device, dtype=torch.bfloat16)
+    _check(load().se_split6_planes_f32(_ptr(x), _ptr(planes), x.numel(), _stream()), "se_split6_planes_f32")
+    return planes
 
 
 def conv3d_skip16(inp, wpack, bpack_sum, skip_in, skip_w, out, batch, dim, cin, cout, flags):

@@ -165,7 +165,9 @@ SeConvPlan se_conv3d_plan(const ConvArgs& a, int batch, int ksize) {
     const bool cout_pairs = ksize == 3 && !(flags & SE_EPI_OUT_PLANAR) && a.nts % 2 == 0;   // these kernels own two cout tiles per workgroup
     if (cout_pairs && try_wavesplit && a.total_vox <= 8192 && a.total_vox * a.cin_pad * 4LL < (1LL << 31) && a.total_vox >= wavesplit_min_vox) {
         // 8^3-sized levels: in-workgroup split-K, single launch (0.063 vs 0.077 ms for grid split-K + reduce at B = 8)
-        if (SE_HALO64 && a.total_vox >= 2048 && (dim == 8 || dim == 16) && (a.cin & 31) == 0) p.kernel = SE_CONV_HALO64, p.form = dim;
+        // ... on the bf16 matrix pipe (six-product split form) when the caller brought the layer's split planes
+        if (SE_HALO64 && a.total_vox >= 2048 && (dim == 8 || dim == 16) && (a.cin & 31) == 0)
+            p.kernel = a.wsplit6 && se_conv3d_halo64_s6_domain(a) ? SE_CONV_HALO64_S6 : SE_CONV_HALO64, p.form = dim;
         else p.kernel = SE_CONV_WAVESPLIT, p.form = a.total_vox >= 2048 ? 4 : a.total_vox >= 256 ? 8 : 16;
         return p;
     }
@@ -191,6 +193,7 @@ static int launch_planned(const SeConvPlan& p, const ConvArgs& a, int batch, hip
         case SE_CONV_TILED_K3:
         case SE_CONV_TILED_K7: return se_conv3d_tiled_launch(a, batch, p.kernel, p.form, s);
         case SE_CONV_HALO64:
+        case SE_CONV_HALO64_S6:
         case SE_CONV_WAVESPLIT:
         case SE_CONV_SPLITK_GRID: return se_conv3d_small_launch(a, p, s);
         case SE_CONV_DIRECT: return se_conv3d_direct_launch(a, p.form, s);
@@ -208,7 +211,7 @@ static int launch_planned(const SeConvPlan& p, const ConvArgs& a, int batch, hip
     }
 }
 
-static int conv3d_f32_impl(const float* in, const float* wpack, const float* bpack, const float* residual, float* out,
+static int conv3d_f32_impl(const float* in, const float* wpack, const unsigned short* wsplit6, const float* bpack, const float* residual, float* out,
                            float* pool_out, const float* skip_w, int batch, int dim, int cin, int cin_pad, int cout, int ksize, int flags,
                            float* workspace, long long workspace_elems, void* stream) {
     if (batch <= 0 || dim <= 0 || cin <= 0 || cin_pad < cin || (cin_pad & 15) || cout <= 0) return SE_ERR_BAD_ARG;
@@ -232,6 +235,7 @@ static int conv3d_f32_impl(const float* in, const float* wpack, const float* bpa
     ConvArgs a;
     a.in = in; a.bpack = bpack; a.res = residual; a.out = out;
     se_conv_args_set_sections(a, wpack, se_conv3d_pack_layout(cout, cin_pad, ksize, 0));
+    a.wsplit6 = wsplit6;
     a.total_vox = batch * vox;
     a.dim = dim; a.cin = cin; a.cin_pad = cin_pad; a.cout = cout; a.nts = round_up16(cout) / 16; a.flags = flags;
     a.pool_out = pool_out;
@@ -259,8 +263,49 @@ static int conv3d_f32_impl(const float* in, const float* wpack, const float* bpa
 extern "C" int se_conv3d_f32(const float* in, const float* wpack, const float* bpack, const float* residual,
                              float* out, int batch, int dim, int cin, int cin_pad, int cout, int ksize, int flags,
                              float* workspace, long long workspace_elems, void* stream) {
-    return conv3d_f32_impl(in, wpack, bpack, residual, out, nullptr, nullptr, batch, dim, cin, cin_pad, cout, ksize, flags, workspace,
+    return conv3d_f32_impl(in, wpack, nullptr, bpack, residual, out, nullptr, nullptr, batch, dim, cin, cin_pad, cout, ksize, flags, workspace,
                            workspace_elems, stream);
+}
+
+// se_conv3d_f32 for a layer that also has split planes (se_conv3d_split6_pack): the plan may then choose a six-product bf16 form
+// (split6.h) where one exists and is the faster kernel; with wsplit6 == NULL this IS se_conv3d_f32.
+extern "C" int se_conv3d_w6_f32(const float* in, const float* wpack, const se_bf16* wsplit6, const float* bpack, const float* residual,
+                                float* out, int batch, int dim, int cin, int cin_pad, int cout, int ksize, int flags,
+                                float* workspace, long long workspace_elems, void* stream) {
+    return conv3d_f32_impl(in, wpack, wsplit6, bpack, residual, out, nullptr, nullptr, batch, dim, cin, cin_pad, cout, ksize, flags, workspace,
+                           workspace_elems, stream);
+}
+
+// 1 when se_conv3d_w6_f32 runs this call (cin_pad == cin, a workspace, split planes given) on a six-product bf16 form, else 0:
+// the plan's own answer, for the route record of the V2V program.
+extern "C" int se_conv3d_f32_split6(int batch, int dim, int cin, int cout, int ksize, int flags) {
+    if (batch <= 0 || dim <= 0 || cin <= 0 || (cin & 15) || cout <= 0 || (cout & 15) || (ksize != 1 && ksize != 3 && ksize != 7)) return 0;
+    static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};      // section pointers are compared with NULL by the plan, never read
+    ConvArgs a;
+    a.in = nullptr; a.bpack = nullptr; a.res = nullptr; a.out = nullptr;
+    se_conv_args_set_sections(a, dummy, se_conv3d_pack_layout(cout, cin, ksize, 0));
+    a.wsplit6 = se_split6_packed_elems(cout, cin, ksize, 0) > 0 ? reinterpret_cast<const unsigned short*>(dummy) : nullptr;
+    a.total_vox = (long long)batch * dim * dim * dim;
+    a.dim = dim; a.cin = cin; a.cin_pad = cin; a.cout = cout; a.nts = round_up16(cout) / 16; a.flags = flags;
+    const SeConvPlan p = se_conv3d_plan(a, batch, ksize);
+    return !p.error && p.kernel == SE_CONV_HALO64_S6;
+}
+
+// The split form of the 64-voxel-tile kernel on its whole domain (se_conv3d_halo64_s6_domain: dim 8 or 16, cin and cin_pad % 32 == 0,
+// cout % 32 == 0, at most 8192 voxels in the batch), whatever the plan would run the call on: what the tests of the form launch.
+// flags: SE_EPI_RELU, SE_EPI_RES_PRE_RELU / _POST_RELU.  SE_ERR_BAD_ARG otherwise (nothing launched).
+extern "C" int se_conv3d_k3_split6_f32(const float* in, const se_bf16* wsplit6, const float* bpack, const float* residual, float* out,
+                                       int batch, int dim, int cin, int cin_pad, int cout, int flags, void* stream) {
+    if (!in || !wsplit6 || !bpack || !out || batch <= 0 || cin <= 0 || cin_pad < cin || cout <= 0 || (cout & 15)) return SE_ERR_BAD_ARG;
+    if (flags & ~(SE_EPI_RELU | SE_EPI_RES_PRE_RELU | SE_EPI_RES_POST_RELU)) return SE_ERR_BAD_ARG;
+    if ((flags & SE_EPI_RES_PRE_RELU) && (flags & SE_EPI_RES_POST_RELU)) return SE_ERR_BAD_ARG;
+    ConvArgs a;
+    a.in = in; a.wpack = nullptr; a.wsplit6 = wsplit6; a.bpack = bpack; a.res = residual; a.out = out;
+    a.total_vox = (long long)batch * dim * dim * dim;
+    a.dim = dim; a.cin = cin; a.cin_pad = cin_pad; a.cout = cout; a.nts = cout / 16; a.flags = flags;
+    if (!se_conv3d_halo64_s6_domain(a)) return SE_ERR_BAD_ARG;
+    const SeConvPlan p = {SE_CONV_HALO64_S6, dim, batch, 1, 0, 0};
+    return se_conv3d_small_launch(a, p, se_stream(stream));
 }
 
 // Same convolution; the kernel also writes max_pool3d(out, kernel 2, stride 2) (channels-last) from its epilogue, so the 2x pool
@@ -269,7 +314,7 @@ extern "C" int se_conv3d_pool_f32(const float* in, const float* wpack, const flo
                                   float* out, float* pool_out, int batch, int dim, int cin, int cin_pad, int cout, int ksize,
                                   int flags, float* workspace, long long workspace_elems, void* stream) {
     if (!pool_out) return SE_ERR_BAD_ARG;
-    return conv3d_f32_impl(in, wpack, bpack, residual, out, pool_out, nullptr, batch, dim, cin, cin_pad, cout, ksize, flags, workspace,
+    return conv3d_f32_impl(in, wpack, nullptr, bpack, residual, out, pool_out, nullptr, batch, dim, cin, cin_pad, cout, ksize, flags, workspace,
                            workspace_elems, stream);
 }
 
@@ -279,6 +324,6 @@ extern "C" int se_conv3d_skip16_f32(const float* in, const float* wpack, const f
     if (!skip_in || !skip_w) return SE_ERR_BAD_ARG;
     const int lay = flags & ~SE_EPI_RELU;
     if (lay != (SE_IN_OCTET | SE_OUT_OCTET) && lay != (SE_IN_QUAD | SE_OUT_QUAD) && lay != (SE_IN_QUAD | SE_OUT_QUAD | SE_RES_QUAD)) return SE_ERR_BAD_ARG;
-    return conv3d_f32_impl(in, wpack, bpack, skip_in, out, nullptr, skip_w, batch, dim, cin, cin, cout, 3,
+    return conv3d_f32_impl(in, wpack, nullptr, bpack, skip_in, out, nullptr, skip_w, batch, dim, cin, cin, cout, 3,
                            flags | SE_EPI_SKIPCONV16, nullptr, 0, stream);
 }

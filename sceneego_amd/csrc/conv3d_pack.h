@@ -369,6 +369,54 @@ SE_PACK_FN float se_pack_i(const SePackSource& s, long long t) {
     return v;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The split planes of a layer (se_conv3d_split6_pack; read by the six-product bf16 forms, split6.h): a buffer of its own beside
+// the float32 one, bf16 elements.  Every folded float32 weight v of section A (se_pack_weight: the same value, bit for bit) is
+// stored as three bf16 values p + q + r, p = bf16(v), q = bf16(v - p), r = bf16(v - p - q), round to nearest even; the
+// subtractions are exact in float32 and |v - p - q - r| <= 2^-27 |v|.  A-fragment order of v_mfma_f32_16x16x32_bf16:
+//   [sg = cin_pad / 32][tap][nt][plane 3][lane 64][j 8] = plane of W[cout = 16 nt + (lane & 15)][cin = 32 sg + 8 (lane >> 4) + j][tap]
+// taps = k^3 (transposed k = 2: the 8 output parities).  Exists for cin_pad % 32 == 0; -1 otherwise.
+// ------------------------------------------------------------------------------------------------
+SE_PACK_FN long long se_split6_packed_elems(int cout, int cin_pad, int ksize, int transposed) {
+    if (cout <= 0 || cin_pad <= 0 || (cin_pad & 31)) return -1;
+    if (transposed ? (ksize != 2) : (ksize != 1 && ksize != 3 && ksize != 7)) return -1;
+    const long long taps = transposed ? 8 : (long long)ksize * ksize * ksize;
+    return taps * (cin_pad / 32) * (round_up16(cout) / 16) * 3 * 512;
+}
+// float32 -> bf16 bits, round to nearest even (finite values: what v_cvt_pk_bf16_f32 gives); and back
+SE_PACK_FN unsigned short se_bf16_rne_bits(float f) {
+    unsigned u;
+    __builtin_memcpy(&u, &f, 4);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (unsigned short)(u >> 16);
+}
+SE_PACK_FN float se_bf16_bits_value(unsigned short h) {
+    const unsigned u = (unsigned)h << 16;
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+// element t of the split planes, from section A of the layer's packed float32 buffer (the folded weights are read, not recomputed:
+// the planes sum to the very value the float32 kernels multiply with)
+SE_PACK_FN unsigned short se_split6_value(const float* section_a, int cout, int ksize, int transposed, long long t) {
+    const int nts = round_up16(cout) / 16, taps = transposed ? 8 : ksize * ksize * ksize;
+    const int j = (int)(t & 7);
+    const int lane = (int)((t >> 3) & 63);
+    long long r = t >> 9;
+    const int plane = (int)(r % 3); r /= 3;
+    const int nt = (int)(r % nts); r /= nts;
+    const int tap = (int)(r % taps); r /= taps;
+    const int ci = (int)r * 32 + 8 * (lane >> 4) + j;
+    const int lane_a = ((ci & 15) >> 2) * 16 + (lane & 15);
+    float v = section_a[((((long long)(ci >> 4) * taps + tap) * nts + nt) * 64 + lane_a) * 4 + (ci & 3)];
+    unsigned short h = se_bf16_rne_bits(v);
+    for (int p = 0; p < plane; ++p) {
+        v -= se_bf16_bits_value(h);
+        h = se_bf16_rne_bits(v);
+    }
+    return h;
+}
+
 SE_PACK_FN float se_pack_value(int section, const SePackSource& s, long long t) {
     switch (section) {
         case SE_PACK_A: return se_pack_a(s, t);

@@ -15,6 +15,7 @@ enum SeConvKernel {
     SE_CONV_TILED_K3,        // LDS-tiled direct 3^3 (conv3d_tiled.hip); form: cout tiles per workgroup (4, 2, 1)
     SE_CONV_TILED_K7,        // LDS-tiled direct 7^3
     SE_CONV_HALO64,          // small levels (conv3d_small.hip): 64-voxel tiles through LDS; form: dim (8, 16)
+    SE_CONV_HALO64_S6,       // small levels: the six-product bf16 form of SE_CONV_HALO64 (split6.h; needs ConvArgs::wsplit6); form: dim (8, 16)
     SE_CONV_WAVESPLIT,       // small levels: in-workgroup split-K; form: waves per workgroup (4: two cout tile pairs of 2 x 4 waves, 8, 16)
     SE_CONV_SPLITK_GRID,     // small levels: taps split over grid.z into the caller's workspace + reduce; `splits`
     SE_CONV_DIRECT,          // any shape (conv3d_direct.hip): activations straight from global memory; form: ksize
@@ -66,7 +67,13 @@ int se_conv3d_k7_wino47_launch_cl(const ConvArgs& a, int batch, int num_cus, hip
 int se_conv3d_k7_wino47_launch_p3(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
 // conv3d_tiled.hip: SE_CONV_TILED_K3 / _K7 (development builds: the retired persistent direct kernels too)
 int se_conv3d_tiled_launch(const ConvArgs& a, int batch, int kernel, int form, hipStream_t s);
-// conv3d_small.hip: SE_CONV_HALO64 / _WAVESPLIT / _SPLITK_GRID, on the whole batch; reads p.kernel, p.form and p.splits
+// conv3d_small.hip: SE_CONV_HALO64 / _HALO64_S6 / _WAVESPLIT / _SPLITK_GRID, on the whole batch; reads p.kernel, p.form and p.splits
+// _s6_domain: what conv3d_k3_halo64_s6_kernel can run at all (whole 64-voxel tiles of rows, 32-channel stages of input and split
+// planes, cout tile pairs, 32-bit byte offsets into the input); when it is the faster kernel is the plan's to say
+inline bool se_conv3d_halo64_s6_domain(const ConvArgs& a) {
+    return (a.dim == 8 || a.dim == 16) && a.cin > 0 && (a.cin & 31) == 0 && (a.cin_pad & 31) == 0 && a.nts > 0 && a.nts % 2 == 0 && a.cout == a.nts * 16 &&
+           a.total_vox > 0 && a.total_vox <= 8192 && a.total_vox * a.cin_pad * 4LL < (1LL << 31);
+}
 int se_conv3d_small_launch(const ConvArgs& a, const SeConvPlan& p, hipStream_t s);
 // conv3d_direct.hip: SE_CONV_DIRECT, on the whole batch
 int se_conv3d_direct_launch(const ConvArgs& a, int ksize, hipStream_t s);

@@ -4,6 +4,7 @@
 #include "common.h"
 
 #include "conv3d_plan.h"
+#include "split6.h"
 
 namespace {
 
@@ -354,6 +355,163 @@ __global__ __launch_bounds__(512) void conv3d_k3_halo64_kernel(ConvArgs a) {
     (void)per_b;
 }
 
+// The split form of the kernel above (split6.h: a float32 product as six bf16 products on v_mfma_f32_16x16x32_bf16): same tiles,
+// stages, wave roles, reduction and epilogue; what changes is the k step and the operands.
+//   A k step is one TAP over the stage's 32 channels (K = 32 of one MFMA): 27 steps per stage, step = wave + 8 j (4, 4, 4, 3, 3, 3,
+//   3, 3 per wave; waves w and w + 4 share a SIMD: 7, 7, 7, 6 steps per SIMD), 48 MFMAs each (6 products x 2 cout x 4 voxel tiles).
+//   Activations are split ONCE, when the stage is committed: a thread loads 8 channels of a halo voxel (two 16-byte loads) and
+//   writes its three bf16 planes, [plane 3][octet 4][16 B] per voxel = 192 of a 224-byte record (6 B per element instead of 4; the
+//   pitch leaves the 16 lanes of a ds_read_b128 group on 16 different 16-byte slots at dim 16, two per slot at dim 8).
+//   Weights are the layer's split planes (conv3d_pack.h), [stage][tap][nt][plane][lane] x 16 B: 6 loads per step, two steps in
+//   flight in a register ring (slot j & 1; a step's 48 MFMAs cover the next one's loads).
+template <int DIM>
+struct Halo64S6 {
+    using F = Halo64<DIM>;
+    static constexpr int PITCH = 224;
+    static constexpr int HB = F::HV * PITCH;
+    static constexpr int PIECES = F::HV * 4;          // (voxel, channel octet) pieces of a stage: 1200 (dim 8) / 1296 (dim 16)
+    static constexpr int HP = (PIECES + 511) / 512;
+    static constexpr int MT_OFF = (16 / DIM) * F::HX * PITCH;
+    static constexpr int LDS_BYTES = 2 * HB > 65536 ? 2 * HB : 65536;
+    static_assert(LDS_BYTES <= 160 * 1024, "two stage buffers in LDS");
+};
+
+template <int DIM>
+__global__ __launch_bounds__(512) void conv3d_k3_halo64_s6_kernel(ConvArgs a) {
+    using G = Halo64<DIM>;
+    using S = Halo64S6<DIM>;
+    constexpr int HX = G::HX, HY = G::HY, PITCH = S::PITCH, HP = S::HP;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int vl = lane & 15, h = lane >> 4;
+    const int stages = a.cin >> 5;
+    const int nt0 = blockIdx.y * 2;
+    constexpr unsigned OOB = 0x80000000u;
+    int t = blockIdx.x;
+    const int ty = t % (DIM / G::R); t /= (DIM / G::R);
+    const int z = t % DIM;
+    const int b = t / DIM;
+    const int y0 = ty * G::R;
+    const long long vid0 = (((long long)b * DIM + z) * DIM + y0) * DIM;
+
+    // this thread's halo pieces (voxel hv, channel octet q): byte offset in the input tensor, out of range outside the volume
+    unsigned goff[HP];
+#pragma unroll
+    for (int j = 0; j < HP; ++j) {
+        const int p = tid + 512 * j;
+        const int hv = p >> 2, q = p & 3;
+        const int hx = hv % HX, hy = (hv / HX) % HY, hz = hv / (HX * HY);
+        const int gz = z + hz - 1, gy = y0 + hy - 1, gx = hx - 1;
+        const bool ok = p < S::PIECES && (unsigned)gz < (unsigned)DIM && (unsigned)gy < (unsigned)DIM && (unsigned)gx < (unsigned)DIM;
+        goff[j] = ok ? (unsigned)(((((long long)b * DIM + gz) * DIM + gy) * DIM + gx) * a.cin_pad * 4 + q * 32) : OOB;
+    }
+    const int lpiece = (tid >> 2) * PITCH + (tid & 3) * 16;                   // piece j: + j * 128 * PITCH; plane k: + 64 k
+    const unsigned in_bytes = (unsigned)(a.total_vox * a.cin_pad * 4);        // launcher: fits 31 bits
+    const unsigned w_bytes = (unsigned)(27 * (a.cin_pad >> 5) * a.nts * 3072);
+    const auto xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, (int)in_bytes, 0x00020000);
+    const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.wsplit6), 0, (int)w_bytes, 0x00020000);
+    const int woff = lane * 16;
+    // operand reads: lane (vl, h) = voxel vl of the tile's first 16, channels 8 h .. 8 h + 7 of the stage, at the tap (-1, -1, -1) corner
+    const int lrow = DIM == 8 ? (vl >> 3) : 0, lx = DIM == 8 ? (vl & 7) : vl;
+    const int lbase = (lrow * HX + lx) * PITCH + h * 16;
+
+    f32x4 st[HP][2];
+    auto load_stage = [&](int sg) {
+#pragma unroll
+        for (int j = 0; j < HP; ++j) {
+            st[j][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (int)goff[j], sg * 128, 0));
+            st[j][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (int)(goff[j] + 16u), sg * 128, 0));
+        }
+    };
+    auto commit_stage = [&](unsigned char* buf) {
+#pragma unroll
+        for (int j = 0; j < HP; ++j) {
+            const Split6Frag f = se_split3_x8(st[j][0], st[j][1]);
+            if (tid + 512 * j < S::PIECES) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) *reinterpret_cast<u16x8*>(buf + lpiece + j * 128 * PITCH + k * 64) = f.p[k];
+            }
+        }
+    };
+    Split6Frag wr[2][2];
+    auto load_w = [&](Split6Frag (&w)[2], int j, int sg) {      // step wave + 8 j of stage sg; a step past the 27 taps is dead: nothing loaded
+        const int tap = wave + 8 * j;
+        if (tap >= 27) return;                         // uniform
+        const int wso = ((sg * 27 + tap) * a.nts + nt0) * 3072;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                w[m].p[k] = __builtin_bit_cast(u16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, wso + (m * 3 + k) * 1024, 0));
+    };
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    // the epilogue's operands (wave w finishes fragment w = (cout tile w >> 2, voxel tile w & 3))
+    const int co0 = (nt0 + (wave >> 2)) * 16 + 4 * h;
+    const long long ooff = (vid0 + (wave & 3) * 16 + vl) * a.cout + co0;
+    f32x4 ebias = (f32x4){0.f, 0.f, 0.f, 0.f}, eres = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    load_stage(0);
+    load_w(wr[0], 0, 0);
+    load_w(wr[1], 1, 0);
+    for (int sg = 0; sg < stages; ++sg) {
+        unsigned char* buf = lds + (sg & 1) * S::HB;
+        commit_stage(buf);
+        __syncthreads();          // the stage is in LDS; every wave has left the stage before the previous one (the buffer written next)
+        const bool more = sg + 1 < stages;
+        if (more) {
+            load_stage(sg + 1);
+        } else {
+            ebias = *reinterpret_cast<const f32x4*>(a.bpack + co0);
+            if (a.res) eres = *reinterpret_cast<const f32x4*>(a.res + ooff);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int tap = wave + 8 * j;
+            if (tap < 27) {                            // uniform
+                const int toff = (((tap / 9) * HY + (tap / 3) % 3) * HX + tap % 3) * PITCH;
+                const unsigned char* p = buf + lbase + toff;
+                Split6Frag x[4];
+#pragma unroll
+                for (int n = 0; n < 4; ++n)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) x[n].p[k] = *reinterpret_cast<const u16x8*>(p + n * S::MT_OFF + k * 64);
+                const Split6Frag(&w)[2] = wr[j & 1];
+#pragma unroll
+                for (int k = 0; k < SE_S6_PRODUCTS; ++k)   // product outer: consecutive MFMAs go to different accumulators
+#pragma unroll
+                    for (int n = 0; n < 4; ++n)
+#pragma unroll
+                        for (int m = 0; m < 2; ++m) acc[m][n] = mfma_bf16(w[m].p[SE_S6_W[k]], x[n].p[SE_S6_X[k]], acc[m][n]);
+            }
+            // the slot's registers are free: the step two ahead (this stage's, then the next stage's first two)
+            if (j + 2 < 4) load_w(wr[j & 1], j + 2, sg);
+            else if (more) load_w(wr[j & 1], j - 2, sg + 1);
+        }
+    }
+    __syncthreads();              // every wave is done with the halo buffers: the partial sums go on top of them
+    f32x4(*red)[8][64] = reinterpret_cast<f32x4(*)[8][64]>(lds);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) red[wave][m * 4 + n][lane] = acc[m][n];
+    __syncthreads();
+    f32x4 v = red[0][wave][lane];                      // partials added in wave order
+#pragma unroll
+    for (int w2 = 1; w2 < 8; ++w2) v += red[w2][wave][lane];
+    v += ebias;
+    if ((a.flags & SE_EPI_RES_PRE_RELU) && a.res) v += eres;
+    if (a.flags & SE_EPI_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if ((a.flags & SE_EPI_RES_POST_RELU) && a.res) v += eres;
+    *reinterpret_cast<f32x4*>(a.out + ooff) = v;
+}
+
 // thread = (voxel, cout quad): sum the split partials in order, then the usual epilogue
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(ConvArgs a, const float* __restrict__ ws, int splits) {
     const int cq = a.cout >> 2;
@@ -394,6 +552,17 @@ int se_conv3d_small_launch(const ConvArgs& a, const SeConvPlan& p, hipStream_t s
             } else {
                 SE_ENSURE_LDS(conv3d_k3_halo64_kernel<16>, Halo64<16>::LDS_BYTES);
                 hipLaunchKernelGGL((conv3d_k3_halo64_kernel<16>), grid, dim3(512), Halo64<16>::LDS_BYTES, s, a);
+            }
+            break;
+        }
+        case SE_CONV_HALO64_S6: {   // the same tiles, six-product bf16 form (the plan has checked se_conv3d_halo64_s6_domain and a.wsplit6)
+            const dim3 grid((unsigned)(a.total_vox / 64), a.nts / 2);
+            if (p.form == 8) {
+                SE_ENSURE_LDS(conv3d_k3_halo64_s6_kernel<8>, Halo64S6<8>::LDS_BYTES);
+                hipLaunchKernelGGL((conv3d_k3_halo64_s6_kernel<8>), grid, dim3(512), Halo64S6<8>::LDS_BYTES, s, a);
+            } else {
+                SE_ENSURE_LDS(conv3d_k3_halo64_s6_kernel<16>, Halo64S6<16>::LDS_BYTES);
+                hipLaunchKernelGGL((conv3d_k3_halo64_s6_kernel<16>), grid, dim3(512), Halo64S6<16>::LDS_BYTES, s, a);
             }
             break;
         }

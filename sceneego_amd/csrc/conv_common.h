@@ -45,6 +45,7 @@ struct ConvArgs {
     const float* wpack_h = nullptr;  // section H
     const float* wpack_i = nullptr;  // section I
     const float* wpack_g = nullptr;  // section G
+    const unsigned short* wsplit6 = nullptr;  // the layer's split planes (se_conv3d_split6_pack; a buffer of its own), NULL: float32 forms only
     const float* skip_w = nullptr;   // SE_EPI_SKIPCONV16: folded 1x1x1 skip weights [cout][16]; `res` then is the skip convolution's 16-channel input
     float* pool_out = nullptr;       // 2-D Winograd kernel only: also write max_pool3d(out, 2, 2), channels-last [B][D/2][D/2][D/2][cout] (else NULL)
     const float* bpack;

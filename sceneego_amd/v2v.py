@@ -203,6 +203,7 @@ class V2VRoute(NamedTuple):
     up: Tuple[int, ...]                 # flag words of decoder_upsample1..5
     fork: frozenset                     # levels (0 = G^3) whose skip block runs on the side stream
     tail: TailRoute
+    split6: frozenset = frozenset()     # blocks with a 3x3x3 launch on a six-product bf16 form (csrc/split6.h; se_conv3d_f32_split6)
 
 
 _BLOCKS = {"front1": (16, 32), "front2": (32, 32), "front3": (32, 32), "mid": (128, 128), "back0": (32, 32)}
@@ -213,10 +214,12 @@ for _k in range(5):
 _LAY = {"quad": (_lib.IN_QUAD, _lib.OUT_QUAD, _lib.RES_QUAD), "oct": (_lib.IN_OCTET, _lib.OUT_OCTET, _lib.RES_OCTET), None: (0, 0, 0)}
 
 
-def v2v_route(cout, dtype, split3, B, G, input_form="cl", fused_softargmax=False, fork=frozenset()) -> V2VRoute:
+def v2v_route(cout, dtype, split3, B, G, input_form="cl", fused_softargmax=False, fork=frozenset(), split6=False) -> V2VRoute:
     """Layouts, flag words and fused forms of one forward of the V2V program: a pure function of these integers and of the library's
     kernel choice (``_lib.conv3d_variant``, a host function).  Nothing is allocated or launched.  ``input_form``: "planar1"
     [B,cin,G,G,G] (frequency-domain front layer), "planar3" (triplet-planar) or "cl" (channels-last; bf16: octet-planar).
+    ``split6``: the float32 program packed split planes (SCENEEGO_SPLIT6, on by default): the route records which blocks the library
+    then runs on a six-product bf16 form; layouts, flag words and variants are the same either way.
 
     Tensor layouts of the float32 program: a Res3DBlock output that is read only by 2-D Winograd convolutions of the same kernel
     family (as input or as skip tensor) and by a max-pool is kept in that family's planar layout (quad-planar at 64^3 / 32^3,
@@ -310,16 +313,18 @@ def v2v_route(cout, dtype, split3, B, G, input_form="cl", fused_softargmax=False
     tail = TailRoute(cout <= 16, sa and kind("back0", G) == "quad", sa)
     block("back0", G, "quad" if up_quad[0] else None, tail.in_quad)
     up = tuple(R | POST | (_lib.OUT_QUAD | _lib.RES_QUAD if q else 0) for q in up_quad)
-    return V2VRoute(front0, MappingProxyType(blocks), up, frozenset(fork), tail)
+    s6 = frozenset(n for n, e in blocks.items() if split6 and forms and any(
+        _lib.conv3d_split6(B, e.dim, ci, e.cout, 3, fl) for ci, fl in ((e.cin, e.flags1), (e.cout, e.flags2))))
+    return V2VRoute(front0, MappingProxyType(blocks), up, frozenset(fork), tail, s6)
 
 
 # ------------------------------------------------------------------------------------------------
 # the launch program
 # ------------------------------------------------------------------------------------------------
 class _PackedConv:
-    __slots__ = ("w", "b", "cin", "cin_pad", "cout", "k", "transposed", "fused", "w_split")
+    __slots__ = ("w", "b", "cin", "cin_pad", "cout", "k", "transposed", "fused", "w_split", "w_split6")
 
-    def __init__(self, conv, bn, cin_pad=None, dtype=torch.float32, scale=1.0, split3=False):
+    def __init__(self, conv, bn, cin_pad=None, dtype=torch.float32, scale=1.0, split3=False, split6=False):
         """``scale``: the packed layer computes scale * conv(x) (weights and bias multiplied before packing).
         ``split3`` (float32 3x3x3 layers, experimental): also pack the two bfloat16 halves of the BatchNorm-folded weights for
         se_conv3d_k3_split3_f32."""
@@ -353,6 +358,10 @@ class _PackedConv:
         if scale != 1.0 and bias is not None:
             bias = bias * float(scale)
         _lib.conv3d_pack(w, bias, g, be, mu, var, eps, self.w, self.b, cout, cin, self.cin_pad, k, transposed)
+        # the six-product bf16 forms of the float32 program (csrc/split6.h): the layer's split planes, hung on self.w for _lib.conv3d
+        self.w_split6 = None
+        if split6 and not bf16 and not transposed and k == 3 and cout % 32 == 0:
+            self.w_split6 = _lib.conv3d_split6_pack(self.w, cout, self.cin_pad, k, transposed)
         self.w_split = None
         if split3 and not bf16 and not transposed and k == 3 and cout % 32 == 0 and self.cin_pad % 8 == 0:
             wf = w if g is None else w * (g / torch.sqrt(var + eps)).view(-1, 1, 1, 1, 1)      # the folding se_conv3d_pack_f32 applies
@@ -365,6 +374,9 @@ class V2VProgram:
         self.output_scale = float(output_scale)
         # EXPERIMENTAL: float32 tensors, 3x3x3 layers of the 64^3 / 32^3 / 16^3 levels on split-bf16 arithmetic (csrc/conv3d_split.hip)
         self.split3 = bool(split3) and dtype == torch.float32
+        # float32 program: the direct-GEMM launches that have a six-product bf16 form (csrc/split6.h) run on it; SCENEEGO_SPLIT6=0
+        # packs no split planes, which keeps every launch on its float32 form (A/B)
+        self.split6 = dtype == torch.float32 and not self.split3 and os.environ.get("SCENEEGO_SPLIT6", "1") != "0"
         p = next(model.parameters())
         if not p.is_cuda:
             raise _lib.HipExtensionError("V2VModel must live on a HIP device to be compiled (got %s)" % p.device)
@@ -410,8 +422,8 @@ class V2VProgram:
         self._routes = {}
 
     def _pack_res(self, m):
-        c1 = _PackedConv(m.res_branch[0], m.res_branch[1], None, self.dtype, split3=self.split3)
-        c2 = _PackedConv(m.res_branch[3], m.res_branch[4], None, self.dtype, split3=self.split3)
+        c1 = _PackedConv(m.res_branch[0], m.res_branch[1], None, self.dtype, split3=self.split3, split6=self.split6)
+        c2 = _PackedConv(m.res_branch[3], m.res_branch[4], None, self.dtype, split3=self.split3, split6=self.split6)
         sk = _PackedConv(m.skip_con[0], m.skip_con[1], None, self.dtype) if len(m.skip_con) else None
         if sk is not None and sk.cin == 16 and self.dtype == torch.float32:
             # 16-channel skip convolution (front_layers.1): folded weights [cout][16] + summed bias for se_conv3d_skip16_f32, which
@@ -498,7 +510,7 @@ class V2VProgram:
         key = (B, G, form, fused_softargmax, self._fork_set(B, G))
         route = self._routes.get(key)
         if route is None:
-            route = self._routes[key] = v2v_route(self.cout, self.dtype, self.split3, *key)
+            route = self._routes[key] = v2v_route(self.cout, self.dtype, self.split3, *key, split6=self.split6)
         return route
 
     def run(self, x, B, G, out=None, softargmax=None, scaled=False, planar1=False):
