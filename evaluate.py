@@ -211,6 +211,9 @@ def build_parser():
     ap.add_argument("--path_alternatives", default=None, help="with --pred_dir path.pkl: the pickle of run_sequence.py "
                     "--path_alternatives_output for the same frames; adds the best-of-two MPJPE per joint (the path or its runner-up "
                     "trajectory) and spearman(error, margin); without --gt only the margins are summarised")
+    ap.add_argument("--samples", default=None, help="with --pred_dir smoothed.pkl: the pickle of run_sequence.py --sample_output for the "
+                    "same frames; adds the best-of-N MPJPE per joint (the closest valid sample of every joint) and the rank correlation "
+                    "of the smoothed joint's error and the samples' spread")
     ap.add_argument("--bones", nargs="?", const="", default=None, metavar="FILE.npy",
                     help="bone-length summary of the predictions (needs no ground truth): the per-bone standard deviation over the "
                     "sequence and, with FILE.npy (14 or 15 lengths, as run_sequence.py --bone_lengths takes them), the mean absolute "
@@ -281,6 +284,12 @@ def main(argv=None):
         print(f"best-of-two MPJPE {a['best_of_two_mpjpe']:.6f} {args.unit} (every joint on its path or on its runner-up trajectory, "
               f"whichever is closer; the runner-up in {a['runner_up_closer_share']:.1%} of the joint-frames); spearman(error, margin): "
               f"{a['spearman_error_margin']:.4f} over {a['joint_frames_with_margin']} joint-frames")
+    if args.samples is not None:
+        from sceneego_amd import metrics as M
+        a = r["samples"] = M.best_of_samples(load_alternatives(args.samples, len(names)), pred, gt)
+        print(f"best-of-{a['samples_per_joint']} MPJPE {a['best_of_n_mpjpe']:.6f} {args.unit} (the closest valid sample of every joint; "
+              f"{a['valid_draws']} of {a['draws']} draws valid); mean spread {a['mean_sample_spread']:.4f} {args.unit}; "
+              f"spearman(error, spread): {a['spearman_error_spread']:.4f}")
     if args.bones is not None:
         r["bones"] = bones(pred, args.bones, args.unit)
     return r

@@ -781,6 +781,49 @@ int se_volume_transition_stats_f32(const float* prob, const float* belief, const
                                    int voxels, int G, int radius, float floor, const int* have_link, void* stream);
 long long se_volume_transition_stats_scratch_bytes(int rows, int G, int radius);
 
+/* Trajectory samples: forward-filter backward-sampling on the model of se_volume_filter_f32 and se_volume_smooth_f32
+ * (sceneego_amd/volume_smoother.py: VolumeSmoother.sample).  Joint draws from the posterior over whole trajectories of each row, given
+ * the filtered beliefs.  It adds no convention: motion model, floor and link rule are the filter's and the smoother's.
+ * tests/volume_sampler_model.py restates what follows in numpy float64 and index, kind and next are compared with it BIT FOR BIT: all
+ * arithmetic is float64, one rounding per operation (no fused multiply-add), every sum SEQUENTIAL in ascending index.
+ *   belief     [frames][rows][voxels] float32: the filter's belief_out b_t;  restarted [frames][rows] int32: the filter's output
+ *   taps, G, radius, floor, rows, frames, voxels, flat index n = (i G + j) G + k: as for se_volume_filter_f32
+ *   keep = (double)(1.0f - floor),  uniform = (double)(floor / (float)voxels)  (float32, as the filter forms them),  w[d] = (double)taps
+ * TRANSITION from x at frame t to y at t + 1: (1 - floor) W(x -> y) + floor / N with W as blur3 has it, q(y) = sum_d w[d] b(y + d): the
+ *            window of y is x = y + d with weight w[di] w[dj] w[dk], NO tap reversal, taps that leave the grid skipped.
+ * CATEGORICAL DRAW over non-negative v_0..v_{n-1} with u in [0, 1): c_m = c_{m-1} + v_m, total = c_{n-1}; the first m with c_m > u total,
+ *            or where rounding leaves none the last m with v_m > 0.  A value of 0 is never drawn.  A total that is not a finite number
+ *            > 0: no draw.
+ * GLOBAL DRAW from b_t with (u1, u2, u3): Rs[i][j] = sum_k b, P[i] = sum_j Rs[i][j], total_t = sum_i P[i]; i from P, j from Rs[i][.], k
+ *            from b[i][j][.].  INVALID (index -1) when total_t is not a finite number > 0, a frame that holds a NaN for one.
+ * WINDOW DRAW given y: r[di][dj] = sum_dk (double)b(y + d) w[dk],  q[di] = sum_dj r[di][dj] w[dj],  Wsum = sum_di q[di] w[di];
+ *            step = keep Wsum, jump = uniform total_t, mass = step + jump.  A mass that is not a finite number > 0: the frame is drawn
+ *            as an unlinked one.  Otherwise it is a jump iff u0 mass >= step: a global draw; else a step: di from q[di] w[di], dj from
+ *            r[di][.] w[dj], dk from b(y + d) w[dk], with (u1, u2, u3).
+ * CHAIN      per sample and row, last frame to first: a frame that is not linked takes a global draw (kind 2); a linked one the window
+ *            draw (kind 0 a step, 1 a jump).  Frame t is linked to t + 1 unless t is the last frame of the track, restarted[t + 1] is
+ *            set or the draw of t + 1 was invalid.
+ * UNIFORMS   Philox4x32-10, key (seed_lo, seed_hi), counter (first_sample + sample, first_frame + frame, row, block).  A block's
+ *            words give two uniforms, (double)((w0 << 32 | w1) >> 11) 2^-53 and the same of (w2, w3): block 0 u0, u1; block 1 u2, u3.
+ *            The indices are GLOBAL: the result depends neither on how the frames are cut into calls nor on how the samples are split.
+ *   next       [samples][rows] int32.  In: the voxel drawn for the frame behind the call's last frame, read only for rows that have_link
+ *              marks (a value outside 0..voxels-1 links nothing).  Out: the voxel of the call's first frame, -1 when invalid.
+ *   have_link  NULL or int32 [rows], as for se_volume_smooth_f32
+ *   index      [samples][frames][rows] int32: x_t, -1 when invalid       kind  [samples][frames][rows] int32: 0, 1 or 2 (the branch taken)
+ *   samples >= 1;  first_sample + samples and first_frame + frames at most 2^32, neither offset negative
+ *   scratch    se_volume_sample_scratch_bytes(frames, rows, G) bytes, 8-byte aligned: Rs and P of every frame in float64,
+ *              frames rows (G^2 + G) doubles; 0 for a shape out of range.  total_t is formed from P by the walk.
+ * Two launches on `stream`: the sums of all frames of the call (one read of the beliefs), then the walk, one workgroup per (sample, row)
+ * that loops over the frames from last to first inside the launch.  No atomics; bitwise identical from run to run.  Allocates nothing.
+ * SE_ERR_BAD_ARG, with nothing launched: a null pointer other than have_link, a pointer that is not 4-byte aligned (scratch: 8-byte),
+ * frames < 1, rows outside 1..65535, G outside 2..128, voxels != G^3, radius outside 0..min(16, G - 1), floor outside [0, 1] or NaN,
+ * samples < 1, an offset out of range, scratch_bytes below se_volume_sample_scratch_bytes(frames, rows, G).                           */
+int se_volume_sample_f32(const float* belief, const int* restarted, const float* taps, int* next, int* index, int* kind, void* scratch,
+                         long long scratch_bytes, int frames, int rows, int voxels, int G, int radius, float floor, int samples,
+                         long long first_sample, long long first_frame, unsigned int seed_lo, unsigned int seed_hi,
+                         const int* have_link, void* stream);
+long long se_volume_sample_scratch_bytes(int frames, int rows, int G);
+
 /* Most probable joint trajectory: the max-product (Viterbi) pass that goes with se_volume_filter_f32 and se_volume_smooth_f32
  * (sceneego_amd/volume_viterbi.py: VolumeViterbi; VoxelNetwork_depth.volume_path returns one).  The filter and the smoother give per
  * frame the marginal of each joint; this gives the single most probable trajectory of each joint through the grid.

@@ -58,6 +58,10 @@ memory) and a backward pass at the end of the sequence conditions every frame on
 ``--filter_radius`` and ``--filter_floor`` and implies the filter, so ``--filter_output`` may be given as well and gets the same joints
 as without it; ``--smooth_info_output`` adds the per-frame dicts (joints, smoothed, agreement, filtered_joints, shift_filtered, shift).
 Smoothed beliefs are not rendered: frames are rendered per batch, before the future exists.
+``--sample_output`` writes a pickle of per-frame dicts of ``--samples`` (default 16) whole trajectories per joint drawn from the posterior
+of that smoother's model (``VolumeSmoother.sample``, seed ``--sample_seed``): index, coord, kind, valid [S,15,...], mean, spread and shift.
+It implies the smoother, draws before the smoother finishes, and prints the mean spread and the best-of-N MPJPE (the closest valid sample
+of every joint) beside the smoothed MPJPE.  The samples are from the model's posterior given the volumes read as likelihoods: not calibrated.
 ``--skeleton_output`` writes a pickle in the format of ``--output`` whose joints are coupled over the kinematic tree inside every frame
 (``VoxelNetwork_depth.skeleton_prior``, ``sceneego_amd/skeleton_prior.py``: belief propagation over the fifteen volumes with a
 bone-length shell of ``--skeleton_tau`` metres on every edge and a uniform floor ``--skeleton_floor``), per batch on the stream the
@@ -320,7 +324,7 @@ class SequenceRunner:
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
             volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False,
-            smooth=None, path=None, map_pose=None):
+            smooth=None, path=None, map_pose=None, sample=None):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -343,7 +347,9 @@ class SequenceRunner:
         are appended after those.  ``map_pose``: a dict of ``bone_lengths`` / ``tau`` / ``floor`` / ``refine`` for
         ``VoxelNetwork_depth.skeleton_pose``, and optionally ``separation`` (then ``SkeletonPose.alternatives`` runs in place of
         ``solve`` and the dicts carry its entries too): the most probable pose of every frame is taken from the batch's raw volumes on the stream
-        the batch ran on and the per-frame pose dicts are appended last."""
+        the batch ran on and the per-frame pose dicts are appended after those.  ``sample`` (with ``smooth``): a dict of ``samples`` /
+        ``seed`` for ``VolumeSmoother.sample``, drawn once behind the last batch and before ``finish()``; the per-frame sample dicts
+        are appended last."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
                                      skeleton_alternatives_to_numpy, skeleton_couple_to_numpy, skeleton_pose_to_numpy,
@@ -358,6 +364,8 @@ class SequenceRunner:
             raise ValueError("render_filtered needs filter and render_volumes")
         if smooth is not None and filter is None:
             raise ValueError("smooth needs filter")
+        if sample is not None and smooth is None:
+            raise ValueError("sample needs smooth")
         vs = self.net.volume_smoother(**filter, **smooth) if smooth is not None else None
         vf = vs.filter if vs is not None else self.net.volume_filter(**filter) if filter is not None else None
         if render_coupled and (skeleton is None or not render_volumes or render_filtered):
@@ -492,6 +500,10 @@ class SequenceRunner:
                 if self.video is not None:
                     self.video.close()
                     self.video = None
+        frame_samples = None
+        if sample is not None:                  # before finish(): the draws read the stored filtered beliefs, finish() releases them
+            from sceneego_amd.op import volume_samples_to_numpy
+            frame_samples = volume_samples_to_numpy(vs.sample(**sample))
         frame_smooth = volume_smoother_to_numpy(vs.finish()) if vs is not None else None
         if vp is not None and path_separation is not None:
             from sceneego_amd.op import volume_path_alternatives_to_numpy
@@ -504,7 +516,8 @@ class SequenceRunner:
             + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
             + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ()) \
             + ((frame_skeleton,) if sp is not None else ()) + ((frame_smooth,) if vs is not None else ()) \
-            + ((frame_path,) if vp is not None else ()) + ((frame_map,) if mpose is not None else ())
+            + ((frame_path,) if vp is not None else ()) + ((frame_map,) if mpose is not None else ()) \
+            + ((frame_samples,) if sample is not None else ())
 
 
 def _size(text):
@@ -580,6 +593,11 @@ def build_parser():
                     "joints, smoothed, agreement, filtered_joints, shift_filtered, shift)")
     ap.add_argument("--smooth_max_gb", type=float, default=None, help="with --smooth_output: the most device memory the stored volumes "
                     "and beliefs may take, in GiB (default: half of what is free at the first batch)")
+    ap.add_argument("--sample_output", default=None, help="pickle of the per-frame dicts of trajectory samples drawn from the smoother's "
+                    "posterior (VolumeSmoother.sample: index, coord, kind, valid [S,15,...], mean, spread, shift); implies the smoother "
+                    "on --filter_sigma / --filter_radius / --filter_floor and draws before it finishes; a convention, not calibrated")
+    ap.add_argument("--samples", type=int, default=None, help="with --sample_output: trajectories per joint (default 16)")
+    ap.add_argument("--sample_seed", type=int, default=None, help="with --sample_output: the seed, 0..2^64-1 (default 0)")
     ap.add_argument("--path_output", default=None, help="pickle in the format of --output holding the joints of the most probable "
                     "trajectory of every joint through the sequence's volumes (sceneego_amd/volume_viterbi.py; --filter_sigma, "
                     "--filter_radius, --filter_floor: the filter's convention, not calibrated); with --skeleton_output it runs on the "
@@ -667,13 +685,23 @@ def parse_args(argv=None):
     if args.filter_output is not None or args.filter_info_output is not None or args.render_filtered:
         args.filter = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor}
     args.smooth = None
-    if args.smooth_output is not None or args.smooth_info_output is not None:
+    if args.smooth_output is not None or args.smooth_info_output is not None or args.sample_output is not None:
         if args.smooth_max_gb is not None and not args.smooth_max_gb >= 0:
             raise SystemExit("--smooth_max_gb must be >= 0")
         args.smooth = {"max_bytes": None if args.smooth_max_gb is None else int(args.smooth_max_gb * 2 ** 30)}
         args.filter = {"sigma": args.filter_sigma, "radius": args.filter_radius, "floor": args.filter_floor}
     elif args.smooth_max_gb is not None:
         raise SystemExit("--smooth_max_gb needs --smooth_output")
+    args.sample = None
+    if args.sample_output is not None:
+        samples, seed = 16 if args.samples is None else args.samples, 0 if args.sample_seed is None else args.sample_seed
+        if samples < 1:
+            raise SystemExit("--samples must be >= 1")
+        if not 0 <= seed < 2 ** 64:
+            raise SystemExit("--sample_seed must be in 0..2^64-1")
+        args.sample = {"samples": samples, "seed": seed}
+    elif args.samples is not None or args.sample_seed is not None:
+        raise SystemExit("--samples and --sample_seed need --sample_output")
     args.path = None
     if args.path_output is not None or args.path_info_output is not None or args.path_alternatives_output is not None:
         if args.path_max_gb is not None and not args.path_max_gb >= 0:
@@ -835,7 +863,7 @@ def main(argv=None):
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
                        volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
                        filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled,
-                       smooth=args.smooth, path=args.path, map_pose=map_pose)
+                       smooth=args.smooth, path=args.path, map_pose=map_pose, sample=args.sample)
     if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None or args.path is not None \
             or map_pose is not None:
         preds, *extra = preds
@@ -849,6 +877,7 @@ def main(argv=None):
         frame_smooth = extra.pop(0) if args.smooth is not None else None
         frame_path = extra.pop(0) if args.path is not None else None
         frame_map = extra.pop(0) if map_pose is not None else None
+        frame_samples = extra.pop(0) if args.sample is not None else None
         if fitted is not None:                                # the info pickles record the fitted values the operators ran on
             for frames in (frame_filter, frame_smooth, frame_path):
                 for fr in frames or ():
@@ -936,6 +965,16 @@ def main(argv=None):
               "joints {:.4f} m, {} of {} joint-frames smoothed".format(
                   result["smoothed_mpjpe"], mpjpe, result["filtered_mpjpe"], float(np.mean([fr["shift_filtered"] for fr in frame_smooth])),
                   int(sum(fr["smoothed"].sum() for fr in frame_smooth)), int(sum(fr["smoothed"].size for fr in frame_smooth))))
+    if args.sample is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(args.sample_output)), exist_ok=True)
+        with open(args.sample_output, "wb") as f:
+            pickle.dump(frame_samples, f)
+        result["samples"] = frame_samples
+        result.update(M.best_of_samples(frame_samples, np.stack(smoothed).astype(np.float64), gt))
+        print("trajectory samples (the model's posterior given the volumes read as likelihoods, not calibrated): {} per joint, seed {}: "
+              "mean spread {:.4f} m, best-of-{} mpjpe: {} (smoothed {}), {} of {} draws valid".format(
+                  args.sample["samples"], args.sample["seed"], result["mean_sample_spread"], args.sample["samples"],
+                  result["best_of_n_mpjpe"], result["smoothed_mpjpe"], result["valid_draws"], result["draws"]))
     if skeleton is not None:
         coupled = [np.asarray(fr["joints"], dtype=np.float32) for fr in frame_skeleton]
         for path, obj in ((args.skeleton_output, coupled), (args.skeleton_info_output, frame_skeleton)):

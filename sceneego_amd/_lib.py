@@ -30,6 +30,7 @@ RES_QUAD = 4096     # ... quad-planar skip tensor
 IN_PLANAR3 = 16     # se_conv3d_f32, k = 7: triplet-planar input [B][ceil(cin/3)][D][D][D][3]
 
 _vp, _i, _f, _d, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong
+_u = ctypes.c_uint
 
 # name -> (restype, argtypes); must list every symbol of include/sceneego_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
@@ -124,6 +125,8 @@ SIGNATURES = {
     "se_volume_smooth_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "se_volume_transition_stats_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_volume_transition_stats_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "se_volume_sample_scratch_bytes": (_ll, [_i, _i, _i]),
+    "se_volume_sample_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _i, _ll, _ll, _u, _u, _vp, _vp]),
     "se_volume_viterbi_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_volume_viterbi_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "se_volume_viterbi_path_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -1363,6 +1366,47 @@ def volume_transition_stats(prob, belief, restarted, taps, state, stats, linked,
                                                  _ptr(linked), _ptr(scratch), scratch.numel(), frames, rows, voxels, grid, radius,
                                                  floor, _ptr(have_link), _stream()), "se_volume_transition_stats_f32")
     return stats, linked
+
+
+# Trajectory samples on the filter's model (csrc/volume_sample.hip: se_volume_sample_f32; VolumeSmoother.sample drives it)
+SAMPLE_STEP, SAMPLE_JUMP, SAMPLE_FRESH = 0, 1, 2      # `kind`: the branch a frame's draw took
+
+
+def volume_sample_scratch_bytes(frames, rows, grid) -> int:
+    return int(load().se_volume_sample_scratch_bytes(int(frames), int(rows), int(grid)))
+
+
+def volume_sample(belief, restarted, taps, next_voxel, index, kind, frames, rows, voxels, grid, radius, floor, samples, first_sample=0,
+                  first_frame=0, seed=0, have_link=None, scratch=None):
+    """se_volume_sample_f32: ``samples`` trajectories per row through ``frames`` consecutive frames, drawn last to first from the
+    filtered beliefs ``belief`` [frames, rows, voxels] with the filter's ``restarted`` [frames, rows] int32 (the header states the
+    definition).  ``next_voxel`` [samples, rows] int32 carries the voxel of the frame behind the call from call to call and is updated
+    in place; ``have_link`` None (the call ends the track) or int32 [rows].  ``index`` and ``kind`` [samples, frames, rows] int32 are
+    written.  ``first_sample`` and ``first_frame``: the global index of the call's first sample and frame (the random numbers depend
+    on the global indices alone); ``seed``: 0..2^64-1.  ``taps``: the filter's, on the device.  ``scratch``: an optional uint8
+    workspace of at least ``volume_sample_scratch_bytes(frames, rows, grid)`` bytes.  Every argument is checked here and a bad one
+    raises HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
+    what = "volume_sample"
+    frames, rows, voxels, grid, radius, floor = _grid_args(what, frames, rows, voxels, grid, radius, floor)
+    samples, first_sample, first_frame, seed = int(samples), int(first_sample), int(first_frame), int(seed)
+    if samples < 1 or first_sample < 0 or first_frame < 0 or first_sample + samples > 2 ** 32 or first_frame + frames > 2 ** 32:
+        raise HipExtensionError(f"{what}: samples = {samples} (>= 1), first_sample = {first_sample} and first_frame = {first_frame} "
+                                "(>= 0, the last index below 2^32) expected")
+    if not 0 <= seed < 2 ** 64:
+        raise HipExtensionError(f"{what}: seed = {seed} (0..2^64-1) expected")
+    dev = _check_args(what, (("belief", belief, torch.float32, frames * rows * voxels),
+                             ("restarted", restarted, torch.int32, frames * rows), ("taps", taps, torch.float32, 2 * radius + 1),
+                             ("next_voxel", next_voxel, torch.int32, samples * rows),
+                             ("index", index, torch.int32, samples * frames * rows), ("kind", kind, torch.int32, samples * frames * rows)),
+                      (("have_link", have_link, torch.int32, rows), ("scratch", scratch, torch.uint8, None)))
+    if _overlap(index, kind) or _overlap(next_voxel, index) or _overlap(next_voxel, kind):
+        raise HipExtensionError(f"{what}: next_voxel, index and kind must not alias")
+    scratch = _grid_scratch(what, scratch, volume_sample_scratch_bytes(frames, rows, grid), rows, grid, radius, dev)
+    _check(load().se_volume_sample_f32(_ptr(belief), _ptr(restarted), _ptr(taps), _ptr(next_voxel), _ptr(index), _ptr(kind),
+                                       _ptr(scratch), scratch.numel(), frames, rows, voxels, grid, radius, floor, samples,
+                                       first_sample, first_frame, seed & 0xFFFFFFFF, seed >> 32, _ptr(have_link), _stream()),
+           "se_volume_sample_f32")
+    return index, kind
 
 
 # The max-product pass on the filter's model (csrc/volume_viterbi.hip; sceneego_amd/volume_viterbi.py drives it)

@@ -143,6 +143,29 @@ def error_by_confidence(estimated, gt, sigma, bins: int = 4):
     return out
 
 
+def best_of_samples(frames, estimated, gt):
+    """The multi-hypothesis figure of trajectory samples.  ``frames``: the per-frame dicts of ``op.volume_samples_to_numpy`` (``coord``
+    [S,J,3], ``valid`` [S,J], ``spread`` [J]); ``estimated`` / ``gt`` [T,J,3].  Per joint and frame the smallest distance to the
+    ground truth over the joint's VALID samples (every joint has trajectories of its own; the estimate itself where none is valid),
+    averaged: ``best_of_n_mpjpe``.  ``mean_sample_spread``: the mean of the finite spreads.  ``spearman_error_spread``: the rank
+    correlation of the estimate's error and the spread (``error_by_confidence``).  No alignment.  numpy, float64."""
+    est = np.asarray(estimated, dtype=np.float64)
+    ref = np.asarray(gt, dtype=np.float64)
+    coord = np.stack([np.asarray(fr["coord"], dtype=np.float64) for fr in frames])               # [T,S,J,3]
+    valid = np.stack([np.asarray(fr["valid"]).astype(bool) for fr in frames])                    # [T,S,J]
+    spread = np.stack([np.asarray(fr["spread"], dtype=np.float64) for fr in frames])             # [T,J]
+    if est.shape != ref.shape or coord.shape[0] != est.shape[0] or coord.shape[2:] != est.shape[1:] or spread.shape != est.shape[:2]:
+        raise ValueError(f"shape mismatch: estimated {est.shape}, gt {ref.shape}, samples {coord.shape}, spread {spread.shape}")
+    with np.errstate(invalid="ignore"):
+        d = np.linalg.norm(coord - ref[:, None], axis=-1)
+    d = np.where(valid, d, np.inf).min(axis=1)                                                   # [T,J]
+    best = np.where(valid.any(axis=1), d, np.linalg.norm(est - ref, axis=-1))
+    finite = np.isfinite(spread)
+    return {"best_of_n_mpjpe": float(best.mean()), "mean_sample_spread": float(spread[finite].mean()) if finite.any() else float("nan"),
+            "spearman_error_spread": error_by_confidence(est, ref, spread, bins=1)["spearman"],
+            "samples_per_joint": int(coord.shape[1]), "valid_draws": int(valid.sum()), "draws": int(valid.size)}
+
+
 def scene_summary(frames):
     """Physical plausibility of a sequence: ``frames`` is the list of per-frame dicts of ``op.scene_check_to_numpy`` (the keys
     ``penetrating``, ``penetration_depth`` and ``contact`` [15] are used).  Returns a dict:

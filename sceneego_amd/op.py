@@ -427,6 +427,21 @@ def volume_smoother_to_numpy(result):
     return _per_frame(result, SMOOTHER_KEYS + (("shift",) if "shift" in result else ()), "agreement")
 
 
+SAMPLE_KEYS = ("index", "coord", "kind", "valid")              # [S,T,...]: the frame is the second dimension
+SAMPLE_FRAME_KEYS = ("mean", "spread")                          # [T,...]
+
+
+def volume_samples_to_numpy(result):
+    """The dict of ``VolumeSmoother.sample`` as a list of per-frame dicts of numpy arrays: ``index`` [S,J], ``coord`` [S,J,3], ``kind``
+    [S,J], ``valid`` [S,J], ``mean`` [J,3], ``spread`` [J] and ``shift`` [J] when joints were pushed: what run_sequence.py
+    --sample_output writes."""
+    host = {k: result[k].cpu().numpy() for k in SAMPLE_KEYS}
+    frame_keys = SAMPLE_FRAME_KEYS + (("shift",) if "shift" in result else ())
+    host.update({k: result[k].cpu().numpy() for k in frame_keys})
+    return [{**{k: host[k][:, t].copy() for k in SAMPLE_KEYS}, **{k: host[k][t].copy() for k in frame_keys}}
+            for t in range(host["mean"].shape[0])]
+
+
 PATH_KEYS = ("joints", "index", "coord", "jumped", "segment_start", "log_score", "moved")
 
 

@@ -21,6 +21,7 @@ explanation under any ``floor > 0``, because one jump is then cheaper than the w
 """
 from __future__ import annotations
 
+import numbers
 from typing import NamedTuple, Optional
 
 import torch
@@ -90,6 +91,67 @@ class VolumeSmoother(StoredTrack):
                          "state": torch.empty((J, f.voxels), device=dev, dtype=torch.float32),
                          "scratch": torch.empty(_lib.volume_smooth_scratch_bytes(J, f.grid, f.radius), device=dev, dtype=torch.uint8)}
         return self._dev
+
+    @torch.no_grad()
+    def sample(self, samples=16, seed=0, stream=None):
+        """``samples`` whole trajectories per joint through the T stored frames, drawn jointly from the posterior of the hidden Markov
+        model that ``finish()`` gives the marginals of: forward-filter backward-sampling on the stored filtered beliefs
+        (``csrc/volume_sample.hip``, ``se_volume_sample_f32``; the header states the definition).  Call it BEFORE ``finish()``: it
+        consumes and modifies nothing, and a later ``finish()`` returns the bits it would have returned.  With nothing stored (after
+        ``finish()`` or ``reset()``) it raises ValueError.  ``seed`` in 0..2^64-1: the same seed gives the same trajectories, however the
+        frames were cut into pushes; sample s of ``samples=n`` is sample s of any larger n.  It runs on ``stream`` (default: the current
+        one), which waits for every push.  Returns a dict of device tensors over all T frames: ``index`` [S,T,J] int32 (the flat voxel,
+        -1 where the frame's belief has no finite positive mass), ``coord`` [S,T,J,3] (the voxel centres, NaN where invalid), ``kind``
+        [S,T,J] int32 (0 a step from the next frame's voxel, 1 a jump, 2 a fresh draw: the last frame, a frame before a restart or
+        before an invalid one), ``valid`` [S,T,J] bool, ``mean`` [T,J,3] and ``spread`` [T,J]: the mean of the valid samples and the
+        root of the trace of their sample covariance in metres (NaN with fewer than two), and ``shift`` [T,J] when joints were pushed
+        (metres from ``mean`` to those).  A sample is a voxel centre: nothing is refined below the voxel edge."""
+        if isinstance(samples, bool) or not isinstance(samples, numbers.Integral) or samples < 1:
+            raise ValueError(f"sample: samples = {samples!r} (an integer >= 1) expected")
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 2 ** 64:
+            raise ValueError(f"sample: seed = {seed!r} (an integer in 0..2^64-1) expected")
+        if not self._pushes:
+            raise ValueError("sample: nothing is stored; push() the frames of the track first and draw before finish()")
+        pushes, dev, J, stream = self._begin_finish(stream)
+        f = self.filter
+        fd = f._dev
+        S = int(samples)
+        with torch.cuda.stream(stream):
+            T = self.frames_stored
+            index = torch.empty((S, T, J), device=dev, dtype=torch.int32)
+            kind = torch.empty((S, T, J), device=dev, dtype=torch.int32)
+            carried = torch.full((S, J), -1, device=dev, dtype=torch.int32)
+            t1 = T
+            for i in range(len(pushes) - 1, -1, -1):
+                bel, restarted = pushes[i].beliefs, pushes[i].restarted
+                for t in (bel, restarted):
+                    t.record_stream(stream)
+                B = int(bel.shape[0])
+                t0 = t1 - B
+                link = None if i == len(pushes) - 1 else (pushes[i + 1].restarted[0] == 0).to(torch.int32)
+                idx = torch.empty((S, B, J), device=dev, dtype=torch.int32)
+                knd = torch.empty((S, B, J), device=dev, dtype=torch.int32)
+                _lib.volume_sample(bel, restarted, fd["taps"], carried, idx, knd, B, J, f.voxels, f.grid, f.radius, f.floor, S,
+                                   first_sample=0, first_frame=t0, seed=int(seed), have_link=link)
+                index[:, t0:t1], kind[:, t0:t1] = idx, knd
+                t1 = t0
+            # a finish() on another stream writes over the beliefs read here: it waits for this event as for a finish() before it
+            self._done = torch.cuda.Event()
+            self._done.record(stream)
+            valid = index >= 0
+            coord = fd["coord"][index.clamp(min=0).long()]
+            coord = torch.where(valid.unsqueeze(-1), coord, torch.full_like(coord, float("nan")))
+            n = valid.sum(dim=0).to(torch.float32)                                          # [T,J]
+            kept = torch.where(valid.unsqueeze(-1), coord, torch.zeros_like(coord))
+            mean = kept.sum(dim=0) / n.unsqueeze(-1)                                        # 0 / 0 = NaN without a valid sample
+            dev2 = torch.where(valid.unsqueeze(-1), (kept - mean) ** 2, torch.zeros_like(kept)).sum(dim=(0, 3))
+            spread = torch.where(n >= 2, (dev2 / (n - 1).clamp(min=1)).sqrt(), torch.full_like(n, float("nan")))
+            result = {"index": index, "coord": coord, "kind": kind, "valid": valid, "mean": mean, "spread": spread}
+            with_joints = {"joints": mean}
+            self._add_shift(with_joints, pushes)
+            if "shift" in with_joints:
+                result["shift"] = with_joints["shift"]
+        return result
 
     @torch.no_grad()
     def finish(self, return_beliefs=False, stream=None):
