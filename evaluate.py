@@ -121,6 +121,20 @@ def load_alternatives(path, count):
     return frames
 
 
+def pose_sample_summary(frames, unit):
+    """What the pose samples say without a ground truth: the mean of the finite spreads and the mean bone error of the samples."""
+    spread = np.concatenate([np.asarray(fr["spread"], dtype=np.float64).reshape(-1) for fr in frames])
+    bone = np.concatenate([np.asarray(fr["bone_error"], dtype=np.float64).reshape(-1) for fr in frames])
+    out = {"mean_sample_spread": float(spread[np.isfinite(spread)].mean()) if np.isfinite(spread).any() else float("nan"),
+           "mean_bone_error": float(bone[np.isfinite(bone)].mean()) if np.isfinite(bone).any() else float("nan"),
+           "samples_per_frame": int(np.asarray(frames[0]["valid"]).shape[0]),
+           "frames_not_sampled": int(sum(not bool(fr["sampled"]) for fr in frames))}
+    print(f"pose samples (the skeleton model's posterior, not calibrated; the spread is no error bar): {out['samples_per_frame']} per "
+          f"frame, mean spread {out['mean_sample_spread']:.4f} {unit}, mean bone error {out['mean_bone_error']:.4f} {unit}, "
+          f"{out['frames_not_sampled']} frames not sampled")
+    return out
+
+
 def best_of_two(frames, pred, gt):
     """Does the runner-up margin say where the most probable pose is wrong?  Per frame the smaller of the mean joint error of the pose
     and of its runner-up pose (``runner_up_joints``; the pose alone where there is none), averaged over the frames; the share of the
@@ -214,6 +228,9 @@ def build_parser():
     ap.add_argument("--samples", default=None, help="with --pred_dir smoothed.pkl: the pickle of run_sequence.py --sample_output for the "
                     "same frames; adds the best-of-N MPJPE per joint (the closest valid sample of every joint) and the rank correlation "
                     "of the smoothed joint's error and the samples' spread")
+    ap.add_argument("--pose_samples", default=None, help="the pickle of run_sequence.py --pose_samples_output for the same frames; adds "
+                    "the best-of-N MPJPE per joint and per whole pose (the closest sample whose joints are all valid), the samples' "
+                    "mean spread and mean bone error; without --gt only the spread and the bone error are summarised")
     ap.add_argument("--bones", nargs="?", const="", default=None, metavar="FILE.npy",
                     help="bone-length summary of the predictions (needs no ground truth): the per-bone standard deviation over the "
                     "sequence and, with FILE.npy (14 or 15 lengths, as run_sequence.py --bone_lengths takes them), the mean absolute "
@@ -233,8 +250,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     names, pred = load_predictions(args.pred_dir)
     if args.gt is None:
-        if args.bones is None and args.alternatives is None and args.path_alternatives is None:
-            raise SystemExit("--gt is required (only --bones, --alternatives and --path_alternatives work without it)")
+        if args.bones is None and args.alternatives is None and args.path_alternatives is None and args.pose_samples is None:
+            raise SystemExit("--gt is required (only --bones, --alternatives, --path_alternatives and --pose_samples work without it)")
         r = {"frames": int(pred.shape[0])}
         if args.path_alternatives is not None:
             margins = np.stack([np.asarray(fr["margin"], dtype=np.float64)
@@ -251,6 +268,8 @@ def main(argv=None):
                                  "below_ln2_share": float((margins < np.log(2.0)).mean()), "frames_with_margin": int(ok.sum())}
             print("runner-up margin: mean {mean_runner_up_margin:.4f} over {frames_with_margin} frames, {below_ln2_share:.1%} below "
                   "ln 2".format(**r["alternatives"]))
+        if args.pose_samples is not None:
+            r["pose_samples"] = pose_sample_summary(load_alternatives(args.pose_samples, len(names)), args.unit)
         if args.bones is not None:
             r["bones"] = bones(pred, args.bones, args.unit)
         return r
@@ -289,6 +308,15 @@ def main(argv=None):
         a = r["samples"] = M.best_of_samples(load_alternatives(args.samples, len(names)), pred, gt)
         print(f"best-of-{a['samples_per_joint']} MPJPE {a['best_of_n_mpjpe']:.6f} {args.unit} (the closest valid sample of every joint; "
               f"{a['valid_draws']} of {a['draws']} draws valid); mean spread {a['mean_sample_spread']:.4f} {args.unit}; "
+              f"spearman(error, spread): {a['spearman_error_spread']:.4f}")
+    if args.pose_samples is not None:
+        from sceneego_amd import metrics as M
+        frames = load_alternatives(args.pose_samples, len(names))
+        a = r["pose_samples"] = {**pose_sample_summary(frames, args.unit), **M.best_of_samples(frames, pred, gt),
+                                 **M.best_pose_of_samples(frames, pred, gt)}
+        print(f"best-of-{a['samples_per_frame']} MPJPE per joint {a['best_of_n_mpjpe']:.6f} {args.unit} (the closest valid sample of "
+              f"every joint), per whole pose {a['best_pose_of_n_mpjpe']:.6f} {args.unit} (the closest sample whose joints are all "
+              f"valid; {a['whole_poses']} of {a['poses']} poses whole, {a['frames_without_pose']} frames without one); "
               f"spearman(error, spread): {a['spearman_error_spread']:.4f}")
     if args.bones is not None:
         r["bones"] = bones(pred, args.bones, args.unit)

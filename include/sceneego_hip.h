@@ -1063,6 +1063,65 @@ int se_skeleton_edge_stats_f32(const float* prob, const float* taps, const float
                                int voxels, int G, int R, float floor, void* stream);
 long long se_skeleton_edge_stats_scratch_bytes(int frames, int J, int G, int R);
 
+/* Pose samples: ancestral draws of whole poses from the posterior of se_skeleton_couple_f32's model (sceneego_amd/skeleton_prior.py:
+ * SkeletonPrior.sample).  That posterior is prod_j p_j(x_j) prod_c F_c(x_parent(c), x_c), normalised, with the edge factor
+ * F_c(x, y) = (1 - floor) w_c(y - x) + floor / N for y inside the grid: CORRELATE's own orientation, the child is y = x_parent + d with
+ * weight taps[c][d], NO tap reversal.  With the upward products A_j = p_j prod_{c in ch(j)} U_c ancestral sampling is exact:
+ *     x_0 ~ A_0;   x_c ~ A_c(y) F_c(x_parent(c), y)  for c = 1..J-1 ascending (parent[c] < c),
+ * and the marginals of the samples are the coupling's beliefs.  It adds no convention to the coupling's.  Everything not stated here
+ * is se_skeleton_couple_f32's: the TREE, the TAPS layout, CORRELATE, the floor and the product order.  Two entry points.
+ *
+ * se_skeleton_upward_f32: the UPWARD pass of se_skeleton_couple_f32 on the same product, fold, run-table and correlation kernels, and
+ * one level more, the root's product A_0 = p_0 prod_c U_c with its sum (the coupling forms it in its downward pass, as T_0).
+ *   upward     [frames][J][voxels] float32: A_j.  It must not be prob.
+ *   sums       [frames][J] float32: s_j = sum A_j, also for j = 0.  For j >= 1 they equal se_skeleton_edge_stats_f32's norms[..][0] and
+ *              s_0 equals se_skeleton_couple_f32's evidence[..][0], bit for bit.
+ *   valid      [frames] int32: 1 iff every s_j, j = 0..J-1, is a finite number > 0.  WEAKER than the coupling's FALLBACK rule, which also
+ *              looks at t_c and Z_j: coupled = 1 implies valid = 1, not the other way round.
+ *   scratch    se_skeleton_upward_scratch_bytes(frames, J, G, R) bytes, 4-byte aligned; 0 for a shape out of range.  About J G^3 floats
+ *              (the messages U) for each of min(frames, 4) frames: longer calls walk their frames in groups of four, and the result
+ *              does not depend on the grouping.
+ * SE_ERR_BAD_ARG, with nothing launched: as se_skeleton_couple_f32, for this call's own pointers (none may be null) and scratch size.
+ *
+ * se_skeleton_sample_f32: `samples` poses per frame from the A_j.  tests/skeleton_sampler_model.py restates what follows in numpy
+ * float64 and index and kind are compared with it BIT FOR BIT: all arithmetic is float64, one rounding per operation (no fused
+ * multiply-add), every sum SEQUENTIAL in ascending index.  keep = (double)(1.0f - floor), uniform = (double)(floor / (float)voxels)
+ * (float32, as the coupling forms them).  CATEGORICAL DRAW and the 53-bit uniforms: as for se_volume_sample_f32.
+ * SUMS       Rs[i][j] = sum_k A, P[i] = sum_j Rs[i][j] of every (frame, joint): se_volume_sample_f32's sums pass with rows = J.
+ * GLOBAL DRAW from A_j with (u1, u2, u3): i from P, j from Rs[i][.], k from A[i][j][.]; total_j is the last running sum of P.  INVALID
+ *            (index -1) when total_j is not a finite number > 0.
+ * WINDOW DRAW of child c given the parent's voxel x, over the taps d that stay inside the grid (clipped ranges per axis, ascending):
+ *            v(d) = (double)A_c(x + d) (double)taps[c][d], an exact product; v(d) = 0 where the tap is exactly 0 WHATEVER A_c holds there
+ *            (a NaN under a zero tap is passed over in these sums, as CORRELATE skips zero taps; it never shows in index or kind,
+            because total_c below is formed from the whole volume and holds that NaN: such a joint has no usable mass either way);
+            r[di][dj] = sum_dk v,  q[di] = sum_dj r[di][dj],
+ *            Wsum = sum_di q[di];  step = keep Wsum, jump = uniform total_c, mass = step + jump.  A mass that is not a finite number
+ *            > 0: the joint is drawn as an unlinked one.  Otherwise it is a jump iff u0 mass >= step: a global draw from A_c; else a
+ *            step: di from q, dj from r[di][.], dk from v(di, dj, .), with (u1, u2, u3).
+ * CHAIN      per sample and frame, j = 0..J-1 ascending: the root and every joint whose parent's draw is invalid take a global draw
+ *            (kind 2); a linked joint the window draw (kind 0 a step, 1 a jump; an unusable mass gives kind 2).
+ * UNIFORMS   Philox4x32-10, key (seed_lo, seed_hi), counter (first_sample + sample, first_frame + frame, joint, block); block 0 gives
+ *            u0, u1 and block 1 u2, u3.  The indices are GLOBAL: the result depends neither on how the frames are cut into calls nor
+ *            on how the samples are split.  Sample s of 16 is sample s of 64.
+ *   upward     [frames][J][voxels] float32, non-negative: se_skeleton_upward_f32's.  Read only.
+ *   valid      NULL (every frame is valid) or [frames] int32: a frame with valid[f] == 0 writes index -1 and kind 2 for every joint and
+ *              sample, and the walk reads nothing of its `upward`.
+ *   index      [samples][frames][J] int32: the flat voxel, -1 when invalid       kind  [samples][frames][J] int32: 0, 1 or 2
+ *   samples >= 1;  first_sample + samples and first_frame + frames at most 2^32, neither offset negative
+ *   scratch    se_skeleton_sample_scratch_bytes(frames, J, G) bytes, 8-byte aligned: frames J (G^2 + G) doubles; 0 out of range.
+ * Two launches on `stream`: the sums, then the walk, one workgroup of 256 per (sample, frame) that loops over the joints inside the
+ * launch; thread 0 of that workgroup writes index and kind.  No atomics; bitwise identical from run to run.  Allocates nothing.
+ * SE_ERR_BAD_ARG, with nothing launched: a null pointer other than valid, a pointer that is not 4-byte aligned (scratch: 8-byte), J
+ * outside 1..32, parent[0] != 0 or a parent[j] outside 0..j-1, G outside 2..128, voxels != G^3, R outside 0..min(24, G - 1), floor outside
+ * [0, 1] or NaN, frames < 1, samples < 1, an offset out of range, scratch_bytes below se_skeleton_sample_scratch_bytes(frames, J, G). */
+int se_skeleton_upward_f32(const float* prob, const float* taps, const int* parent, float* upward, float* sums, int* valid, void* scratch,
+                           long long scratch_bytes, int frames, int J, int voxels, int G, int R, float floor, void* stream);
+long long se_skeleton_upward_scratch_bytes(int frames, int J, int G, int R);
+int se_skeleton_sample_f32(const float* upward, const int* valid, const float* taps, const int* parent, int* index, int* kind,
+                           void* scratch, long long scratch_bytes, int frames, int J, int voxels, int G, int R, float floor, int samples,
+                           long long first_sample, long long first_frame, unsigned int seed_lo, unsigned int seed_hi, void* stream);
+long long se_skeleton_sample_scratch_bytes(int frames, int J, int G);
+
 /* Most probable pose: the max-product pass over the kinematic tree that goes with se_skeleton_couple_f32, as se_volume_viterbi_f32
  * goes with the filter (sceneego_amd/skeleton_pose.py: SkeletonPose; VoxelNetwork_depth.skeleton_pose returns one).  The coupling gives
  * per joint a marginal and its expectation; this gives the single most probable configuration of all J joints of a frame under the same

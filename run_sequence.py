@@ -62,6 +62,12 @@ Smoothed beliefs are not rendered: frames are rendered per batch, before the fut
 of that smoother's model (``VolumeSmoother.sample``, seed ``--sample_seed``): index, coord, kind, valid [S,15,...], mean, spread and shift.
 It implies the smoother, draws before the smoother finishes, and prints the mean spread and the best-of-N MPJPE (the closest valid sample
 of every joint) beside the smoothed MPJPE.  The samples are from the model's posterior given the volumes read as likelihoods: not calibrated.
+``--pose_samples_output`` writes a pickle of per-frame dicts of ``--pose_samples`` (default 16) whole poses drawn from the posterior of
+the skeleton model (``SkeletonPrior.sample``, seed ``--pose_sample_seed``, the frame's number in the sequence as its global index):
+index, coord, kind, valid [S,15,...], bone_error [S,14], mean, spread, sampled and shift.  It uses ``--bone_lengths`` /
+``--bone_frames``, ``--skeleton_tau`` and ``--skeleton_floor`` exactly as ``--skeleton_output`` does, and the fitted values with
+``--skeleton_fit_frames``.
+
 ``--skeleton_output`` writes a pickle in the format of ``--output`` whose joints are coupled over the kinematic tree inside every frame
 (``VoxelNetwork_depth.skeleton_prior``, ``sceneego_amd/skeleton_prior.py``: belief propagation over the fifteen volumes with a
 bone-length shell of ``--skeleton_tau`` metres on every edge and a uniform floor ``--skeleton_floor``), per batch on the stream the
@@ -324,7 +330,7 @@ class SequenceRunner:
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
             volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False,
-            smooth=None, path=None, map_pose=None, sample=None):
+            smooth=None, path=None, map_pose=None, sample=None, pose_sample=None):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -349,11 +355,13 @@ class SequenceRunner:
         ``solve`` and the dicts carry its entries too): the most probable pose of every frame is taken from the batch's raw volumes on the stream
         the batch ran on and the per-frame pose dicts are appended after those.  ``sample`` (with ``smooth``): a dict of ``samples`` /
         ``seed`` for ``VolumeSmoother.sample``, drawn once behind the last batch and before ``finish()``; the per-frame sample dicts
-        are appended last."""
+        are appended after those.  ``pose_sample``: a dict of ``bone_lengths`` / ``tau`` / ``floor`` / ``samples`` / ``seed``: whole poses
+        drawn from the skeleton posterior of every batch's raw volumes (``SkeletonPrior.sample`` with the running frame count as
+        ``first_frame``) on the stream the batch ran on; the per-frame pose-sample dicts are appended last."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
                                      skeleton_alternatives_to_numpy, skeleton_couple_to_numpy, skeleton_pose_to_numpy,
-                                     volume_filter_to_numpy, volume_path_to_numpy,
+                                     skeleton_samples_to_numpy, volume_filter_to_numpy, volume_path_to_numpy,
                                      volume_smoother_to_numpy)
         from sceneego_amd.preprocess import load_image_bgr
         load = JpegFile if self.image_decode == "device" else load_image_bgr
@@ -371,6 +379,8 @@ class SequenceRunner:
         if render_coupled and (skeleton is None or not render_volumes or render_filtered):
             raise ValueError("render_coupled needs skeleton and render_volumes, and excludes render_filtered")
         sp = self.net.skeleton_prior(**skeleton) if skeleton is not None else None
+        frame_pose_samples = []
+        psp = self.net.skeleton_prior(**{k: pose_sample[k] for k in ("bone_lengths", "tau", "floor")}) if pose_sample is not None else None
         path_separation = None
         if path is not None:                # "separation": the backward pass too (--path_alternatives_output)
             path = dict(path)
@@ -379,11 +389,15 @@ class SequenceRunner:
         separation = map_pose.get("separation") if map_pose is not None else None
         mpose = self.net.skeleton_pose(**{k: v for k, v in map_pose.items() if k != "separation"}) if map_pose is not None else None
 
-        def couple_and_filter(vol, kp, job, stream=None):
-            """The most probable pose (from the raw volumes), the skeleton coupling and the filter of one batch, in that order:
-            (filter dict, skeleton dict, job, pose dict)."""
+        def couple_and_filter(vol, kp, job, stream=None, first_frame=0):
+            """The most probable pose and the pose samples (from the raw volumes), the skeleton coupling and the filter of one batch,
+            in that order: (filter dict, skeleton dict, job, pose dict, pose-sample dict).  ``first_frame``: the batch's first frame
+            in the sequence."""
             fr = sk = None
-            mp = None
+            mp = ps = None
+            if psp is not None:
+                ps = psp.sample(vol, samples=pose_sample["samples"], seed=pose_sample["seed"], first_frame=first_frame, joints=kp,
+                                stream=stream)
             if mpose is not None:                                        # alternatives: the pose with the same bits, and the runner-up
                 mp = mpose.solve(vol, joints=kp, stream=stream) if separation is None else \
                     mpose.alternatives(vol, separation=separation, joints=kp, stream=stream)
@@ -404,7 +418,7 @@ class SequenceRunner:
                     job = job[:-1] + (fr["beliefs"],)
             if vp is not None:             # on the raw volumes, or the coupled beliefs: never on the filter's
                 vp.push(vol, joints=kp, stream=stream)
-            return fr, sk, job, mp
+            return fr, sk, job, mp, ps
 
         rendering = render_dir is not None or render_video is not None
         if rendering:
@@ -420,7 +434,7 @@ class SequenceRunner:
 
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done, job, sc, con, md, fr, sk, mp = pending.pop(0)
+                kp, st, done, job, sc, con, md, fr, sk, mp, ps = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 kp_host = kp.cpu().numpy()
@@ -441,6 +455,8 @@ class SequenceRunner:
                     frame_skeleton.extend(skeleton_couple_to_numpy(sk))
                 if mp is not None:
                     frame_map.extend(skeleton_pose_to_numpy(mp) if separation is None else skeleton_alternatives_to_numpy(mp))
+                if ps is not None:
+                    frame_pose_samples.extend(skeleton_samples_to_numpy(ps))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -465,16 +481,18 @@ class SequenceRunner:
                     if constrain:
                         c = self.net.constrain_to_scene(vol, kp, depth)
                         con = (c, self._scene().check(depth, c["joints"]) if scene else None)
-                    fr, sk, job, mp = couple_and_filter(vol, kp, job)     # before the next forward overwrites the volumes
+                    fr, sk, job, mp, ps = couple_and_filter(vol, kp, job, first_frame=i * batch_size)   # before the next forward
+                    # overwrites the volumes
                     pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
                                     self._scene().check(depth, kp) if scene else None, con,
-                                    self.net.joint_modes(vol, k=modes) if modes else None, fr, sk, mp))
+                                    self.net.joint_modes(vol, k=modes) if modes else None, fr, sk, mp, ps))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
-                    st = sc = con = md = fr = sk = mp = None
-                    if stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None:
+                    st = sc = con = md = fr = sk = mp = ps = None
+                    if stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None \
+                            or psp is not None:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
@@ -489,10 +507,10 @@ class SequenceRunner:
                                 md = net.joint_modes(vol, k=modes)
                             # one filter for all slots: its own event chain makes this stream wait for the step of the batch before;
                             # one skeleton prior too: it carries no state and keeps one workspace per stream
-                            fr, sk, job, mp = couple_and_filter(vol, kp, job, stream)
+                            fr, sk, job, mp, ps = couple_and_filter(vol, kp, job, stream, first_frame=i * batch_size)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done, job, sc, con, md, fr, sk, mp))
+                    pending.append((kp, st, done, job, sc, con, md, fr, sk, mp, ps))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             try:
                 drain(0)
@@ -510,14 +528,15 @@ class SequenceRunner:
             frame_path = volume_path_alternatives_to_numpy(vp.alternatives(separation=path_separation))
         else:
             frame_path = volume_path_to_numpy(vp.finish()) if vp is not None else None
-        if not (stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None):
+        if not (stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None
+                or psp is not None):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
             + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
             + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ()) \
             + ((frame_skeleton,) if sp is not None else ()) + ((frame_smooth,) if vs is not None else ()) \
             + ((frame_path,) if vp is not None else ()) + ((frame_map,) if mpose is not None else ()) \
-            + ((frame_samples,) if sample is not None else ())
+            + ((frame_samples,) if sample is not None else ()) + ((frame_pose_samples,) if psp is not None else ())
 
 
 def _size(text):
@@ -598,6 +617,12 @@ def build_parser():
                     "on --filter_sigma / --filter_radius / --filter_floor and draws before it finishes; a convention, not calibrated")
     ap.add_argument("--samples", type=int, default=None, help="with --sample_output: trajectories per joint (default 16)")
     ap.add_argument("--sample_seed", type=int, default=None, help="with --sample_output: the seed, 0..2^64-1 (default 0)")
+    ap.add_argument("--pose_samples_output", default=None, help="pickle of the per-frame dicts of whole poses drawn from the posterior of "
+                    "the skeleton model (SkeletonPrior.sample: index, coord, kind, valid [S,15,...], bone_error [S,14], mean, spread, "
+                    "sampled, shift); implies the skeleton model options --bone_lengths / --bone_frames, --skeleton_tau, "
+                    "--skeleton_floor, and the fitted values with --skeleton_fit_frames; samples of the model's posterior, not calibrated")
+    ap.add_argument("--pose_samples", type=int, default=None, help="with --pose_samples_output: poses per frame (default 16)")
+    ap.add_argument("--pose_sample_seed", type=int, default=None, help="with --pose_samples_output: the seed, 0..2^64-1 (default 0)")
     ap.add_argument("--path_output", default=None, help="pickle in the format of --output holding the joints of the most probable "
                     "trajectory of every joint through the sequence's volumes (sceneego_amd/volume_viterbi.py; --filter_sigma, "
                     "--filter_radius, --filter_floor: the filter's convention, not calibrated); with --skeleton_output it runs on the "
@@ -744,6 +769,17 @@ def parse_args(argv=None):
         raise SystemExit("--skeleton_floor must lie in [0, 1]")
     if args.bone_frames < 1:
         raise SystemExit("--bone_frames must be >= 1")
+    args.pose_sample = None
+    if args.pose_samples_output is not None:
+        samples = 16 if args.pose_samples is None else args.pose_samples
+        seed = 0 if args.pose_sample_seed is None else args.pose_sample_seed
+        if samples < 1:
+            raise SystemExit("--pose_samples must be >= 1")
+        if not 0 <= seed < 2 ** 64:
+            raise SystemExit("--pose_sample_seed must be in 0..2^64-1")
+        args.pose_sample = {"samples": samples, "seed": seed}
+    elif args.pose_samples is not None or args.pose_sample_seed is not None:
+        raise SystemExit("--pose_samples and --pose_sample_seed need --pose_samples_output")
     args.skeleton = args.skeleton_output is not None or args.skeleton_info_output is not None or args.render_coupled
     args.map = args.map_output is not None or args.map_info_output is not None or args.map_alternatives_output is not None
     if args.map_refine is not None and not args.map:
@@ -779,8 +815,8 @@ def main(argv=None):
     print(f"dataset length: {len(images)}")
     runner = SequenceRunner(config, weights=args.weights, streams=args.streams, depth_decode=args.depth_decode,
                             workers=args.workers, image_decode=args.image_decode)
-    skeleton = map_pose = skeleton_fitted = None
-    if args.skeleton or args.map or args.skeleton_fit is not None:
+    skeleton = map_pose = skeleton_fitted = pose_sample = None
+    if args.skeleton or args.map or args.skeleton_fit is not None or args.pose_sample is not None:
         from sceneego_amd.skeleton_prior import estimate_bone_lengths
         if args.bone_lengths is not None:
             lengths = np.load(args.bone_lengths)
@@ -823,6 +859,8 @@ def main(argv=None):
                 raise SystemExit(f"the shells reach {reach} voxels of {h:.5f} m; at most min({MAX_RADIUS}, grid - 1) = {most} are supported")
         if args.skeleton:
             skeleton = {"bone_lengths": lengths, "tau": tau, "floor": floor}
+        if args.pose_sample is not None:
+            pose_sample = {"bone_lengths": lengths, "tau": tau, "floor": floor, **args.pose_sample}
         if args.map:
             map_pose = {"bone_lengths": lengths, "tau": tau, "floor": floor, "refine": 1 if args.map_refine is None else args.map_refine}
             if args.map_alternatives_output is not None:
@@ -863,9 +901,10 @@ def main(argv=None):
                        render_quality=args.render_quality, render_size=args.render_size, render_volumes=args.render_volumes,
                        volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
                        filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled,
-                       smooth=args.smooth, path=args.path, map_pose=map_pose, sample=args.sample)
+                       smooth=args.smooth, path=args.path, map_pose=map_pose, sample=args.sample,
+                       pose_sample=pose_sample)
     if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None or args.path is not None \
-            or map_pose is not None:
+            or map_pose is not None or pose_sample is not None:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
         frame_scene = extra.pop(0) if want_scene else None
@@ -878,12 +917,13 @@ def main(argv=None):
         frame_path = extra.pop(0) if args.path is not None else None
         frame_map = extra.pop(0) if map_pose is not None else None
         frame_samples = extra.pop(0) if args.sample is not None else None
+        frame_pose_samples = extra.pop(0) if pose_sample is not None else None
         if fitted is not None:                                # the info pickles record the fitted values the operators ran on
             for frames in (frame_filter, frame_smooth, frame_path):
                 for fr in frames or ():
                     fr.update(fitted)
         if skeleton_fitted is not None:
-            for frames in (frame_skeleton, frame_map):
+            for frames in (frame_skeleton, frame_map, frame_pose_samples):
                 for fr in frames or ():
                     fr.update(skeleton_fitted)
     torch.cuda.synchronize()
@@ -1050,6 +1090,26 @@ def main(argv=None):
                   "below ln 2, {} frames not complete".format(map_pose["separation"], result["map_runner_up_margin"],
                                                               result["map_runner_up_close"], len(margins),
                                                               int(sum(not fr["complete"] for fr in frame_alternatives))))
+    if pose_sample is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(args.pose_samples_output)), exist_ok=True)
+        with open(args.pose_samples_output, "wb") as f:
+            pickle.dump(frame_pose_samples, f)
+        result["pose_samples"], result["bone_lengths"] = frame_pose_samples, np.asarray(lengths, dtype=np.float64)
+        # nested: --sample_output puts the trajectory sampler's figures under the same names at the top level
+        ps = result["pose_samples_summary"] = {**M.best_of_samples(frame_pose_samples, pred, gt),
+                                               **M.best_pose_of_samples(frame_pose_samples, pred, gt)}
+        from sceneego_amd.skeleton_prior import KINEMATIC_PARENTS
+        bone = np.asarray(lengths, dtype=np.float64).reshape(-1)[-(len(KINEMATIC_PARENTS) - 1):]
+        raw_bone = np.abs(np.linalg.norm(pred[:, 1:] - pred[:, list(KINEMATIC_PARENTS[1:])], axis=-1) - bone)
+        sample_bone = np.concatenate([np.asarray(fr["bone_error"], dtype=np.float64).reshape(-1) for fr in frame_pose_samples])
+        ps["mean_bone_error"] = float(np.nanmean(sample_bone)) if np.isfinite(sample_bone).any() else float("nan")
+        ps["estimate_bone_error"] = float(raw_bone.mean())
+        print("pose samples (the skeleton model's posterior given the volumes read as likelihoods, not calibrated; the spread is no error "
+              "bar): {} per frame, seed {}: mean spread {:.4f} m, mean bone error {:.4f} m (soft-argmax joints {:.4f} m), best-of-{} mpjpe "
+              "per joint: {}, per whole pose: {} (soft-argmax {}), {} of {} draws valid, {} frames without a whole pose".format(
+                  pose_sample["samples"], pose_sample["seed"], ps["mean_sample_spread"], ps["mean_bone_error"],
+                  ps["estimate_bone_error"], pose_sample["samples"], ps["best_of_n_mpjpe"], ps["best_pose_of_n_mpjpe"], mpjpe,
+                  ps["valid_draws"], ps["draws"], ps["frames_without_pose"]))
     return result
 
 

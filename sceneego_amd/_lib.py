@@ -143,6 +143,10 @@ SIGNATURES = {
     "se_shell_moments_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _vp]),
     "se_skeleton_edge_stats_scratch_bytes": (_ll, [_i, _i, _i, _i]),
     "se_skeleton_edge_stats_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
+    "se_skeleton_upward_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_skeleton_upward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
+    "se_skeleton_sample_scratch_bytes": (_ll, [_i, _i, _i]),
+    "se_skeleton_sample_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _i, _ll, _ll, _u, _u, _vp]),
     "se_shell_maxcorr_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _vp]),
     "se_shell_argmax_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "se_skeleton_pose_scratch_bytes": (_ll, [_i, _i, _i, _i]),
@@ -1750,6 +1754,79 @@ def skeleton_edge_stats(prob, taps, taps_r, taps_r2, parents, stats, norms, vali
                                              _ptr(stats), _ptr(norms), _ptr(valid), _ptr(scratch), scratch.numel(), frames, J, voxels,
                                              grid, radius, floor, _stream()), "se_skeleton_edge_stats_f32")
     return stats, norms, valid
+
+
+# Pose samples from the skeleton posterior (csrc/skeleton_sample.hip: se_skeleton_upward_f32, se_skeleton_sample_f32;
+# SkeletonPrior.sample drives them).  `kind` takes SAMPLE_STEP / SAMPLE_JUMP / SAMPLE_FRESH, as the trajectory sampler's.
+def skeleton_upward_scratch_bytes(frames, joints, grid, radius) -> int:
+    return int(load().se_skeleton_upward_scratch_bytes(int(frames), int(joints), int(grid), int(radius)))
+
+
+def skeleton_upward(prob, taps, parents, upward, sums, valid, frames, voxels, grid, radius, floor, scratch=None):
+    """se_skeleton_upward_f32: the upward pass of ``skeleton_couple`` over the tree ``parents`` on ``prob`` [frames, J, voxels] with the
+    shell taps ``taps`` [J, (2 radius + 1)^3] on the device, and the root's product (the header states it).  ``upward`` [frames, J,
+    voxels] float32 (the A_j), ``sums`` [frames, J] float32 (s_j, also for j = 0) and ``valid`` [frames] int32 are written.
+    ``scratch``: an optional uint8 workspace of at least ``skeleton_upward_scratch_bytes(frames, J, grid, radius)`` bytes.  Every
+    argument is checked here and a bad one raises HipExtensionError before anything is launched."""
+    what = "skeleton_upward"
+    parents, J, frames, voxels, grid, radius, floor = _tree_args(what, parents, frames, voxels, grid, radius, floor)
+    dev = _check_args(what, (("prob", prob, torch.float32, frames * J * voxels),
+                             ("taps", taps, torch.float32, J * (2 * radius + 1) ** 3),
+                             ("upward", upward, torch.float32, frames * J * voxels), ("sums", sums, torch.float32, frames * J),
+                             ("valid", valid, torch.int32, frames)), (("scratch", scratch, torch.uint8, None),))
+    if _overlap(upward, prob):
+        raise HipExtensionError(f"{what}: upward must not alias prob")
+    scratch = _scratch(what, scratch, skeleton_upward_scratch_bytes(frames, J, grid, radius), torch.uint8, dev)
+    par = (ctypes.c_int * J)(*parents)
+    _check(load().se_skeleton_upward_f32(_ptr(prob), _ptr(taps), ctypes.cast(par, ctypes.c_void_p), _ptr(upward), _ptr(sums),
+                                         _ptr(valid), _ptr(scratch), scratch.numel(), frames, J, voxels, grid, radius, floor,
+                                         _stream()), "se_skeleton_upward_f32")
+    return upward, sums, valid
+
+
+def skeleton_sample_scratch_bytes(frames, joints, grid) -> int:
+    return int(load().se_skeleton_sample_scratch_bytes(int(frames), int(joints), int(grid)))
+
+
+def _sample_args(what, samples, count, first_sample, first_frame, seed):
+    """The arguments of a sampler's call as ints: ``samples`` >= 1, the offsets of the first sample and of the first of ``count``
+    frames not negative with the last index below 2^32 (the counter words of the generator are 32 bits), ``seed`` in 0..2^64-1."""
+    samples, first_sample, first_frame, seed = int(samples), int(first_sample), int(first_frame), int(seed)
+    if samples < 1 or first_sample < 0 or first_frame < 0 or first_sample + samples > 2 ** 32 or first_frame + count > 2 ** 32:
+        raise HipExtensionError(f"{what}: samples = {samples} (>= 1), first_sample = {first_sample} and first_frame = {first_frame} "
+                                "(>= 0, the last index below 2^32) expected")
+    if not 0 <= seed < 2 ** 64:
+        raise HipExtensionError(f"{what}: seed = {seed} (0..2^64-1) expected")
+    return samples, first_sample, first_frame, seed
+
+
+def skeleton_sample(upward, valid, taps, parents, index, kind, frames, voxels, grid, radius, floor, samples, first_sample=0,
+                    first_frame=0, seed=0, scratch=None):
+    """se_skeleton_sample_f32: ``samples`` poses per frame, drawn joint by joint down the tree ``parents`` from ``upward`` [frames, J,
+    voxels] (``skeleton_upward``'s) with the shell taps ``taps`` on the device (the header states the definition).  ``valid`` None
+    (every frame is valid) or int32 [frames].  ``index`` and ``kind`` [samples, frames, J] int32 are written.  ``first_sample`` and
+    ``first_frame``: the global index of the call's first sample and frame (the random numbers depend on the global indices alone);
+    ``seed``: 0..2^64-1, split into the two key words.  ``scratch``: an optional uint8 workspace of at least
+    ``skeleton_sample_scratch_bytes(frames, J, grid)`` bytes, 8-byte aligned.  Every argument is checked here and a bad one raises
+    HipExtensionError before anything is launched: the kernels trust the sizes they are given."""
+    what = "skeleton_sample"
+    parents, J, frames, voxels, grid, radius, floor = _tree_args(what, parents, frames, voxels, grid, radius, floor)
+    samples, first_sample, first_frame, seed = _sample_args(what, samples, frames, first_sample, first_frame, seed)
+    dev = _check_args(what, (("upward", upward, torch.float32, frames * J * voxels),
+                             ("taps", taps, torch.float32, J * (2 * radius + 1) ** 3),
+                             ("index", index, torch.int32, samples * frames * J), ("kind", kind, torch.int32, samples * frames * J)),
+                      (("valid", valid, torch.int32, frames), ("scratch", scratch, torch.uint8, None)))
+    if _overlap(index, kind) or _overlap(index, upward) or _overlap(kind, upward):
+        raise HipExtensionError(f"{what}: index, kind and upward must not alias")
+    scratch = _scratch(what, scratch, skeleton_sample_scratch_bytes(frames, J, grid), torch.uint8, dev)
+    if scratch.data_ptr() % 8:
+        raise HipExtensionError(f"{what}: scratch must be 8-byte aligned")
+    par = (ctypes.c_int * J)(*parents)
+    _check(load().se_skeleton_sample_f32(_ptr(upward), _ptr(valid), _ptr(taps), ctypes.cast(par, ctypes.c_void_p), _ptr(index),
+                                         _ptr(kind), _ptr(scratch), scratch.numel(), frames, J, voxels, grid, radius, floor, samples,
+                                         first_sample, first_frame, seed & 0xFFFFFFFF, seed >> 32, _stream()),
+           "se_skeleton_sample_f32")
+    return index, kind
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

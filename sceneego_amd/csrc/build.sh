@@ -22,7 +22,7 @@ newer() {  # source $1, a header or (development builds) a devtools/ include new
   return 1
 }
 OBJS=()
-for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume_viterbi volume_sample skeleton_prior skeleton_pose conv2d_1x1 conv2d_3x3 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc render render_volume scene_probe scene_constraint; do
+for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume_viterbi volume_sample skeleton_prior skeleton_pose skeleton_sample conv2d_1x1 conv2d_3x3 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc render render_volume scene_probe scene_constraint; do
   [ -f $f.hip ] || { echo "build.sh: source $f.hip is missing" >&2; exit 1; }
   OBJS+=($OBJ/$f.o)
   extra=""
@@ -35,6 +35,7 @@ for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume
   [ "$f" = volume_viterbi ] && extra="-ffp-contract=off" # likewise: every score and back-pointer is compared with its float32 model bit for bit
   [ "$f" = volume_sample ] && extra="-ffp-contract=off"  # likewise: every drawn voxel is compared with its float64 model bit for bit
   [ "$f" = skeleton_pose ] && extra="-ffp-contract=off"  # likewise: every message and pose voxel is compared with its float32 model bit for bit
+  [ "$f" = skeleton_sample ] && extra="-ffp-contract=off" # likewise: every drawn pose voxel is compared with its float64 model bit for bit
   # no SLP packing of float32 arithmetic into v_pk_*_f32: packed VALU beside an MFMA stream is an anti-lever (see commit() there)
   [ "$f" = conv3d_wino2d ] && extra="-fno-slp-vectorize"
   [ "$f" = conv3d_wino44pp ] && extra="-fno-slp-vectorize -Wno-inline-asm"      # -Wno-inline-asm: the "m0" clobber of the LDS-DMA asm (reserved register)

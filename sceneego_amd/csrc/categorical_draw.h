@@ -1,6 +1,7 @@
 // Draw primitives of the samplers: the Philox4x32-10 counter-based generator, its uniforms and the categorical draw by a sequential
-// running sum.  volume_sample.hip (forward-filter backward-sampling over the joint volumes of a sequence) stands on them;
-// tests/volume_sampler_model.py restates each in numpy and every draw is compared with it bit for bit.  Nothing here touches memory
+// running sum.  volume_sample.hip (forward-filter backward-sampling over the joint volumes of a sequence) and skeleton_sample.hip
+// (ancestral sampling of whole poses down the kinematic tree) stand on them; categorical_sums.h holds the sums pass both launch.
+// tests/volume_sampler_model.py restates each in numpy and every draw of either sampler is compared with it bit for bit.  Nothing here touches memory
 // other than the array it is given, and every function is plain C++ that compiles for the host as well.
 //
 // Include it from a file built with -ffp-contract=off: a running sum is one rounded addition per entry, a threshold one rounded product.

@@ -48,6 +48,11 @@
 // THE EDGE STATISTICS (se_skeleton_edge_stats_f32; sceneego_amd/skeleton_fit.py: SkeletonModelFit) are the same walk (sk_walk) with E_c
 // kept beside A_c - a fourth J N buffer per frame in flight - and one sk_moments_kernel launch behind every downward level; they are
 // described with that kernel, below.  Both entry points launch the same product, fold and correlation kernels in the same order.
+//
+// THE UPWARD WALK (se_skeleton_upward_f32 in skeleton_sample.hip, through sk_upward_walk at the end of this file) is the third mode of
+// sk_walk: the upward levels above, then one product-and-fold level more for the root, A_0 = p_0 prod U_c and s_0 - the product the
+// coupling forms as T_0 in its downward pass, by the same kernel on the same operands, so s_0 equals its evidence[0] bit for bit -
+// and sk_upward_finish_kernel.  A_j goes straight into the caller's buffer; the scratch holds U, the chunk records and the sums.
 #include <float.h>
 #include <stdint.h>
 
@@ -457,6 +462,22 @@ __global__ __launch_bounds__(64) void sk_edge_finish_kernel(const float* __restr
     }
 }
 
+// grid (frames), block 64: the upward walk's outputs (se_skeleton_upward_f32).  out_sums [frames][J] = s_j, now also s_0 (the sum of
+// the root's product); valid [frames] = 1 iff every one of them is a finite number > 0, at the call's frame f0 + frame.
+__global__ __launch_bounds__(64) void sk_upward_finish_kernel(const float* __restrict__ sums, float* __restrict__ out_sums,
+                                                              int* __restrict__ valid, int J) {
+    const int t = threadIdx.x, f = blockIdx.x;
+    int bad = 0;
+    if (t < J) {
+        const float v = sums[(((size_t)f * J + t) * 3 + 0) * SK_PART];
+        out_sums[(size_t)f * J + t] = v;
+        bad = !(v > 0.f && v <= FLT_MAX);                                // a NaN fails both comparisons
+    }
+    const int any = __syncthreads_or(bad);
+    if (t == 0) valid[f] = any ? 0 : 1;
+}
+static_assert(SK_MAX_J <= 64, "sk_upward_finish_kernel gives every joint a lane");
+
 inline int sk_moment_records(int G) { return G * ((G + SK_TJ - 1) / SK_TJ) * ((G + SK_KC - 1) / SK_KC); }
 inline long long sk_packed_bytes(int tap_rows, int R) {                  // 16 more: the records are aligned inside the scratch
     const long long W = 2 * R + 1;
@@ -525,9 +546,11 @@ extern "C" int se_shell_moments_f32(const float* e, const float* a, const float*
 
 namespace {
 
-// What the two walks over the tree write.  se_skeleton_couple_f32: beliefs (or NULL), joints, evidence, coupled, with coord.
+// What the three walks over the tree write.  se_skeleton_couple_f32: beliefs (or NULL), joints, evidence, coupled, with coord.
 // se_skeleton_edge_stats_f32: stats, norms, valid, with the two further tap blocks; it keeps A_c beside E_c (a fourth J N buffer per
-// frame in flight), packs the three blocks and adds one moments launch per downward level.
+// frame in flight), packs the three blocks and adds one moments launch per downward level.  se_skeleton_upward_f32 (sk_upward_walk;
+// the entry point is in skeleton_sample.hip): upward, up_sums, valid; the upward levels alone and one more for the root's product
+// A_0, written straight into `upward`, so that only U, the chunk records and the sums live in the scratch.
 struct SkOutputs {
     const float* coord;
     float *beliefs, *joints, *evidence;
@@ -535,7 +558,14 @@ struct SkOutputs {
     const float *taps_r, *taps_r2;
     float *stats, *norms;
     int* valid;
+    float *upward, *up_sums;
 };
+
+// the floats per frame in flight of the upward walk: U, the chunk records, the folded sums
+inline long long sk_upward_frame_floats(int J, int G) {
+    const long long N = (long long)G * G * G;
+    return J * N + (long long)SK_MAX_ITEMS * sk_chunks((int)N) * SK_PART + 3LL * J * SK_PART;
+}
 
 inline long long sk_walk_scratch_bytes(int frames, int J, int G, int R, bool moments) {
     long long bytes = ((long long)min(frames, SK_GROUP) * sk_frame_floats(J, G) + sk_runs_ints(J, R)) * 4;
@@ -545,15 +575,16 @@ inline long long sk_walk_scratch_bytes(int frames, int J, int G, int R, bool mom
     return bytes;
 }
 
-// The arguments both entry points share are checked by the caller; `out` says which of the two walks this is (out.stats != NULL).
+// The arguments the entry points share are checked by the caller; `out` says which of the three walks this is (out.stats != NULL: the
+// edge statistics; out.upward != NULL: the upward walk).
 int sk_walk(const float* prob, const float* taps, const int* parent, const SkOutputs& out, void* scratch, int frames, int J, int voxels,
             int G, int R, float floor, const SkTree& tree, const int* depth, int deepest, hipStream_t st) {
-    const bool moments = out.stats != nullptr;
+    const bool moments = out.stats != nullptr, upward = out.upward != nullptr;
     const size_t N = (size_t)voxels;
     const int group = min(frames, SK_GROUP), CH = sk_chunks(voxels), records = sk_moment_records(G);
-    float* A = reinterpret_cast<float*>(scratch);
-    float* U = A + (size_t)group * J * N;
-    float* D = U + (size_t)group * J * N;
+    float* A = reinterpret_cast<float*>(scratch);                        // the upward walk: A is the caller's `upward`, no D
+    float* U = upward ? A : A + (size_t)group * J * N;
+    float* D = upward ? U : U + (size_t)group * J * N;
     float* part = D + (size_t)group * J * N;
     float* sums = part + (size_t)group * SK_MAX_ITEMS * CH * SK_PART;
     int* runs = reinterpret_cast<int*>(sums + (size_t)group * 3 * J * SK_PART);
@@ -582,6 +613,7 @@ int sk_walk(const float* prob, const float* taps, const int* parent, const SkOut
     for (int f0 = 0; f0 < frames; f0 += group) {
         const int nf = min(group, frames - f0);
         const float* p = prob + (size_t)f0 * J * N;
+        if (upward) E = A = out.upward + (size_t)f0 * J * N;
         // one level: the products, their sums, then the messages of `rows` from `src`
         auto level = [&](const SkItems& items, const SkRows& rows, int plane, const float* src, float* msg) -> int {
             if (items.n) {
@@ -608,6 +640,15 @@ int sk_walk(const float* prob, const float* taps, const int* parent, const SkOut
                 }
             const int rc = level(items, rows, 0, A, U);
             if (rc) return rc;
+        }
+        if (upward) {                                                    // one level more: A_0 = p_0 prod U_c and its sum; no message
+            SkItems items{};
+            items.j[0] = 0; items.excl[0] = -1; items.kind[0] = 0; items.n = 1;
+            const int rc = level(items, SkRows{}, 0, A, U);
+            if (rc) return rc;
+            hipLaunchKernelGGL(sk_upward_finish_kernel, dim3(nf), dim3(64), 0, st, sums, out.up_sums + (size_t)f0 * J, out.valid + f0, J);
+            SE_CHECK_LAUNCH();
+            continue;
         }
         for (int d = 0; d <= deepest; ++d) {
             SkItems items{};
@@ -687,3 +728,18 @@ extern "C" int se_skeleton_edge_stats_f32(const float* prob, const float* taps, 
     return sk_walk(prob, taps, parent, out, scratch, frames, J, voxels, G, R, floor, tree, depth, deepest, se_stream(stream));
 }
 
+// The upward walk for se_skeleton_upward_f32 (skeleton_sample.hip; declared in skeleton_shell.h): the pointers and the scratch size are
+// that entry point's to check, the shape, the floor and the tree are checked here, before anything is launched.
+long long sk_upward_scratch_bytes(int frames, int J, int G, int R) {
+    if (frames < 1 || J < 1 || J > SK_MAX_J || !sk_shape_ok(G, R)) return 0;
+    return ((long long)min(frames, SK_GROUP) * sk_upward_frame_floats(J, G) + sk_runs_ints(J, R)) * 4;
+}
+
+int sk_upward_walk(const float* prob, const float* taps, const int* parent, float* upward, float* sums, int* valid, void* scratch,
+                   int frames, int J, int voxels, int G, int R, float floor, void* stream) {
+    SkTree tree{};
+    int depth[SK_MAX_J], deepest;
+    if (!sk_walk_args(parent, frames, J, voxels, G, R, floor, tree, depth, deepest)) return SE_ERR_BAD_ARG;
+    const SkOutputs out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, valid, upward, sums};
+    return sk_walk(prob, taps, parent, out, scratch, frames, J, voxels, G, R, floor, tree, depth, deepest, se_stream(stream));
+}

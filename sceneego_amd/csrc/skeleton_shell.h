@@ -86,3 +86,10 @@ inline bool sk_build_tree(const int* parent, int J, SkTree& tree, int* depth, in
 }
 
 }  // namespace
+
+// The upward pass of se_skeleton_couple_f32 on its own, with one level more for the root (skeleton_prior.hip: the third mode of sk_walk);
+// se_skeleton_upward_f32 in skeleton_sample.hip is its entry point and checks the pointers and the scratch size.  SE_ERR_BAD_ARG with
+// nothing launched for a bad shape, floor or tree; the size is 0 for a shape out of range.
+int sk_upward_walk(const float* prob, const float* taps, const int* parent, float* upward, float* sums, int* valid, void* scratch,
+                   int frames, int J, int voxels, int G, int R, float floor, void* stream);
+long long sk_upward_scratch_bytes(int frames, int J, int G, int R);

@@ -7,7 +7,8 @@
 // and row:  x_T ~ b_T;  x_t ~ b_t(x) [(1 - floor) W(x -> x_{t+1}) + floor / N] where frame t is linked to t + 1;  x_t ~ b_t where not.
 // W(x -> y) = w[di] w[dj] w[dk] with x = y + d: the window of y in blur3's own orientation, no tap reversal.
 // Two launches per call:
-//   vsm_sums_kernel   grid (G, rows, frames), block 256: one i-plane [G j][G k] of b_t staged in LDS (rows padded by one float), the row
+//   se_draw_sums_kernel (categorical_sums.h, shared with skeleton_sample.hip)
+//                     grid (G, rows, frames), block 256: one i-plane [G j][G k] of b_t staged in LDS (rows padded by one float), the row
 //                     sums Rs[i][j] = sum_k b (thread j, ascending k) and the slab sum P[i] = sum_j Rs[i][j] (thread 0), in float64, to
 //                     the scratch.  The one read of the beliefs that is proportional to the volume.
 //   vsm_walk_kernel   grid (samples, rows), block 256: one workgroup per chain, looping over the call's frames from last to first INSIDE
@@ -32,46 +33,14 @@
 #include <float.h>
 
 #include "categorical_draw.h"
+#include "categorical_sums.h"    // se_draw_sums_kernel, the sums pass: shared with skeleton_sample.hip
 #include "volume_grid.h"          // the limits, the shape predicate and the launch parameters: shared with volume_filter.hip
 
 #pragma clang fp contract(off)
 
 #define SE_VSM_WIN (2 * SE_VG_MAX_R + 1)          // the taps of an axis at most
-#define SE_VSM_MAX_Z 65535                        // grid.z of the sums pass; more frames than that take turns
 
 namespace {
-
-// grid (G, rows, min(frames, 65535)), block 256, dynamic LDS G (G + 1) floats
-__global__ __launch_bounds__(SE_VG_THREADS) void vsm_sums_kernel(const float* __restrict__ belief, double* __restrict__ Rs,
-                                                                 double* __restrict__ P, int frames, int rows, int G) {
-    extern __shared__ __align__(16) float plane[];                  // [G j][G + 1]: a thread walks its own row, rows on distinct banks
-    __shared__ double rsum[SE_VG_MAX_G];
-    const int t = threadIdx.x, i = blockIdx.x, row = blockIdx.y;
-    const int GG = G * G, pitch = G + 1;
-    for (int f = blockIdx.z; f < frames; f += gridDim.z) {
-        const size_t fr = (size_t)f * rows + row;
-        const float* src = belief + (fr * G + i) * GG;
-        for (int e = t; e < GG; e += SE_VG_THREADS) {
-            const int j = e / G;
-            plane[j * pitch + (e - j * G)] = src[e];
-        }
-        __syncthreads();
-        if (t < G) {
-            const float* p = plane + t * pitch;
-            double acc = 0.0;
-            for (int k = 0; k < G; ++k) acc = acc + (double)p[k];
-            rsum[t] = acc;
-            Rs[(fr * G + i) * G + t] = acc;
-        }
-        __syncthreads();
-        if (t == 0) {
-            double acc = 0.0;
-            for (int j = 0; j < G; ++j) acc = acc + rsum[j];
-            P[fr * G + i] = acc;
-        }
-        __syncthreads();                                            // the next frame of this workgroup writes plane and rsum again
-    }
-}
 
 // grid (samples, rows), block 256.  No __restrict__ on next: read and written (by this workgroup alone).
 __global__ __launch_bounds__(SE_VG_THREADS) void vsm_walk_kernel(const float* __restrict__ belief, const int* __restrict__ restarted,
@@ -219,10 +188,8 @@ extern "C" int se_volume_sample_f32(const float* belief, const int* restarted, c
     double* Rs = reinterpret_cast<double*>(scratch);
     double* P = Rs + (size_t)frames * rows * G * G;
     const VgLaunch l = vg_launch(voxels, G, floor);                 // keep and uniform in float32, as the filter's kernels form them
-    SE_ENSURE_LDS(vsm_sums_kernel, SE_VG_MAX_G * (SE_VG_MAX_G + 1) * 4);
-    hipLaunchKernelGGL(vsm_sums_kernel, dim3(G, rows, min(frames, SE_VSM_MAX_Z)), dim3(SE_VG_THREADS), G * (G + 1) * 4, s, belief, Rs,
-                       P, frames, rows, G);
-    SE_CHECK_LAUNCH();
+    const int rc = se_draw_sums_launch(belief, Rs, P, frames, rows, G, s);
+    if (rc) return rc;
     hipLaunchKernelGGL(vsm_walk_kernel, dim3(samples, rows), dim3(SE_VG_THREADS), 0, s, belief, restarted, taps, Rs, P, have_link, next,
                        index, kind, frames, rows, G, radius, (double)l.keep, (double)l.uniform, (uint32_t)first_sample,
                        (uint32_t)first_frame, (uint32_t)seed_lo, (uint32_t)seed_hi);

@@ -166,6 +166,28 @@ def best_of_samples(frames, estimated, gt):
             "samples_per_joint": int(coord.shape[1]), "valid_draws": int(valid.sum()), "draws": int(valid.size)}
 
 
+def best_pose_of_samples(frames, estimated, gt):
+    """The whole-pose figure of pose samples, beside the per-joint ``best_of_samples``.  ``frames``: the per-frame dicts of
+    ``op.skeleton_samples_to_numpy`` (``coord`` [S,J,3], ``valid`` [S,J]); ``estimated`` / ``gt`` [T,J,3].  Per frame the smallest
+    MEAN joint error over the samples whose joints are ALL valid (the estimate's own mean joint error where there is none), averaged
+    over the frames: ``best_pose_of_n_mpjpe``.  A sampled pose is one joint draw, so its joints may not be picked apart: this is the
+    honest figure for whole poses, and it is never below ``best_of_n_mpjpe``.  No alignment.  numpy, float64."""
+    est = np.asarray(estimated, dtype=np.float64)
+    ref = np.asarray(gt, dtype=np.float64)
+    coord = np.stack([np.asarray(fr["coord"], dtype=np.float64) for fr in frames])               # [T,S,J,3]
+    valid = np.stack([np.asarray(fr["valid"]).astype(bool) for fr in frames])                    # [T,S,J]
+    if est.shape != ref.shape or coord.shape[0] != est.shape[0] or coord.shape[2:] != est.shape[1:] or valid.shape != coord.shape[:3]:
+        raise ValueError(f"shape mismatch: estimated {est.shape}, gt {ref.shape}, samples {coord.shape}, valid {valid.shape}")
+    whole = valid.all(axis=2)                                                                    # [T,S]
+    with np.errstate(invalid="ignore"):
+        err = np.linalg.norm(coord - ref[:, None], axis=-1).mean(axis=2)                         # [T,S]
+    err = np.where(whole, err, np.inf).min(axis=1)
+    own = np.linalg.norm(est - ref, axis=-1).mean(axis=1)
+    best = np.where(whole.any(axis=1), err, own)
+    return {"best_pose_of_n_mpjpe": float(best.mean()), "estimate_mpjpe": float(own.mean()), "samples_per_frame": int(coord.shape[1]),
+            "whole_poses": int(whole.sum()), "poses": int(whole.size), "frames_without_pose": int((~whole.any(axis=1)).sum())}
+
+
 def scene_summary(frames):
     """Physical plausibility of a sequence: ``frames`` is the list of per-frame dicts of ``op.scene_check_to_numpy`` (the keys
     ``penetrating``, ``penetration_depth`` and ``contact`` [15] are used).  Returns a dict:

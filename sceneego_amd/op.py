@@ -442,6 +442,22 @@ def volume_samples_to_numpy(result):
             for t in range(host["mean"].shape[0])]
 
 
+POSE_SAMPLE_KEYS = ("index", "coord", "kind", "valid", "bone_error")   # [S,B,...]
+POSE_SAMPLE_FRAME_KEYS = ("mean", "spread", "sampled")                 # [B,...]
+
+
+def skeleton_samples_to_numpy(result):
+    """The dict of ``SkeletonPrior.sample`` as a list of per-frame dicts of numpy arrays: ``index`` [S,J], ``coord`` [S,J,3], ``kind``
+    [S,J], ``valid`` [S,J], ``bone_error`` [S,J-1], ``mean`` [J,3], ``spread`` [J], ``sampled`` (a bool) and ``shift`` [J] when joints
+    were given: what run_sequence.py --pose_samples_output writes, and the keys ``metrics.best_of_samples`` and
+    ``metrics.best_pose_of_samples`` read."""
+    host = {k: result[k].cpu().numpy() for k in POSE_SAMPLE_KEYS}
+    frame_keys = POSE_SAMPLE_FRAME_KEYS + (("shift",) if "shift" in result else ())
+    host.update({k: result[k].cpu().numpy() for k in frame_keys})
+    return [{**{k: host[k][:, t].copy() for k in POSE_SAMPLE_KEYS}, **{k: host[k][t].copy() for k in frame_keys}}
+            for t in range(host["mean"].shape[0])]
+
+
 PATH_KEYS = ("joints", "index", "coord", "jumped", "segment_start", "log_score", "moved")
 
 

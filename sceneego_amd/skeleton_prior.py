@@ -33,6 +33,7 @@ KINEMATIC_PARENTS = _lib.KINEMATIC_PARENTS
 MAX_RADIUS = _lib.SKELETON_MAX_RADIUS
 MAX_GRID = _lib.SKELETON_MAX_GRID
 MAX_JOINTS = _lib.SKELETON_MAX_JOINTS
+SAMPLE_GROUP = 8            # frames per pair of library calls inside SkeletonPrior.sample: bounds the buffer of the upward products
 
 
 def check_parents(parents):
@@ -205,4 +206,108 @@ class SkeletonPrior:
                 given = joints.to(device=dev, dtype=torch.float32)
                 result["shift"] = (out_j - given).norm(dim=-1)
                 result["bone_error_before"] = self._bone_error(d, given)
+        return result
+
+    def _workspace(self, d, dev, stream, name, need, dtype=torch.uint8):
+        """A buffer of ``sample``: one per stream and name, grown when a call needs more."""
+        key = (stream.cuda_stream, name)
+        have = d["scratch"].get(key)
+        if have is None or have.numel() < need:
+            have = d["scratch"][key] = torch.empty(need, device=dev, dtype=dtype)
+        return have
+
+    @torch.no_grad()
+    def sample(self, volumes, samples=16, seed=0, first_frame=0, first_sample=0, joints=None, return_upward=False, stream=None):
+        """Draw ``samples`` whole poses per frame from the posterior of the coupling's own model, for the B frames ``volumes``
+        [B,J,G,G,G] (softmaxed, as ``forward()`` returns them): x_0 ~ A_0, then every child given its parent's voxel, down the tree
+        (``se_skeleton_upward_f32`` and ``se_skeleton_sample_f32``; the header states the definition).  Every sample is a member of the
+        posterior - its elbow and wrist lie on the same side - and the marginals of the samples are ``couple``'s beliefs.
+
+        Stateless, like ``couple``.  The random numbers are a function of (``seed``, global sample, global frame, joint) alone:
+        ``first_frame`` is the global number of ``volumes[0]`` and ``first_sample`` that of the first sample, so a sequence cut into
+        batches, or samples drawn in several calls, give the bits of one call.  ``seed``: 0..2^64-1.  The batch is walked in groups
+        of at most ``SAMPLE_GROUP`` = 8 frames, which bounds the buffer of the A_j (126 MB at 15 x 64^3); the results do not depend
+        on the grouping.
+
+        Returns a dict of device tensors, S = ``samples``: ``index`` [S,B,J] int32 (the flat voxel, -1 where invalid), ``coord``
+        [S,B,J,3] (the voxel centres: nothing is refined; NaN where invalid), ``kind`` [S,B,J] int32 (0 a step along the bone, 1 a
+        jump of the floor, 2 a fresh draw: the root, or a joint whose parent has no draw), ``valid`` [S,B,J] bool, ``sampled`` [B]
+        bool (False where one of the frame's upward sums is not a finite number > 0: nothing is drawn there), ``mean`` [B,J,3] (over
+        the valid samples), ``spread`` [B,J] (the root of the trace of the sample covariance over the valid samples, metres; NaN with
+        fewer than two), ``bone_error`` [S,B,J-1] (| |x_c - x_parent| - L_c | of every sample, NaN where an end is invalid); with
+        ``joints`` [B,J,3] given also ``shift`` [B,J] (metres between ``mean`` and them); with ``return_upward`` also ``upward``
+        [B,J,G,G,G] (the A_j) and ``sums`` [B,J].
+
+        ``stream``: the stream to run on (default: the current one).  Shapes and ranges are checked before anything touches the
+        device (ValueError)."""
+        G, J, N = self.grid, self.joints, self.voxels
+        if not isinstance(volumes, torch.Tensor) or volumes.dim() != 5 or tuple(volumes.shape[1:]) != (J, G, G, G) \
+                or volumes.dtype != torch.float32 or volumes.shape[0] < 1:
+            raise ValueError("sample: volumes must be a [B,%d,%d,%d,%d] float32 tensor with B >= 1, got %s"
+                             % (J, G, G, G, (tuple(volumes.shape), volumes.dtype) if isinstance(volumes, torch.Tensor) else type(volumes)))
+        B = int(volumes.shape[0])
+        if joints is not None and (not isinstance(joints, torch.Tensor) or tuple(joints.shape) != (B, J, 3)):
+            raise ValueError("sample: joints %s, expected %s" % (tuple(getattr(joints, "shape", ())), (B, J, 3)))
+        try:
+            S, seed, first_frame, first_sample = int(samples), int(seed), int(first_frame), int(first_sample)
+        except (TypeError, ValueError):
+            raise ValueError("sample: samples, seed, first_frame and first_sample must be integers") from None
+        if S < 1:
+            raise ValueError(f"sample: samples = {S} (>= 1) expected")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"sample: seed = {seed} (0..2^64-1) expected")
+        if first_frame < 0 or first_sample < 0 or first_frame + B > 2 ** 32 or first_sample + S > 2 ** 32:
+            raise ValueError(f"sample: first_frame = {first_frame} and first_sample = {first_sample} must not be negative and the "
+                             "last frame and sample index must lie below 2^32")
+        _lib.require_hip(volumes, joints)
+        dev = volumes.device
+        d = self._device_state(dev)
+        stream = stream if stream is not None else torch.cuda.current_stream(dev)
+        group = min(B, SAMPLE_GROUP)
+        with torch.cuda.stream(stream):
+            vol = volumes.contiguous().reshape(B, J, N)
+            index = torch.empty((S, B, J), device=dev, dtype=torch.int32)
+            kind = torch.empty((S, B, J), device=dev, dtype=torch.int32)
+            sums = torch.empty((B, J), device=dev, dtype=torch.float32)
+            sampled = torch.empty((B,), device=dev, dtype=torch.int32)
+            if return_upward:
+                upward = torch.empty((B, J, N), device=dev, dtype=torch.float32)
+            else:
+                upward = self._workspace(d, dev, stream, "upward", group * J * N, torch.float32)[:group * J * N].view(group, J, N)
+            up_scratch = self._workspace(d, dev, stream, "upward_scratch",
+                                         _lib.skeleton_upward_scratch_bytes(group, J, G, self.radius))
+            # 8 bytes more: the float64 sums start on an 8-byte boundary whatever the allocator returns
+            sm_scratch = self._workspace(d, dev, stream, "sample_scratch", _lib.skeleton_sample_scratch_bytes(group, J, G) + 8)
+            sm_scratch = sm_scratch[(-sm_scratch.data_ptr()) % 8:]
+            for b0 in range(0, B, group):
+                n = min(group, B - b0)
+                A = upward[b0:b0 + n] if return_upward else upward[:n]
+                _lib.skeleton_upward(vol[b0:b0 + n], d["taps"], self.parents, A, sums[b0:b0 + n], sampled[b0:b0 + n], n, N, G,
+                                     self.radius, self.floor, scratch=up_scratch)
+                if n == B:
+                    idx, knd = index, kind
+                else:
+                    idx = torch.empty((S, n, J), device=dev, dtype=torch.int32)
+                    knd = torch.empty((S, n, J), device=dev, dtype=torch.int32)
+                _lib.skeleton_sample(A, sampled[b0:b0 + n], d["taps"], self.parents, idx, knd, n, N, G, self.radius, self.floor, S,
+                                     first_sample=first_sample, first_frame=first_frame + b0, seed=seed, scratch=sm_scratch)
+                if n != B:
+                    index[:, b0:b0 + n] = idx
+                    kind[:, b0:b0 + n] = knd
+            valid = index >= 0
+            nan = torch.full((), float("nan"), device=dev, dtype=torch.float32)
+            coord = torch.where(valid[..., None], d["coord"][index.clamp(min=0).long()], nan)
+            count = valid.sum(dim=0).to(torch.float32)                                       # [B,J]
+            kept = torch.where(valid[..., None], coord, torch.zeros_like(nan))
+            mean = torch.where(count[..., None] > 0, kept.sum(dim=0) / count[..., None].clamp(min=1), nan)
+            dev2 = torch.where(valid, ((coord - mean[None]) ** 2).sum(dim=-1), torch.zeros_like(nan)).sum(dim=0)
+            spread = torch.where(count > 1, (dev2 / (count - 1).clamp(min=1)).sqrt(), nan)
+            bone = ((coord[:, :, d["child"]] - coord[:, :, d["parent"]]).norm(dim=-1) - d["lengths"]).abs()
+            result = {"index": index, "coord": coord, "kind": kind, "valid": valid, "sampled": sampled != 0, "mean": mean,
+                      "spread": spread, "bone_error": bone}
+            if joints is not None:
+                result["shift"] = (mean - joints.to(device=dev, dtype=torch.float32)).norm(dim=-1)
+            if return_upward:
+                result["upward"] = upward.view(B, J, G, G, G)
+                result["sums"] = sums
         return result
