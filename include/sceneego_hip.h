@@ -497,7 +497,7 @@ int se_exr_zip_decode_f32(const void* payload, long long payload_bytes, const lo
                           void* scratch, long long scratch_bytes, int* status, void* stream);
 
 /* Baseline JPEG frames -> uint8 B, G, R on the device (stands in for sceneego_amd/preprocess.py load_image_bgr, PIL on libjpeg-turbo;
- * bit-identical to it).  sceneego_amd/jpeg_device.py parses, validates and unstuffs on the host.
+ * bit-identical to it on files of plain blocks, see status 4 below).  sceneego_amd/jpeg_device.py parses, validates and unstuffs on the host.
  *   img_desc  int32 [n_images][64]: 0 width, 1 height, 2 components (1 or 3), 3 MCUs per row, 4 MCU rows, 5 blocks per MCU (<= 10),
  *             6 first segment, 7 segments, 8 output slot (sample of out), 9 hmax, 10 vmax, 12-14 h per component (frame order),
  *             15-17 v, 18-20 quantisation slot (== component), 21-23 DC table slot (0-3), 24-26 AC table slot (4-7), 27-29 plane
@@ -517,7 +517,13 @@ int se_exr_zip_decode_f32(const void* payload, long long payload_bytes, const lo
  *   (B, G, R) gets every image at its output slot.  `rounds`: inter-workgroup synchronisation launches (< 0: the default, 3); 0
  *   leaves every unsynchronised workgroup to the sequential repair kernel, with the same result.  status int32 [n_segs][2]:
  *   {code, value}; 0 ok, 1 descriptor out of range, 2 no code matches (value: bit offset in the segment), 3 stream ended (value:
- *   blocks completed of mcus * blocks per MCU).  Kernels se_jpeg_sync_intra_kernel, se_jpeg_sync_inter_kernel,
+ *   blocks completed of mcus * blocks per MCU), 4 a block outside the plain domain (value: one such block, counted from the
+ *   segment's first; se_jpeg_idct_kernel sets it only where the entry still holds 0, and not for a block of the MCU padding that
+ *   holds no sample of its component).  A block is plain when every dequantised
+ *   coefficient and every pass-1 workspace value of the ISLOW IDCT fits int16 and every pass-2 value after its descale, before the
+ *   +128, lies in [-512, 511]: there jidctint.c's C code, which the kernel follows, equals libjpeg-turbo's SIMD IDCT, and the
+ *   bit-identity with PIL holds only there; the caller decodes a file with any non-zero status on the host (jpeg_device.py does).
+ *   Kernels se_jpeg_sync_intra_kernel, se_jpeg_sync_inter_kernel,
  *   se_jpeg_sync_repair_kernel, se_jpeg_scan_kernel, se_jpeg_scan_top_kernel, se_jpeg_write_kernel, se_jpeg_dc_kernel,
  *   se_jpeg_idct_kernel, se_jpeg_color_kernel; every read stays inside payload_bytes and the segment's slot, every write inside
  *   the scratch layout and out. */

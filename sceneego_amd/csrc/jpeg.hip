@@ -1,8 +1,13 @@
 // Baseline JPEG frames decoded on the device: the restart segments of any number of same-sized files -> uint8 B, G, R.
 //
-// Stands in for PIL's decode in sceneego_amd/preprocess.py load_image_bgr (libjpeg-turbo with its defaults) and is bit-identical to
-// it: ISLOW IDCT (jidctint.c), libjpeg v6b fancy upsampling for h2v1 / h2v2 (jdsample.c; box replication when the chroma plane has
-// at most 2 columns, as libjpeg-turbo selects it), jdmainct.c's repeated edge rows and jdcolor.c's fixed-point YCbCr -> RGB.
+// Stands in for PIL's decode in sceneego_amd/preprocess.py load_image_bgr (libjpeg-turbo with its defaults): ISLOW IDCT (jidctint.c),
+// libjpeg v6b fancy upsampling for h2v1 / h2v2 (jdsample.c; box replication when the chroma plane has at most 2 columns, as
+// libjpeg-turbo selects it), jdmainct.c's repeated edge rows and jdcolor.c's fixed-point YCbCr -> RGB.  It is bit-identical to PIL on
+// every file whose blocks are all *plain*: every dequantised coefficient and every pass-1 workspace value fits int16 and every
+// pass-2 value after its descale (before the +128) lies in [-512, 511].  Outside that domain libjpeg-turbo's SIMD IDCT (int16 lanes,
+// saturating packs) and jidctint.c's C code (64-bit sums, a wrapping range-limit table), which this file follows, part ways: such a
+// block is reported as status 4 in its segment's entry and sceneego_amd/jpeg_device.py decodes the file with PIL instead, as it does
+// for any file with a non-zero status.  Ordinary files are far inside (tests/test_jpeg_craft_host.py: the margin test).
 //
 // The entropy-coded data of a segment (between RSTn markers, unstuffed on the host) is one serial bit stream.  It is decoded in
 // parallel by self-synchronisation (Weissenberger & Schmidt, ICPP 2018): every segment is cut into lanes of JPEG_LANE_BITS bits,
@@ -23,7 +28,8 @@
 //                               difference) into the zero-filled int16 [blocks][64] scratch; a segment stops at exactly its block
 //                               count; the lane that meets a bad code or the end of the bits reports it.
 //   se_jpeg_dc_kernel           DC prediction: running sum of the differences per (segment, component) in MCU order.
-//   se_jpeg_idct_kernel         dequantisation + ISLOW IDCT, 8 threads per block, into per-component uint8 planes (padded MCU grid).
+//   se_jpeg_idct_kernel         dequantisation + ISLOW IDCT, 8 threads per block, into per-component uint8 planes (padded MCU grid);
+//                               a block that is not plain (above) sets status 4 in its segment's entry unless a code is there already.
 //   se_jpeg_color_kernel        upsampling + YCbCr -> B, G, R (gray: B = G = R = Y), cropped to the image.
 //
 // Bounds: every segment and image descriptor is checked on the device against payload_bytes and the scratch layout before use
@@ -41,6 +47,7 @@
 #define SE_JPEG_BAD_DESC 1
 #define SE_JPEG_NO_CODE 2         // value: bit offset in the segment
 #define SE_JPEG_STREAM_END 3      // value: blocks completed
+#define SE_JPEG_NOT_PLAIN 4       // value: a block of the segment (counted from the segment's first) outside the plain domain
 
 #define ST_ERR (1ull << 16)
 #define ST_END (1ull << 17)
@@ -551,11 +558,11 @@ __device__ int find_img(const Ctx& c, long long b) {
 }  // namespace
 
 __global__ void __launch_bounds__(JPEG_WG) se_jpeg_idct_kernel(Ctx c, const short* __restrict__ coef, const int* __restrict__ quant,
-                                                               uint8_t* __restrict__ planes) {
+                                                               uint8_t* __restrict__ planes, int* __restrict__ status) {
     __shared__ int ws[JPEG_WG / 8][64];
     const int sub = threadIdx.x >> 3, t = threadIdx.x & 7;
     const long long b = (long long)blockIdx.x * (JPEG_WG / 8) + sub;
-    bool ok = b < c.blocks;
+    bool ok = b < c.blocks, plain = true;
     int ii = 0;
     if (ok) {
         ii = find_img(c, b);
@@ -575,7 +582,11 @@ __global__ void __launch_bounds__(JPEG_WG) se_jpeg_idct_kernel(Ctx c, const shor
         long long v[8], o[8];
         for (int r = 0; r < 8; ++r) v[r] = (long long)(int)((uint32_t)(int)in[8 * r + t] * (uint32_t)q[8 * r + t]);
         idct8(v, o);
-        for (int r = 0; r < 8; ++r) ws[sub][8 * r + t] = (int)((o[r] + (1ll << 10)) >> 11);
+        for (int r = 0; r < 8; ++r) {
+            const long long w = (o[r] + (1ll << 10)) >> 11;
+            ws[sub][8 * r + t] = (int)w;
+            plain = plain && v[r] == (short)v[r] && w == (short)w;
+        }
     }
     __syncthreads();
     if (!ok) return;
@@ -586,10 +597,22 @@ __global__ void __launch_bounds__(JPEG_WG) se_jpeg_idct_kernel(Ctx c, const shor
     const int h = im[12 + f], kk = k - im[33 + f];
     const int bx = (m % im[3]) * h + kk % h, by = (m / im[3]) * im[15 + f] + kk / h;
     uint32_t lo = 0, hi = 0;
-    for (int i = 0; i < 4; ++i) lo |= range_limit((o[i] + (1ll << 17)) >> 18) << (8 * i);
-    for (int i = 0; i < 4; ++i) hi |= range_limit((o[4 + i] + (1ll << 17)) >> 18) << (8 * i);
+    for (int i = 0; i < 8; ++i) {
+        const long long x = (o[i] + (1ll << 17)) >> 18;
+        plain = plain && x >= -512 && x <= 511;
+        (i < 4 ? lo : hi) |= range_limit(x) << (8 * (i & 3));
+    }
     uint8_t* dst = planes + im[37 + f] + (long long)(8 * by + t) * im[27 + f] + 8 * bx;
     *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+    if (!plain) {                 // rare: the block's segment entry, from the image's first segment, restart interval and the MCU
+        // a block wholly outside the component's samples (MCU padding) reaches no pixel, and libjpeg never transforms it
+        const bool real = 8 * bx < (im[0] * h + im[9] - 1) / im[9] && 8 * by < (im[1] * im[15 + f] + im[10] - 1) / im[10];
+        const long long si = (long long)im[6] + (im[50] > 0 ? m / im[50] : 0);
+        if (real && si >= 0 && si < c.n_segs && c.segs[si].img == ii && status[2 * si] == SE_JPEG_OK) {
+            status[2 * si + 1] = (int)(rel - c.segs[si].mcu0 * im[5]);
+            status[2 * si] = SE_JPEG_NOT_PLAIN;
+        }
+    }
 }
 
 namespace {
@@ -748,7 +771,7 @@ extern "C" int se_jpeg_decode_bgr_u8(const void* payload, long long payload_byte
                        c, coef, per_thread);
     SE_CHECK_LAUNCH();
     hipLaunchKernelGGL(se_jpeg_idct_kernel, dim3((unsigned)((blocks + JPEG_WG / 8 - 1) / (JPEG_WG / 8))), dim3(JPEG_WG), 0, s, c, coef,
-                       quant, sc + L.planes);
+                       quant, sc + L.planes, status);
     SE_CHECK_LAUNCH();
     hipLaunchKernelGGL(se_jpeg_color_kernel, dim3((unsigned)(((long long)out_h * out_w + JPEG_WG - 1) / JPEG_WG), n_images),
                        dim3(JPEG_WG), 0, s, c, sc + L.planes, out, n_out, out_h, out_w);

@@ -6,13 +6,21 @@ segments, strips the 0x00 after every 0xFF with bytes-level operations, validate
 descriptors, tables and unstuffed segments into one pinned buffer, copies it to the device in one transfer on the current stream and
 launches ``se_jpeg_decode_bgr_u8`` (``csrc/jpeg.hip``: parallel Huffman decode by self-synchronisation, DC prediction, ISLOW IDCT,
 fancy upsampling and YCbCr -> BGR).  The result is bit-identical to ``preprocess.load_image_bgr`` (PIL on libjpeg-turbo with its
-defaults).
+defaults).  The kernels follow libjpeg's C code; PIL runs libjpeg-turbo's SIMD IDCT, and the two agree on *plain* blocks only: every
+dequantised coefficient and every pass-1 workspace value fits int16, every pass-2 value after its descale lies in [-512, 511]
+(``tests/jpeg_model.py`` ``plain_blocks`` has the argument; files of any ordinary encoder are far inside).  The IDCT kernel reports
+any other block as status 4, and a file whose decode reports any status (a block that is not plain, no matching code, a stream that
+ends early: damage libjpeg only warns about) is decoded again by PIL on the host and copied into its slot, so the result equals
+``load_image_bgr``'s there too; ``DecodeStatus.redecoded`` lists those slots.  Only when PIL refuses the file as well does the
+status raise.
 
 The device path takes baseline or extended sequential (SOF0 / SOF1) Huffman-coded 8-bit files with one scan holding every component:
 gray, or three components libjpeg's colour-space guess treats as YCbCr, sampled 4:4:4, 4:2:2 (h2v1) or 4:2:0 (h2v2); any size, any
 restart interval, 8- or 16-bit quantisation tables.  Every other file (progressive, arithmetic, lossless, 12-bit, CMYK / YCCK, Adobe
-RGB, multi-scan, other sampling layouts, and files of other formats) is decoded by PIL on the host and uploaded, so every file ``load_image_bgr`` accepts is
-accepted here, in the same output order.  As in libjpeg-turbo, a scan that references Huffman table 0 or 1 without a DHT for it
+RGB, multi-scan, a scan that lists the components in another order than the frame, entropy-coded data with no marker after it, other
+sampling layouts, and files of other formats) is decoded by PIL on the host and uploaded, so every file ``load_image_bgr`` accepts is
+accepted here, in the same output order, and a file PIL refuses raises ``HostDecodeError`` (a ``ValueError`` and an ``OSError``)
+that names the file and carries PIL's message.  As in libjpeg-turbo, a scan that references Huffman table 0 or 1 without a DHT for it
 uses the standard tables of the JPEG specification (Annex K.3).
 """
 from __future__ import annotations
@@ -33,6 +41,7 @@ _STATUS = {
     1: "descriptor out of range",
     2: "no code matches at bit {v}",
     3: "stream ended after {v} of {n} blocks",
+    4: "block {v} of {n} is outside the plain-block domain of the IDCT",
 }
 
 # Annex K.3 tables (libjpeg-turbo's std_huff_tables): (bits[1..16], values)
@@ -59,6 +68,10 @@ _SOF_OTHER = (0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF)
 
 def _name(src, i):
     return src if isinstance(src, str) else f"<bytes #{i}>"
+
+
+class HostDecodeError(ValueError, OSError):
+    """PIL refused a file the host decodes: both what this module raises for a bad file and what ``load_image_bgr`` raises."""
 
 
 class HuffTable:
@@ -245,6 +258,8 @@ class JpegFile:
         ss, se, a = body[1 + 2 * ns], body[2 + 2 * ns], body[3 + 2 * ns]
         if ns != nf or len({s[0] for s in scan}) != nf:
             return self._fallback("multi-scan")
+        if [s[0] for s in scan] != sorted(s[0] for s in scan):      # libjpeg takes the scan's components in frame order only
+            return self._fallback("scan order differs from the frame's")
         if ss != 0 or se != 63 or a != 0:
             self._err(f"sequential scan with Ss={ss} Se={se} Ah/Al=0x{a:02X}")
         for fi, _, _ in scan:
@@ -291,8 +306,11 @@ class JpegFile:
         kinds = arr[mk + 1]
         is_rst = (kinds >= 0xD0) & (kinds <= 0xD7)
         stop = np.flatnonzero(~is_rst)
-        end = int(mk[stop[0]]) if len(stop) else len(buf)
-        if len(stop) and kinds[stop[0]] == 0xDA:
+        if not len(stop):                             # PIL calls such a file truncated, whether or not every block is there
+            self._fallback("entropy-coded stream ended without a marker")
+            return False
+        end = int(mk[stop[0]])
+        if kinds[stop[0]] == 0xDA:
             self._fallback("multi-scan")
             return False
         rst = mk[is_rst & (mk < end)]
@@ -337,7 +355,10 @@ def parse(sources):
         if f.device:
             shapes.setdefault((f.H, f.W), f.name)
         else:
-            img = f.host_decode()
+            try:
+                img = f.host_decode()
+            except Exception as e:                    # PIL's UnidentifiedImageError, OSError, SyntaxError, ...
+                raise HostDecodeError(f"{f.name}: {f.why}: {e}") from e
             f.host_image = img
             shapes.setdefault(img.shape[:2], f.name)
     if len(shapes) > 1:
@@ -384,7 +405,7 @@ class Packed:
             d[50] = f.restart
             for si, (m0, mc, data) in enumerate(f.segments):
                 seg[r, 0:5] = [data_len, len(data), i, m0, mc]
-                seg_names.append((f.name, si, mc * f.blocks_per_mcu, len(f.segments)))
+                seg_names.append((f.name, si, mc * f.blocks_per_mcu, len(f.segments), b))
                 data_len += ((len(data) + 3) & ~3) + 8
                 r += 1
         self.img, self.seg, self.tables, self.quant = img, seg, tables, quant
@@ -420,30 +441,48 @@ class Packed:
 
 class DecodeStatus:
     """Per-segment status of a decode whose check was deferred (``check=False``): ``status`` is the device int32 [segments, 2]
-    vector, ``check()`` reads it back and raises ``ValueError`` naming the first bad file and segment."""
+    vector.  ``check()`` reads it back; every file with a non-zero status is decoded by PIL on the host and copied into its slot of
+    the output (on the current stream), and ``redecoded`` lists those slots.  Where PIL refuses the file too, ``check()`` raises
+    ``ValueError`` naming the file, its first bad segment and the status, chained from PIL's error; status 1 (a descriptor out of
+    range, which no file can cause) raises at once."""
 
-    def __init__(self, status, seg_names):
+    def __init__(self, status, seg_names, files, out):
         self.status = status
-        self._segs = seg_names                       # (file name, segment index, blocks, segments of the file)
+        self._segs = seg_names                       # (file name, segment index, blocks, segments of the file, output slot)
+        self._files, self._out = files, out
+        self.redecoded = []
 
     def check(self):
         if self.status.numel() == 0:
             return
         st = self.status.cpu().numpy()
-        bad = np.nonzero(st[:, 0])[0]
-        if len(bad):
-            i = int(bad[0])
-            name, si, n, ns = self._segs[i]
+        done = set(self.redecoded)
+        for i in np.nonzero(st[:, 0])[0]:
+            i = int(i)
+            name, si, n, ns, slot = self._segs[i]
+            if slot in done:
+                continue
+            done.add(slot)
             msg = _STATUS.get(int(st[i, 0]), f"status {int(st[i, 0])}").format(v=int(st[i, 1]), n=n)
             where = f"restart segment {si}: " if ns > 1 else ""
-            raise ValueError(f"{name}: {where}{msg}")
+            if int(st[i, 0]) == 1:                    # not the file's fault: the descriptors this module packed are wrong
+                raise ValueError(f"{name}: {where}{msg}")
+            try:
+                img = self._files[slot].host_decode()
+                if tuple(img.shape) != tuple(self._out.shape[1:]):
+                    raise RuntimeError(f"PIL decodes it as {img.shape}")
+            except Exception as e:
+                raise ValueError(f"{name}: {where}{msg}") from e
+            self._out[slot].copy_(torch.from_numpy(img))
+            self.redecoded.append(slot)
 
 
 def decode_jpeg_batch(sources, device, out=None, check=True, rounds=None):
     """JPEG files (paths, bytes or parsed ``JpegFile``) of one size -> uint8 [B, H, W, 3], B, G, R order, on ``device``.
 
     Bit-identical to ``preprocess.load_image_bgr``.  ``out``: a caller's contiguous uint8 [B, H, W, 3] tensor.  ``check``: read
-    the per-segment status back and raise ``ValueError`` naming the file; ``False`` returns ``(tensor, DecodeStatus)``.
+    the per-segment status back, decode every file that reports one with PIL on the host into its slot, and raise ``ValueError``
+    naming the file where PIL refuses it too; ``False`` returns ``(tensor, DecodeStatus)`` and leaves that to ``DecodeStatus.check()``.
     ``rounds``: inter-workgroup synchronisation launches (default: the library's); 0 sends every unsynchronised workgroup
     through the sequential repair kernel.  Everything runs on ``device``'s current stream."""
     device = torch.device(device)
@@ -481,7 +520,7 @@ def decode_jpeg_batch(sources, device, out=None, check=True, rounds=None):
         for b, f in enumerate(files):
             if not f.device:
                 out[b].copy_(torch.from_numpy(f.host_image))
-    st = DecodeStatus(status, pk.seg_names)
+    st = DecodeStatus(status, pk.seg_names, files, out)
     if not check:
         return out, st
     st.check()

@@ -1,7 +1,7 @@
 """A small numpy model of the integer stages of csrc/jpeg.hip, for the CPU tests: sequential Huffman decode (one step per codeword,
 exactly as the device steps), DC prediction, libjpeg's ISLOW IDCT (jidctint.c), libjpeg v6b fancy upsampling (jdsample.c h2v1 /
 h2v2 with jdmainct.c's edge rows) and jdcolor.c's YCbCr -> RGB, plus the speculative / synchronisation rounds of the parallel decode
-with a free lane size.  It works on ``sceneego_amd.jpeg_device.JpegFile`` and is meant for small images (pure Python per codeword).
+with a free lane size, and the predicate of the blocks on which that IDCT equals libjpeg-turbo's SIMD one (``plain_blocks``).  It works on ``sceneego_amd.jpeg_device.JpegFile`` and is meant for small images (pure Python per codeword).
 """
 from __future__ import annotations
 
@@ -217,6 +217,93 @@ def idct_islow(coef, quant):
     return out
 
 
+def plain_blocks(coef, quant):
+    """bool [n]: the blocks (int [n, 64] natural-order coefficients, quantisation as ISLOW_MULT_TYPE) on which jidctint.c's C code,
+    which ``idct_islow`` and csrc/jpeg.hip follow, and libjpeg-turbo's SIMD ISLOW IDCT (jidctint-sse2 / -avx2, what PIL runs) give
+    the same samples.  A block is plain when
+      (a) every dequantised coefficient fits int16,
+      (b) every pass-1 workspace value (after its descale by 11 bits) fits int16,
+      (c) every pass-2 value after its descale by 18 bits, before the +128, lies in [-512, 511].
+
+    Why these three suffice.  The SIMD code differs from the C code in four ways only: it multiplies coefficient and quantisation
+    value in int16 lanes (low 16 bits of the product), forms a few sums of two inputs in int16 lanes (in0 +- in4, in7 + in3,
+    in5 + in1), sums the int16 x constant products in 32 bits where the C code has 64, and narrows with saturating packs (to int16
+    after pass 1; to int16, then to int8, then +128 after pass 2) where the C code stores an int and reads
+    range_limit[x & 1023].  (a) makes the int16 product the true product.  The 1-D transform is linear; its even part is
+    (in0 +- in4) << 13 plus terms of in2, in6, and its odd part is 8192 * 2 * Q with Q orthogonal (the rows are sqrt(2) cos((2x+1)
+    u pi / 16), u odd, and sum of cos^2 over the four odd u is 2).  (b) bounds all eight outputs of a column below 2^15 * 2^11 =
+    2^26 in magnitude, so every true 32-bit sum fits (and wrapping partial sums leave the true result), the half sums and half
+    differences of mirrored outputs bound |in0 +- in4| by 2^13 and the odd inputs' 2-norm by 2^13 (a sum of two of them by
+    sqrt(2) 2^13): no int16 lane wraps, and the saturating pack to int16 passes the value through.  In pass 2 (c) bounds the outputs
+    below 2^9 * 2^18 = 2^27 and gives the same with 2^14 and sqrt(2) 2^14 < 2^15; the two saturating packs and the +128 then are
+    min(max(x, -128), 127) + 128, which is what range_limit[x & 1023] holds for x in [-512, 511] and for no other x in general
+    (the table wraps at 1024).  The zero-AC shortcut of both codes is the general formula's value.  Outside (a), (b) or (c) some lane
+    may wrap or saturate where the C code does neither: tests/test_jpeg_craft_host.py counts how many such blocks differ."""
+    a, b, c = plain_classes(coef, quant)
+    return a & b & c
+
+
+def plain_classes(coef, quant):
+    """(a, b, c) of ``plain_blocks`` as three bool [n] arrays (True: the condition holds)."""
+    c = coef.astype(np.int64).reshape(-1, 8, 8)
+    q = quant.astype(np.int64).reshape(8, 8)
+    true = c * q
+    a = ((true >= -32768) & (true <= 32767)).all(axis=(1, 2))
+    dq = true.astype(np.int32).astype(np.int64)
+    ws = np.stack([_descale(x, CONST_BITS - PASS1_BITS) for x in _idct_1d(*[dq[:, r, :] for r in range(8)])], axis=1)
+    b = ((ws >= -32768) & (ws <= 32767)).all(axis=(1, 2))
+    ws = ws.astype(np.int32).astype(np.int64)
+    out = np.stack([_descale(x, CONST_BITS + PASS1_BITS + 3) for x in _idct_1d(*[ws[:, :, i] for i in range(8)])], axis=2)
+    return a, b, ((out >= -512) & (out <= 511)).all(axis=(1, 2))
+
+
+def file_coefficients(f):
+    """int32 [blocks, 64] of a device-path JpegFile in MCU order: natural order, DC predicted."""
+    bpm = f.blocks_per_mcu
+    rows, nbs = [], []
+    for _, mc, data in f.segments:
+        rows.append(decode_segment(f, data, mc * bpm)[0])
+        nbs.append(mc * bpm)
+    return dc_predict(np.concatenate(rows), f, nbs)
+
+
+def file_real(f):
+    """bool per block (MCU order): the block holds at least one sample of its component (the others pad the MCU grid: they reach
+    no pixel and libjpeg never transforms them)."""
+    bpm = f.blocks_per_mcu
+    k0, first = 0, {}
+    for fi, _, _ in f.scan:
+        h, v = f.comp_hv(fi)
+        first[fi] = k0
+        k0 += h * v
+    out = np.zeros(f.mcus_x * f.mcus_y * bpm, dtype=bool)
+    for i in range(len(out)):
+        m, k = divmod(i, bpm)
+        fi = f.block_comp[k]
+        h, v = f.comp_hv(fi)
+        kk = k - first[fi]
+        bx, by = (m % f.mcus_x) * h + kk % h, (m // f.mcus_x) * v + kk // h
+        out[i] = 8 * bx < -(-f.W * h // f.hmax) and 8 * by < -(-f.H * v // f.vmax)
+    return out
+
+
+def file_classes(f):
+    """(a, b, c) of ``plain_classes`` per block (MCU order) of a device-path JpegFile."""
+    coef = file_coefficients(f)
+    comp = np.array([f.block_comp[i % f.blocks_per_mcu] for i in range(len(coef))])
+    out = [np.ones(len(coef), dtype=bool) for _ in range(3)]
+    for fi in set(f.block_comp):
+        for o, x in zip(out, plain_classes(coef[comp == fi], f.quant[fi].astype(np.uint16).view(np.int16))):
+            o[comp == fi] = x
+    return out
+
+
+def file_plain(f):
+    """bool per block (MCU order) of a device-path JpegFile: plain, or a padding block."""
+    a, b, c = file_classes(f)
+    return (a & b & c) | ~file_real(f)
+
+
 def dc_predict(coef, f, seg_blocks):
     """Running sum of the DC differences per component, reset at every segment (coef rows in MCU order, all segments)."""
     out = coef.copy()
@@ -300,14 +387,7 @@ def ycc_to_bgr(y, cb, cr):
 
 def decode(f):
     """uint8 [H, W, 3] B, G, R of a device-path JpegFile, through the sequential decode."""
-    bpm = f.blocks_per_mcu
-    rows, nbs = [], []
-    for _, mc, data in f.segments:
-        c, _ = decode_segment(f, data, mc * bpm)
-        rows.append(c)
-        nbs.append(mc * bpm)
-    coef = dc_predict(np.concatenate(rows), f, nbs)
-    pls = planes(f, coef)
+    pls = planes(f, file_coefficients(f))
     if len(f.comps) == 1:
         g = pls[0][:f.H, :f.W]
         return np.stack([g, g, g], axis=-1)
