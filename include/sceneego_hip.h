@@ -166,8 +166,9 @@ int se_deconv2d_k4s2_assemble_f32(const float* z, const float* bias, float* out,
  *   gamma,beta,mean,var  BatchNorm3d weight/bias/running_mean/running_var [cout], or all NULL (no BN)
  *   wpack  out, se_conv3d_packed_elems(...) floats;  bpack out, cout_pad floats (cout rounded up to 16)
  * cin_pad >= cin is the channel count of the activation tensor the conv will read (multiple of 16;
- * extra channels get zero weights).  The buffer's sections, their sizes and the value of every element:
- * csrc/conv3d_pack.h; the kernels that write it: csrc/conv3d_pack.hip.                             */
+ * extra channels get zero weights).  The buffer's sections (A, B, E, F, G, H, I: one per kernel family that reads
+ * the layer), their sizes and the value of every element: csrc/conv3d_pack.h; the kernels that write it:
+ * csrc/conv3d_pack.hip.  se_conv3d_packed_elems is the sum of the sections the layer has.           */
 int se_conv3d_pack_f32(const float* w, const float* b, const float* gamma, const float* beta,
                        const float* mean, const float* var, float eps,
                        float* wpack, float* bpack,
@@ -1320,9 +1321,21 @@ int se_render_volume_overlay_f64(const float* packed, const double* scale, const
 
 #ifdef SE_DEVTOOLS
 /* Development builds only (csrc/build.sh --devtools; absent from the production library): A/B kernel selection for
- * tools/bench_conv.py and the cycle-stamp diagnostics.  The selector is thread-local. */
+ * tools/bench_conv.py and the cycle-stamp diagnostics.  The selector is thread-local; 0 is the production dispatch.  Every number
+ * chooses among kernels that production runs for some shape, or among instances of a production kernel template:
+ *   float32 3D convolutions (se_conv3d_plan, csrc/conv3d.hip, states each once):
+ *     1 - 9     no Winograd kernel (LDS-tiled direct, small-level and direct kernels)
+ *     10 - 19   no 2-D Winograd kernel; 18 / 19: grid / in-workgroup split-K for every small level
+ *     21 - 23   3^3 on the LDS-tiled direct kernel with 8 x 8 x {4, 8, 16} output tiles
+ *     30        1-D F(4,3) in place of the 2-D Winograd kernels
+ *     40        the production families;  64: the 2-D family stays on F(4,3) x F(2,3)
+ *     41 - 60   3^3: experiment / attribution instances of the F(4,3) x F(2,3) kernel (csrc/conv3d_wino2d.hip)
+ *     47        7^3: F(4,7) in place of F(6,7)
+ *   bf16 3D convolutions (csrc/conv3d_bf16_tiled.hip): 1 = 7^3 on 8 x 8 x 8 tiles, 4 = 3^3 on 4 x 4 x 16 tiles, 5 = 7^3 dz-phase form
+ *   2D convolutions (csrc/conv2d_1x1.hip, csrc/conv2d_3x3.hip): 73 - 79 */
 void se_debug_set_variant(int variant);
-/* u64 device buffer [workgroups][8 waves][6]; non-NULL switches the Winograd conv to its cycle-stamp build. */
+/* u64 device buffer [workgroups][8 waves][6] ([8] for F(6,7)) that the cycle-stamp builds (-DSE_STAMPPP, -DSE_STAMP47, -DSE_STAMP67)
+ * of the 1-D Winograd kernels fill; other builds never read it. */
 void se_debug_set_stamp_buffer(void* device_buffer);
 #endif
 

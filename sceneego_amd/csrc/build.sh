@@ -1,8 +1,8 @@
 #!/bin/bash
 # Builds libsceneego_hip.so for gfx950 (cross-compiles without a GPU).
 # Usage: build.sh [--devtools] [extra hipcc flags]
-#   --devtools  builds ../libsceneego_hip_dev.so instead (tools/ load it through SCENEEGO_HIP_LIB) with -DSE_DEVTOOLS: the A/B kernel selector (se_debug_set_variant), the retired kernel variants it selects
-#               (devtools/*.inc, included only under SE_DEVTOOLS) and the cycle-stamp hooks used by tools/.  The production library is built WITHOUT it.
+#   --devtools  builds ../libsceneego_hip_dev.so instead (tools/ load it through SCENEEGO_HIP_LIB) with -DSE_DEVTOOLS: the A/B kernel selector (se_debug_set_variant)
+#               and the cycle-stamp hooks used by tools/.  The production library is built WITHOUT it.
 # Objects live in _obj/<key>/ where <key> hashes the compiler version and the flag line, so objects of another compiler or
 # another flag set are never reused; inside a key a source is rebuilt when it or any header is newer than its object.
 set -euo pipefail
@@ -15,10 +15,9 @@ KEY=$( (hipcc --version 2>/dev/null; echo "$FLAGS") | sha256sum | cut -c1-12)
 OBJ=_obj/$KEY
 mkdir -p "$OBJ"
 pids=()
-newer() {  # source $1, a header or (development builds) a devtools/ include newer than object $2
+newer() {  # source $1 or a header newer than object $2
   [ ! -f "$2" ] || [ "$1" -nt "$2" ] && return 0
   for i in *.h ../../include/sceneego_hip.h; do [ "$i" -nt "$2" ] && return 0; done
-  if [ -n "$DEV" ]; then for i in devtools/*.inc; do [ "$i" -nt "$2" ] && return 0; done; fi
   return 1
 }
 OBJS=()
@@ -45,14 +44,6 @@ for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume
     pids+=($!)
   fi
 done
-# development builds: the F(4,3) x F(4,3) experiment of round 3 (se_debug_set_variant(63))
-if [ -n "$DEV" ]; then
-  OBJS+=($OBJ/conv3d_wino44.o)
-  if newer conv3d_wino44.hip $OBJ/conv3d_wino44.o; then
-    hipcc $FLAGS -c conv3d_wino44.hip -o $OBJ/conv3d_wino44.o &
-    pids+=($!)
-  fi
-fi
 # the F(4,7) 7^3 kernel: one object per input layout (each takes minutes to compile: 390 unrolled MFMAs under sched_group_barrier)
 for v in 0 1; do
   OBJS+=($OBJ/conv3d_wino47_$v.o)

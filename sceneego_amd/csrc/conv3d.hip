@@ -20,7 +20,7 @@
 
 #include "conv3d_plan.h"
 
-extern "C" int se_abi_version(void) { return 39; }
+extern "C" int se_abi_version(void) { return 40; }
 
 // Which family of kernels a default channels-last call (no SE_EPI_OUT_PLANAR / SE_EPI_RES_POST_RELU, cin_pad == cin) of this shape
 // belongs to: 2 = 2-D Winograd, 1 = 1-D Winograd F(4,3), 7 = Winograd 7^3, 0 = none of them.  The shape predicates are the plan's.
@@ -80,8 +80,6 @@ SeConvPlan se_conv3d_plan(const ConvArgs& a, int batch, int ksize) {
 
     const bool forms = (flags & SE_FORM_FLAGS) || a.pool_out || a.skip_w;
     const bool plain_epilogue = !(flags & (SE_EPI_RES_POST_RELU | SE_EPI_OUT_PLANAR));
-    // in_1d and in_k7w ask for the sections their production kernels read, E and F.  The retired kernels of development builds read C
-    // and D through the same predicates: the layout creates C with E and D with F (conv3d_pack.h), so those are there whenever these are.
     const bool in_2d = ksize == 3 && a.wpack_g && a.cin_pad == a.cin && se_wino2d_shape_ok(dim, a.cin, a.cout) && plain_epilogue;
     const bool in_1d = ksize == 3 && a.wpack_e && a.cin_pad == a.cin && se_wino1d_shape_ok(dim, a.cin, a.cout) && plain_epilogue &&
                        !(flags & (SE_LAYOUT_OCTET_BITS | SE_LAYOUT_QUAD_BITS));
@@ -94,18 +92,26 @@ SeConvPlan se_conv3d_plan(const ConvArgs& a, int batch, int ksize) {
     bool small_to_splitk = true, try_2d = true, try_44pp = true, try_1d = true, try_k7w = true, try_67 = true, try_wavesplit = true;
     long long wavesplit_min_vox = 2048;
 #ifdef SE_DEVTOOLS
-    // se_debug_set_variant(g): which families g switches off, and the retired kernels and experiments it names (each where the
-    // production order would reach it).  The only place of the plan that knows about variants; g = 0 is the production plan.
+    // se_debug_set_variant(g): which kernel families g switches off, and which instance of a production kernel template it names
+    // (reached where the production order would reach that kernel).  The only place of the plan that knows about variants; g = 0
+    // is the production plan, every other g also keeps tiny 2-D Winograd shapes off the small-level kernels.
+    //   1 - 9     no Winograd kernel: the LDS-tiled direct, small-level and direct kernels
+    //   10 - 19   no 2-D Winograd kernel: 1-D F(4,3) and the Winograd 7^3 kernels;
+    //             18: grid split-K for every small level, 19: in-workgroup split-K for every small level
+    //   21 - 23   3^3 on the LDS-tiled direct kernel with 8 x 8 x {4, 8, 16} output tiles (the tile-size sweep of BASELINE config 5)
+    //   30        1-D F(4,3) where production runs a 2-D Winograd kernel
+    //   40        the production families
+    //   41 - 60   3^3: experiment and attribution instances of the F(4,3) x F(2,3) kernel (conv3d_wino2d.hip lists them);
+    //             47 on a 7^3 layer: F(4,7) where production runs F(6,7)
+    //   64        the 2-D family stays on F(4,3) x F(2,3)
+    //   70 - 79   read by conv2d_1x1.hip and conv2d_3x3.hip
     if (const int g = g_variant) {
         small_to_splitk = false;
-        try_2d = g >= 40 && g < 70, try_44pp = g == 40;                         // 64: the 2-D family stays on F(4,3) x F(2,3)
-        try_1d = g == 4 || g == 30 || (g >= 10 && g < 20);                      // 30: 1-D instead of 2-D
-        try_k7w = g >= 10, try_67 = g != 47;                                    // 47: F(4,7) instead of F(6,7)
-        try_wavesplit = g != 18, wavesplit_min_vox = g == 19 ? 0 : 2048;        // 18 / 19: grid / in-workgroup split-K for every small level
-        const bool past_2d = !(try_2d && in_2d && fits_2d) && !forms, past_1d = past_2d && !(try_1d && fits_1d);
-        if (try_2d && in_2d && g == 63 && se_conv3d_wino44_takes(a))
-            return sliced(SE_CONV_DEV_WINO44, 0);
-        if (try_2d && in_2d && fits_2d && g >= 41) {                            // 41 - 61: experiments of the F(4,3) x F(2,3) kernel, which exist
+        try_2d = g >= 40 && g < 70, try_44pp = g == 40;
+        try_1d = g == 30 || (g >= 10 && g < 20);
+        try_k7w = g >= 10, try_67 = g != 47;
+        try_wavesplit = g != 18, wavesplit_min_vox = g == 19 ? 0 : 2048;
+        if (try_2d && in_2d && fits_2d && g >= 41) {
             const int octets = ((flags & SE_IN_OCTET) ? 1 : 0) | ((flags & SE_OUT_OCTET) ? 2 : 0) | ((flags & SE_RES_OCTET) && a.res ? 4 : 0);
             const bool quad_ok = !(flags & SE_LAYOUT_QUAD_BITS) || se_conv3d_wino2d_form(a) >= 0;   // for forms 0 and 3 (and run AS those)
             if (quad_ok && (octets == 0 || octets == 3)) {
@@ -113,22 +119,8 @@ SeConvPlan se_conv3d_plan(const ConvArgs& a, int batch, int ksize) {
                 return sliced(SE_CONV_WINO2D, octets);
             }
         }
-        if (past_2d && in_1d && g == 4 && fits([&](int nb) { return se_conv3d_wino1d_fits(SE_CONV_DEV_WINO23_1D, nb, dim, a.cout, cus); }))
-            return sliced(SE_CONV_DEV_WINO23_1D, 0);
-        if (past_2d && in_1d && g == 19 && fits([&](int nb) { return se_conv3d_wino1d_fits(SE_CONV_DEV_WINO43_1D, nb, dim, a.cout, cus); }))
-            return sliced(SE_CONV_DEV_WINO43_1D, 0);
-        if (past_1d && in_tiled && ksize == 3 && g >= 21 && g <= 23 && a.nts % 2 == 0 && dim % 16 == 0)
+        if (g >= 21 && g <= 23 && !forms && in_tiled && ksize == 3 && a.nts % 2 == 0 && dim % 16 == 0)   // no Winograd kernel is tried
             return sliced(SE_CONV_DEV_TILED_K3_TZ, 4 << (g - 21));
-        if (past_1d && in_tiled && ksize == 3 && (g == 2 || g == 3) && a.cout == 32 && dim >= 32 && (a.cin == 16 || a.cin == 32) && a.cin_pad == a.cin && plain_epilogue)
-            return sliced(SE_CONV_DEV_K3_C32_PERSISTENT, a.cin / 16 | (g == 3 ? 4 : 0));
-        if (!forms && in_tiled && try_k7w && in_k7w && (g == 17 || g == 19)) {
-            if (flags & SE_IN_PLANAR3) return bad_arg();                        // only the F(4,7) / F(6,7) kernels read the triplet-planar layout
-            const int k = g == 17 ? SE_CONV_DEV_K7_WINO27 : SE_CONV_DEV_K7_WINO27PP;
-            if (fits([&](int nb) { return se_conv3d_wino1d_fits(k, nb, dim, a.cout, cus); })) return sliced(k, 0);
-            try_k7w = false;
-        }
-        if (!forms && in_tiled && ksize == 7 && g == 2 && !(flags & SE_IN_PLANAR3) && dim >= 32 && a.cout == 16 && !a.res && !(flags & SE_EPI_OUT_PLANAR))
-            return sliced(SE_CONV_DEV_K7_PERSISTENT, 0);
     }
 #endif
 
@@ -198,14 +190,7 @@ static int launch_planned(const SeConvPlan& p, const ConvArgs& a, int batch, hip
         case SE_CONV_SPLITK_GRID: return se_conv3d_small_launch(a, p, s);
         case SE_CONV_DIRECT: return se_conv3d_direct_launch(a, p.form, s);
 #ifdef SE_DEVTOOLS
-        case SE_CONV_DEV_WINO44: return se_conv3d_wino44_launch(a, batch, s);
-        case SE_CONV_DEV_WINO23_1D:
-        case SE_CONV_DEV_WINO43_1D: return se_conv3d_wino1d_launch(a, batch, p.kernel, s);
-        case SE_CONV_DEV_K7_WINO27:
-        case SE_CONV_DEV_K7_WINO27PP: return se_conv3d_k7_wino_launch(a, batch, p.kernel, s);
-        case SE_CONV_DEV_TILED_K3_TZ:
-        case SE_CONV_DEV_K3_C32_PERSISTENT:
-        case SE_CONV_DEV_K7_PERSISTENT: return se_conv3d_tiled_launch(a, batch, p.kernel, p.form, s);
+        case SE_CONV_DEV_TILED_K3_TZ: return se_conv3d_tiled_launch(a, batch, p.kernel, p.form, s);
 #endif
         default: return SE_ERR_BAD_ARG;
     }

@@ -209,10 +209,6 @@ __global__ __launch_bounds__(256, TY == 8 ? 2 : 3) void conv_bf16_k3_kernel(Conv
     K3_STAMP(6);
 }
 
-#ifdef SE_DEVTOOLS   // retired A/B variant: persistent double-buffered form of the bf16 3x3x3 kernel
-#include "devtools/bf16_persistent_k3_kernel.inc"
-#endif  // SE_DEVTOOLS (persistent bf16 3x3x3 kernel)
-
 // ------------------------------------------------------------------------------------------------
 // 7x7x7 front layer, cout = 16, dim % 8 == 0, octet-planar input [B][octs][D^3][8].
 // Workgroup = 4 waves, output tile 8x8x8; wave w owns x in {2w, 2w+1}; its 8 voxel tiles are (x, y pair): a tile's 16
@@ -562,21 +558,6 @@ static int launch_k3(const ConvBArgs& a, int batch, hipStream_t s) {
 static bool epi_has_res_host(const ConvBArgs& a) { return a.res && (a.flags & (SE_EPI_RES_PRE_RELU | SE_EPI_RES_POST_RELU)); }
 
 int se_conv3d_bf16_tiled_try(const ConvBArgs& a, int batch, int ksize, hipStream_t s) {
-#ifdef SE_DEVTOOLS
-    if (ksize == 3 && a.dim % 16 == 0 && a.cin_pad % 16 == 0 && a.cout % 32 == 0 && a.kpc == K3_KPC && a.total_vox < (1LL << 31) &&
-        g_variant == 3) {      // A/B only: the persistent form measured 13-18 % SLOWER than two independent workgroups per CU
-        SE_ENSURE_LDS(conv_bf16_k3p_kernel, K3P_LDS_BYTES);
-        const int num_cus = se_num_cus();
-        const int tx = a.dim / K3_TX, ty = a.dim / K3_TY, tz = a.dim / K3_TZ;
-        const long long nitems = (long long)batch * tx * ty * tz * (a.cout / 32);
-        if (nitems < (1LL << 31)) {
-            const int grid = (int)(nitems < num_cus ? nitems : num_cus);
-            hipLaunchKernelGGL(conv_bf16_k3p_kernel, dim3(grid), dim3(512), K3P_LDS_BYTES, s, a, tx, ty, tz, (int)nitems);
-            SE_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-#endif
     if (ksize == 3 && a.dim % 16 == 0 && a.cin_pad % 16 == 0 && a.cout % 32 == 0 && a.kpc == K3_KPC && a.total_vox < (1LL << 31))
         return g_variant == 4 ? launch_k3<4>(a, batch, s) : launch_k3<8>(a, batch, s);   // 4: tile 4x4x16, 3 workgroups per CU (A/B)
     if (ksize == 7 && a.dim % 8 == 0 && a.cout == 16 && a.kpc == SE_K7B_KPC && !epi_has_res_host(a) &&

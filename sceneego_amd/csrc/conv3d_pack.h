@@ -18,20 +18,17 @@
 // 7x7x7 tiled kernel: the 343 taps are taken 4 at a time on the MFMA k lanes -> 86 groups (last one has 1 pad tap)
 #define SE_K7_TAPS 343
 #define SE_K7_GROUPS 86
-// 1-D Winograd section of the packed 3x3x3 weights: per (16-cin group, 32-cout block): 9 (dy,dx) x 4 xi x 2 cout tiles x 1 KiB
-#define SE_WINO_CHUNK_FLOATS (9 * 4 * 2 * 256)
-// F(4,3) variant (section E): 9 (dy,dx) x 6 xi x 2 cout tiles x 1 KiB = 108 KB per (16-cin group, 32-cout block)
+// 1-D Winograd F(4,3) section (E) of the packed 3x3x3 weights: 9 (dy,dx) x 6 xi x 2 cout tiles x 1 KiB = 108 KB per (16-cin group, 32-cout block)
 #define SE_WINO43_CHUNK_FLOATS (9 * 6 * 2 * 256)
 // 2-D Winograd F(4,3) x F(2,3) section (G) of the packed 3x3x3 weights (conv3d_wino2d.hip): per (32-cout block, 8-cin chunk)
 // 24 xi x 3 dx x 2 cout tiles x 64 lanes x 2 = 73,728 B
 #define SE_WINO2D_CHUNK_FLOATS (24 * 3 * 2 * 128)
-// 2-D Winograd F(4,3) x F(4,3) section (I) of the packed 3x3x3 weights (conv3d_wino44.hip): per (32-cout block, 4-cin chunk)
+// 2-D Winograd F(4,3) x F(4,3) section (I) of the packed 3x3x3 weights (conv3d_wino44pp.hip): per (32-cout block, 4-cin chunk)
 // 9 xi quads x 3 dx x 2 cout tiles x 64 lanes x 4 = 55,296 B
 #define SE_WINO44_CHUNK_FLOATS (9 * 3 * 2 * 256)
-// 1-D Winograd F(2,7) section of the packed 7x7x7 weights: per 4-channel chunk 13 (dy,dx) tap groups x 8 xi x 1 KiB
+// 1-D Winograd F(4,7) section (F) of the packed 7x7x7 weights: per 3-channel chunk 13 (dy,dx) tap groups (the 49 taps 4 at a time on
+// the MFMA k lanes) x 10 xi x 64 lanes x 3
 #define SE_K7W_GROUPS 13
-#define SE_K7W_CHUNK_FLOATS (SE_K7W_GROUPS * 8 * 256)
-// 1-D Winograd F(4,7) section (F) of the packed 7x7x7 weights: per 3-channel chunk 13 (dy,dx) tap groups x 10 xi x 64 lanes x 3
 #define SE_K7F_XI 10
 #define SE_K7F_CHUNK_FLOATS (SE_K7W_GROUPS * SE_K7F_XI * 64 * 3)
 // 1-D Winograd F(6,7) section (H) of the packed 7x7x7 weights (conv3d_wino67.hip): per 3-channel chunk the 147 (channel, dy, dx)
@@ -47,15 +44,14 @@ SE_PACK_FN int round_up16(int v) { return (v + 15) & ~15; }
 // ConvArgs::wpack_* at them.
 //   A  every layer:        direct form                      [cg][tap][nt][lane][4]
 //   B  k = 7:              tap-lane form of the tiled kernel [chunk4][group 86][nt][lane][4]
-//   C  k = 3, cout % 32 == 0: 1-D Winograd F(2,3)            (development builds read it)
-//   D  k = 7, cout <= 16:  1-D Winograd F(2,7)               [chunk4][g13][xi8][lane][4] (development builds read it)
 //   E  k = 3, cout % 32 == 0: 1-D Winograd F(4,3)
 //   F  k = 7, cout <= 16:  1-D Winograd F(4,7)               [chunk3][g13][xi10][lane][3]
 //   G  k = 3, cout % 32 == 0: 2-D Winograd F(4,3) x F(2,3)
 //   H  k = 7, cout <= 16:  1-D Winograd F(6,7)               [chunk3][g37][lane][xi12]
 //   I  k = 3, cout % 32 == 0: 2-D Winograd F(4,3) x F(4,3)
-// Buffer order: A B D F H (k = 7), A C E G I (k = 3), A alone (k = 1, transposed k = 2).
-enum SePackSection { SE_PACK_A, SE_PACK_B, SE_PACK_C, SE_PACK_D, SE_PACK_E, SE_PACK_F, SE_PACK_G, SE_PACK_H, SE_PACK_I, SE_PACK_SECTIONS };
+// (The letters C and D belonged to the F(2,3) and F(2,7) forms, which no kernel reads any more.)
+// Buffer order: A B F H (k = 7), A E G I (k = 3), A alone (k = 1, transposed k = 2).
+enum SePackSection { SE_PACK_A, SE_PACK_B, SE_PACK_E, SE_PACK_F, SE_PACK_G, SE_PACK_H, SE_PACK_I, SE_PACK_SECTIONS };
 struct SePackLayout {
     long long at[SE_PACK_SECTIONS], elems[SE_PACK_SECTIONS], total;
     const float* section(const float* wpack, int s) const { return at[s] >= 0 ? wpack + at[s] : nullptr; }
@@ -72,8 +68,6 @@ inline SePackLayout se_conv3d_pack_layout(int cout, int cin_pad, int ksize, int 
     };
     section(SE_PACK_A, true, taps * (cin_pad / 16) * nts * 256);
     section(SE_PACK_B, k7, (long long)(cin_pad / 4) * SE_K7_GROUPS * nts * 256);
-    section(SE_PACK_C, k3w, (cin_pad / 16) * cb * SE_WINO_CHUNK_FLOATS);
-    section(SE_PACK_D, k7w, (long long)(cin_pad / 4) * SE_K7W_CHUNK_FLOATS);
     section(SE_PACK_E, k3w, (cin_pad / 16) * cb * SE_WINO43_CHUNK_FLOATS);
     section(SE_PACK_F, k7w, (long long)((cin_pad + 2) / 3) * SE_K7F_CHUNK_FLOATS);
     section(SE_PACK_G, k3w, (cin_pad / 8) * cb * SE_WINO2D_CHUNK_FLOATS);
@@ -106,20 +100,6 @@ SE_PACK_FN float se_pack_bias(const SePackSource& s, const float* b, const float
     return v;
 }
 
-// G matrix of F(2,7) with interpolation points {0, 1, -1, 2, -2, 1/2, -1/2, inf} (Cook-Toom; tools/wino27_matrices.py):
-// row xi, column kz.  y = A^T [(G g) .* (B^T d)].
-SE_PACK_FN float se_wino27_G(int xi, int kz) {
-    switch (xi) {
-        case 0: return kz == 0 ? -1.f : 0.f;
-        case 1: return -2.f / 9.f;
-        case 2: return (kz & 1) ? 2.f / 9.f : -2.f / 9.f;
-        case 3: return (float)(1 << kz) / 90.f;
-        case 4: return ((kz & 1) ? -1.f : 1.f) * (float)(1 << kz) / 90.f;
-        case 5: return (float)(64 >> kz) / 90.f;
-        case 6: return ((kz & 1) ? -1.f : 1.f) * (float)(64 >> kz) / 90.f;
-        default: return kz == 6 ? 1.f : 0.f;
-    }
-}
 // G of F(4,3), points {0, 1, -1, 2, -2, inf}; G of F(2,3)
 static constexpr float SE_W43_G[6][3] = {{0.25f, 0.f, 0.f},          {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
                                          {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0.f, 0.f, 1.f}};
@@ -161,54 +141,6 @@ SE_PACK_FN float se_pack_b(const SePackSource& s, long long t) {
     const int tap = 4 * g + (lane >> 4);
     const int ci = (int)r * 4 + j;
     return se_pack_weight(s, nt * 16 + (lane & 15), ci, tap, SE_K7_TAPS);
-}
-
-// section C: 1-D Winograd F(2,3) along z.  U0 = g0, U1 = (g0+g1+g2)/2, U2 = (g0-g1+g2)/2, U3 = g2 of the
-// three z taps (g0: dz=-1) for every (dy,dx); blocks [cg][cb][tap2d][xi][nt2][lane][j], cb = 32-cout block
-SE_PACK_FN float se_pack_c(const SePackSource& s, long long t) {
-    const int nts = round_up16(s.cout) / 16;
-    const int j = (int)(t & 3);
-    const int lane = (int)((t >> 2) & 63);
-    long long r = t >> 8;
-    const int nt2 = (int)(r % 2); r /= 2;
-    const int xi = (int)(r % 4); r /= 4;
-    const int tap2d = (int)(r % 9); r /= 9;
-    const int n_cb = nts / 2;
-    const int cb = (int)(r % n_cb); r /= n_cb;
-    const int co = cb * 32 + nt2 * 16 + (lane & 15);
-    const int cc = (int)r * 16 + 4 * (lane >> 4) + j;
-    float v = 0.f;
-    if (co < s.cout && cc < s.cin) {
-        const float sc = se_pack_scale(s, co);
-        const float* wp = s.w + ((size_t)co * s.cin + cc) * 27 + tap2d;
-        const float g0 = wp[0], g1 = wp[9], g2 = wp[18];
-        const float u = xi == 0 ? g0 : xi == 1 ? (g0 + g1 + g2) * 0.5f : xi == 2 ? (g0 - g1 + g2) * 0.5f : g2;
-        v = u * sc;
-    }
-    return v;
-}
-
-// section D (k = 7, cout <= 16): 1-D Winograd F(2,7) along z.  U_xi = sum_kz G[xi][kz] * W[..][kz][dy][dx];
-// blocks [chunk4][g(13)][xi(8)][lane][j]: k lane h carries the (dy,dx) tap 4g+h (taps >= 49 are zero padding)
-SE_PACK_FN float se_pack_d(const SePackSource& s, long long t) {
-    const int j = (int)(t & 3);
-    const int lane = (int)((t >> 2) & 63);
-    long long r = t >> 8;
-    const int xi = (int)(r % 8); r /= 8;
-    const int g = (int)(r % SE_K7W_GROUPS); r /= SE_K7W_GROUPS;
-    const int tap2d = 4 * g + (lane >> 4);
-    const int cc = (int)r * 4 + j;
-    const int co = lane & 15;
-    float v = 0.f;
-    if (co < s.cout && cc < s.cin && tap2d < 49) {
-        const float sc = se_pack_scale(s, co);
-        const float* wp = s.w + ((size_t)co * s.cin + cc) * 343 + tap2d;
-        float u = 0.f;
-#pragma unroll
-        for (int kz = 0; kz < 7; ++kz) u += se_wino27_G(xi, kz) * wp[kz * 49];
-        v = u * sc;
-    }
-    return v;
 }
 
 // section E: 1-D Winograd F(4,3) along z, U = G g with G = [[1/4,0,0],[-1/6,-1/6,-1/6],[-1/6,1/6,-1/6],
@@ -421,8 +353,6 @@ SE_PACK_FN float se_pack_value(int section, const SePackSource& s, long long t) 
     switch (section) {
         case SE_PACK_A: return se_pack_a(s, t);
         case SE_PACK_B: return se_pack_b(s, t);
-        case SE_PACK_C: return se_pack_c(s, t);
-        case SE_PACK_D: return se_pack_d(s, t);
         case SE_PACK_E: return se_pack_e(s, t);
         case SE_PACK_F: return se_pack_f(s, t);
         case SE_PACK_G: return se_pack_g(s, t);

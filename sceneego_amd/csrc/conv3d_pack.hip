@@ -21,8 +21,7 @@ __global__ void pack_bias_kernel(SePackSource src, const float* __restrict__ b, 
 
 using PackKernel = void (*)(SePackSource, float*, long long, long long);
 constexpr PackKernel PACK_KERNELS[SE_PACK_SECTIONS] = {
-    pack_section_kernel<SE_PACK_A>, pack_section_kernel<SE_PACK_B>, pack_section_kernel<SE_PACK_C>,
-    pack_section_kernel<SE_PACK_D>, pack_section_kernel<SE_PACK_E>, pack_section_kernel<SE_PACK_F>,
+    pack_section_kernel<SE_PACK_A>, pack_section_kernel<SE_PACK_B>, pack_section_kernel<SE_PACK_E>, pack_section_kernel<SE_PACK_F>,
     pack_section_kernel<SE_PACK_G>, pack_section_kernel<SE_PACK_H>, pack_section_kernel<SE_PACK_I>};
 
 // the split planes of a layer (conv3d_pack.h: se_split6_value), from section A of its packed float32 buffer

@@ -19,15 +19,8 @@ enum SeConvKernel {
     SE_CONV_WAVESPLIT,       // small levels: in-workgroup split-K; form: waves per workgroup (4: two cout tile pairs of 2 x 4 waves, 8, 16)
     SE_CONV_SPLITK_GRID,     // small levels: taps split over grid.z into the caller's workspace + reduce; `splits`
     SE_CONV_DIRECT,          // any shape (conv3d_direct.hip): activations straight from global memory; form: ksize
-#ifdef SE_DEVTOOLS           // retired kernels, reachable only through se_debug_set_variant (devtools/*.inc, conv3d_wino44.hip)
-    SE_CONV_DEV_WINO44,            // (63) F(4,3) x F(4,3), lockstep form; form: octet layout bits
-    SE_CONV_DEV_WINO23_1D,         // (4) 1-D Winograd F(2,3)
-    SE_CONV_DEV_WINO43_1D,         // (19) 1-D Winograd F(4,3), single-phase form
-    SE_CONV_DEV_TILED_K3_TZ,       // (21-23) LDS-tiled direct 3^3 with 8 x 8 x form output tiles (4, 8, 16), 2 cout tiles
-    SE_CONV_DEV_K3_C32_PERSISTENT, // (2, 3) persistent direct 3^3, 32 output channels; form: cin / 16 | (variant 3 ? 4 : 0)
-    SE_CONV_DEV_K7_WINO27,         // (17) 7^3: 1-D Winograd F(2,7), single-phase form
-    SE_CONV_DEV_K7_WINO27PP,       // (19) 7^3: 1-D Winograd F(2,7), ping-pong form
-    SE_CONV_DEV_K7_PERSISTENT,     // (2) persistent direct 7^3
+#ifdef SE_DEVTOOLS           // reachable only through se_debug_set_variant
+    SE_CONV_DEV_TILED_K3_TZ, // (21-23) LDS-tiled direct 3^3 with 8 x 8 x form output tiles (4, 8, 16), 2 cout tiles
 #endif
 };
 
@@ -54,8 +47,8 @@ int se_conv3d_wino44pp_launch(const ConvArgs& a, int batch, int form, hipStream_
 bool se_conv3d_wino2d_fits(int batch, int dim, int cout);
 int se_conv3d_wino2d_form(const ConvArgs& a);
 int se_conv3d_wino2d_launch(const ConvArgs& a, int batch, int form, int exp, hipStream_t s);
-// conv3d_wino.hip: the 1-D Winograd kernels; `kernel` is the plan's (SE_CONV_WINO43PP_1D, SE_CONV_K7_*, in development builds their
-// retired forms).  _fits: the unit table of `kernel` holds a launch of `batch` samples
+// conv3d_wino.hip: the 1-D Winograd kernels; `kernel` is the plan's (SE_CONV_WINO43PP_1D, SE_CONV_K7_*).  _fits: the unit table of
+// `kernel` holds a launch of `batch` samples
 bool se_conv3d_wino1d_fits(int kernel, int batch, int dim, int cout, int num_cus);
 int se_conv3d_wino1d_launch(const ConvArgs& a, int batch, int kernel, hipStream_t s);
 int se_conv3d_k7_wino_launch(const ConvArgs& a, int batch, int kernel, hipStream_t s);
@@ -65,7 +58,7 @@ int se_conv3d_k7_wino67_launch(const ConvArgs& a, int batch, int num_cus, hipStr
 bool se_conv3d_k7_wino47_fits(int batch, int dim, int num_cus);
 int se_conv3d_k7_wino47_launch_cl(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
 int se_conv3d_k7_wino47_launch_p3(const ConvArgs& a, int batch, int num_cus, hipStream_t s, unsigned long long* dbg);
-// conv3d_tiled.hip: SE_CONV_TILED_K3 / _K7 (development builds: the retired persistent direct kernels too)
+// conv3d_tiled.hip: SE_CONV_TILED_K3 / _K7 (development builds: SE_CONV_DEV_TILED_K3_TZ too)
 int se_conv3d_tiled_launch(const ConvArgs& a, int batch, int kernel, int form, hipStream_t s);
 // conv3d_small.hip: SE_CONV_HALO64 / _HALO64_S6 / _WAVESPLIT / _SPLITK_GRID, on the whole batch; reads p.kernel, p.form and p.splits
 // _s6_domain: what conv3d_k3_halo64_s6_kernel can run at all (whole 64-voxel tiles of rows, 32-channel stages of input and split
@@ -77,8 +70,3 @@ inline bool se_conv3d_halo64_s6_domain(const ConvArgs& a) {
 int se_conv3d_small_launch(const ConvArgs& a, const SeConvPlan& p, hipStream_t s);
 // conv3d_direct.hip: SE_CONV_DIRECT, on the whole batch
 int se_conv3d_direct_launch(const ConvArgs& a, int ksize, hipStream_t s);
-#ifdef SE_DEVTOOLS
-// conv3d_wino44.hip
-bool se_conv3d_wino44_takes(const ConvArgs& a);
-int se_conv3d_wino44_launch(const ConvArgs& a, int batch, hipStream_t s);
-#endif

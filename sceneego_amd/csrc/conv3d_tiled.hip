@@ -19,12 +19,8 @@
 // 4*M_T*N_T MFMAs of 32 cycles each (k3 32->32: 6 loads for 32 MFMAs = 1024 SIMD cycles).
 #include "conv3d_plan.h"
 
-#include <type_traits>
-
-#define SE_K7_TSTRIDE 92   // per-k-lane row of the 7^3 tap-offset table (86 groups + pad, multiple of 4)
-
 #ifdef SE_DEVTOOLS
-thread_local int g_variant = 0;   // A/B switch of development builds (se_debug_set_variant): 1 = disable the persistent 64^3 kernel
+thread_local int g_variant = 0;   // A/B switch of development builds (se_debug_set_variant; include/sceneego_hip.h lists the numbers)
 #endif
 
 namespace {
@@ -164,10 +160,6 @@ __global__ __launch_bounds__(256) void conv3d_tiled_kernel(ConvArgs a, int tiles
     }
 }
 
-#ifdef SE_DEVTOOLS   // retired A/B variants: persistent direct (non-Winograd) kernels of the 64^3 level
-#include "devtools/tiled_persistent_direct_kernels.inc"
-#endif  // SE_DEVTOOLS (persistent direct kernels)
-
 template <int KS, int CK, int TZ, int N_T>
 int launch_tiled(const ConvArgs& a, int batch, hipStream_t s) {
     using G = TileGeom<KS, CK, TZ>;
@@ -186,7 +178,7 @@ int launch_tiled(const ConvArgs& a, int batch, hipStream_t s) {
 
 // The LDS-tiled direct kernels: shapes no Winograd kernel covers (3^3 with cout % 32 != 0 or cin % 16 != 0; 7^3 with a residual or
 // planar output).  Preconditions (se_conv3d_plan): channels-last tensors, dim >= 16, dim % 8 == 0, cout % 16 == 0; 7^3: cout == 16.
-// `form`: cout tiles per workgroup of SE_CONV_TILED_K3 (divides a.nts).  Development builds: the retired persistent direct kernels.
+// `form`: cout tiles per workgroup of SE_CONV_TILED_K3 (divides a.nts).  Development builds: the tile-size sweep of the 3^3 kernel.
 int se_conv3d_tiled_launch(const ConvArgs& a, int batch, int kernel, int form, hipStream_t s) {
     switch (kernel) {
         case SE_CONV_TILED_K3: return form == 4 ? launch_tiled<3, 16, 4, 4>(a, batch, s) : form == 2 ? launch_tiled<3, 16, 4, 2>(a, batch, s) : launch_tiled<3, 16, 4, 1>(a, batch, s);
@@ -195,10 +187,6 @@ int se_conv3d_tiled_launch(const ConvArgs& a, int batch, int kernel, int form, h
         // BASELINE config 5 (LDS tile-size sweep, tools/bench_conv.py --variants 21,22,23): 8x8x{4,8,16} output tiles = 38 / 64 / 115 KB
         // of halo per 16-channel chunk (needs nts % 2 == 0, dim % 16 == 0)
         case SE_CONV_DEV_TILED_K3_TZ: return form == 4 ? launch_tiled<3, 16, 4, 2>(a, batch, s) : form == 8 ? launch_tiled<3, 16, 8, 2>(a, batch, s) : launch_tiled<3, 16, 16, 2>(a, batch, s);
-        case SE_CONV_DEV_K3_C32_PERSISTENT:   // cout 32, cin 16 / 32 = cin_pad, dim >= 32, no SE_EPI_RES_POST_RELU / SE_EPI_OUT_PLANAR
-            if (form & 4) return (form & 3) == 2 ? launch_k3_c32_persistent<2, true>(a, batch, s) : launch_k3_c32_persistent<1, true>(a, batch, s);
-            return (form & 3) == 2 ? launch_k3_c32_persistent<2, false>(a, batch, s) : launch_k3_c32_persistent<1, false>(a, batch, s);
-        case SE_CONV_DEV_K7_PERSISTENT: return launch_k7_persistent(a, batch, s);   // dim >= 32, cout 16, no residual, channels-last output
 #endif
         default: return SE_ERR_BAD_ARG;
     }

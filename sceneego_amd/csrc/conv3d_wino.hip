@@ -1,22 +1,11 @@
-// 3x3x3 convolution with a 1-D Winograd F(2,3) transform along z, on the f32 MFMA — the V2V workhorse.
+// 3x3x3 convolution with a 1-D Winograd F(4,3) transform along z, on the f32 MFMA, in "ping-pong" form: the kernel of the 3^3 shapes
+// with cout % 32 == 0 and cin % 16 == 0 that the 2-D Winograd kernels do not take (dim % 16 == 8).  This file also holds the launcher
+// that routes the 7^3 layer to its Winograd kernels (conv3d_wino67.hip, conv3d_wino47.hip).
 //
-// For two output voxels that are neighbours in z, (y0, y1), and the four inputs d0..d3 on that z line,
-//     m0 = (d0 - d2) g0      m1 = (d1 + d2)(g0+g1+g2)/2      m2 = (d2 - d1)(g0-g1+g2)/2      m3 = (d1 - d3) g2
-//     y0 = m0 + m1 + m2      y1 = m1 - m2 - m3
-// i.e. 4 multiplies instead of 6 per (dy, dx, cin, cout): the MFMA work of a 3x3x3 layer drops by 1.5x.  All of
-// it is linear, so the four M_xi = sum over (dy, dx, cin) of U_xi * V_xi are accumulated by the matrix cores
-// (U_xi: transformed weights, packed by se_conv3d_pack_f32 section C; V_xi: 3 packed adds per lane on the four
-// 16-byte activation fragments it has just read from LDS) and only the epilogue forms y0 / y1.
-// The LDS traffic per MFMA is the same as for the direct form (one ds_read_b128 per 4 MFMAs per operand), the
-// halo tile is the same 6 x 10 x 10, and no transformed tensor is ever materialised.
-//
-// Structure (as conv3d_k7_persistent_kernel): one persistent 512-thread workgroup per CU; a work unit is
-// (32-cout block, 4x8x8 output tile); loop order cout block -> 16-channel chunk -> unit, so the 72 KB of
-// transformed weights of a (block, chunk) are loaded once and the halo tiles are double buffered (one barrier per
-// item).  For cin > 16 the per-chunk results are summed through the output tensor (read y-partial, add, write),
-// prefetched one item ahead; residual add + ReLU happen on the last chunk.
-// Wave w of 8: z pair w>>2 (outputs z = 2*zp, 2*zp+1 of the tile), rows 2*(w&3), 2*(w&3)+1 -> one 16-position tile,
-// 4 xi x 2 cout tiles = 8 accumulators.
+// Structure: one persistent 512-thread workgroup per CU; a work unit is (32-cout block, 4x8x8 output tile); loop order cout block ->
+// 16-channel chunk -> unit, so the 108 KB of transformed weights of a (block, chunk) (se_conv3d_pack_f32 section E) are loaded once
+// per run of units.  For cin > 16 the per-chunk results are summed through the output tensor (read y-partial, add, write), prefetched
+// one item ahead; residual add + ReLU happen on the last chunk.  The arithmetic and the two wave groups are described at the kernel.
 #include "conv3d_plan.h"
 
 #include <type_traits>
@@ -24,9 +13,7 @@
 
 namespace {
 
-constexpr int HZ = 6, HY = 10, HX = 10, HV = HZ * HY * HX;   // halo voxels of a 4x8x8 tile
-[[maybe_unused]] constexpr int TILE_FLOATS = HV * 16;                          // one 16-channel chunk
-[[maybe_unused]] constexpr int PF = (HV * 4 + 511) / 512;                      // 16-byte pieces per thread (5)
+constexpr int HX = 10;   // halo columns of an 8-wide tile row
 
 template <typename F, int... S>
 __device__ __forceinline__ void for_each_index(F&& f, std::integer_sequence<int, S...>) {
@@ -57,38 +44,27 @@ struct WinoIter {   // uniform walk over this workgroup's items: runs of units w
     bool valid;
 };
 
-#ifdef SE_DEVTOOLS   // retired A/B variants: F(2,3) 3^3 kernel, F(2,7) 7^3 kernels (single-phase and ping-pong)
-#include "devtools/wino_f23_f27_kernels.inc"
-#endif  // SE_DEVTOOLS (retired F(2,3) / F(2,7) kernels)
 // ------------------------------------------------------------------------------------------------
 // 3x3x3 convolution with 1-D Winograd F(4,3) along z: 6 multiplies per 4 z-neighbouring outputs instead of 12
-// -> HALF the MFMAs of the direct form (F(2,3) above: 2/3).  Lavin-Gray matrices, points {0, +-1, +-2, inf}:
+// -> HALF the MFMAs of the direct form.  Lavin-Gray matrices, points {0, +-1, +-2, inf}:
 //   B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
 //   A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]          (G is folded into the packed weights)
 // A 4x8x8 output tile is exactly one z quad; its 6 raw input slabs become 6 transformed slabs V_xi when the halo is
 // committed to LDS (B^T applied once per element, as in the 7^3 kernel), so the inner loop is LDS reads + MFMAs only.
-// LDS: 108 KB transformed weights of one (32-cout block, 16-channel chunk) + ONE 6 x 10 x 10 x 16-channel V tile
-// (38.4 KB).  Wave w of 8: 16 positions (rows 2(w&3), +1), cout tile w>>2 -> 6 accumulators (one per xi).
-// fp32 error of the transform ~4e-7 mean / 5e-6 max per 3-tap dot product (tools/wino_matrices.py).
-// ------------------------------------------------------------------------------------------------
-constexpr int W43_FLOATS = SE_WINO43_CHUNK_FLOATS;
-[[maybe_unused]] constexpr int V43_FLOATS = 6 * HY * HX * 16;
-
-#ifdef SE_DEVTOOLS   // retired A/B variant: single-phase form of the F(4,3) kernel
-#include "devtools/wino_f43_single_phase_kernel.inc"
-#endif  // SE_DEVTOOLS (single-phase F(4,3) kernel)
-
-// ------------------------------------------------------------------------------------------------
-// F(4,3) kernel, "ping-pong" form (production; 4-7 % faster than the single-phase form in one-process A/B runs): the same arithmetic, weights and work units as conv3d_k3_wino43_kernel,
-// but the 8 waves form two groups of 4 (one wave per SIMD each) that work on the two y-halves (4 rows) of every 4x8x8 tile
+// fp32 error of the transform ~4e-7 mean / 5e-6 max per 3-tap dot product (tools/wino43_matrices.py).
+//
+// "Ping-pong" form (4-7 % faster in one-process A/B runs than a single-phase form in which all 8 waves share one whole V tile):
+// the 8 waves form two groups of 4 (one wave per SIMD each) that work on the two y-halves (4 rows) of every 4x8x8 tile
 // HALF A PHASE APART: while group A issues the 216 MFMAs of its half tile, group B runs everything else for its own
 // half — A^T, partial-sum add, epilogue, output stores and the B^T transform + LDS commit of its next half tile — and in the
-// next phase the roles swap.  One workgroup barrier per phase.  In the single-phase kernel all 8 waves do these things at
-// the same time, so the matrix pipe idles through every staging step (MFMA busy 62 % of the launch); here a SIMD always has
-// one wave in its MFMA block.  A lone MFMA wave per SIMD must not issue dependent MFMAs back to back (40-cycle latency vs
-// 32-cycle issue), so two (tap, xi) sub-steps are interleaved on two different accumulators.
+// next phase the roles swap.  One workgroup barrier per phase.  With all 8 waves doing these things at the same time the
+// matrix pipe idles through every staging step (MFMA busy 62 % of the launch); here a SIMD always has one wave in its MFMA
+// block.  In a group, wave wg: cout tile wg>>1, rows 2(wg&1), +1 of the half tile -> 6 accumulators (one per xi).  A lone
+// MFMA wave per SIMD must not issue dependent MFMAs back to back (40-cycle latency vs 32-cycle issue), so two (tap, xi)
+// sub-steps are interleaved on two different accumulators.
 // LDS: 108 KB weights + 2 x 23 KB half V tiles (6 slabs x 6 rows x 10 columns x 16 channels) + unit table.
 // ------------------------------------------------------------------------------------------------
+constexpr int W43_FLOATS = SE_WINO43_CHUNK_FLOATS;
 constexpr int PP_ROWS = 6;                                    // 4 rows + halo
 constexpr int PP_COLS = PP_ROWS * HX;                         // 60 halo columns per half tile
 constexpr int PP_VH_FLOATS = 6 * PP_COLS * 16;                // 5760 floats = 23040 B
@@ -360,8 +336,7 @@ __global__ __launch_bounds__(512) void conv3d_k3_wino43pp_kernel(ConvArgs a, int
 #endif
 }
 
-[[maybe_unused]] unsigned long long* g_wino_dbg = nullptr;
-unsigned long long* g_wino_dbg43 = nullptr;
+unsigned long long* g_wino_dbg43 = nullptr;   // se_debug_set_stamp_buffer: read by the stamp builds (SE_STAMPPP / SE_STAMP47 / SE_STAMP67)
 
 constexpr int LDS43 = 160 * 1024;
 
@@ -375,51 +350,24 @@ int per_wg(int n_units, int num_cus) {
 
 // The unit table (16 B per unit in the LDS left beside weights and tiles) of `kernel` holds a launch of `batch` samples.
 bool se_conv3d_wino1d_fits(int kernel, int batch, int dim, int cout, int num_cus) {
+    if (kernel != SE_CONV_WINO43PP_1D) return false;
     const int total_tiles = batch * (dim / 4) * (dim / 8) * (dim / 8);   // 4 x 8 x 8 output tiles
-    int n_units = (cout / 32) * total_tiles, fixed_floats;              // 3^3: a unit is (tile, 32-cout block);  LDS floats beside the table
-    switch (kernel) {
-        case SE_CONV_WINO43PP_1D: fixed_floats = W43_FLOATS + 2 * PP_VH_FLOATS; break;
-#ifdef SE_DEVTOOLS
-        case SE_CONV_DEV_WINO23_1D: fixed_floats = SE_WINO_CHUNK_FLOATS + 2 * TILE_FLOATS; break;
-        case SE_CONV_DEV_WINO43_1D: fixed_floats = W43_FLOATS + V43_FLOATS; break;
-        case SE_CONV_DEV_K7_WINO27:
-        case SE_CONV_DEV_K7_WINO27PP: n_units = total_tiles; fixed_floats = K7_W_FLOATS + K7_VT_FLOATS; break;
-#endif
-        default: return false;
-    }
+    const int n_units = (cout / 32) * total_tiles;                       // a unit is (tile, 32-cout block)
+    const int fixed_floats = W43_FLOATS + 2 * PP_VH_FLOATS;              // LDS floats beside the table
     return n_units > 0 && per_wg(n_units, num_cus) <= (LDS43 - fixed_floats * 4) / 16;
 }
 
-// The 1-D Winograd 3^3 kernels: the ping-pong F(4,3) kernel (shapes the 2-D kernels do not take, e.g. dim % 16 != 0); development
-// builds add the retired forms (F(2,3): its stamp build if se_debug_set_stamp_buffer gave a buffer; single-phase F(4,3)).
+// The 1-D Winograd 3^3 kernel: ping-pong F(4,3) (shapes the 2-D kernels do not take, e.g. dim % 16 != 0).
 // Preconditions (se_conv3d_plan): se_wino1d_shape_ok, cin_pad == cin, channels-last tensors, no SE_EPI_RES_POST_RELU /
-// SE_EPI_OUT_PLANAR, sections C and E present, se_conv3d_wino1d_fits.
+// SE_EPI_OUT_PLANAR, section E present, se_conv3d_wino1d_fits.
 int se_conv3d_wino1d_launch(const ConvArgs& a, int batch, int kernel, hipStream_t s) {
+    if (kernel != SE_CONV_WINO43PP_1D) return SE_ERR_BAD_ARG;
     const int tiles = a.dim / 8, ztiles = a.dim / 4;
     const int total_tiles = batch * ztiles * tiles * tiles;
     const int n_cb = a.cout / 32;
     const int n_units = n_cb * total_tiles;
     const int per = per_wg(n_units, se_num_cus());
     const dim3 grid((n_units + per - 1) / per);
-#ifdef SE_DEVTOOLS
-    if (kernel == SE_CONV_DEV_WINO23_1D) {
-        SE_ENSURE_LDS(conv3d_k3_wino_kernel<false>, LDS43);
-        SE_ENSURE_LDS(conv3d_k3_wino_kernel<true>, LDS43);
-        if (g_wino_dbg)
-            hipLaunchKernelGGL(conv3d_k3_wino_kernel<true>, grid, dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, n_cb, per, 0, g_wino_dbg);
-        else
-            hipLaunchKernelGGL(conv3d_k3_wino_kernel<false>, grid, dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, n_cb, per, 0, nullptr);
-        SE_CHECK_LAUNCH();
-        return 0;
-    }
-    if (kernel == SE_CONV_DEV_WINO43_1D) {
-        SE_ENSURE_LDS(conv3d_k3_wino43_kernel, LDS43);
-        hipLaunchKernelGGL(conv3d_k3_wino43_kernel, grid, dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, n_cb, per, 0, g_wino_dbg43);
-        SE_CHECK_LAUNCH();
-        return 0;
-    }
-#endif
-    if (kernel != SE_CONV_WINO43PP_1D) return SE_ERR_BAD_ARG;
     SE_ENSURE_LDS(conv3d_k3_wino43pp_kernel, LDS43);
     hipLaunchKernelGGL(conv3d_k3_wino43pp_kernel, grid, dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, n_cb, per, 0, g_wino_dbg43);
     SE_CHECK_LAUNCH();
@@ -427,41 +375,20 @@ int se_conv3d_wino1d_launch(const ConvArgs& a, int batch, int kernel, hipStream_
 }
 
 #ifdef SE_DEVTOOLS
-// Debug only: device buffer (grid * 8 waves * 4 u64) that makes the Winograd kernel run its STAMP build.
-extern "C" void se_debug_set_stamp_buffer(void* p) {
-#if defined(SE_STAMP43) || defined(SE_STAMPPP) || defined(SE_STAMP47) || defined(SE_STAMP67)
-    g_wino_dbg43 = reinterpret_cast<unsigned long long*>(p);
-#else
-    g_wino_dbg = reinterpret_cast<unsigned long long*>(p);
-#endif
-}
+// Debug only: device buffer (u64 [workgroups][8 waves][6]; F(6,7): [8]) that the stamp builds of the kernels launched from this file
+// fill with their cycle sums.  A build without one of those flags never reads it.
+extern "C" void se_debug_set_stamp_buffer(void* p) { g_wino_dbg43 = reinterpret_cast<unsigned long long*>(p); }
 #endif
 
-// The Winograd 7^3 kernels: F(6,7) (conv3d_wino67.hip), F(4,7) per input layout (conv3d_wino47.hip); development builds add the
-// retired F(2,7) kernels.  Preconditions (se_conv3d_plan): se_k7_wino_shape_ok, no residual, channels-last output, sections D and F
-// (F(6,7): H) present, the kernel's _fits; only F(6,7) and F(4,7) read the triplet-planar input.
+// The Winograd 7^3 kernels: F(6,7) (conv3d_wino67.hip), F(4,7) per input layout (conv3d_wino47.hip).
+// Preconditions (se_conv3d_plan): se_k7_wino_shape_ok, no residual, channels-last output, section F (F(6,7): H) present, the
+// kernel's _fits.
 int se_conv3d_k7_wino_launch(const ConvArgs& a, int batch, int kernel, hipStream_t s) {
     const int num_cus = se_num_cus();
     switch (kernel) {
         case SE_CONV_K7_WINO67: return se_conv3d_k7_wino67_launch(a, batch, num_cus, s, g_wino_dbg43);
         case SE_CONV_K7_WINO47_P3: return se_conv3d_k7_wino47_launch_p3(a, batch, num_cus, s, g_wino_dbg43);
         case SE_CONV_K7_WINO47_CL: return se_conv3d_k7_wino47_launch_cl(a, batch, num_cus, s, g_wino_dbg43);
-#ifdef SE_DEVTOOLS
-        case SE_CONV_DEV_K7_WINO27:
-        case SE_CONV_DEV_K7_WINO27PP: {
-            const int tiles = a.dim / 8, ztiles = a.dim / 4;
-            const int total_tiles = batch * ztiles * tiles * tiles;
-            const int per = per_wg(total_tiles, num_cus);
-            SE_ENSURE_LDS(conv3d_k7_wino_kernel, LDS43);
-            SE_ENSURE_LDS(conv3d_k7_winopp_kernel, LDS43);
-            if (kernel == SE_CONV_DEV_K7_WINO27)
-                hipLaunchKernelGGL(conv3d_k7_wino_kernel, dim3((total_tiles + per - 1) / per), dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, per);
-            else
-                hipLaunchKernelGGL(conv3d_k7_winopp_kernel, dim3((total_tiles + per - 1) / per), dim3(512), LDS43, s, a, tiles, ztiles, total_tiles, per);
-            SE_CHECK_LAUNCH();
-            return 0;
-        }
-#endif
         default: return SE_ERR_BAD_ARG;
     }
 }

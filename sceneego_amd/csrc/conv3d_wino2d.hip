@@ -600,9 +600,6 @@ __global__ __launch_bounds__(512) void conv3d_k3_wino2d_kernel(ConvArgs a, const
         for_each_idx(group, std::make_integer_sequence<int, 18>{});
     };
 
-#ifdef SE_DEVTOOLS
-#include "devtools/wino2d_lockstep.inc"      // experiment (exp & 0x200000): both waves of a SIMD in the same phase, no ping-pong
-#endif
     // ---- prologue: each group's V tile of step 0; weight half 0 of step 0 (by group 1's threads - half 1 of step 0 is written by
     // group 0 inside its first MFMA phase) ----
     fetch_setup(ucur);
@@ -762,7 +759,6 @@ int se_conv3d_wino2d_launch(const ConvArgs& a, int batch, int form, int exp, hip
             case 57: W2_VAR(0x20000); break; // attribution: no skip-tensor loads
             case 58: W2_VAR(0x40000); break; // attribution: no output stores
             case 60: W2_VAR(0x100000); break; // experiment: LDS-counter group barriers + cross-group waits instead of workgroup barriers
-            case 61: W2_VAR(0x200000); break; // experiment (round 3): lockstep form, no ping-pong
             default: W2_VAR(0); break;
         }
 #undef W2_VAR

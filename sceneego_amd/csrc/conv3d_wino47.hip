@@ -1,5 +1,5 @@
 // 7x7x7 convolution (V2V front layer, cout = 16) with the 1-D Winograd transform F(4,7) along z on the f32 MFMA (production):
-// 10 multiplies per 4 z-neighbouring outputs instead of 28 — 1.6x fewer MFMAs than the F(2,7) kernel in conv3d_wino.hip, 2.8x
+// 10 multiplies per 4 z-neighbouring outputs instead of 28 — 1.6x fewer MFMAs than the F(2,7) form (16 per 4 outputs), 2.8x
 // fewer than the direct form.  Points {0, +-1, +-2, +-1/2, +-3/4, inf} (tools/wino47_matrices.py -> wino47_matrices.h); float32
 // error of the transform on N(0,1) data: 3.6e-6 mean, 3.2e-5 max per 7-tap dot product (F(2,7): 8.6e-7 / 8.2e-6; direct float32:
 // 1.4e-7 / 7.8e-7).  Replaces Basic3DBlock(33, 16, 7) of network/v2v.py:75-77 (conv + folded BN + ReLU).

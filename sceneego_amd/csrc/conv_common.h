@@ -38,9 +38,8 @@ inline bool se_k7_wino_shape_ok(int dim, int cout) { return dim >= 16 && (dim & 
 struct ConvArgs {
     const float* in;
     const float* wpack;    // section A
-    const float* wpack_b = nullptr;  // k = 7: section B;  k = 3: section C (NULL when absent, as every section pointer below)
+    const float* wpack_b = nullptr;  // section B (NULL when absent, as every section pointer below)
     const float* wpack_e = nullptr;  // section E
-    const float* wpack_d = nullptr;  // section D
     const float* wpack_f = nullptr;  // section F
     const float* wpack_h = nullptr;  // section H
     const float* wpack_i = nullptr;  // section I
@@ -62,13 +61,10 @@ struct ConvArgs {
     long long ws_elems = 0;
 };
 
-// Points a call's section pointers at the sections its packed buffer has (NULL where the layout has none).  wpack_b has two meanings:
-// section B of a 7^3 layer (the LDS-tiled kernel reads it), section C of a 3^3 layer (the retired F(2,3) kernel of development
-// builds reads it); no layer has both.
+// Points a call's section pointers at the sections its packed buffer has (NULL where the layout has none).
 inline void se_conv_args_set_sections(ConvArgs& a, const float* wpack, const SePackLayout& l) {
     a.wpack = wpack;
-    a.wpack_b = l.section(wpack, l.at[SE_PACK_B] >= 0 ? SE_PACK_B : SE_PACK_C);
-    a.wpack_d = l.section(wpack, SE_PACK_D);
+    a.wpack_b = l.section(wpack, SE_PACK_B);
     a.wpack_e = l.section(wpack, SE_PACK_E);
     a.wpack_f = l.section(wpack, SE_PACK_F);
     a.wpack_g = l.section(wpack, SE_PACK_G);

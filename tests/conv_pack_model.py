@@ -5,10 +5,9 @@ csrc/conv3d_pack.h and independent of its code: for every element of every secti
 Sections (all index lists are C order, the last index runs fastest; lane = 16 * h + c16):
   A  [cin_pad/16 cg][tap][nt][lane][j 4]           W[16 nt + c16][16 cg + 4 h + j][tap]
   B  [cin_pad/4 ch][g 86][nt][lane][j 4]           W[16 nt + c16][4 ch + j][tap 4 g + h], tap 343 is padding
-  C  [cg][cb][tap2d 9][xi 4][nt2 2][lane][j 4]     F(2,3) along z of W[32 cb + 16 nt2 + c16][16 cg + 4 h + j][. , tap2d]
-  D  [cin_pad/4 ch][g 13][xi 8][lane][j 4]         F(2,7) along z of W[c16][4 ch + j][. , tap2d 4 g + h], taps >= 49 padding
-  E  as C with xi 6                                F(4,3) along z
-  F  [ceil(cin_pad/3) ch][g 13]{[lane][xi 0..3][j 3], [lane][xi 4..7][j 3], [lane][xi 8..9][j 3]}   F(4,7) of W[c16][3 ch + j][. , 4 g + h]
+  E  [cg][cb][tap2d 9][xi 6][nt2 2][lane][j 4]     F(4,3) along z of W[32 cb + 16 nt2 + c16][16 cg + 4 h + j][. , tap2d]
+  F  [ceil(cin_pad/3) ch][g 13]{[lane][xi 0..3][j 3], [lane][xi 4..7][j 3], [lane][xi 8..9][j 3]}   F(4,7) of W[c16][3 ch + j][. , tap2d 4 g + h],
+                                                   taps >= 49 padding
   G  [cb][cin_pad/8 ch][xi_z 6][q 2][dx 3][ct 2][lane][e 2][c 2]   (F(4,3) over dz) x (F(2,3) over dy), xi_y = 2 q + e,
                                                    of W[32 cb + 16 ct + c16][8 ch + 2 h + c][., ., dx]
   H  [ceil(cin_pad/3) ch][g 37][lane][xi 12]       F(6,7) along z; slot 4 g + h = channel * 49 + tap2d, slot 147 padding
@@ -44,10 +43,9 @@ def _pm(*ps):
 G23 = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=np.float64)
 G43 = np.array([[Fr(1, 4), 0, 0], [Fr(-1, 6)] * 3, [Fr(-1, 6), Fr(1, 6), Fr(-1, 6)], [Fr(1, 24), Fr(1, 12), Fr(1, 6)],
                 [Fr(1, 24), Fr(-1, 12), Fr(1, 6)], [0, 0, 1]], dtype=np.float64)
-G27 = cook_toom_G(_pm(Fr(1), Fr(2), Fr(1, 2)), 7)                       # points {0, 1, -1, 2, -2, 1/2, -1/2, inf}
 G47 = cook_toom_G(_pm(Fr(1), Fr(2), Fr(1, 2), Fr(3, 4)), 7)             # points 0, +-1, +-2, +-1/2, +-3/4, inf
 G67 = cook_toom_G(_pm(Fr(1), Fr(3, 4), Fr(3, 2), Fr(1, 3), Fr(5, 2)), 7)  # points 0, +-1, +-3/4, +-3/2, +-1/3, +-5/2, inf
-assert G43.shape == (6, 3) and G27.shape == (8, 7) and G47.shape == (10, 7) and G67.shape == (12, 7)
+assert G43.shape == (6, 3) and G47.shape == (10, 7) and G67.shape == (12, 7)
 
 
 def round_up(v, m):
@@ -62,11 +60,9 @@ def section_sizes(cout, cin_pad, k, transposed):
     if not transposed and k == 7:
         s["B"] = (cin_pad // 4) * 86 * nts * 256
         if cout <= 16:
-            s["D"] = (cin_pad // 4) * 13 * 8 * 256
             s["F"] = round_up(cin_pad, 3) // 3 * 13 * 10 * 64 * 3
             s["H"] = round_up(cin_pad, 3) // 3 * 37 * 64 * 12
     if not transposed and k == 3 and cout % 32 == 0:
-        s["C"] = (cin_pad // 16) * cb * 9 * 4 * 2 * 256
         s["E"] = (cin_pad // 16) * cb * 9 * 6 * 2 * 256
         s["G"] = cb * (cin_pad // 8) * 6 * 2 * 3 * 2 * 64 * 2 * 2
         s["I"] = cb * (cin_pad // 4) * 9 * 3 * 2 * 256
@@ -130,16 +126,10 @@ def _section(c, name):
         h, c16 = _lane(lane)
         tap = 4 * g + h
         return _terms(c, 16 * nt + c16, 4 * ch + j, one, tap[..., None], tap >= 343)
-    if name in "CE":
-        G = G23 if name == "C" else G43
-        cg, b, tap2d, xi, nt2, lane, j = np.indices((cin_pad // 16, cb, 9, len(G), 2, 64, 4))
+    if name == "E":
+        cg, b, tap2d, xi, nt2, lane, j = np.indices((cin_pad // 16, cb, 9, 6, 2, 64, 4))
         h, c16 = _lane(lane)
-        return _terms(c, 32 * b + 16 * nt2 + c16, 16 * cg + 4 * h + j, G[xi], tap2d[..., None] + 9 * np.arange(3))
-    if name == "D":
-        ch, g, xi, lane, j = np.indices((cin_pad // 4, 13, 8, 64, 4))
-        h, c16 = _lane(lane)
-        tap2d = 4 * g + h
-        return _terms(c, c16, 4 * ch + j, G27[xi], tap2d[..., None] + 49 * np.arange(7), tap2d >= 49)
+        return _terms(c, 32 * b + 16 * nt2 + c16, 16 * cg + 4 * h + j, G43[xi], tap2d[..., None] + 9 * np.arange(3))
     if name == "F":
         parts = []
         for xi0, nxi in ((0, 4), (4, 4), (8, 2)):

@@ -53,7 +53,7 @@ def test_the_chain_length_mirrors_the_header():
     with open(os.path.join(os.path.dirname(GOLD), "..", "include", "sceneego_hip.h")) as f:
         text = f.read()
     assert "#define SE_SK_MOMENT_CHAIN(G) (18 + ((G) * (((G) + 15) / 16) * (((G) + 63) / 64) + 63) / 64)" in text
-    assert _lib.MOMENT_CHAIN(64) == 22 and _lib.MOMENT_CHAIN(128) == 50 and _lib.MOMENT_CHAIN(6) == 19 and _lib.ABI_VERSION == 39
+    assert _lib.MOMENT_CHAIN(64) == 22 and _lib.MOMENT_CHAIN(128) == 50 and _lib.MOMENT_CHAIN(6) == 19 and _lib.ABI_VERSION >= 39
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. the moments

@@ -1,6 +1,10 @@
 """A/B timing of se_conv3d_f32 variants on the GPU (interleaved rounds in one process, guide rule 24).
 
-usage: python tools/bench_conv.py [--batch 8] [--rounds 10]
+usage: python tools/bench_conv.py [--batch 8] [--rounds 10] [--variants 0,30,...]
+
+Variants other than 0 are se_debug_set_variant numbers (include/sceneego_hip.h lists them) and need the development library: run
+sceneego_amd/csrc/build.sh --devtools first and set SCENEEGO_HIP_LIB=sceneego_amd/libsceneego_hip_dev.so; the production library
+has no selector and times its own dispatch for every number.
 """
 import argparse
 import os
@@ -32,7 +36,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=10)
-    ap.add_argument("--variants", default="0,1")
+    ap.add_argument("--variants", default="0,1", help="se_debug_set_variant numbers (development library), timed in interleaved rounds")
     ap.add_argument("--no-res", action="store_true")
     ap.add_argument("--only", type=int, default=-1, help="index into SHAPES")
     ap.add_argument("--octet", type=int, default=0, help="extra flags for 2-D Winograd shapes: 1 = IN_OCTET, 2 = OUT_OCTET, 3 = both (timing only)")

@@ -1,3 +1,5 @@
+"""Diagnostic: experiment 60 of conv3d_k3_wino2d_kernel against the production instance, bit for bit (needs the development library:
+sceneego_amd/csrc/build.sh --devtools, run with SCENEEGO_HIP_LIB=sceneego_amd/libsceneego_hip_dev.so)."""
 import os, sys, torch
 sys.path.insert(0, os.getcwd())
 from sceneego_amd import _lib

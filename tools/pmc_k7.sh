@@ -1,5 +1,6 @@
 #!/bin/bash
-# clock and MFMA-busy of the 7^3 Winograd kernels under the conv micro-benchmark ($1 = variant: 0 = F(4,7), 17 = F(2,7))
+# clock and MFMA-busy of the 7^3 Winograd kernels under the conv micro-benchmark ($1 = variant: 0 = F(6,7), 47 = F(4,7); the
+# variant needs the development library: sceneego_amd/csrc/build.sh --devtools, SCENEEGO_HIP_LIB=sceneego_amd/libsceneego_hip_dev.so)
 export TMPDIR=/tmp
 V=${1:-0}
 for pass in "GRBM_GUI_ACTIVE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES" "SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do

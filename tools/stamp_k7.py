@@ -1,4 +1,5 @@
-"""Diagnostic: phase timing of the F(4,7) 7^3 kernel (needs sceneego_amd/csrc/build.sh -DSE_STAMP47)."""
+"""Diagnostic: phase timing of the F(4,7) 7^3 kernel (needs sceneego_amd/csrc/build.sh --devtools -DSE_STAMP47, run with
+SCENEEGO_HIP_LIB=sceneego_amd/libsceneego_hip_dev.so)."""
 import ctypes, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 from sceneego_amd import _lib

@@ -1,4 +1,5 @@
-"""Diagnostic: phase timing of the ping-pong F(4,3) kernel (needs sceneego_amd/csrc/build.sh -DSE_STAMPPP)."""
+"""Diagnostic: phase timing of the ping-pong F(4,3) kernel (needs sceneego_amd/csrc/build.sh --devtools -DSE_STAMPPP, run with
+SCENEEGO_HIP_LIB=sceneego_amd/libsceneego_hip_dev.so)."""
 import ctypes, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 from sceneego_amd import _lib
@@ -9,7 +10,7 @@ conv = torch.nn.Conv3d(cin, cout, 3, padding=1).to(dev)
 pc = _PackedConv(conv, None)
 x = torch.randn(B, dim, dim, dim, cin, device=dev); res = torch.randn(B, dim, dim, dim, cout, device=dev)
 out = torch.empty_like(res)
-lib.se_debug_set_variant(19)
+lib.se_debug_set_variant(30)       # 1-D F(4,3) where production runs a 2-D Winograd kernel
 dbg = torch.zeros(256 * 8 * 6, dtype=torch.int64, device=dev)
 for _ in range(3):
     _lib.conv3d(x, pc.w, pc.b, res, out, B, dim, cin, cin, cout, 3, 3, None)
