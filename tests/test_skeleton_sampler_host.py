@@ -47,9 +47,11 @@ def case(tree, floor, asym=False, frames=1, scale=1.0):
     return {"parents": parents, "J": J, "p": p, "w": w, "A64": A64, "A": A64.astype(np.float32), "s": s}
 
 
-def law_error(k, floor, taps, exact=False):
+def law_error(k, floor, taps, exact=False, G=G, R=R):
     """Worst |model's probabilities - A_c(y) F_c(x, y) / sum_y|, as a share of the peak, over every edge and parent voxel, and the
-    root's against A_0 / sum.  ``taps``: the blocks handed to the MODEL; the reference uses the case's own."""
+    root's against A_0 / sum.  ``taps``: the blocks handed to the MODEL; the reference uses the case's own.  ``G``, ``R``: another
+    grid than this file's (tests/test_path_sampler_domain_host.py takes it at 3^3)."""
+    N = G ** 3
     A = k["A64"][0] if exact else k["A"][0]
     worst = 0.0
     root = A[0].astype(np.float64)

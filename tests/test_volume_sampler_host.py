@@ -40,12 +40,25 @@ def case(floor, asym=False, frames=T):
     return {"p": p, "c": c, "w": w, "b": b.astype(np.float32), "rs": rs}
 
 
-def dense_transition(w, floor):
+def dense_transition(w, floor, grid=G):
     """D[x, y] = keep W(x -> y) + uniform, W from blur3 itself: column m of K is blur3 of the unit vector at m, so K[y, x] is the weight
-    with which b(x) enters q(y).  keep and uniform are the definition's: formed in float32 as the filter's kernels form them."""
-    K = np.stack([blur3(np.eye(N)[m][None], w, G)[0] for m in range(N)], axis=1)
-    keep, uniform = constants(floor, N)
+    with which b(x) enters q(y).  keep and uniform are the definition's: formed in float32 as the filter's kernels form them.
+    ``grid``: another grid than this file's (tests/test_path_sampler_domain_host.py takes it at 3^3)."""
+    n = grid ** 3
+    K = np.stack([blur3(np.eye(n)[m][None], w, grid)[0] for m in range(n)], axis=1)
+    keep, uniform = constants(floor, n)
     return keep * K.T + uniform
+
+
+def conditional_law_error(b, w, floor, grid=G):
+    """Worst |conditional_law - b(x) D[x, y] normalised| as a share of the peak, over every y, for one belief ``b`` [grid^3] float32."""
+    D = dense_transition(w, floor, grid)
+    worst = 0.0
+    for y in range(grid ** 3):
+        want = b.astype(np.float64) * D[:, y]
+        want /= want.sum()
+        worst = max(worst, float(np.abs(conditional_law(b, y, w, grid, floor) - want).max() / want.max()))
+    return worst
 
 
 def bound(prob):
