@@ -25,6 +25,9 @@ predicted skeleton against the scene of its own depth map (``sceneego_amd/scene_
 ``DIR/<img_name>.constraint.pkl``: free_mass, moved, constrained, the free peak, ... of every joint.
 ``--modes true [--modes_k 4]`` writes ``<img_name>.modes.pkl`` beside each ``<img_name>.pkl``: the strongest peaks of every joint's
 volume with their mass and sub-voxel centroid (``VoxelNetwork_depth.joint_modes``); ``evaluate.py --modes`` reads them.
+``--scene_field true`` writes ``<img_name>.scene_field.pkl`` beside each ``<img_name>.pkl``: contact probability, blocked probability
+and expected distance to the scene of every joint's volume (``VoxelNetwork_depth.scene_expectations``: the volumes against the distance
+field of the frame's depth map on the voxel grid; distances are quantised to voxel centres, the contact radii are conventions).
 """
 import argparse
 import os
@@ -36,7 +39,7 @@ import torch
 from sceneego_amd import load_config, synth
 from sceneego_amd.jpeg_device import JpegFile, decode_jpeg_batch
 from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
-                             skeleton_couple_to_numpy)
+                             scene_field_to_numpy, skeleton_couple_to_numpy)
 from sceneego_amd.preprocess import (DEPTH_CLAMP, load_depth, load_image_bgr, prepare_depth, preprocess_image,
                                      preprocess_image_device)
 from sceneego_amd.voxel_net_depth import VoxelNetwork_depth
@@ -49,7 +52,7 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 class Demo:
     def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False,
                  render_format="png", render_volumes=False, volume_joints=None, save_volumes=None, constrain=False, modes=0,
-                 bone_lengths=None):
+                 bone_lengths=None, scene_field=False):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
@@ -66,6 +69,7 @@ class Demo:
         self.save_volumes = save_volumes
         self.scene_check = scene_check
         self.constrain = constrain
+        self.scene_field = scene_field
         self.modes = int(modes)                # modes kept per joint; 0: off
         self.bone_lengths = bone_lengths       # 14 or 15 metres: couple the joints over the skeleton (--skeleton_dir); None: off
         self.skeleton = None
@@ -124,6 +128,9 @@ class Demo:
                 if self.constrain:
                     # likewise before the next frame: the volumes are the graph's static buffers
                     results[-1]["constraint"] = scene_constraint_to_numpy(self.network.constrain_to_scene(volumes, kp, depth))[0]
+                if self.scene_field:
+                    # likewise before the next frame
+                    results[-1]["scene_field"] = scene_field_to_numpy(self.network.scene_expectations(volumes, depth=depth))[0]
                 if self.modes:
                     # likewise before the next frame
                     results[-1]["modes"] = joint_modes_to_numpy(self.network.joint_modes(volumes, k=self.modes))[0]
@@ -203,6 +210,9 @@ def build_parser():
     ap.add_argument("--constrained_dir", type=str, default=None,
                     help="also write <img_name>.pkl here: the joints re-estimated over the free space in front of the depth surface "
                          "(float32 [15,3], readable by evaluate.py --pred_dir), and <img_name>.constraint.pkl (free_mass, moved, ...)")
+    ap.add_argument("--scene_field", type=str, default="false",
+                    help="true: also write <img_name>.scene_field.pkl (contact_prob, contact_free_prob, blocked_prob, expected_distance, "
+                         "expected_free_distance, mass, radii2 of every joint's volume against the depth map's scene on the voxel grid)")
     ap.add_argument("--modes", type=str, default="false",
                     help="true: also write <img_name>.modes.pkl (the strongest peaks of every joint's volume: coord, peak_coord, "
                          "peak_prob, mass, index, count, total, valid)")
@@ -230,7 +240,7 @@ def parse_args(argv=None):
     args.scene_check = args.scene_check.lower() == "true"
     if not 1 <= args.modes_k <= 16:
         raise SystemExit("--modes_k must be in 1..16")
-    for flag in ("render_volumes", "save_volumes", "modes"):
+    for flag in ("render_volumes", "save_volumes", "modes", "scene_field"):
         if getattr(args, flag).lower() not in ("true", "false"):
             raise SystemExit(f"--{flag} must be true or false")
         setattr(args, flag, getattr(args, flag).lower() == "true")
@@ -253,7 +263,7 @@ def main(argv=None):
                 scene_check=args.scene_check, render_format=args.render_format, render_volumes=args.render_volumes,
                 volume_joints=args.volume_joints, save_volumes=args.output_dir if args.save_volumes else None,
                 constrain=args.constrained_dir is not None, modes=args.modes_k if args.modes else 0,
-                bone_lengths=np.load(args.bone_lengths) if args.bone_lengths is not None else None)
+                bone_lengths=np.load(args.bone_lengths) if args.bone_lengths is not None else None, scene_field=args.scene_field)
     os.makedirs(args.output_dir, exist_ok=True)
     if args.constrained_dir is not None:
         os.makedirs(args.constrained_dir, exist_ok=True)
@@ -271,6 +281,9 @@ def main(argv=None):
         if args.scene_check:
             with open(out_path[:-4] + ".scene.pkl", "wb") as f:
                 pickle.dump(r["scene"], f)                # dict of numpy arrays, the keys of SceneConsistency.check
+        if args.scene_field:
+            with open(out_path[:-4] + ".scene_field.pkl", "wb") as f:
+                pickle.dump(r["scene_field"], f)          # dict of numpy arrays, the keys of op.EXPECT_KEYS and radii2
         if args.constrained_dir is not None:
             c = dict(r["constraint"])
             name = os.path.join(args.constrained_dir, os.path.split(r["img_path"])[1])

@@ -642,6 +642,65 @@ int se_softargmax3d_masked_f32(const float* prob, const float* coord, const unsi
                                float* scratch, int rows, int rows_per_frame, int voxels, void* stream);
 long long se_softargmax3d_masked_scratch_elems(int rows);
 
+/* Scene distance field (no counterpart in the reference; sceneego_amd/scene_field.py: SceneField; sceneego_amd/op.py: scene_sites,
+ * scene_distance, scene_expect, scene_field_lookup; VoxelNetwork_depth.scene_field / scene_expectations drive them): the scene of a
+ * depth map as a field on the network's own G^3 voxel grid - per voxel the exact squared distance, in voxel index units, to the
+ * nearest voxel that holds scene, and that voxel's flat index - and any [rows][voxels] distribution reduced against it.  Flat index
+ * n = (i G + j) G + k as everywhere.  tests/scene_field_model.py restates all three.
+ *
+ * SITES, se_scene_sites_u8:  depth [B][depth_h][depth_w] float32 metres     ray_tab [height][width][3] float64 (the table of
+ *   se_scene_probe_f64)     sites [B][G^3] uint8, cleared inside (one memset node on `stream`, then one launch).
+ *   The SCENE POINTS are exactly those of se_scene_probe_f64: pixel n = y * width + x, d = depth[b][(y * depth_h) / height]
+ *   [(x * depth_w) / width] (integer division); the pixel has a surface iff d > 0 && d <= max_depth (a NaN fails); s = ray * (double)d
+ *   per component; it is a scene point iff it has a surface and s.z > min_z.  A pixel whose ray has a non-finite component takes part
+ *   in nothing.  Voxel centres follow build_coord_volume: their spacing is side / (G - 1).  In float64, unfused, in this order:
+ *     qx = rint(((s.x + side / 2) * (G - 1)) / side)      qy likewise from s.y      qz = rint((s.z * (G - 1)) / side)
+ *   with rint rounding half to even.  A point with 0 <= qx, qy, qz <= G - 1 (a NaN or an infinity fails) marks
+ *   sites[b][(qx G + qy) G + qz] = 1; any other point marks nothing.  Every writer stores the same byte with an ordinary store: the
+ *   result does not depend on the write order, and there are no atomics.  One right answer, bit for bit.
+ *   SE_ERR_BAD_ARG: a null pointer, batch outside 1..65535, a non-positive size, height * width above 0x7fff0000, grid outside
+ *   2..1024, side <= 0, infinite or NaN, min_z < 0 or NaN, max_depth <= 0 or NaN.
+ *
+ * DISTANCE, se_scene_distance_i32:  sites [B][G^3] uint8, any non-zero byte is a SITE; 2 <= G <= 128.
+ *   d2 [B][G^3] int32 = min over the frame's sites m of |n - m|^2 = (i - i')^2 + (j - j')^2 + (k - k')^2, in integers (at most
+ *   3 * 127^2 = 48 387);   nearest [B][G^3] int32 = the flat index of the site that minimises the key (|n - m|^2, m) taken
+ *   lexicographically: among the sites at the least distance, the lowest index.  A frame without a site: d2 = 0x7fffffff and
+ *   nearest = -1 at every voxel.  scratch: se_scene_distance_scratch_bytes(batch, grid) bytes of device workspace, 8-byte aligned
+ *   (-1: bad shape).  Two launches: passes k and j of a separable transform per (frame, i) slab in LDS, pass i per (frame, j, 32 k)
+ *   tile; each pass is the plain minimum of the key over the G candidates of a grid line, the candidate's d2 raised by the squared
+ *   offset along the line.  Integers only, no atomics, nothing allocated (legal inside hipGraph capture): one right answer, bit for
+ *   bit, the same from run to run.
+ *   SE_ERR_BAD_ARG: a null pointer, batch outside 1..65535, grid outside 2..128, scratch_bytes too small, a scratch that is not
+ *   8-byte aligned, a d2 / nearest that is not 4-byte aligned.
+ *
+ * EXPECTATION, se_scene_expect_f32, per row r = b * rows_per_frame + j:
+ *   prob [rows][voxels] float32     d2 [rows / rows_per_frame][voxels] int32, as se_scene_distance_i32 writes it
+ *   free_mask [rows / rows_per_frame][voxels] uint8, as se_scene_free_mask_u8 writes it (any non-zero byte is free, 0 is BLOCKED)
+ *   radii2 [K] int32 on the device, 1 <= K <= 8, ascending by convention (the sums do not depend on their order)
+ *   out [rows][24] float32, NOT divided (the kernel does no division):
+ *     0          sum_n p_n
+ *     1          sum_n p_n [blocked_n]
+ *     2          sum_n p_n * sqrtf((float)d2_n) over the voxels with d2_n != 0x7fffffff (they have a nearest site); the product is
+ *                rounded to float32, then added (unfused)
+ *     3          slot 2 over the free voxels alone
+ *     4 + k      sum_n p_n [d2_n <= radii2[k]], k < K (a voxel without a nearest site counts when radii2[k] is 0x7fffffff)
+ *     12 + k     slot 4 + k over the free voxels alone
+ *     the rest   0
+ *   scratch: se_scene_expect_scratch_elems(rows) floats of workspace.
+ * A row that holds a NaN probability (free or blocked) gets 24 NaNs; other rows are unaffected.  Two launches on `stream`
+ * (se_sa_splits(rows) chunks per row as the soft-argmax, then one wave per row), a fixed reduction order and no atomics: bitwise
+ * identical from run to run.  Allocates nothing (legal inside hipGraph capture).  rows <= 0, rows > 65535, rows_per_frame <= 0,
+ * rows % rows_per_frame, voxels <= 0, voxels & 3, n_radii outside 1..8, a null pointer, a prob / d2 that is not 16-byte aligned or a
+ * free_mask / radii2 that is not 4-byte aligned -> SE_ERR_BAD_ARG.                                                                  */
+int se_scene_sites_u8(const float* depth, const double* ray_tab, unsigned char* sites, int batch, int depth_h, int depth_w, int height,
+                      int width, int grid, double side, double min_z, double max_depth, void* stream);
+long long se_scene_distance_scratch_bytes(int batch, int grid);
+int se_scene_distance_i32(const unsigned char* sites, int* d2, int* nearest, void* scratch, long long scratch_bytes, int batch,
+                          int grid, void* stream);
+long long se_scene_expect_scratch_elems(int rows);
+int se_scene_expect_f32(const float* prob, const int* d2, const unsigned char* free_mask, const int* radii2, float* out, float* scratch,
+                        int rows, int rows_per_frame, int voxels, int n_radii, void* stream);
+
 /* Multi-hypothesis joints (no counterpart in the reference; sceneego_amd/op.py: joint_modes; VoxelNetwork_depth.joint_modes drives
  * it): the K strongest local maxima (modes) of every softmaxed joint volume, each with the mass and the first moments of its
  * neighbourhood.  One right answer, bit for bit (tests/joint_modes_model.py restates it).

@@ -62,6 +62,12 @@ Smoothed beliefs are not rendered: frames are rendered per batch, before the fut
 of that smoother's model (``VolumeSmoother.sample``, seed ``--sample_seed``): index, coord, kind, valid [S,15,...], mean, spread and shift.
 It implies the smoother, draws before the smoother finishes, and prints the mean spread and the best-of-N MPJPE (the closest valid sample
 of every joint) beside the smoothed MPJPE.  The samples are from the model's posterior given the volumes read as likelihoods: not calibrated.
+``--scene_field_output sf.pkl [--contact_radii 1,2,3]`` writes a pickle of per-frame dicts of the volumes against the scene distance
+field of each frame's depth map on the voxel grid (``VoxelNetwork_depth.scene_expectations``: contact probability within the radii,
+given in voxel spacings, blocked probability and expected distance of every joint): ``volumes`` for the raw volumes, ``coupled`` and
+``filtered`` for the beliefs of ``--skeleton_output`` / ``--filter_output`` where those are on, and with ``--pose_samples_output``
+``pose_samples``, the sampled poses looked up in the field (``op.scene_field_lookup``); prints ``metrics.scene_field_summary``.
+Distances are quantised to voxel centres and the radii are conventions: nothing is calibrated.
 ``--pose_samples_output`` writes a pickle of per-frame dicts of ``--pose_samples`` (default 16) whole poses drawn from the posterior of
 the skeleton model (``SkeletonPrior.sample``, seed ``--pose_sample_seed``, the frame's number in the sequence as its global index):
 index, coord, kind, valid [S,15,...], bone_error [S,14], mean, spread, sampled and shift.  It uses ``--bone_lengths`` /
@@ -330,7 +336,7 @@ class SequenceRunner:
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
             volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False,
-            smooth=None, path=None, map_pose=None, sample=None, pose_sample=None):
+            smooth=None, path=None, map_pose=None, sample=None, pose_sample=None, scene_field=None):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -357,10 +363,15 @@ class SequenceRunner:
         ``seed`` for ``VolumeSmoother.sample``, drawn once behind the last batch and before ``finish()``; the per-frame sample dicts
         are appended after those.  ``pose_sample``: a dict of ``bone_lengths`` / ``tau`` / ``floor`` / ``samples`` / ``seed``: whole poses
         drawn from the skeleton posterior of every batch's raw volumes (``SkeletonPrior.sample`` with the running frame count as
-        ``first_frame``) on the stream the batch ran on; the per-frame pose-sample dicts are appended last."""
+        ``first_frame``) on the stream the batch ran on; the per-frame pose-sample dicts are appended after those.  ``scene_field``: a dict
+        with ``radii2`` (squared contact radii in voxel spacings, or None for 1, 4, 9): every batch's volumes - and the coupled and filtered
+        beliefs, and the sampled poses, where those are on - against the scene distance field of the batch's depth maps
+        (``VoxelNetwork_depth.scene_expectations``, ``op.scene_field_lookup``) on the stream the batch ran on; the per-frame dicts
+        (``volumes``, ``coupled``, ``filtered``, ``pose_samples``) are appended last."""
         from sceneego_amd.jpeg_device import JpegFile
         from sceneego_amd.op import (joint_modes_to_numpy, joint_statistics_to_numpy, scene_check_to_numpy, scene_constraint_to_numpy,
-                                     skeleton_alternatives_to_numpy, skeleton_couple_to_numpy, skeleton_pose_to_numpy,
+                                     scene_field_lookup, scene_field_to_numpy, skeleton_alternatives_to_numpy,
+                                     skeleton_couple_to_numpy, skeleton_pose_to_numpy,
                                      skeleton_samples_to_numpy, volume_filter_to_numpy, volume_path_to_numpy,
                                      volume_smoother_to_numpy)
         from sceneego_amd.preprocess import load_image_bgr
@@ -379,7 +390,7 @@ class SequenceRunner:
         if render_coupled and (skeleton is None or not render_volumes or render_filtered):
             raise ValueError("render_coupled needs skeleton and render_volumes, and excludes render_filtered")
         sp = self.net.skeleton_prior(**skeleton) if skeleton is not None else None
-        frame_pose_samples = []
+        frame_pose_samples, frame_scene_field = [], []
         psp = self.net.skeleton_prior(**{k: pose_sample[k] for k in ("bone_lengths", "tau", "floor")}) if pose_sample is not None else None
         path_separation = None
         if path is not None:                # "separation": the backward pass too (--path_alternatives_output)
@@ -389,21 +400,35 @@ class SequenceRunner:
         separation = map_pose.get("separation") if map_pose is not None else None
         mpose = self.net.skeleton_pose(**{k: v for k, v in map_pose.items() if k != "separation"}) if map_pose is not None else None
 
-        def couple_and_filter(vol, kp, job, stream=None, first_frame=0):
+        def couple_and_filter(vol, kp, job, stream=None, first_frame=0, net=None, depth=None):
             """The most probable pose and the pose samples (from the raw volumes), the skeleton coupling and the filter of one batch,
-            in that order: (filter dict, skeleton dict, job, pose dict, pose-sample dict).  ``first_frame``: the batch's first frame
-            in the sequence."""
+            in that order: (filter dict, skeleton dict, job, pose dict, pose-sample dict, scene-field dict).  ``first_frame``: the
+            batch's first frame in the sequence.  ``net``, ``depth`` (with ``scene_field``): the module replica and the depth maps of
+            the batch, for the scene field of the raw volumes and of every belief computed here."""
             fr = sk = None
             mp = ps = None
+            sf = expect = None
+            if scene_field is not None:
+                field = net.scene_field(depth)
+
+                def expect(v):
+                    return net.scene_expectations(v, depth=depth, field=field, radii2=scene_field["radii2"])
+                sf = {"volumes": expect(vol)}
             if psp is not None:
                 ps = psp.sample(vol, samples=pose_sample["samples"], seed=pose_sample["seed"], first_frame=first_frame, joints=kp,
                                 stream=stream)
+                if sf is not None:
+                    sf["pose_samples"] = scene_field_lookup(field, sf["volumes"]["free"], ps["index"], radii2=scene_field["radii2"])
             if mpose is not None:                                        # alternatives: the pose with the same bits, and the runner-up
                 mp = mpose.solve(vol, joints=kp, stream=stream) if separation is None else \
                     mpose.alternatives(vol, separation=separation, joints=kp, stream=stream)
             if sp is not None:
-                sk = sp.couple(vol, joints=kp, return_beliefs=vf is not None or vp is not None or (render_coupled and job is not None),
-                               stream=stream)
+                sk = sp.couple(vol, joints=kp, stream=stream, return_beliefs=vf is not None or vp is not None or sf is not None
+                               or (render_coupled and job is not None))
+                if sf is not None:
+                    sf["coupled"] = expect(sk["beliefs"])
+                    if not (vf is not None or vp is not None or (render_coupled and job is not None)):
+                        sk = {k: v for k, v in sk.items() if k != "beliefs"}
                 if vf is not None or vp is not None:
                     vol = sk["beliefs"]
                 if render_coupled and job is not None:
@@ -411,14 +436,19 @@ class SequenceRunner:
             if vf is not None:
                 want_beliefs = render_filtered and job is not None
                 if vs is not None:     # the same dict; the smoother keeps copies of its own, so the beliefs are dropped unless drawn
-                    fr = {k: v for k, v in vs.push(vol, joints=kp, stream=stream).items() if k != "beliefs" or want_beliefs}
+                    fr = vs.push(vol, joints=kp, stream=stream)
                 else:
-                    fr = vf.step(vol, joints=kp, return_beliefs=want_beliefs, stream=stream)
+                    fr = vf.step(vol, joints=kp, return_beliefs=want_beliefs or sf is not None, stream=stream)
+                if sf is not None:
+                    sf["filtered"] = expect(fr["beliefs"])
+                fr = {k: v for k, v in fr.items() if k != "beliefs" or want_beliefs}
                 if "beliefs" in fr:
                     job = job[:-1] + (fr["beliefs"],)
             if vp is not None:             # on the raw volumes, or the coupled beliefs: never on the filter's
                 vp.push(vol, joints=kp, stream=stream)
-            return fr, sk, job, mp, ps
+            if sf is not None:         # the mask is the module's cached buffer, overwritten by the next batch: not kept
+                sf = {k: {n: t for n, t in v.items() if n != "free"} for k, v in sf.items()}
+            return fr, sk, job, mp, ps, sf
 
         rendering = render_dir is not None or render_video is not None
         if rendering:
@@ -434,7 +464,7 @@ class SequenceRunner:
 
         def drain(keep):
             while len(pending) > keep:
-                kp, st, done, job, sc, con, md, fr, sk, mp, ps = pending.pop(0)
+                kp, st, done, job, sc, con, md, fr, sk, mp, ps, sf = pending.pop(0)
                 if done is not None:
                     done.synchronize()
                 kp_host = kp.cpu().numpy()
@@ -457,6 +487,9 @@ class SequenceRunner:
                     frame_map.extend(skeleton_pose_to_numpy(mp) if separation is None else skeleton_alternatives_to_numpy(mp))
                 if ps is not None:
                     frame_pose_samples.extend(skeleton_samples_to_numpy(ps))
+                if sf is not None:
+                    per = {k: scene_field_to_numpy(v) for k, v in sf.items()}
+                    frame_scene_field.extend({k: per[k][b] for k in per} for b in range(len(kp_host)))
                 if job is not None:
                     self._render(job, kp_host)         # the joints of this batch are final here, with any number of streams
 
@@ -481,18 +514,19 @@ class SequenceRunner:
                     if constrain:
                         c = self.net.constrain_to_scene(vol, kp, depth)
                         con = (c, self._scene().check(depth, c["joints"]) if scene else None)
-                    fr, sk, job, mp, ps = couple_and_filter(vol, kp, job, first_frame=i * batch_size)   # before the next forward
+                    fr, sk, job, mp, ps, sf = couple_and_filter(vol, kp, job, first_frame=i * batch_size, net=self.net,
+                                                                depth=depth)                           # before the next forward
                     # overwrites the volumes
                     pending.append((kp, self.net.joint_statistics(vol, kp) if stats else None, None, job,
                                     self._scene().check(depth, kp) if scene else None, con,
-                                    self.net.joint_modes(vol, k=modes) if modes else None, fr, sk, mp, ps))
+                                    self.net.joint_modes(vol, k=modes) if modes else None, fr, sk, mp, ps, sf))
                 else:
                     net, stream = self.pipe.next_slot()
                     (kp, _, vol, _), done = self.pipe(img, self.net.grid_coord_proj_batch, self.net.coord_volumes, depth_map_batch=depth)
                     job = job + (vol,) if job is not None else None       # the slot's buffers: handed back only after drain()
-                    st = sc = con = md = fr = sk = mp = ps = None
+                    st = sc = con = md = fr = sk = mp = ps = sf = None
                     if stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None \
-                            or psp is not None:
+                            or psp is not None or scene_field is not None:
                         # on the stream the batch ran on, with that replica's workspace; `done` moves behind it, so drain() hands the
                         # buffers back only after the statistics are complete
                         with torch.cuda.stream(stream):
@@ -507,10 +541,11 @@ class SequenceRunner:
                                 md = net.joint_modes(vol, k=modes)
                             # one filter for all slots: its own event chain makes this stream wait for the step of the batch before;
                             # one skeleton prior too: it carries no state and keeps one workspace per stream
-                            fr, sk, job, mp, ps = couple_and_filter(vol, kp, job, stream, first_frame=i * batch_size)
+                            fr, sk, job, mp, ps, sf = couple_and_filter(vol, kp, job, stream, first_frame=i * batch_size, net=net,
+                                                                        depth=depth)
                             done = torch.cuda.Event()
                             done.record(stream)
-                    pending.append((kp, st, done, job, sc, con, md, fr, sk, mp, ps))
+                    pending.append((kp, st, done, job, sc, con, md, fr, sk, mp, ps, sf))
                 drain(len(self.pipe) - 1 if self.pipe is not None else 0)
             try:
                 drain(0)
@@ -529,14 +564,15 @@ class SequenceRunner:
         else:
             frame_path = volume_path_to_numpy(vp.finish()) if vp is not None else None
         if not (stats or scene or constrain or modes or vf is not None or sp is not None or vp is not None or mpose is not None
-                or psp is not None):
+                or psp is not None or scene_field is not None):
             return preds
         return (preds,) + ((frame_stats,) if stats else ()) + ((frame_scene,) if scene else ()) \
             + ((frame_constraint,) if constrain else ()) + ((frame_scene_constrained,) if constrain and scene else ()) \
             + ((frame_modes,) if modes else ()) + ((frame_filter,) if vf is not None else ()) \
             + ((frame_skeleton,) if sp is not None else ()) + ((frame_smooth,) if vs is not None else ()) \
             + ((frame_path,) if vp is not None else ()) + ((frame_map,) if mpose is not None else ()) \
-            + ((frame_samples,) if sample is not None else ()) + ((frame_pose_samples,) if psp is not None else ())
+            + ((frame_samples,) if sample is not None else ()) + ((frame_pose_samples,) if psp is not None else ()) \
+            + ((frame_scene_field,) if scene_field is not None else ())
 
 
 def _size(text):
@@ -621,6 +657,12 @@ def build_parser():
                     "the skeleton model (SkeletonPrior.sample: index, coord, kind, valid [S,15,...], bone_error [S,14], mean, spread, "
                     "sampled, shift); implies the skeleton model options --bone_lengths / --bone_frames, --skeleton_tau, "
                     "--skeleton_floor, and the fitted values with --skeleton_fit_frames; samples of the model's posterior, not calibrated")
+    ap.add_argument("--scene_field_output", default=None, help="pickle of the per-frame dicts of the volumes against the scene distance "
+                    "field of the frame's depth map (volumes, and coupled / filtered / pose_samples where those options are on: "
+                    "contact_prob, contact_free_prob, blocked_prob, expected_distance, expected_free_distance, mass, radii2; distances are "
+                    "quantised to voxel centres, the radii are conventions, not calibrated)")
+    ap.add_argument("--contact_radii", default=None, help="with --scene_field_output: 1..8 ascending contact radii in voxel spacings, "
+                    "e.g. 1,2,3 (the default)")
     ap.add_argument("--pose_samples", type=int, default=None, help="with --pose_samples_output: poses per frame (default 16)")
     ap.add_argument("--pose_sample_seed", type=int, default=None, help="with --pose_samples_output: the seed, 0..2^64-1 (default 0)")
     ap.add_argument("--path_output", default=None, help="pickle in the format of --output holding the joints of the most probable "
@@ -888,6 +930,20 @@ def main(argv=None):
         for model in (args.filter, args.path):
             if model is not None:
                 model.update(fitted)
+    scene_field = None
+    if args.scene_field_output is not None:
+        radii2 = None
+        if args.contact_radii is not None:
+            try:
+                spacings = [float(v) for v in args.contact_radii.split(",")]
+            except ValueError:
+                raise SystemExit("--contact_radii must be a comma-separated list of radii in voxel spacings, e.g. 1,2,3")
+            if not 1 <= len(spacings) <= 8 or spacings != sorted(spacings) or spacings[0] < 0:
+                raise SystemExit("--contact_radii: 1..8 ascending non-negative radii expected")
+            radii2 = [int(np.floor(v * v)) for v in spacings]       # squared distances on the grid are integers
+        scene_field = {"radii2": radii2}
+    elif args.contact_radii is not None:
+        raise SystemExit("--contact_radii needs --scene_field_output")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     want_stats = args.stats_output is not None
@@ -902,9 +958,9 @@ def main(argv=None):
                        volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
                        filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled,
                        smooth=args.smooth, path=args.path, map_pose=map_pose, sample=args.sample,
-                       pose_sample=pose_sample)
+                       pose_sample=pose_sample, scene_field=scene_field)
     if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None or args.path is not None \
-            or map_pose is not None or pose_sample is not None:
+            or map_pose is not None or pose_sample is not None or scene_field is not None:
         preds, *extra = preds
         frame_stats = extra.pop(0) if want_stats else None
         frame_scene = extra.pop(0) if want_scene else None
@@ -918,6 +974,7 @@ def main(argv=None):
         frame_map = extra.pop(0) if map_pose is not None else None
         frame_samples = extra.pop(0) if args.sample is not None else None
         frame_pose_samples = extra.pop(0) if pose_sample is not None else None
+        frame_scene_field = extra.pop(0) if scene_field is not None else None
         if fitted is not None:                                # the info pickles record the fitted values the operators ran on
             for frames in (frame_filter, frame_smooth, frame_path):
                 for fr in frames or ():
@@ -1110,6 +1167,15 @@ def main(argv=None):
                   pose_sample["samples"], pose_sample["seed"], ps["mean_sample_spread"], ps["mean_bone_error"],
                   ps["estimate_bone_error"], pose_sample["samples"], ps["best_of_n_mpjpe"], ps["best_pose_of_n_mpjpe"], mpjpe,
                   ps["valid_draws"], ps["draws"], ps["frames_without_pose"]))
+    if scene_field is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(args.scene_field_output)), exist_ok=True)
+        with open(args.scene_field_output, "wb") as f:
+            pickle.dump(frame_scene_field, f)
+        result["scene_field"] = frame_scene_field
+        result["scene_field_summary"] = M.scene_field_summary(
+            [fr["volumes"] for fr in frame_scene_field],
+            sample_frames=[fr["pose_samples"] for fr in frame_scene_field] if pose_sample is not None else None)
+        print(M.format_scene_field_summary(result["scene_field_summary"]))
     return result
 
 

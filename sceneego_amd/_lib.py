@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -117,6 +117,11 @@ SIGNATURES = {
     "se_scene_free_mask_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _vp]),
     "se_softargmax3d_masked_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "se_softargmax3d_masked_scratch_elems": (_ll, [_i]),
+    "se_scene_sites_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp]),
+    "se_scene_distance_scratch_bytes": (_ll, [_i, _i]),
+    "se_scene_distance_i32": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp]),
+    "se_scene_expect_scratch_elems": (_ll, [_i]),
+    "se_scene_expect_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "se_joint_modes_scratch_bytes": (_ll, [_i, _i, _i]),
     "se_joint_modes_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp]),
     "se_volume_filter_scratch_bytes": (_ll, [_i, _i, _i]),
@@ -1193,6 +1198,88 @@ def softargmax3d_masked(prob, coord, free, out, peak_index, rows, rows_per_frame
     _check(load().se_softargmax3d_masked_f32(_ptr(prob), _ptr(coord), _ptr(free), _ptr(out), _ptr(peak_index), _ptr(scratch), rows,
                                              rows_per_frame, voxels, _stream()), "se_softargmax3d_masked_f32")
     return out, peak_index
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Scene distance field (csrc/scene_field.hip; sceneego_amd/scene_field.py, op.py and VoxelNetwork_depth.scene_expectations drive them)
+EXPECT_SLOTS = 24          # mass, blocked, sum p sqrt(d2), the same over free voxels, 8 contact sums, 8 free contact sums, 4 zeros
+EXPECT_MAX_RADII = 8
+SCENE_NO_SITE = 0x7fffffff  # d2 of a voxel in a frame without a site (nearest = -1 there)
+SCENE_DISTANCE_MAX_GRID = 128
+
+
+def scene_sites(depth, ray_tab, sites, grid, side, min_z=0.1, max_depth=100.0):
+    """se_scene_sites_u8: depth [B,dh,dw] float32, ray_tab [H,W,3] float64 -> sites uint8 with B * grid^3 elements (cleared inside),
+    1 where a scene point of the frame rounds to the voxel (the header states the rule).  Every argument is checked here and a bad
+    one raises HipExtensionError before anything is launched.  Returns ``sites``."""
+    what = "scene_sites"
+    _check_args(what, (("depth", depth, torch.float32, (None, None, None)), ("ray_tab", ray_tab, torch.float64, (None, None, 3))))
+    B, dh, dw = (int(v) for v in depth.shape)
+    H, W = int(ray_tab.shape[0]), int(ray_tab.shape[1])
+    grid, side, min_z, max_depth = int(grid), float(side), float(min_z), float(max_depth)
+    if B <= 0 or B > 65535 or dh <= 0 or dw <= 0 or H <= 0 or W <= 0 or H * W > 0x7fff0000 or not 2 <= grid <= 1024:
+        raise HipExtensionError(f"{what}: batch {B}, depth {dh}x{dw}, frame {H}x{W}, grid {grid} not supported")
+    if not (0.0 < side < float("inf")) or not min_z >= 0.0 or not max_depth > 0.0:
+        raise HipExtensionError(f"{what}: side {side} must be positive and finite, min_z {min_z} >= 0 and max_depth {max_depth} > 0")
+    _check_args(what, (("sites", sites, torch.uint8, B * grid ** 3),), device=depth.device)
+    _check(load().se_scene_sites_u8(_ptr(depth), _ptr(ray_tab), _ptr(sites), B, dh, dw, H, W, grid, side, min_z, max_depth, _stream()),
+           "se_scene_sites_u8")
+    return sites
+
+
+def scene_distance_scratch_bytes(batch, grid) -> int:
+    n = int(load().se_scene_distance_scratch_bytes(int(batch), int(grid)))
+    if n < 0:
+        raise HipExtensionError(f"scene_distance: batch = {batch} (1..65535), grid = {grid} (2..{SCENE_DISTANCE_MAX_GRID}) not supported")
+    return n
+
+
+def scene_distance(sites, d2, nearest, batch, grid, scratch=None):
+    """se_scene_distance_i32: sites uint8 [batch * grid^3] (any non-zero byte is a site) -> d2, nearest int32 of the same size: the
+    exact squared distance to the nearest site in voxel index units and that site's flat index, the lowest among equals
+    (0x7fffffff / -1 in a frame without a site).  ``scratch``: an optional uint8 workspace of at least
+    ``scene_distance_scratch_bytes(batch, grid)`` bytes (allocated per call otherwise).  Returns (d2, nearest)."""
+    what = "scene_distance"
+    batch, grid = int(batch), int(grid)
+    need = scene_distance_scratch_bytes(batch, grid)
+    n = batch * grid ** 3
+    dev = _check_args(what, (("sites", sites, torch.uint8, n), ("d2", d2, torch.int32, n), ("nearest", nearest, torch.int32, n)),
+                      (("scratch", scratch, torch.uint8, None),))
+    scratch = _scratch(what, scratch, need, torch.uint8, dev)
+    if scratch.data_ptr() % 8:
+        raise HipExtensionError(f"{what}: scratch must be 8-byte aligned")
+    _check(load().se_scene_distance_i32(_ptr(sites), _ptr(d2), _ptr(nearest), _ptr(scratch), scratch.numel(), batch, grid, _stream()),
+           "se_scene_distance_i32")
+    return d2, nearest
+
+
+def scene_expect_scratch_elems(rows) -> int:
+    return int(load().se_scene_expect_scratch_elems(int(rows)))
+
+
+def scene_expect(prob, d2, free, radii2, out, rows, rows_per_frame, voxels, scratch=None):
+    """se_scene_expect_f32: ``prob`` [rows, voxels] float32 against the field ``d2`` int32 and the free mask ``free`` uint8, both
+    [rows / rows_per_frame, voxels], with the squared contact radii ``radii2`` int32 [K] (1 <= K <= 8) on the device, into ``out``
+    [rows, 24] float32 (the header states every slot; nothing is divided).  Every argument is checked here and a bad one raises
+    HipExtensionError before anything is launched: the kernel reads with 16-byte loads and trusts the sizes it is given."""
+    what = "scene_expect"
+    rows, rows_per_frame, voxels = int(rows), int(rows_per_frame), int(voxels)
+    if rows <= 0 or rows > 65535 or rows_per_frame <= 0 or rows % rows_per_frame or voxels <= 0 or voxels % 4:
+        raise HipExtensionError(f"{what}: rows = {rows} (1..65535, a multiple of rows_per_frame = {rows_per_frame}), voxels = {voxels} "
+                                "(a positive multiple of 4) expected")
+    frames = rows // rows_per_frame
+    dev = _check_args(what, (("prob", prob, torch.float32, rows * voxels), ("d2", d2, torch.int32, frames * voxels),
+                             ("free", free, torch.uint8, frames * voxels), ("radii2", radii2, torch.int32, (None,)),
+                             ("out", out, torch.float32, rows * EXPECT_SLOTS)), (("scratch", scratch, torch.float32, None),))
+    K = int(radii2.numel())
+    if not 1 <= K <= EXPECT_MAX_RADII:
+        raise HipExtensionError(f"{what}: {K} radii, 1..{EXPECT_MAX_RADII} supported")
+    if prob.data_ptr() % 16 or d2.data_ptr() % 16 or free.data_ptr() % 4 or radii2.data_ptr() % 4:
+        raise HipExtensionError(f"{what}: prob and d2 must be 16-byte aligned, free and radii2 4-byte aligned")
+    scratch = _scratch(what, scratch, scene_expect_scratch_elems(rows), torch.float32, dev)
+    _check(load().se_scene_expect_f32(_ptr(prob), _ptr(d2), _ptr(free), _ptr(radii2), _ptr(out), _ptr(scratch), rows, rows_per_frame,
+                                      voxels, K, _stream()), "se_scene_expect_f32")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ newer() {  # source $1 or a header newer than object $2
   return 1
 }
 OBJS=()
-for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume_viterbi volume_sample skeleton_prior skeleton_pose skeleton_sample conv2d_1x1 conv2d_3x3 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc render render_volume scene_probe scene_constraint; do
+for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume_viterbi volume_sample skeleton_prior skeleton_pose skeleton_sample conv2d_1x1 conv2d_3x3 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc render render_volume scene_probe scene_constraint scene_field; do
   [ -f $f.hip ] || { echo "build.sh: source $f.hip is missing" >&2; exit 1; }
   OBJS+=($OBJ/$f.o)
   extra=""
@@ -30,6 +30,7 @@ for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume
   [ "$f" = scene_probe ] && extra="-ffp-contract=off" # likewise: every value it writes is tested bit for bit
   [ "$f" = render_volume ] && extra="-ffp-contract=off" # likewise: the walk is compared with its float64 model pixel for pixel
   [ "$f" = scene_constraint ] && extra="-ffp-contract=off" # likewise: the free mask is tested bit for bit
+  [ "$f" = scene_field ] && extra="-ffp-contract=off" # likewise: the sites and the distance transform are tested bit for bit
   [ "$f" = joint_modes ] && extra="-ffp-contract=off"   # likewise: the window sums are compared with their float64 model bit for bit
   [ "$f" = volume_viterbi ] && extra="-ffp-contract=off" # likewise: every score and back-pointer is compared with its float32 model bit for bit
   [ "$f" = volume_sample ] && extra="-ffp-contract=off"  # likewise: every drawn voxel is compared with its float64 model bit for bit

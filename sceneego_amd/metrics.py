@@ -213,6 +213,47 @@ def format_scene_summary(s, unit="m") -> str:
             f"{s['mean_penetration_depth']:.6f} {unit}  foot contact rate {s['foot_contact_rate']:.4f}")
 
 
+def scene_field_summary(frames, sample_frames=None, radius_index=None):
+    """The beliefs of a sequence against the scene field: ``frames`` is the list of per-frame dicts of ``op.scene_field_to_numpy``
+    over ``VoxelNetwork_depth.scene_expectations`` (the keys ``contact_prob`` [15,K] and ``blocked_prob`` [15] are used);
+    ``radius_index``: which of the K contact radii counts (default: the second, two voxel spacings with the default radii, or the
+    only one).  ``sample_frames``: optionally the per-frame dicts of ``op.scene_field_to_numpy`` over ``op.scene_field_lookup`` of
+    sampled poses (``blocked`` [S,15]).  Returns a dict:
+      ``mean_foot_contact_prob``  mean contact probability of the ankle and foot joints (9, 10, 13, 14) over the frames
+      ``mean_blocked_prob``       mean blocked probability over all joints and frames
+      ``frames``                  number of frames
+      ``blocked_pose_rate``       with ``sample_frames``: the share of whole sampled poses with any joint in a blocked voxel
+      ``poses``                   with ``sample_frames``: the number of sampled poses
+    NaN entries (a NaN volume) are left out of the means; the means are NaN for an empty list."""
+    n = len(frames)
+    nan = float("nan")
+    out = {"mean_foot_contact_prob": nan, "mean_blocked_prob": nan, "frames": n}
+    if n:
+        contact = np.stack([np.asarray(f["contact_prob"], dtype=np.float64).reshape(15, -1) for f in frames])     # [T,15,K]
+        k = min(1, contact.shape[2] - 1) if radius_index is None else int(radius_index)
+        blocked = np.stack([np.asarray(f["blocked_prob"], dtype=np.float64).reshape(15) for f in frames])
+        feet = contact[:, list(FOOT_JOINTS), k]
+        if np.isfinite(feet).any():
+            out["mean_foot_contact_prob"] = float(np.nanmean(feet))
+        if np.isfinite(blocked).any():
+            out["mean_blocked_prob"] = float(np.nanmean(blocked))
+    if sample_frames is not None:
+        poses = [np.asarray(f["blocked"], dtype=bool).reshape(-1, 15).any(axis=1) for f in sample_frames]
+        whole = np.concatenate(poses) if poses else np.zeros(0, dtype=bool)
+        out["blocked_pose_rate"] = float(whole.mean()) if whole.size else nan
+        out["poses"] = int(whole.size)
+    return out
+
+
+def format_scene_field_summary(s) -> str:
+    """The one line the sequence tool prints for ``scene_field_summary``."""
+    line = (f"scene field: {s['frames']} frames  mean foot contact probability {s['mean_foot_contact_prob']:.4f}  mean blocked "
+            f"probability {s['mean_blocked_prob']:.4f}")
+    if "blocked_pose_rate" in s:
+        line += f"  sampled poses with a blocked joint {s['blocked_pose_rate']:.4f} of {s['poses']}"
+    return line
+
+
 # Skeleton.kinematic_parents of the reference (utils/skeleton.py); sceneego_amd/_lib.py holds the same table beside SKELETON_LINES
 KINEMATIC_PARENTS = (0, 0, 1, 2, 0, 4, 5, 1, 7, 8, 9, 4, 11, 12, 13)
 

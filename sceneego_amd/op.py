@@ -351,6 +351,166 @@ def scene_constraint_to_numpy(result):
 
 
 # ----------------------------------------------------------------------------------------------
+# scene distance field (csrc/scene_field.hip; no counterpart in the reference)
+# ----------------------------------------------------------------------------------------------
+FIELD_KEYS = ("sites", "d2", "nearest", "distance", "has_scene")                    # of SceneField.build, beside the float "spacing"
+EXPECT_KEYS = ("contact_prob", "contact_free_prob", "blocked_prob", "expected_distance", "expected_free_distance", "mass")
+LOOKUP_KEYS = ("distance", "nearest_index", "blocked", "contact")
+DEFAULT_RADII2 = (1, 4, 9)       # contact radii of 1, 2 and 3 voxel spacings, squared, in voxel index units
+
+
+def scene_sites(depth, ray_tab, grid, side, min_z, max_depth, out=None):
+    """Which voxels of a ``grid``^3 cuboid of ``side`` metres hold scene, per frame (``se_scene_sites_u8``): ``depth`` [B,dh,dw]
+    float32 and the calibrated ``ray_tab`` [H,W,3] float64 on the device -> uint8 [B,G,G,G], 1 where a scene point of
+    ``se_scene_probe_f64`` (d > 0, d <= ``max_depth``, z > ``min_z``, a finite ray) has the voxel's centre as its nearest:
+    q = rint((s - origin) * (G - 1) / side) per axis, half to even, points outside the grid dropped.  ``out``: an optional uint8
+    buffer of B * G^3 elements."""
+    _lib.require_hip(depth, ray_tab)
+    if depth.dim() != 3:
+        raise _lib.HipExtensionError("scene_sites: depth [B,dh,dw] expected, got %s" % (tuple(depth.shape),))
+    B, G = int(depth.shape[0]), int(grid)
+    if out is None:
+        out = torch.empty((B, G, G, G), device=depth.device, dtype=torch.uint8)
+    return _lib.scene_sites(depth, ray_tab, out, G, side, min_z, max_depth).view(B, G, G, G)
+
+
+def scene_distance(sites, scratch=None, out=None):
+    """The exact Euclidean distance transform of ``sites`` uint8 [B,G,G,G] (any non-zero byte is a site; 2 <= G <= 128), per frame
+    (``se_scene_distance_i32``).  Returns (d2, nearest), both int32 [B,G,G,G]: the squared distance to the nearest site in voxel index
+    units, and that site's flat index (the lowest among the nearest); 0x7fffffff and -1 in a frame without a site.  ``scratch``: an
+    optional uint8 workspace of ``_lib.scene_distance_scratch_bytes(B, G)`` bytes; ``out``: an optional (d2, nearest) pair to fill."""
+    _lib.require_hip(sites)
+    if sites.dim() != 4 or not sites.shape[1] == sites.shape[2] == sites.shape[3]:
+        raise _lib.HipExtensionError("scene_distance: sites [B,G,G,G] expected, got %s" % (tuple(sites.shape),))
+    B, G = int(sites.shape[0]), int(sites.shape[1])
+    if out is None:
+        out = (torch.empty((B, G, G, G), device=sites.device, dtype=torch.int32),
+               torch.empty((B, G, G, G), device=sites.device, dtype=torch.int32))
+    d2, nearest = _lib.scene_distance(sites, out[0], out[1], B, G, scratch=scratch)
+    return d2.view(B, G, G, G), nearest.view(B, G, G, G)
+
+
+def _radii2(radii2, device):
+    """The squared contact radii as (tuple of ints, int32 device tensor): 1..8 of them, non-negative and ascending."""
+    r = tuple(int(v) for v in (DEFAULT_RADII2 if radii2 is None else radii2))
+    if not 1 <= len(r) <= _lib.EXPECT_MAX_RADII or any(v < 0 or v >= _lib.SCENE_NO_SITE for v in r) or list(r) != sorted(r):
+        raise ValueError(f"radii2 = {r}: 1..{_lib.EXPECT_MAX_RADII} ascending non-negative squared radii expected")
+    return r, torch.tensor(r, device=device, dtype=torch.int32)
+
+
+def contact_radii2(contact_radii, spacing):
+    """Contact radii in metres -> squared radii in voxel index units, floor((r / spacing)^2) in float64; None -> the default of 1, 2
+    and 3 voxel spacings, (1, 4, 9) exactly."""
+    if contact_radii is None:
+        return DEFAULT_RADII2
+    return tuple(int(np.floor((float(r) / float(spacing)) ** 2)) for r in contact_radii)
+
+
+def scene_expect(volumes, d2, free, radii2=None, scratch=None):
+    """The raw sums of ``se_scene_expect_f32``: ``volumes`` [B,J,X,Y,Z] float32 against ``d2`` int32 and ``free`` uint8, both
+    [B,X,Y,Z] (or [B,N]) -> float32 [B,J,24] (include/sceneego_hip.h states every slot; nothing is divided)."""
+    _lib.require_hip(volumes, d2, free)
+    if volumes.dim() != 5 or volumes.dtype != torch.float32:
+        raise _lib.HipExtensionError("scene_expect: volumes must be [B,J,X,Y,Z] float32, got %s %s" % (tuple(volumes.shape), volumes.dtype))
+    B, J = int(volumes.shape[0]), int(volumes.shape[1])
+    N = int(volumes[0, 0].numel())
+    for name, t, dtype in (("d2", d2, torch.int32), ("free", free, torch.uint8)):
+        if t.dtype != dtype or t.shape[0] != B or t.numel() != B * N:
+            raise _lib.HipExtensionError("scene_expect: %s must be %s with %d x %d elements, got %s %s"
+                                         % (name, dtype, B, N, tuple(t.shape), t.dtype))
+    _, rad = _radii2(radii2, volumes.device)
+    return _scene_expect_flat(volumes.contiguous(), d2.contiguous(), free.contiguous(), rad, B, J, N, scratch)
+
+
+def _scene_expect_flat(vol, d2, free, rad, B, J, N, scratch):
+    out = torch.empty((B * J, _lib.EXPECT_SLOTS), device=vol.device, dtype=torch.float32)
+    _lib.scene_expect(vol, d2, free, rad, out, B * J, J, N, scratch=scratch)
+    return out.view(B, J, _lib.EXPECT_SLOTS)
+
+
+def scene_expectations(volumes, field, free, radii2=None, scratch=None):
+    """A distribution against the scene field, one pass over the volumes on the device (``se_scene_expect_f32``).  ``volumes``
+    [B,J,G,G,G] float32 softmaxed (``forward()``'s volumes, the filtered / smoothed / coupled beliefs, the normalised max-marginals);
+    ``field``: the dict of ``SceneField.build``; ``free`` uint8 [B,G,G,G] of ``scene_free_mask``; ``radii2``: 1..8 ascending squared
+    contact radii in voxel index units (default 1, 4, 9).  Divisions, square roots and thresholds are taken here, in float32 torch.
+    Returns a dict of device tensors:
+
+      ``contact_prob``            [B,J,K]  the share of the mass within each radius of the scene: sum p [d2 <= radii2[k]] / mass
+      ``contact_free_prob``       [B,J,K]  the same over the free voxels alone (still divided by the whole mass)
+      ``blocked_prob``            [B,J]    the share of the mass in blocked voxels, behind the depth surface
+      ``expected_distance``       [B,J]    sum p distance / mass in metres; NaN in a frame without a scene
+      ``expected_free_distance``  [B,J]    the same over the free voxels, divided by the free mass (mass - blocked mass); NaN in a
+                                           frame without a scene or without free mass
+      ``mass``                    [B,J]    sum p (1 up to rounding for a softmaxed volume)
+      ``radii2``                  [K]      int32, the squared radii used
+
+    Distance is quantised to voxel centres; the radii are conventions, not calibrated.  A (sample, joint) whose volume holds a NaN
+    gets NaN everywhere."""
+    _, rad = _radii2(radii2, volumes.device)
+    raw = scene_expect(volumes, field["d2"], free, radii2, scratch=scratch)
+    return _scene_expectations_of(raw, rad, field["has_scene"], float(field["spacing"]))
+
+
+def _scene_expectations_of(raw, rad, has_scene, spacing):
+    K = int(rad.numel())
+    mass = raw[..., 0]
+    nan = torch.full_like(mass, float("nan"))
+    scene = has_scene[:, None].expand_as(mass)
+    free_mass = mass - raw[..., 1]
+    return {"contact_prob": raw[..., 4:4 + K] / mass[..., None], "contact_free_prob": raw[..., 12:12 + K] / mass[..., None],
+            "blocked_prob": raw[..., 1] / mass,
+            "expected_distance": torch.where(scene, raw[..., 2] / mass * spacing, nan),
+            "expected_free_distance": torch.where(scene & (free_mass > 0), raw[..., 3] / free_mass * spacing, nan),
+            "mass": mass, "radii2": rad}
+
+
+def scene_field_lookup(field, free, index, radii2=None):
+    """The field at given voxels: a plain gather.  ``field``: the dict of ``SceneField.build`` for B frames; ``free`` uint8
+    [B,G,G,G] of ``scene_free_mask`` (None: nothing counts as blocked); ``index``: any integer tensor [..., B, J] of flat voxel
+    indices, -1 (any negative) for an invalid entry - ``SkeletonPrior.sample``'s and ``VolumeSmoother.sample``'s ``index`` (with the
+    frames as B), ``solve``'s and the path's ``index``, ``alt_index``, ``free_peak_index``.  Returns a dict of device tensors shaped
+    like ``index``:
+
+      ``distance``       float32 metres to the nearest scene voxel (+inf in a frame without a scene, NaN for an invalid entry)
+      ``nearest_index``  int32 flat index of that voxel (-1 without one or for an invalid entry)
+      ``blocked``        bool: the voxel lies behind the depth surface (False for an invalid entry)
+      ``contact``        [..., K] bool: d2 <= radii2[k] (False for an invalid entry)
+      ``radii2``         [K] int32, the squared radii used (default 1, 4, 9)"""
+    d2 = field["d2"]
+    _lib.require_hip(d2, index)
+    B = int(d2.shape[0])
+    N = int(d2[0].numel())
+    if index.dim() < 2 or index.shape[-2] != B or index.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+        raise _lib.HipExtensionError("scene_field_lookup: index must be an integer tensor [..., %d, J], got %s %s"
+                                     % (B, tuple(index.shape), index.dtype))
+    _, rad = _radii2(radii2, d2.device)
+    idx = index.to(device=d2.device, dtype=torch.int64)
+    valid = (idx >= 0) & (idx < N)
+    base = torch.arange(B, device=d2.device, dtype=torch.int64)[:, None] * N                    # broadcasts over [..., B, J]
+    at = torch.where(valid, idx, torch.zeros_like(idx)) + base
+    g_d2 = d2.reshape(-1)[at]
+    dist = field["distance"].reshape(-1)[at]
+    near = field["nearest"].reshape(-1)[at]
+    blocked = (free.reshape(-1)[at] == 0) if free is not None else torch.zeros_like(valid)
+    return {"distance": torch.where(valid, dist, torch.full_like(dist, float("nan"))),
+            "nearest_index": torch.where(valid, near, torch.full_like(near, -1)),
+            "blocked": blocked & valid,
+            "contact": (g_d2[..., None] <= rad.to(g_d2.dtype)) & valid[..., None], "radii2": rad}
+
+
+def scene_field_to_numpy(result):
+    """A dict of ``scene_expectations`` (or of ``scene_field_lookup`` with ``index`` [B,J]) as a list of per-frame dicts of numpy
+    arrays, the keys without the batch dimension and ``radii2`` copied into every frame: what demo.py --scene_field and
+    run_sequence.py --scene_field_output write.  A lookup of samples [S,B,J] gives per-frame arrays [S,J]."""
+    keys = EXPECT_KEYS if "mass" in result else LOOKUP_KEYS
+    host = {k: result[k].cpu().numpy() for k in keys}
+    rad = result["radii2"].cpu().numpy()
+    lead = host[keys[0]].ndim - (3 if keys[0] in ("contact_prob",) else 2)                        # dimensions before the batch
+    nb = host[keys[0]].shape[lead]
+    return [{**{k: np.take(host[k], b, axis=lead).copy() for k in keys}, "radii2": rad.copy()} for b in range(nb)]
+
+
+# ----------------------------------------------------------------------------------------------
 # multi-hypothesis joints (csrc/joint_modes.hip; no counterpart in the reference)
 # ----------------------------------------------------------------------------------------------
 MODES_KEYS = ("coord", "peak_coord", "peak_prob", "mass", "index", "count", "total", "valid")

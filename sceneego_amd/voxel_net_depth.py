@@ -443,6 +443,74 @@ class VoxelNetwork_depth(nn.Module):
         out["free"] = free.view(B, G, G, G)
         return out
 
+    def _scene_depth(self, what, depth, B=None):
+        """``depth`` [B,dh,dw] (or [B,1,dh,dw]) on a HIP device as the float32 [B,dh,dw] the scene kernels read."""
+        _lib.require_hip(depth)
+        if depth.dim() not in (3, 4) or (B is not None and depth.shape[0] != B) \
+                or depth.numel() != depth.shape[0] * depth.shape[-2] * depth.shape[-1]:
+            raise _lib.HipExtensionError("%s: depth [%s,dh,dw] expected, got %s" % (what, "B" if B is None else B, tuple(depth.shape)))
+        return depth.reshape(depth.shape[0], depth.shape[-2], depth.shape[-1]).float().contiguous()
+
+    @torch.no_grad()
+    def scene_field(self, depth):
+        """The scene of ``depth`` [B,dh,dw] (or [B,1,dh,dw]; metres, any size) as a field on the module's own grid: a
+        ``sceneego_amd.scene_field.SceneField`` of the module's calibration, frame size, ``volume_size`` and ``cuboid_side``, built
+        once per device (its calibrated ray table: 31 MB at 1024 x 1280), and its ``build(depth)``: the dict of device tensors
+        described there (sites, d2, nearest, distance, has_scene, spacing).  One memset and three launches on the current stream;
+        ``forward()`` itself is unchanged."""
+        d = self._scene_depth("scene_field", depth)
+        dev = d.device
+
+        def make():
+            from .scene_field import SceneField
+            cam = self.fisheye_camera_model
+            ys, xs = np.meshgrid(np.arange(self.image_height), np.arange(self.image_width), indexing="ij")
+            rays = cam.camera2world_ray(np.stack([xs.reshape(-1), ys.reshape(-1)], axis=1))    # render.calibrated_ray_table's arithmetic
+            tab = torch.from_numpy(np.ascontiguousarray(rays.reshape(self.image_height, self.image_width, 3))).to(dev)
+            from types import SimpleNamespace
+            cfg = SimpleNamespace(model=SimpleNamespace(volume_size=self.volume_size, cuboid_side=self.cuboid_side))
+            return SceneField(None, frame_size=(self.image_height, self.image_width), config=cfg, ray_tab=tab, device=dev)
+        return self._head_cached(("field", str(dev)), make).build(d)
+
+    @torch.no_grad()
+    def scene_expectations(self, volumes, depth=None, field=None, contact_radii=None, margin=None, radii2=None):
+        """Any joint distribution on the module's grid against the scene of its frame: contact probability, blocked mass and expected
+        distance per joint.  ``volumes`` [B,J,G,G,G] float32: ``forward()``'s volumes, ``VolumeFilter`` / ``VolumeSmoother`` /
+        ``SkeletonPrior`` beliefs or the normalised max-marginals, unchanged.  ``depth`` [B,dh,dw] (or [B,1,dh,dw]): the frames' depth
+        maps, needed for the free mask (the ``op.scene_free_mask`` path of ``constrain_to_scene``, with the same default ``margin``
+        of one voxel edge) and, without ``field``, for ``scene_field(depth)``; ``field``: a field built before, to share it between
+        calls.  ``contact_radii``: 1..8 ascending radii in metres, ``radii2 = floor((r / spacing)^2)``; the default is 1, 2 and 3
+        voxel spacings (two is ``SceneConsistency``'s contact convention); ``radii2`` gives the squared radii in voxel spacings directly
+        instead.  ``op.scene_expectations`` with these: the dict of device
+        tensors described there (contact_prob [B,J,K], contact_free_prob [B,J,K], blocked_prob, expected_distance,
+        expected_free_distance, mass, radii2) plus ``free`` [B,G,G,G] uint8.  One pass over the volumes on the current stream
+        (``se_scene_expect_f32``); the mask and the workspace are cached per (device, rows), so ``free`` is overwritten by the next
+        call with the same batch.  Distance is quantised to voxel centres and the radii are conventions: nothing here is calibrated.
+
+        Raises ValueError when ``config.model.volume_softmax`` is false: the ReLU volumes are not a distribution."""
+        B, J, G, N, dev = self._head_args("scene_expectations", volumes)
+        if depth is None:
+            raise ValueError("scene_expectations: depth is needed for the free mask")
+        d = self._scene_depth("scene_expectations", depth, B)
+        if field is None:
+            field = self.scene_field(d)
+        if tuple(field["d2"].shape) != (B, G, G, G):
+            raise _lib.HipExtensionError("scene_expectations: field of %s, expected %s" % (tuple(field["d2"].shape), (B, G, G, G)))
+        pix, rng = self._head_cached(("sight", str(dev)), lambda: tuple(t.to(dev) for t in op.build_sight_table(
+            self.grid_coord_proj, self.coord_volume, self.image_height, self.image_width)))
+        free, scratch = self._head_cached(("expect", str(dev), B * J), lambda: (
+            torch.empty((B, N), device=dev, dtype=torch.uint8),
+            torch.empty(_lib.scene_expect_scratch_elems(B * J), device=dev, dtype=torch.float32)))
+        from .render import MAX_DEPTH
+        op.scene_free_mask(d, pix, rng, self.image_height, self.image_width,
+                           self.cuboid_side / self.volume_size if margin is None else float(margin), MAX_DEPTH, out=free)
+        if radii2 is not None and contact_radii is not None:
+            raise ValueError("scene_expectations: give contact_radii (metres) or radii2 (squared voxel spacings), not both")
+        out = op.scene_expectations(volumes, field, free, radii2 if radii2 is not None else
+                                    op.contact_radii2(contact_radii, field["spacing"]), scratch=scratch)
+        out["free"] = free.view(B, G, G, G)
+        return out
+
     @torch.no_grad()
     def joint_modes(self, volumes, k=4, radius=2, min_prob=0.0, min_rel=0.02):
         """The ``k`` strongest modes of every joint's softmaxed volume [B,J,G,G,G]: where the peaks are, how much probability each
