@@ -12,7 +12,8 @@ scanline OpenEXR, NONE/ZIP/PIZ, decoded by ``sceneego_amd/exr.py``) or ``.npy`` 
 ``--render_dir DIR`` writes ``<img_name>.render.png`` (scene point cloud and skeleton from a third-person view) and
 ``<img_name>.overlay.png`` (the skeleton in the fisheye frame) per frame, rendered on the device (``sceneego_amd/render.py``);
 ``--render_format jpg`` writes ``.render.jpg`` / ``.overlay.jpg`` instead: quality-90 4:4:4 JPEG files encoded on the device
-(``sceneego_amd/jpeg_encode.py``), so that only compressed bytes cross to the host.
+(``sceneego_amd/jpeg_encode.py``), so that only compressed bytes cross to the host.  ``--png_encoder device`` does the same for
+the PNG files (``sceneego_amd/png_encode.py``: lossless, the same pixels as PIL's files).
 ``--render_volumes true`` (with ``--render_dir``) also writes ``<img_name>.volumes.render.*`` and ``<img_name>.volumes.overlay.*``: the same
 two pictures with the joint probability volumes drawn over them as a maximum-intensity projection in per-joint colours
 (``SceneRenderer.render_volumes`` / ``overlay_volumes``); ``--volume_joints 9,10,13,14`` draws only those joints.
@@ -52,7 +53,7 @@ JOINT_NAMES = ["Neck", "Right_shoulder", "Right_elbow", "Right_wrist", "Left_sho
 class Demo:
     def __init__(self, config, img_dir, depth_dir, weights=None, image_decode="device", stats=False, render_dir=None, scene_check=False,
                  render_format="png", render_volumes=False, volume_joints=None, save_volumes=None, constrain=False, modes=0,
-                 bone_lengths=None, scene_field=False):
+                 bone_lengths=None, scene_field=False, png_encoder="host"):
         if not torch.cuda.is_available():
             raise RuntimeError("demo.py needs an MI355X (HIP device); the hot path has no CPU fallback")
         self.device = torch.device("cuda")
@@ -63,6 +64,9 @@ class Demo:
         if render_format not in ("png", "jpg"):
             raise ValueError(f"render_format must be png or jpg, got {render_format!r}")
         self.render_format = render_format
+        if png_encoder not in ("host", "device"):
+            raise ValueError(f"png_encoder must be host or device, got {png_encoder!r}")
+        self.png_encoder = png_encoder
         self.renderer = None
         self.render_volumes = render_volumes
         self.volume_joints = volume_joints
@@ -172,6 +176,8 @@ class Demo:
                 self.renderer.ray_tab = self.scene.ray_tab                              # the same table: keep one copy
         os.makedirs(self.render_dir, exist_ok=True)
         save = save_jpeg if self.render_format == "jpg" else save_png
+        if self.render_format == "png" and self.png_encoder == "device":
+            from sceneego_amd.png_encode import save_png_device as save
         ext = "." + self.render_format
         save(os.path.join(self.render_dir, img_name + ".render" + ext), self.renderer.render(depth, frame_u8, kp)[0])
         save(os.path.join(self.render_dir, img_name + ".overlay" + ext), self.renderer.overlay(frame_u8, kp, depth=depth)[0])
@@ -197,6 +203,9 @@ def build_parser():
                     help="also write <img_name>.render.png and <img_name>.overlay.png here (rendered on the device; no display needed)")
     ap.add_argument("--render_format", type=str, default="png", choices=("png", "jpg"),
                     help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG encoded on the device)")
+    ap.add_argument("--png_encoder", type=str, default="host", choices=("host", "device"),
+                    help="with --render_format png: host (PIL) or device (lossless, sceneego_amd/png_encode.py: the same pixels, only "
+                         "the compressed bytes cross to the host)")
     ap.add_argument("--render_volumes", type=str, default="false",
                     help="true (with --render_dir): also write <img_name>.volumes.render.* and <img_name>.volumes.overlay.*, the two "
                          "pictures with the joint probability volumes drawn over them")
@@ -263,7 +272,8 @@ def main(argv=None):
                 scene_check=args.scene_check, render_format=args.render_format, render_volumes=args.render_volumes,
                 volume_joints=args.volume_joints, save_volumes=args.output_dir if args.save_volumes else None,
                 constrain=args.constrained_dir is not None, modes=args.modes_k if args.modes else 0,
-                bone_lengths=np.load(args.bone_lengths) if args.bone_lengths is not None else None, scene_field=args.scene_field)
+                bone_lengths=np.load(args.bone_lengths) if args.bone_lengths is not None else None, scene_field=args.scene_field,
+                png_encoder=args.png_encoder)
     os.makedirs(args.output_dir, exist_ok=True)
     if args.constrained_dir is not None:
         os.makedirs(args.constrained_dir, exist_ok=True)

@@ -1325,6 +1325,35 @@ int se_jpeg_encode_u8(const unsigned char* frames, int batch, int height, int wi
                       const unsigned short* quant_chroma, int subsampling, int restart_rows, unsigned char* out, long long capacity,
                       int* length, int* status, void* scratch, long long scratch_bytes, void* stream);
 
+/* Lossless PNG encoder (no counterpart in the reference; sceneego_amd/png_encode.py writes the signature and the chunks around it).
+ *   frames    uint8 [batch][height][width][channels] on the device; channels 3 (R, G, B: colour type 2) or 1 (gray: colour type 0);
+ *             bit depth 8, no interlace; R = 1 + width * channels, height * R < 2^31
+ *   out       uint8 [batch][capacity]: per frame the complete zlib stream (78 01, the deflate blocks, Adler-32), the payload of one IDAT
+ *   capacity  at least se_png_encode_bound(height, width, channels) = 2 + sum over segments of (len + 10) + 4, which no stream exceeds
+ *             (a segment is stored when no Huffman form is smaller); a smaller capacity is SE_ERR_BAD_ARG, so there is no retry path
+ *   length    int32 [batch]: bytes of the frame's stream          status   int32 [batch][2]: {0, bytes}
+ *   scratch   se_png_encode_scratch_bytes(batch, height, width, channels) bytes of device workspace, 16-byte aligned; the helpers
+ *             allocate nothing and return SE_ERR_BAD_ARG for a bad shape
+ * The bytes (integer rules only; DESIGN.md 4h2 states them, tests/png_encode_model.py restates them and the kernel equals it byte
+ * for byte):
+ *   filter    per row the filter 0..4 with the smallest sum of min(v, 256 - v) of its filtered bytes, ties to the lowest number
+ *   segments  the filtered stream in pieces of 16384 bytes, one deflate block each
+ *   parse     greedy over the candidate distances (1, channels; duplicates removed): the longest run (<= 258, not beyond the
+ *             segment's end, never before the stream's first byte, but back into the segment before), the first listed among
+ *             equals; a match from 3 bytes on
+ *   codes     per segment minimum-redundancy lengths of the counted symbols sorted by (count, symbol), limited to 15 bits (7 for the
+ *             code-length code) by miniz's Kraft repair; at least two coded distance symbols
+ *   block     the smallest of the stored, fixed and dynamic forms by exact bit count, ties in that order; every block but the last
+ *             is followed by an empty stored block unless it is stored itself, so segments join on byte boundaries
+ * Four kernel launches on `stream`, nothing allocated, no memset node, no synchronisation: legal under hipGraph capture; bitwise
+ * reproducible and independent of the batch a frame is in.
+ * SE_ERR_BAD_ARG: a null pointer, batch outside 1..65535, a non-positive size, channels not 1 / 3, height * R >= 2^31, capacity below
+ * the bound or above 2^31-1, scratch too small or misaligned, length / status misaligned. */
+long long se_png_encode_scratch_bytes(int batch, int height, int width, int channels);
+long long se_png_encode_bound(int height, int width, int channels);
+int se_png_encode_u8(const unsigned char* frames, unsigned char* out, int* length, int* status, void* scratch, long long scratch_bytes,
+                     int batch, int height, int width, int channels, long long capacity, void* stream);
+
 /* Volume renderer (no counterpart in the reference; sceneego_amd/render.py: SceneRenderer.render_volumes / overlay_volumes): a
  * maximum-intensity projection of the 15 per-joint volumes along every pixel's ray, composited joint by joint over a picture
  * se_render_resolve_f64 / se_render_overlay_f64 made.  All arithmetic is float64, unfused, in the order written here

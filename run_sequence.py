@@ -191,8 +191,10 @@ class SequenceRunner:
         self.pipe = PipelinedForward(self.net, n_streams=streams) if streams > 1 else None
         self.renderer = None
         self.encoder = None
+        self.png_encoder = None
         self.video = None
-        self.render_options = {"format": "png", "video": None, "fps": 25, "view": "render", "quality": 90, "renderer": {}}
+        self.render_options = {"format": "png", "png_encoder": "host", "video": None, "fps": 25, "view": "render", "quality": 90,
+                               "renderer": {}}
         self.scenes = {}
 
     def _scene(self, slot=0):
@@ -239,8 +241,8 @@ class SequenceRunner:
 
     def _render(self, job, kp):
         """The image pair of every picked frame of one batch and / or their video frames; ``kp``: the batch's final joints on the
-        host.  PNG files go through the host; JPEG files and video frames are encoded on the device in the batch they were
-        rendered in, and only their compressed bytes cross to the host."""
+        host.  PNG files go through the host unless ``--png_encoder device``; those, JPEG files and video frames are encoded on the
+        device in the batch they were rendered in, and only their compressed bytes cross to the host."""
         from sceneego_amd.config import resolve_calibration_path
         from sceneego_amd.render import SceneRenderer, save_png
         render_dir, pick, names, frames_u8, depth, vol = job
@@ -253,7 +255,11 @@ class SequenceRunner:
         def write(view, images):
             if render_dir is None:
                 return
-            if opt["format"] == "png":
+            if opt["format"] == "png" and opt["png_encoder"] == "device":
+                for name, data in zip(names, self._png_encoder().encode(images)):
+                    with open(os.path.join(render_dir, f"{name}.{view}.png"), "wb") as f:
+                        f.write(data)
+            elif opt["format"] == "png":
                 images_h = images.cpu()
                 for k, name in enumerate(names):
                     save_png(os.path.join(render_dir, f"{name}.{view}.png"), images_h[k])
@@ -296,6 +302,12 @@ class SequenceRunner:
             self.encoder = JpegEncoder(self.device)
         return self.encoder
 
+    def _png_encoder(self):
+        if self.png_encoder is None:
+            from sceneego_amd.png_encode import PngEncoder
+            self.png_encoder = PngEncoder(self.device)
+        return self.png_encoder
+
     @torch.no_grad()
     def fit_motion(self, images, depths, batch_size, model, iterations=8, max_bytes=None):
         """The first pass of ``--fit_frames``: the forward over the consecutive frames ``images`` / ``depths`` in batches, their raw
@@ -336,7 +348,7 @@ class SequenceRunner:
     def run(self, images, depths, batch_size, stats=False, render_dir=None, render_every=1, scene=False, render_format="png",
             render_video=None, render_fps=25, render_view="render", render_quality=90, render_size=None, render_volumes=False,
             volume_joints=None, constrain=False, modes=0, filter=None, render_filtered=False, skeleton=None, render_coupled=False,
-            smooth=None, path=None, map_pose=None, sample=None, pose_sample=None, scene_field=None):
+            smooth=None, path=None, map_pose=None, sample=None, pose_sample=None, scene_field=None, png_encoder="host"):
         """Predicted [15,3] joints of every frame; with ``stats`` a pair (joints, per-frame statistics dicts).  ``render_dir``: also
         write the rendered image pair (``render_format``: png or jpg) of every ``render_every``-th frame there.  ``render_video``:
         those frames (``render_view``: render, overlay or both side by side) as one Motion-JPEG AVI.  ``scene``: the per-frame
@@ -456,9 +468,11 @@ class SequenceRunner:
                 raise ValueError(f"--render_every must be >= 1, got {render_every}")
             if render_format not in ("png", "jpg") or render_view not in ("render", "overlay", "both"):
                 raise ValueError(f"bad render_format {render_format!r} or render_view {render_view!r}")
+            if png_encoder not in ("host", "device"):
+                raise ValueError(f"png_encoder must be host or device, got {png_encoder!r}")
             if render_dir is not None:
                 os.makedirs(render_dir, exist_ok=True)
-            self.render_options = {"format": render_format, "video": render_video, "fps": render_fps, "view": render_view,
+            self.render_options = {"format": render_format, "png_encoder": png_encoder, "video": render_video, "fps": render_fps, "view": render_view,
                                    "quality": render_quality, "renderer": {} if render_size is None else {"out_size": tuple(render_size)},
                                    "volumes": bool(render_volumes), "volume_joints": volume_joints}
 
@@ -716,6 +730,9 @@ def build_parser():
                     "the bone prior is wrong for an edge")
     ap.add_argument("--render_format", default="png", choices=("png", "jpg"),
                     help="with --render_dir: png (PIL on the host) or jpg (quality-90 4:4:4 JPEG files encoded on the device)")
+    ap.add_argument("--png_encoder", default="host", choices=("host", "device"),
+                    help="with --render_dir and --render_format png: host (PIL) or device (lossless, sceneego_amd/png_encode.py: the "
+                         "picked frames of a batch are encoded where they were rendered, only the files' bytes cross to the host)")
     ap.add_argument("--render_video", default=None, help="write the picked frames as one Motion-JPEG AVI (4:2:0, encoded on the device)")
     ap.add_argument("--render_fps", type=_fps, default=25, help="with --render_video: frames per second of the file")
     ap.add_argument("--render_view", default="render", choices=("render", "overlay", "both"),
@@ -958,7 +975,7 @@ def main(argv=None):
                        volume_joints=args.volume_joints, constrain=want_constraint, modes=args.modes_k if want_modes else 0,
                        filter=args.filter, render_filtered=args.render_filtered, skeleton=skeleton, render_coupled=args.render_coupled,
                        smooth=args.smooth, path=args.path, map_pose=map_pose, sample=args.sample,
-                       pose_sample=pose_sample, scene_field=scene_field)
+                       pose_sample=pose_sample, scene_field=scene_field, png_encoder=args.png_encoder)
     if want_stats or want_scene or want_constraint or want_modes or want_filter or skeleton is not None or args.path is not None \
             or map_pose is not None or pose_sample is not None or scene_field is not None:
         preds, *extra = preds

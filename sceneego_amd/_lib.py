@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -104,6 +104,9 @@ SIGNATURES = {
     "se_jpeg_decode_bgr_u8": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _i, _vp]),
     "se_jpeg_encode_scratch_bytes": (_ll, [_i, _i, _i, _i]),
     "se_jpeg_encode_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _ll, _vp, _vp, _vp, _ll, _vp]),
+    "se_png_encode_scratch_bytes": (_ll, [_i, _i, _i, _i]),
+    "se_png_encode_bound": (_ll, [_i, _i, _i]),
+    "se_png_encode_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _ll, _vp]),
     "se_render_splat_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _d, _d, _d, _vp]),
     "se_render_resolve_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "se_render_overlay_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
@@ -2059,3 +2062,35 @@ def jpeg_encode(frames, quant_luma, quant_chroma, subsampling, restart_rows, out
     _check(load().se_jpeg_encode_u8(_ptr(frames), B, H, W, 1 if bgr else 0, ql.ctypes.data, qc.ctypes.data, int(subsampling),
                                     int(restart_rows), _ptr(out), out.shape[1], _ptr(length), _ptr(status), _ptr(scratch),
                                     scratch.numel(), _stream()), "se_jpeg_encode_u8")
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Lossless PNG encoder (csrc/png_enc.hip; sceneego_amd/png_encode.py drives it)
+def png_encode_scratch_bytes(batch, height, width, channels) -> int:
+    """se_png_encode_scratch_bytes: device workspace of one encode call; ``channels`` is 3 (RGB) or 1 (gray)."""
+    n = load().se_png_encode_scratch_bytes(int(batch), int(height), int(width), int(channels))
+    if n < 0:
+        raise HipExtensionError(f"se_png_encode_scratch_bytes: bad shape (batch {batch}, {height}x{width}, channels {channels})")
+    return int(n)
+
+
+def png_encode_bound(height, width, channels) -> int:
+    """se_png_encode_bound: bytes no zlib stream of a frame of this shape exceeds; the capacity ``png_encode`` asks for."""
+    n = load().se_png_encode_bound(int(height), int(width), int(channels))
+    if n < 0:
+        raise HipExtensionError(f"se_png_encode_bound: bad shape ({height}x{width}, channels {channels})")
+    return int(n)
+
+
+def png_encode(frames, out, length, status, scratch):
+    """se_png_encode_u8: frames uint8 [B,H,W,3] or [B,H,W] -> out uint8 [B,capacity] (the zlib stream of every frame), length int32
+    [B], status int32 [B,2].  Runs on the current stream."""
+    what = "png_encode"
+    _check_args(what, (("frames", frames, torch.uint8, None),))
+    if frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3):
+        raise HipExtensionError(f"{what}: frames has shape {tuple(frames.shape)}, expected [B,H,W,3] or [B,H,W]")
+    B, H, W = frames.shape[:3]
+    _check_args(what, (("out", out, torch.uint8, (B, None)), ("length", length, torch.int32, B), ("status", status, torch.int32, (B, 2)),
+                       ("scratch", scratch, torch.uint8, None)), device=frames.device)
+    _check(load().se_png_encode_u8(_ptr(frames), _ptr(out), _ptr(length), _ptr(status), _ptr(scratch), scratch.numel(), B, H, W,
+                                   3 if frames.dim() == 4 else 1, out.shape[1], _stream()), "se_png_encode_u8")

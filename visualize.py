@@ -50,6 +50,8 @@ def parse_args(argv=None):
                     help="the skeleton drawn into the fisheye frame (default: overlay.png, or overlay.jpg with --format jpg)")
     ap.add_argument("--format", type=str, default="png", choices=("png", "jpg"),
                     help="png (PIL on the host) or jpg (quality-90 4:4:4 JPEG encoded on the device)")
+    ap.add_argument("--png_encoder", type=str, default="host", choices=("host", "device"),
+                    help="with --format png: host (PIL) or device (lossless, sceneego_amd/png_encode.py: the same pixels)")
     ap.add_argument("--ply", type=str, default="scene.ply", help="the coloured point cloud (binary PLY)")
     ap.add_argument("--azimuth", type=float, default=35.0, help="degrees around the cuboid centre (0, 0, 1)")
     ap.add_argument("--elevation", type=float, default=25.0, help="degrees towards the head camera")
@@ -104,6 +106,8 @@ def visualize(args):
     renderer = SceneRenderer(args.calibration, frame_size=tuple(frame.shape[1:3]), out_size=args.size, fov_y_deg=args.fov,
                              splat=args.splat, device=device)
     save = save_jpeg if getattr(args, "format", "png") == "jpg" else save_png
+    if getattr(args, "format", "png") == "png" and getattr(args, "png_encoder", "host") == "device":
+        from sceneego_amd.png_encode import save_png_device as save
     volumes = None
     if getattr(args, "volumes_path", None):
         import numpy as np
