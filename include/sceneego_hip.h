@@ -376,6 +376,24 @@ int se_conv3d_k3_split3_f32(const float* in, const se_bf16* wsplit, const float*
  * se_split6_planes_f32 (test entry point): the device split of n (even) float32 values -> planes [3][n].                       */
 long long se_conv3d_split6_packed_elems(int cout, int cin_pad, int ksize, int transposed);
 int se_conv3d_split6_pack(const float* wpack, se_bf16* wsplit, int cout, int cin_pad, int ksize, int transposed, void* stream);
+
+/* The 2-D pose head's ConvTranspose2d(k=4, s=2, p=1) + BatchNorm2d + ReLU (se_deconv2d_k4s2_assemble_f32 above) as ONE launch,
+ * product and assembly together: a four-phase implicit GEMM with every float32 product taken as six bf16 products on
+ * v_mfma_f32_16x16x32_bf16 (csrc/split6.h; float32 accuracy), bias and ReLU in the epilogue.
+ *   x      [batch][cin][h][w] float32 (x_elem_bytes = 4; any other element size: SE_ERR_BAD_ARG)
+ *   wsplit se_deconv2d_k4s2_s6_pack of the folded ConvTranspose2d weight w [cin][cout][4][4]: three bf16 planes that sum to w exactly,
+ *          in the order the kernel walks them, [cin / 32][cout / 16][a 2][fragment 8][plane 3][lane 64][8]: fragment 4 dy + f is
+ *          kernel row ky = 3 - a - 2 dy and column kx = 3, 1, 2, 0 for f = 0 .. 3; lane l, element j is input channel
+ *          32 chunk + 8 (l >> 4) + j and output channel 16 tile + (l & 15); se_deconv2d_k4s2_s6_packed_elems elements (-1: none)
+ *   out    [batch][cout][2h][2w] = bias[co] + the four taps that reach each output pixel (zero outside the map), ReLU if `relu`
+ * Domain (se_deconv2d_k4s2_s6_domain returns 1; else the launch returns SE_ERR_BAD_ARG and nothing is launched): cin % 32 == 0,
+ * cout % 64 == 0, w % 16 == 0, h % 8 == 0, the input below 2^31 bytes.  No atomics, fixed summation order: launches repeat bit for
+ * bit and a sample's result does not depend on the batch it is in. */
+int se_deconv2d_k4s2_s6_domain(int batch, int cin, int cout, int h, int w);
+long long se_deconv2d_k4s2_s6_packed_elems(int cin, int cout);
+int se_deconv2d_k4s2_s6_pack(const float* w, se_bf16* wsplit, int cin, int cout, void* stream);
+int se_deconv2d_k4s2_s6_f32(const void* x, int x_elem_bytes, const se_bf16* wsplit, const float* bias, float* out, int batch, int cin,
+                            int cout, int h, int w, int relu, void* stream);
 int se_conv3d_w6_f32(const float* in, const float* wpack, const se_bf16* wsplit6, const float* bpack, const float* residual,
                      float* out, int batch, int dim, int cin, int cin_pad, int cout, int ksize, int flags,
                      float* workspace, long long workspace_elems, void* stream);

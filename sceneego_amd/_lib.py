@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # tools/ may point at the development build (csrc/build.sh --devtools -> libsceneego_hip_dev.so)
 LIB_PATH = os.environ.get("SCENEEGO_HIP_LIB") or os.path.join(_HERE, "libsceneego_hip.so")
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 EPI_RELU = 1
 EPI_RES_PRE_RELU = 2
@@ -92,6 +92,10 @@ SIGNATURES = {
     "se_conv3d_k3_split3_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "se_conv3d_split6_packed_elems": (_ll, [_i, _i, _i, _i]),
     "se_conv3d_split6_pack": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "se_deconv2d_k4s2_s6_domain": (_i, [_i, _i, _i, _i, _i]),
+    "se_deconv2d_k4s2_s6_packed_elems": (_ll, [_i, _i]),
+    "se_deconv2d_k4s2_s6_pack": (_i, [_vp, _vp, _i, _i, _vp]),
+    "se_deconv2d_k4s2_s6_f32": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "se_conv3d_w6_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp]),
     "se_conv3d_f32_split6": (_i, [_i, _i, _i, _i, _i, _i]),
     "se_conv3d_k3_split6_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -620,14 +624,54 @@ def conv2d_3x3_s2(x, wpack, bias, relu):
     return out
 
 
-def deconv2d_k4s2_assemble(z, bias, batch, cout, h, w, relu=True):
-    """``z`` [B,16,cout,h,w] (per-tap GEMM results of a ConvTranspose2d(4, 2, 1), tap = 4 ky + kx) -> relu?(y + bias) [B,cout,2h,2w]."""
+def deconv2d_k4s2_assemble(z, bias, batch, cout, h, w, relu=True, split6=None):
+    """``z`` [B,16,cout,h,w] (per-tap GEMM results of a ConvTranspose2d(4, 2, 1), tap = 4 ky + kx) -> relu?(y + bias) [B,cout,2h,2w].
+
+    With ``split6`` (``deconv2d_k4s2_s6_pack`` of the layer's folded weight) the first argument is the layer's INPUT [B,cin,h,w] and one
+    launch does product and assembly together (se_deconv2d_k4s2_s6_f32: six bf16 products per float32 product)."""
     require_hip(z, bias)
+    if split6 is not None:
+        return deconv2d_k4s2_s6(z, split6, bias, cout, relu=relu)
     _chk_f32(z, bias)
     assert z.is_contiguous() and z.numel() == batch * 16 * cout * h * w
     out = torch.empty((batch, cout, 2 * h, 2 * w), device=z.device, dtype=torch.float32)
     _check(load().se_deconv2d_k4s2_assemble_f32(_ptr(z), _ptr(bias), _ptr(out), batch, cout, h, w, 1 if relu else 0, _stream()),
            "se_deconv2d_k4s2_assemble_f32")
+    return out
+
+
+def deconv2d_k4s2_s6_ok(batch, cin, cout, h, w) -> bool:
+    """Shapes se_deconv2d_k4s2_s6_f32 covers (cin % 32, cout % 64, w % 16, h % 8, 32-bit byte offsets into the input)."""
+    return bool(load().se_deconv2d_k4s2_s6_domain(batch, cin, cout, h, w))
+
+
+def deconv2d_k4s2_s6_pack(w):
+    """Folded ConvTranspose2d(4, 2, 1) weight ``w`` [cin, cout, 4, 4] (float32, on the device) -> its three bf16 planes in the order
+    se_deconv2d_k4s2_s6_f32 walks them, [cin / 32, cout / 16, 2, 8, 3, 64, 8]; None for a shape that has none."""
+    require_hip(w)
+    _chk_f32(w)
+    cin, cout = int(w.shape[0]), int(w.shape[1])
+    assert w.dim() == 4 and tuple(w.shape[2:]) == (4, 4)
+    n = int(load().se_deconv2d_k4s2_s6_packed_elems(cin, cout))
+    if n <= 0:
+        return None
+    out = torch.empty((cin // 32, cout // 16, 2, 8, 3, 64, 8), device=w.device, dtype=torch.bfloat16)
+    assert out.numel() == n
+    _check(load().se_deconv2d_k4s2_s6_pack(_ptr(w), _ptr(out), cin, cout, _stream()), "se_deconv2d_k4s2_s6_pack")
+    return out
+
+
+def deconv2d_k4s2_s6(x, wsplit, bias, cout, relu=True):
+    """``x`` [B,cin,h,w] -> relu?(ConvTranspose2d(4, 2, 1)(x) + bias) [B,cout,2h,2w] in one launch; HipExtensionError (bad argument)
+    outside the kernel's domain - the entry point checks, nothing is launched then."""
+    require_hip(x, wsplit, bias)
+    assert x.dim() == 4 and x.is_contiguous() and wsplit.dtype == torch.bfloat16 and wsplit.is_contiguous()
+    _chk_f32(bias)
+    B, cin, h, w = x.shape
+    assert wsplit.numel() == (cin // 32) * (cout // 16) * 2 * 8 * 3 * 512 and bias.numel() == cout
+    out = torch.empty((B, cout, 2 * h, 2 * w), device=x.device, dtype=torch.float32)
+    _check(load().se_deconv2d_k4s2_s6_f32(_ptr(x), x.element_size(), _ptr(wsplit), _ptr(bias), _ptr(out), B, cin, cout, h, w,
+                                          1 if relu else 0, _stream()), "se_deconv2d_k4s2_s6_f32")
     return out
 
 

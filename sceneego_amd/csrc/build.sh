@@ -21,7 +21,7 @@ newer() {  # source $1 or a header newer than object $2
   return 1
 }
 OBJS=()
-for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume_viterbi volume_sample skeleton_prior skeleton_pose skeleton_sample conv2d_1x1 conv2d_3x3 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc png_enc render render_volume scene_probe scene_constraint scene_field; do
+for f in voxelize gather softargmax joint_stats joint_modes volume_filter volume_viterbi volume_sample skeleton_prior skeleton_pose skeleton_sample conv2d_1x1 conv2d_3x3 deconv2d_k4s2 conv3d conv3d_pack conv3d_direct conv3d_small conv3d_tail conv3d_tiled conv3d_wino conv3d_wino2d conv3d_wino44pp conv3d_wino67 conv3d_fft7 conv3d_bf16 conv3d_bf16_tiled conv3d_split exr_piz exr_zip jpeg jpeg_enc png_enc render render_volume scene_probe scene_constraint scene_field; do
   [ -f $f.hip ] || { echo "build.sh: source $f.hip is missing" >&2; exit 1; }
   OBJS+=($OBJ/$f.o)
   extra=""

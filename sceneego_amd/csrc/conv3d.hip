@@ -20,7 +20,7 @@
 
 #include "conv3d_plan.h"
 
-extern "C" int se_abi_version(void) { return 42; }
+extern "C" int se_abi_version(void) { return 43; }
 
 // Which family of kernels a default channels-last call (no SE_EPI_OUT_PLANAR / SE_EPI_RES_POST_RELU, cin_pad == cin) of this shape
 // belongs to: 2 = 2-D Winograd, 1 = 1-D Winograd F(4,3), 7 = Winograd 7^3, 0 = none of them.  The shape predicates are the plan's.

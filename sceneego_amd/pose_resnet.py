@@ -157,6 +157,8 @@ class FoldedBackbone:
         self.conv3x3_min_wg = int(os.environ.get("SCENEEGO_CONV3X3_MIN_WG", self.CONV3X3_MIN_WORKGROUPS))
         self.conv1x1_min_wg = int(os.environ.get("SCENEEGO_CONV1X1_MIN_WG", self.CONV1X1_MIN_WORKGROUPS))    # A/B knobs of the routing rule
         self.conv1x1_max_cin = int(os.environ.get("SCENEEGO_CONV1X1_MAX_CIN", self.CONV1X1_MAX_CIN))
+        self.deconv_s6 = os.environ.get("SCENEEGO_DECONV_S6", "1") != "0"
+        self.deconv_s6_min_wg = int(os.environ.get("SCENEEGO_DECONV_S6_MIN_WG", self.DECONV_S6_MIN_WORKGROUPS))
         self.conv1x1_small_max_wg = int(os.environ.get("SCENEEGO_CONV1X1_SMALL_MAX_WG", self.CONV1X1_SMALL_MAX_WORKGROUPS))
         self.memory_format = torch.channels_last if channels_last else torch.contiguous_format
         cvt = lambda wb: (wb[0].to(dtype).contiguous(memory_format=self.memory_format), wb[1].to(dtype))
@@ -328,7 +330,7 @@ class FoldedBackbone:
             x = self._pw(y, c3, sc, True, (bi, 3), in_bias=c2[1])
         for li, (w, b) in enumerate(self.ups):
             B, _, H, W = x.shape
-            if B * H * W <= self.DECONV_GEMM_MAX_POSITIONS and x.dtype == torch.float32:
+            if x.dtype == torch.float32 and (B * H * W <= self.DECONV_GEMM_MAX_POSITIONS or self._deconv_s6_plan(li, x) is not False):
                 x = self._deconv_gemm(li, x, b)
             else:
                 x = ba(F.conv_transpose2d(x, w, None, stride=2, padding=1), b, None, True)
@@ -340,12 +342,39 @@ class FoldedBackbone:
     # 0, 2 on j+1, j), which ``se_deconv2d_k4s2_assemble_f32`` sums together with the bias and the ReLU.  Round 2 gathered the 16
     # shifted copies of x first (index_select: 67 MB for the 2048-channel layer) and summed four batched GEMMs per parity - 8 launches,
     # ~150 us for the 2048 -> 256 layer at 8 x 8; MIOpen's backward-data igemm takes 300 us there (profiles/r04_backbone_solvers.txt).
-    # At 32 x 32 MIOpen's Winograd form (204 us, 84 TFLOP/s) is faster than any GEMM of Z's size and stays.
+    # At 32 x 32 MIOpen's Winograd form (204 us, 84 TFLOP/s) is faster than any GEMM of Z's size.
     DECONV_GEMM_MAX_POSITIONS = 2048
+    # A layer runs as ONE launch of se_deconv2d_k4s2_s6_f32 instead (a four-phase implicit GEMM, float32 products as six bf16 MFMA
+    # products, bias and ReLU in its epilogue) where the shape is in its domain and fills the chip: a workgroup is 128 positions x 64
+    # output channels and takes the same time whether 32 or 256 of them run, while MIOpen's and rocBLAS's times fall with the batch -
+    # routed from one workgroup per CU on (the 32 x 32 -> 64 x 64 layer from batch 8; profiles/deconv2d_split6_ab.txt).  The
+    # threshold rests on two measured points, 256 workgroups (71 us against MIOpen's 190) and 64 workgroups at the 16 x 16 layer (60 us
+    # against rocBLAS + assembly's 52: not routed); nothing between was measured, and grids with a partial last wave of
+    # workgroups (B = 9 ... 15 at this map) and other maps of 8192 positions or more are routed by the same reasoning, unmeasured.
+    # SCENEEGO_DECONV_S6=0: the routes above for every layer.
+    DECONV_S6_MIN_WORKGROUPS = 256
+
+    def _deconv_s6_plan(self, li, x):
+        """The split planes of transposed layer ``li`` when ``x`` goes to se_deconv2d_k4s2_s6_f32, else False."""
+        from . import _lib
+
+        def make():
+            B, cin, H, W = x.shape
+            w = self.ups[li][0]
+            cout = w.shape[1]
+            if (not self.deconv_s6 or self.dtype != torch.float32 or not _lib.deconv2d_k4s2_s6_ok(B, cin, cout, H, W)
+                    or (B * H * W // 128) * (cout // 64) < self.deconv_s6_min_wg):
+                return False
+            return self._packed("up_s6", li, 64, x.device, lambda: _lib.deconv2d_k4s2_s6_pack(w.float().contiguous()))
+
+        return self._plan("up", li, x, make)
 
     def _deconv_gemm(self, li, x, bias):
         from . import _lib
         B, C, H, W = x.shape
+        planes = self._deconv_s6_plan(li, x)
+        if planes is not False:
+            return _lib.deconv2d_k4s2_assemble(x, bias, B, self.ups[li][0].shape[1], H, W, relu=True, split6=planes)
         cache = self.__dict__.setdefault("_deconv_gemm_cache", {})
         key = (li, x.device)
         if key not in cache:

@@ -30,7 +30,7 @@ def fused(images):
         x = maddrelu(y, c3[0], sc, 1.0, c3[1], [1, 1], [0, 0], [1, 1], 1)
     for li, (w, b) in enumerate(fb.ups):
         Bn, _, H, W = x.shape
-        if Bn * H * W <= fb.DECONV_GEMM_MAX_POSITIONS:
+        if Bn * H * W <= fb.DECONV_GEMM_MAX_POSITIONS or fb._deconv_s6_plan(li, x) is not False:      # the production route of the layer
             x = fb._deconv_gemm(li, x, b)
         else:
             x = ba(F.conv_transpose2d(x, w, None, stride=2, padding=1), b, None, True)
